@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- interpolated frames/s of the MoCoPCI point-set hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N>1 invoked plainly: this process spawns `python -m torch.distributed.run --nproc-per-node N ... bench.py ...`, one rank per
      GPU, and relays rank 0's JSON line; under torch.distributed.run already: reads RANK/LOCAL_RANK/WORLD_SIZE from the env)
 
@@ -11,13 +11,19 @@ frames/s = 3 * B_total * K / t.  Workload at every N: BASELINE.json configs[1]/[
 (weak scaling; configs[2] is 8 GPUs x 8).  Multi-GPU: sequences shard across ranks with no data-path collective; the only
 exchange is the final all_gather of the output frames over RCCL (inside the timed step).
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times K steps and prints the JSON line (metric, value, unit, higher_is_better, dtype,
+ms_per_step and the run's configuration).  --dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step
+returned to its caller as DIR/<name>.npy (float32; see dump_outputs); the inputs are seeded, so two builds can be compared
+output for output.
+
+Extra objects on the JSON line, measured only with --full:
   roofline          the dominant hand-written kernel of the step's critical (main) stream, timed live with hipEvents around every
                     launch on its launch stream inside the timed region; achieved = algorithmic flops or bytes per launch
                     (SURVEY.md 8(d) per-unit figure x units per launch) / average launch duration
   roofline_others   the same for every other hand-written kernel family (FPS runs on a side stream, beside the main stream)
   parity            sequence 0 of this very run against the REFERENCE'S stored forward (tests/golden/forward_c2_n8192.npz)
   cpu_baseline      the same graph on the CPU oracle backend (oracle/, "port") for one full batch, rank 0, N=1 only
+  chamfer_vs_gt_untrained_weights / emd_vs_gt_untrained_weights, quality, pointset_end_to_end (see full_extras)
 """
 import argparse
 import json
@@ -107,9 +113,6 @@ def pmc_is_stale():
         return json.load(open(PMC_STAMP))["csrc_sha256"] != kernel_sources_digest()
     except (OSError, KeyError, ValueError):
         return True
-
-
-PMC_IS_STALE = pmc_is_stale()
 
 
 def algorithmic_work(kernel, calls):
@@ -223,6 +226,7 @@ def log_call_shapes(be, step):
 
 def roofline_entries(timed, calls, steps, pmc):
     entries = []
+    pmc_stale = pmc_is_stale()
     for kname in FAMILIES:
         launches, kms = timed[kname]
         if not launches or kms <= 0:
@@ -248,7 +252,7 @@ def roofline_entries(timed, calls, steps, pmc):
         if "hbm_bytes_per_launch" in p:
             e["traffic"] = p["hbm_bytes_per_launch"]
             e["traffic_source"] = "profiles/r05_pmc.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this round's build, read side doubled per the gfx950 rule)"
-            e["traffic_stale"] = PMC_IS_STALE
+            e["traffic_stale"] = pmc_stale
         for key in ("valu_busy_frac_of_chip", "mfma_busy_frac_of_chip", "mfma_valu_coexec_frac_of_chip", "simd_issue_busy_frac_of_chip",
                     "mean_resident_waves_per_simd"):
             if key in p:
@@ -310,6 +314,20 @@ def quality_on_scan_weights(dev):
             "chamfer_vs_gt": cd, "emd_vs_gt": emd, "chamfer_of_copying_frame_1": ident, "mean_sq_norm_of_gt": e_gt2}
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as out_dir/<name>.npy in float32 (float64 for float64 tensors; indices below 2**24 are exact in float32)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {k: v.detach().cpu().numpy().astype(np.float64 if v.dtype == torch.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes > {DUMP_LIMIT_BYTES}"
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def run_train_step(args):
     """One JSON line: milliseconds per training step on one GPU (SURVEY 8(f) #3; see DESIGN.md section 8)."""
     from mocopci_amd import synth, training
@@ -332,8 +350,10 @@ def run_train_step(args):
         losses.append(training.train_step(net, opt, x1, x2, gtc)[0])   # returns the loss as a float: one host sync per step, as train.py has
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) * 1e3 / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": torch.tensor([losses[-1]], dtype=torch.float64)})   # what train_step returns
     print(json.dumps({"metric": "training step time", "value": ms, "unit": "ms", "higher_is_better": False, "n_gpus": 1, "steps": args.steps,
-                      "warmup": max(1, args.warmup), "dtype": "f32", "data": "synthetic",
+                      "warmup": max(1, args.warmup), "ms_per_step": ms, "dtype": "f32", "data": "synthetic",
                       "config": {"workload": f"MoCoPCI training step, N={CONFIGS['c2']['npoints']}, B={CONFIGS['c2']['batch']}, module mode {args.train_step}",
                                  "objective": "train.py:135-160 multi-scale Chamfer, clip 2.0, Adam"},
                       "loss_first_last": [losses[0], losses[-1]], "peak_memory_GiB": torch.cuda.max_memory_allocated() / 2 ** 30,
@@ -343,9 +363,15 @@ def run_train_step(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: per-kernel roofline (hipEvents around the headline kernel in "
+                         "the timed region, an instrumented pass after it), Chamfer / EMD, parity with the reference's stored forward, "
+                         "quality on the second weight set, the CPU baseline, and the extra launches of --config c4 / c5")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--config", choices=("c2", "c4", "c5"), default="c2",
                     help="BASELINE.json configuration: c2 = configs[1]/[2] (N=8192, B=8 per GPU: the one the metric is quoted on, default); "
                          "c4 = configs[3] (N=16384, B=8, model forward + ball_query / three_nn launches); c5 = configs[4] (N=65536, B=8: "
@@ -362,6 +388,8 @@ def main():
                          "backward + clipped Adam, mocopci_amd/training.py) at the configs[1] shape instead; eval = the inference graph "
                          "differentiated, train = after net.train() (batch-statistics BatchNorm, dropout: the reference's mode, train.py:130)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.train_step is not None:
         if args.gpus != 1:
             raise SystemExit("--train-step is a single-GPU measurement")
@@ -456,14 +484,16 @@ def main():
 
     for i in range(args.warmup):
         step(last=i == args.warmup - 1)
-    calls = log_call_shapes(ops.backend(), lambda: step(last=True))
+    if args.full:
+        calls = log_call_shapes(ops.backend(), lambda: step(last=True))
     for _ in range(n_streams - 1):  # every lane has run at least once before the clock starts
         step(last=True)
 
     # Inside the timed region only the headline kernel is bracketed by hipEvents (two records per step).  Bracketing all nine
     # families (~45 launches per step) costs ~0.4 ms per step of stream time and serialises the steps in flight, so the other
     # families are timed in a second, instrumented pass right after the timed region (same process, same inputs, one stream).
-    ops.prof_enable(() if os.environ.get("MCP_BENCH_NOPROF") == "1" else (HEADLINE,))  # MCP_BENCH_NOPROF: A/B of the event overhead only
+    if args.full:
+        ops.prof_enable(() if os.environ.get("MCP_BENCH_NOPROF") == "1" else (HEADLINE,))  # MCP_BENCH_NOPROF: A/B of the event overhead only
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -474,24 +504,22 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    headline_timed = ops.prof_collect(HEADLINE)
-    inst_steps = min(args.steps, 10)
-    ops.prof_enable(FAMILIES)
-    for i in range(inst_steps):
-        step(last=i == inst_steps - 1)   # the same calls as in the timed region (same kernels and shapes)
-    torch.cuda.synchronize()
-    timed = {k: ops.prof_collect(k) for k in FAMILIES}
-    ops.prof_enable(None)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step hands its caller: the frames of its batch, (world*B, 3 frames, N, 3)
+        dump_outputs(args.dump_outputs, {"frames": frames})
+    if args.full:
+        headline_timed = ops.prof_collect(HEADLINE)
+        inst_steps = min(args.steps, 10)
+        ops.prof_enable(FAMILIES)
+        for i in range(inst_steps):
+            step(last=i == inst_steps - 1)   # the same calls as in the timed region (same kernels and shapes)
+        torch.cuda.synchronize()
+        timed = {k: ops.prof_collect(k) for k in FAMILIES}
+        ops.prof_enable(None)
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-
-    local = frames[rank * B_PER_GPU:(rank + 1) * B_PER_GPU]
-    chamfer = [float(ops.backend().chamfer(local[:, j].contiguous(), gt[j])) for j in range(3)]
-    # second metric of test.py:90 (approximate EMD, per-point normalised as models/utils.py:223-235), outside the timed region
-    from mocopci_amd import emd as emd_mod
-    emd = [float(emd_mod.EMD(local[:, j].permute(0, 2, 1).contiguous(), gt[j].permute(0, 2, 1).contiguous())) for j in range(3)]
 
     total_frames = 3 * B_PER_GPU * world * args.steps
     result = {
@@ -530,11 +558,27 @@ def main():
                                                    "its own and the last step prefetches nothing: exactly `steps` pyramids run inside the timed region"}[pipeline],
                    "arithmetic": "fp32 values throughout; the fused MLP layers form each fp32 product from six bf16 MFMA partial products of an "
                                  "exact 3-way operand split (fp32 accumulation, ~4 ulp from the f32-input MFMA build)"},
-        # Random (untrained) weights: the network's frames are nowhere near the scan, so these two are NOT quality numbers -- they only
-        # pin the metric code path (test.py:88-90).  Parity of the run itself is the `parity` object below.
-        "chamfer_vs_gt_untrained_weights": chamfer,
-        "emd_vs_gt_untrained_weights": emd,
     }
+    if args.full:
+        full_extras(result, args, cfg, rank, world, dev, frames, gt, x1, calls, timed, headline_timed, inst_steps, n_streams)
+
+    if rank == 0:
+        print(json.dumps(result))
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_extras(result, args, cfg, rank, world, dev, frames, gt, x1, calls, timed, headline_timed, inst_steps, n_streams):
+    """--full: everything on the line beside the headline figure, measured after the timed region."""
+    from mocopci_amd import ops
+    local = frames[rank * B_PER_GPU:(rank + 1) * B_PER_GPU]
+    # Random (untrained) weights: the network's frames are nowhere near the scan, so these two are NOT quality numbers -- they only
+    # pin the metric code path (test.py:88-90).  Parity of the run itself is the `parity` object below.
+    result["chamfer_vs_gt_untrained_weights"] = [float(ops.backend().chamfer(local[:, j].contiguous(), gt[j])) for j in range(3)]
+    # second metric of test.py:90 (approximate EMD, per-point normalised as models/utils.py:223-235), outside the timed region
+    from mocopci_amd import emd as emd_mod
+    result["emd_vs_gt_untrained_weights"] = [float(emd_mod.EMD(local[:, j].permute(0, 2, 1).contiguous(), gt[j].permute(0, 2, 1).contiguous()))
+                                             for j in range(3)]
     if rank == 0 and args.config == "c2":
         result["quality"] = quality_on_scan_weights(dev)
     par = parity_vs_reference(local, rank) if cfg["golden"] else None
@@ -563,11 +607,6 @@ def main():
 
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(cfg, batch=B_PER_GPU if args.config == "c2" else 2)
-
-    if rank == 0:
-        print(json.dumps(result))
-    if world > 1:
-        dist.destroy_process_group()
 
 
 def spawn_ranks(n, argv):
@@ -680,7 +719,7 @@ def run_c5(args):
             state["knn_q"] = be.knn(pts, x, K)
             main.wait_stream(side)
             state["knn_n"].record_stream(main)
-        state["sel"] = sel
+        state["sel"], state["pts"] = sel, pts
     for _ in range(max(args.warmup, 1)):
         step()
     torch.cuda.synchronize()
@@ -689,7 +728,25 @@ def run_c5(args):
         step()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    # per-kernel durations, HIP events on the launch stream, same calls
+    if args.dump_outputs:
+        # the step's four results; of the self search (64 MiB of indices) the rows of a fixed, seeded sample of 16384 of the B*N queries
+        rows = torch.randperm(B * N, generator=torch.Generator().manual_seed(0))[:16384].sort().values.to(dev)
+        dump_outputs(args.dump_outputs, {"fps_indices": state["sel"], "fps_points": state["pts"], "knn_sampled": state["knn_q"],
+                                         "knn_self_sample": state["knn_n"].reshape(B * N, K)[rows]})
+    result = {"metric": "clouds/sec through FPS 65536->2048 + 32-NN (Q=2048 and Q=N) [BASELINE configs[4]: kernels only]", "value": B * args.steps / elapsed,
+              "unit": "clouds/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
+              "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+              "config": {"workload": "synthetic N=65536 dense scan (x,y in +-40, z in +-3, 5 % duplicated points), batch=8, 1xMI355X: FPS 65536->2048 + "
+                                     "32-NN Q=2048 + 32-NN Q=N per step (BASELINE configs[4])", "bench_config": "c5", "npoints": N, "batch_per_gpu": B,
+                         "streams": "the self search (with the sorted form of the cloud) runs on a second stream beside the sampling chain, as the "
+                                    "level-0 self search of a forward does; the step ends when both streams have"}}
+    if args.full:
+        c5_kernels(result, args, be, x, state, B, N, M, K)
+    print(json.dumps(result))
+
+
+def c5_kernels(result, args, be, x, state, B, N, M, K):
+    """--full: per-kernel durations of the configs[4] step, HIP events on the launch stream, same calls; the CPU baseline."""
     pts = be.group_rows(x, state["sel"])
     t_fps = _event_time(lambda: be.fps(x, M), 5)
     with be.cloud_scope():
@@ -716,17 +773,9 @@ def run_c5(args):
                reference_formulation_GBs=24.0 * B * N * N / t_kn / 1e9)
     bc = entry("mcp_morton_codes + sort + mcp_tile_boxes (sorted form of the 65536-point clouds)", t_build, B * (12 * N * 2 + 4 * N),
                "bytes: cloud read, sorted cloud + permutation written; torch.sort of the Morton codes in between (N > 16384: outside the fused builder)")
-    result = {"metric": "clouds/sec through FPS 65536->2048 + 32-NN (Q=2048 and Q=N) [BASELINE configs[4]: kernels only]", "value": B * args.steps / elapsed,
-              "unit": "clouds/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
-              "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-              "config": {"workload": "synthetic N=65536 dense scan (x,y in +-40, z in +-3, 5 % duplicated points), batch=8, 1xMI355X: FPS 65536->2048 + "
-                                     "32-NN Q=2048 + 32-NN Q=N per step (BASELINE configs[4])", "bench_config": "c5", "npoints": N, "batch_per_gpu": B,
-                         "streams": "the self search (with the sorted form of the cloud) runs on a second stream beside the sampling chain, as the "
-                                    "level-0 self search of a forward does; the step ends when both streams have"},
-              "roofline": kn, "roofline_others": [fps, kq, bc]}
+    result["roofline"], result["roofline_others"] = kn, [fps, kq, bc]
     if not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline_c5(x.cpu(), M, K)
-    print(json.dumps(result))
 
 
 def cpu_baseline_c5(x, M, K):

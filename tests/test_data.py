@@ -1,6 +1,5 @@
-"""NL-Drive data path: format round trip, sampling rule, and (in the build container) identity with the
-reference's own NLDriveDataset on the same files and the same np.random seed."""
-import importlib.util
+"""NL-Drive data path: format round trip, sampling rule, and identity with the reference's own NLDriveDataset on the
+same files and the same np.random seed (its sample stored by oracle/make_golden.py)."""
 import os
 
 import numpy as np
@@ -8,8 +7,6 @@ import pytest
 import torch
 
 from mocopci_amd import data
-
-REF = "/root/reference/data/no_norm_datasets.py"
 
 
 def make_files(tmp_path, sizes=(9000, 8192, 5000, 12000, 8500, 300, 8192)):
@@ -38,14 +35,15 @@ def test_format_and_sampling_rule(tmp_path):
     assert gt[1].shape == (8192, 3)                                                  # 300-point frame is padded too
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference tree only exists in the build container")
-def test_identical_to_reference_dataset(tmp_path):
-    spec = importlib.util.spec_from_file_location("ref_no_norm_datasets", REF)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+def test_identical_to_reference_dataset(tmp_path, golden_dir):
+    """The reference's NLDriveDataset on these files with np.random seeded 123 selected the rows stored in
+    tests/golden/nldrive_sample_seed123.npz (in0..in3 of the four input files, gt0..gt2 of the three ground-truth files)."""
+    g = np.load(os.path.join(golden_dir, "nldrive_sample_seed123.npz"))
     root, lst, _ = make_files(tmp_path)
-    np.random.seed(123)
-    want_in, want_gt = mod.NLDriveDataset(root, lst, num_points=8192)[0]
+    names = open(lst).read().split()
+    raw = [data.read_frame(os.path.join(root, name)) for name in names]
+    want_in = [torch.from_numpy(raw[i][g["in%d" % i]]) for i in range(4)]
+    want_gt = [torch.from_numpy(raw[4 + j][g["gt%d" % j]]) for j in range(3)]
     np.random.seed(123)
     got_in, got_gt = data.NLDriveDataset(root, lst, num_points=8192)[0]
     for a, b in zip(want_in + want_gt, got_in + got_gt):

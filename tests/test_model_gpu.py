@@ -169,15 +169,48 @@ def test_bench_two_ranks_rehearsal_as_child_process():
     assert res["value"] > 0 and res["metric"] == "interpolated frames/sec"
 
 
-def test_bench_config5_line_as_child_process():
-    """`bench.py --config c5` (BASELINE configs[4]: FPS 65536 -> 2048 + 32-NN, kernels only) prints one JSON line with the roofline objects
-    of its three kernels; run as the driver would, in a fresh process."""
+def test_bench_config5_line_as_child_process(tmp_path):
+    """`bench.py --config c5 --full` (BASELINE configs[4]: FPS 65536 -> 2048 + 32-NN, kernels only) prints one JSON line with the roofline
+    objects of its three kernels and dumps the step's results; run as the driver would, in a fresh process."""
     import json, os, subprocess, sys
+    import numpy as np
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "c5", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"],
-                         capture_output=True, text=True, timeout=300)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "c5", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--full",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line["unit"] == "clouds/s" and line["value"] > 0 and line["config"]["bench_config"] == "c5"
     kernels = [line["roofline"]] + line["roofline_others"]
     assert len(kernels) == 4 and all(k["avg_launch_us"] > 0 and 0 < k["frac"] for k in kernels)
+    shapes = {"fps_indices": (8, 2048), "fps_points": (8, 2048, 3), "knn_sampled": (8, 2048, 32), "knn_self_sample": (16384, 32)}
+    for name, shape in shapes.items():
+        a = np.load(tmp_path / (name + ".npy"))
+        assert a.shape == shape and a.dtype == np.float32 and np.isfinite(a).all(), name
+    idx = np.load(tmp_path / "knn_self_sample.npy")
+    assert (idx == np.round(idx)).all() and idx.min() >= 0 and idx.max() < 65536
+
+
+def test_bench_plain_line_and_dumped_frames(tmp_path):
+    """A plain `bench.py --steps 2 --warmup 1 --dump-outputs DIR` in a fresh process: one JSON line with the headline fields and
+    none of the --full objects, and DIR/frames.npy = the frames of the last timed step, bit-identical to an isolated forward of
+    the same seeded batch in this process (the pipelined serving loop changes no result)."""
+    import json, os, subprocess, sys
+    import numpy as np
+    from mocopci_amd import synth
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    res = json.loads(lines[0])
+    assert res["metric"] == "interpolated frames/sec" and res["unit"] == "frames/s" and res["higher_is_better"] is True and res["dtype"]
+    assert res["steps"] == 2 and res["value"] > 0 and abs(res["value"] - 3 * 8 * 1000.0 / res["ms_per_step"]) <= 1e-6 * res["value"]
+    assert not {"roofline", "roofline_others", "parity", "quality", "cpu_baseline", "chamfer_vs_gt_untrained_weights"} & set(res)
+    got = np.load(tmp_path / "frames.npy")
+    assert got.shape == (8, 3, 8192, 3) and got.dtype == np.float32
+    net = hc.build_model("cuda:0")
+    x1, x2, _ = synth.make_batch(2, 8, 8192, device="cuda:0")
+    want = net(x1, x2)
+    for j in range(3):
+        assert np.array_equal(got[:, j], want[j].cpu().numpy()), j

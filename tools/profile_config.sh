@@ -6,7 +6,7 @@ cfg=$1; tag=${2:-prof_$1}
 out=gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
-B="python3 bench.py --config $cfg --steps 4 --warmup 2 --no-cpu-baseline"
+B="python3 bench.py --config $cfg --steps 4 --warmup 2 --full --no-cpu-baseline"
 timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o t -- $B > "$out/bench_under_rocprof.json" 2> "$out/trace.err"
 cp $(find "$out/trace" -name '*kernel_stats.csv' | head -1) "$out/kernel_stats.csv"
 timeout -k 5 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out/pmc_fetch" -o f -- $B > "$out/pmc_fetch.log" 2>&1

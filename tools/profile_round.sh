@@ -7,7 +7,7 @@ tag=${1:-prof}
 out=gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
-B="python3 bench.py --steps 6 --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-}"
+B="python3 bench.py --steps 6 --warmup 3 --full --no-cpu-baseline ${BENCH_ARGS:-}"
 timeout -k 5 300 rocprofv3 --kernel-trace --stats -d "$out/trace" -o t -- $B > "$out/trace_bench.json" 2> "$out/trace.err"
 db=$(find "$out/trace" -name '*.db' | head -1)
 python3 tools/rocpd_stats.py "$db" "$out/kernel_stats.csv" "$out/step_by_queue.txt" > /dev/null

@@ -5,7 +5,7 @@ tag=${1:-trace}; shift || true
 out=gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d "$out/trace" -o t -- python3 bench.py --steps 6 --warmup 3 --no-cpu-baseline "$@" > "$out/trace_bench.json" 2> "$out/trace.err"
+rocprofv3 --kernel-trace --stats -d "$out/trace" -o t -- python3 bench.py --steps 6 --warmup 3 --full --no-cpu-baseline "$@" > "$out/trace_bench.json" 2> "$out/trace.err"
 db=$(find "$out/trace" -name '*.db' | head -1)
 python3 tools/rocpd_stats.py "$db" "$out/kernel_stats.csv" "$out/step_by_queue.txt" > /dev/null
 python3 tools/step_timeline.py "$db" > "$out/step_timeline.txt" 2>&1 || true
