@@ -1163,11 +1163,13 @@ class HipBackend:
         """act(W [x_0 | x_1 | x_2] + b) [+ res] over the last axis (policy_rows: the kernel of a product with that many rows, see
         linear_supported): xs one tensor or up to three pieces of a concatenation (read in
         place, column slices allowed); act(v) = v > 0 ? v : slope v (1.0: none, 0.1: LeakyReLU, 0: ReLU, a PReLU slope).
-        One kernel instead of cat + GEMM + activation + add.  Differentiable.  packed: linear_pack(w, b, widths) if kept."""
-        def fused(xs_, w_, b_, slope_, res_):
+        One kernel instead of cat + GEMM + activation + add.  Differentiable.  packed: linear_pack(w, b, widths) if kept.  A kept
+        pack belongs to one piece layout (each piece is padded to whole 32-channel chunks): pieces that want a gradient run
+        concatenated, on a pack of the concatenation, and the kept one is not used there."""
+        def fused(xs_, w_, b_, slope_, res_, packed_=packed):
             ps = self._pieces(xs_)
             ks = [p.shape[1] for p in ps]
-            pk = packed if packed is not None else self.linear_pack(w_, b_, ks)
+            pk = packed_ if packed_ is not None else self.linear_pack(w_, b_, ks)
             rows, n = ps[0].shape[0], w_.shape[0]
             first = xs_[0] if isinstance(xs_, (tuple, list)) else xs_
             out = torch.empty((rows, n), dtype=torch.float32, device=first.device)
@@ -1180,10 +1182,11 @@ class HipBackend:
             return out.reshape(*first.shape[:-1], n)
         if isinstance(xs, (tuple, list)) and grad.wants_grad(*xs, w, b, res):
             # training: the pieces are concatenated (autograd splits the gradient again) so that the layer takes the explicit
-            # backward below -- the streaming dx / dW kernels -- instead of plain autograd over library GEMMs
+            # backward below -- the streaming dx / dW kernels -- instead of plain autograd over library GEMMs.  The caller's pack
+            # is laid out for the pieces ([36, 36] pads to 4 chunks, [72] has 3), so the concatenation is packed for itself.
             cat = torch.cat(list(xs), dim=-1)
             if isinstance(slope, (int, float)) and 0.0 <= slope <= 1.0 and self.linear_supported(cat, w.shape[0], few_rows=False):
-                return _LinearFn.apply(fused, cat, w, b, float(slope), res)
+                return _LinearFn.apply(lambda *a: fused(*a, packed_=None), cat, w, b, float(slope), res)
             return grad.linear_twin(cat, w, b, slope, res)
         if grad.wants_grad(xs, w, b, res) and isinstance(slope, (int, float)) and 0.0 <= slope <= 1.0:
             return _LinearFn.apply(fused, xs, w, b, float(slope), res)
