@@ -534,6 +534,37 @@ int mcp_ptblock_grad(int b, int n, int c, int k, int qkv_stride, const float *xy
 int mcp_emd(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, float *cost, float *workspace,
             mcp_stream_t stream);
 
+/* EMD backward (emd_cuda.matchcost_backward, emd.py:16-21; emd_kernel.cu matchcostgrad1 / matchcostgrad2) without the match matrix.
+ * The transport plan is a sum over the MCP_EMD_LEVELS levels, in level order j = 0..9 (level = -4^(7-j) for j = 0..8, then 0):
+ *   match[l][k] = (((0 + w_0) + w_1) + ... + w_9),  w_j = __expf(level_j * d) * ratioL_j[k] * ratioR_j[l],
+ *   d = |xyz2[l] - xyz1[k]|^2, ratioL_j written by pass 1 of level j, ratioR_j by pass 2.
+ * mcp_emd_keep is mcp_emd (match not written; cost bit-identical) that also stores each level's ratios in `levels`,
+ * mcp_emd_levels_floats(b, n, m) = B*10*(N+M) floats laid out (B, 10, N+M): levels[b][j][0..N) = ratioL_j,
+ * levels[b][j][N..N+M) = ratioR_j.  workspace: B*(3N+2M) floats as mcp_emd.
+ * mcp_emd_grad rebuilds match[l][k] pair by pair from `levels` (same expression and order as the forward) and writes, with
+ * the match held constant as the reference does,
+ *   grad1 (B,N,3): grad1[k] = (sum_l (xyz1[k] - xyz2[l]) * match[l][k]) * 2 grad_cost[b]
+ *   grad2 (B,M,3): grad2[l] = (sum_k (xyz2[l] - xyz1[k]) * match[l][k]) * 2 grad_cost[b]
+ * grad_cost (B).  Each sum runs over the other set in tiles of 512 entries: entry t of every tile goes to partial sum t/64, each
+ * partial ascends, and the eight partials are added in order: no atomics, bit-reproducible.  A level whose level*d is below -128 for every lane of a wave is skipped (its __expf is exactly 0).
+ * grad1 or grad2 may be NULL (not computed). */
+#define MCP_EMD_LEVELS 10
+size_t mcp_emd_levels_floats(int b, int n, int m);
+int mcp_emd_keep(int b, int n, int m, const float *xyz1, const float *xyz2, float *cost, float *levels, float *workspace,
+                 mcp_stream_t stream);
+int mcp_emd_grad(int b, int n, int m, const float *grad_cost, const float *xyz1, const float *xyz2, const float *levels, float *grad1,
+                 float *grad2, mcp_stream_t stream);
+
+/* emd_cuda.matchcost_forward / matchcost_backward on a caller's match (B,M,N) (emd_kernel.cu:204-247, matchcostgrad1/2).
+ * mcp_matchcost: cost[b] = sum_{l,k} match[l][k] |xyz2[l]-xyz1[k]|^2; one workgroup per batch element, lane t sums
+ *   k = t, t+1024, ... each over ascending l (float products, double sums), then a fixed-shape tree over the 1024 lanes.
+ * mcp_matchcost_grad: grad1 (B,N,3), grad2 (B,M,3) as mcp_emd_grad, from the given match.  grad1: one lane per k (match rows
+ *   read along k), the l sum in eight contiguous eighths added in order; grad2: a workgroup per 8 rows l, lane t sums
+ *   k = t, t+256, ..., then a fixed-shape tree over the 256 lanes.  No atomics.  grad1 or grad2 may be NULL. */
+int mcp_matchcost(int b, int n, int m, const float *xyz1, const float *xyz2, const float *match, float *cost, mcp_stream_t stream);
+int mcp_matchcost_grad(int b, int n, int m, const float *grad_cost, const float *xyz1, const float *xyz2, const float *match,
+                       float *grad1, float *grad2, mcp_stream_t stream);
+
 /* ---------------- Instrumentation (bench.py roofline leg) --------------------------- */
 /* mcp_prof_enable(mask): every launch of a kernel whose id bit (1 << MCP_KERNEL_*) is set in mask is bracketed
  * by hipEvents recorded on the launch stream; mask 0 disables and clears.  mcp_prof_collect(id, ...) synchronises

@@ -104,6 +104,11 @@ SIGNATURES = {
     "mcp_mlp2_pack": [_i, _i, _i, _p, _p, _p, _p, _p, _p],
     "mcp_mlp2": [ctypes.c_longlong, _i, _i, _i, _f, _p, _i, _p, _i, _p, _p, _i, _p],
     "mcp_emd": [_i, _i, _i, _p, _p, _p, _p, _p, _p],
+    "mcp_emd_levels_floats": [_i, _i, _i],
+    "mcp_emd_keep": [_i, _i, _i, _p, _p, _p, _p, _p, _p],
+    "mcp_emd_grad": [_i, _i, _i, _p, _p, _p, _p, _p, _p, _p],
+    "mcp_matchcost": [_i, _i, _i, _p, _p, _p, _p, _p],
+    "mcp_matchcost_grad": [_i, _i, _i, _p, _p, _p, _p, _p, _p, _p],
     "mcp_prof_enable": [_i],
     "mcp_prof_collect": [_i, _p, _p],
 }
@@ -112,7 +117,7 @@ _RESTYPES = {"mcp_error_string": ctypes.c_char_p, "mcp_fps_workspace_bytes": cty
              "mcp_fusion_bn_workspace_bytes": ctypes.c_size_t, "mcp_fusion_bn_grad_workspace_bytes": ctypes.c_size_t,
              "mcp_ptblock_grad_workspace_bytes": ctypes.c_size_t, "mcp_attention_small_grad_workspace_bytes": ctypes.c_size_t,
              "mcp_linear_wgrad_workspace_bytes": ctypes.c_size_t, "mcp_scatter_segments_workspace_bytes": ctypes.c_size_t,
-             "mcp_prelu_dropout_grad_workspace_bytes": ctypes.c_size_t}
+             "mcp_prelu_dropout_grad_workspace_bytes": ctypes.c_size_t, "mcp_emd_levels_floats": ctypes.c_size_t}
 
 _lib = None
 

@@ -1,7 +1,8 @@
 """Drop-in installation for an unmodified checkout of the reference.
 
 The reference reaches its extension through two import roots, both ending in `import pointnet2_cuda`
-(pointnet2/pointnet2_utils.py:7; models/pointnet2/pointnet2_utils.py:7 via mocopci.py:8), and
+(pointnet2/pointnet2_utils.py:7; models/pointnet2/pointnet2_utils.py:7 via mocopci.py:8), its EMD metric through
+`import emd_cuda` (models/EMD/emd.py:2), and
 models/layers.py:15 expects a `models.common` module that the repository does not ship.
 `install()` registers this package's implementations under those names BEFORE the reference's
 modules are imported:
@@ -18,7 +19,7 @@ import types
 
 import torch
 
-from . import ops, pointnet2_cuda, pointnet2_utils
+from . import emd_cuda, ops, pointnet2_cuda, pointnet2_utils
 
 
 def _common_module():
@@ -62,6 +63,7 @@ def knn_points(p1, p2, K=1, **_):
 
 def install(patch_helpers=False):
     sys.modules["pointnet2_cuda"] = pointnet2_cuda
+    sys.modules["emd_cuda"] = emd_cuda                                # models/EMD/emd.py:2
     for name in ("pointnet2.pointnet2_utils", "models.pointnet2.pointnet2_utils"):
         sys.modules[name] = pointnet2_utils
     for pkg in ("pointnet2", "models.pointnet2"):

@@ -133,12 +133,18 @@ __global__ __launch_bounds__(BLK) void emd_reduce_kernel(int n, int m, const flo
     if (threadIdx.x == 0) cost[blockIdx.x] = part[0];
 }
 
-}  // namespace
+// levels[b][j] = ratioL_j (n floats) | ratioR_j (m floats): the level's two ratios, as pass 3 of level j read them
+__global__ __launch_bounds__(BLK) void emd_keep_kernel(int j, int n, int m, const float *__restrict__ ws_c, float *__restrict__ levels) {
+    const EmdWs w = ws_of(const_cast<float *>(ws_c), blockIdx.y, n, m);
+    float *dst = levels + ((size_t)blockIdx.y * MCP_EMD_LEVELS + j) * ((size_t)n + m);
+    const int i = blockIdx.x * BLK + threadIdx.x;
+    if (i < n) dst[i] = w.ratioL[i];
+    if (i < m) dst[n + i] = w.ratioR[i];
+}
 
-MCP_EXPORT int mcp_emd(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, float *cost, float *workspace,
-                       mcp_stream_t stream) {
-    MCP_CHECK_ARGS(b > 0 && n > 0 && m > 0 && xyz1 && xyz2 && cost && workspace);
-    hipStream_t s = (hipStream_t)stream;
+// the level loop of mcp_emd; levels != NULL also keeps each level's ratios (one copy launch per level, after pass 3)
+int emd_run(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, float *cost, float *workspace, float *levels,
+            hipStream_t s) {
     float multiL, multiR;  // emd_kernel.cu:32-38 (integer division)
     if (n >= m) { multiL = 1.f; multiR = (float)(n / m); } else { multiL = (float)(m / n); multiR = 1.f; }
     if (match) {
@@ -154,7 +160,28 @@ MCP_EXPORT int mcp_emd(int b, int n, int m, const float *xyz1, const float *xyz2
                            (float *)nullptr);
         hipLaunchKernelGGL(emd_right_kernel, dim3(mcp_divup(m, BLK), b), dim3(BLK), 0, s, level, n, m, xyz1, xyz2, workspace);
         hipLaunchKernelGGL(emd_left_kernel<3>, dim3(mcp_divup(n, BLK), b), dim3(BLK), 0, s, level, n, m, xyz1, xyz2, workspace, match);
+        if (levels)
+            hipLaunchKernelGGL(emd_keep_kernel, dim3(mcp_divup(big, BLK), b), dim3(BLK), 0, s, 7 - j, n, m, workspace, levels);
     }
     hipLaunchKernelGGL(emd_reduce_kernel, dim3(b), dim3(BLK), 0, s, n, m, workspace, cost);
     return mcp_launch_status();
+}
+
+}  // namespace
+
+MCP_EXPORT int mcp_emd(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, float *cost, float *workspace,
+                       mcp_stream_t stream) {
+    MCP_CHECK_ARGS(b > 0 && n > 0 && m > 0 && xyz1 && xyz2 && cost && workspace);
+    return emd_run(b, n, m, xyz1, xyz2, match, cost, workspace, nullptr, (hipStream_t)stream);
+}
+
+MCP_EXPORT size_t mcp_emd_levels_floats(int b, int n, int m) {
+    if (b <= 0 || n <= 0 || m <= 0) return 0;
+    return (size_t)b * MCP_EMD_LEVELS * ((size_t)n + m);
+}
+
+MCP_EXPORT int mcp_emd_keep(int b, int n, int m, const float *xyz1, const float *xyz2, float *cost, float *levels, float *workspace,
+                            mcp_stream_t stream) {
+    MCP_CHECK_ARGS(b > 0 && n > 0 && m > 0 && xyz1 && xyz2 && cost && levels && workspace);
+    return emd_run(b, n, m, xyz1, xyz2, nullptr, cost, workspace, levels, (hipStream_t)stream);
 }
