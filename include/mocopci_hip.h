@@ -210,6 +210,12 @@ int mcp_interp3_weights(int b, int n, int s, const float *dense, const float *sp
                         mcp_stream_t stream);
 int mcp_interp3_apply(int b, int n, int s, int c, const float *feat, const int *idx3, const float *w3, float *out,
                       mcp_stream_t stream);
+/* backward of mcp_interp3_weights: grad_w3 (B,N,3) = dL/dw3 -> grad_dense (B,N,3) and grad_nb (B,N,3,3) = dL/d(sparse[idx3_j]) per
+ * gathered neighbour, which the caller scatters with mcp_group_rows_grad_sorted (C = 3, the (order, seg) pair of idx3 viewed as
+ * (B,3N)).  The three distances are recomputed; a neighbour whose distance was clamped to 1e-10 gets a zero gradient (as torch's
+ * norm + clamp), grad_dense = -((g_0 + g_1) + g_2).  Either output may be NULL, not both.  Bit-reproducible. */
+int mcp_interp3_weights_grad(int b, int n, int s, const float *dense, const float *sparse, const int *idx3, const float *grad_w3,
+                             float *grad_dense, float *grad_nb, mcp_stream_t stream);
 /* backward of mcp_interp3_apply w.r.t. feat (channel-last counterpart of three_interpolate_grad, interpolate_gpu.cu:126-150):
  * grad_out (B,N,C) -> grad_feat (B,S,C) += w3 * grad_out at idx3; the caller zero-initialises grad_feat. */
 int mcp_interp3_apply_grad(int b, int n, int s, int c, const float *grad_out, const int *idx3, const float *w3, float *grad_feat,
@@ -321,13 +327,29 @@ int mcp_cross_volume(int b, int n1, int n2, int d, int k, const float *xyz1, con
  * The layer is re-evaluated in the kernel; the arg-max neighbour of a channel is the lowest list position among equal maxima;
  * all sums run in fixed orders (results repeat bit for bit).  workspace: mcp_cross_grad_workspace_bytes(b, n1, d) bytes.
  * D = 64 and 128 (the level-1 and level-2 cost volumes, 97 % of the layer's backward time at the training shape); D = 256:
- * MCP_ERR_UNSUPPORTED, mcp_cross_grad_floats returns 0 (the caller differentiates the unfused layer).  workspace 16-byte aligned. */
+ * MCP_ERR_UNSUPPORTED and mcp_cross_grad_floats returns 0 here -- that width has its own entry, mcp_cross256_grad below.
+ * workspace 16-byte aligned. */
 int mcp_cross_grad_floats(int d);
 size_t mcp_cross_grad_workspace_bytes(int b, int n1, int d);
 int mcp_cross_grad(int b, int n1, int n2, int d, int k, const float *xyz1, const float *xyz2, const float *points1, const float *points2,
                    const int *idx, const int *idx2, const float *wpos, const float *bpos, const float *wmlp, const float *bmlp,
                    const float *grad_out, float *grad_xyz1, float *grad_dir, float *grad_points1, float *grad_rows, float *grad_weights,
                    void *workspace, size_t workspace_bytes, mcp_stream_t stream);
+
+/* Backward of mcp_cross_volume at D = 256 (cross3, pointconv_util.py:783-791).  Arguments, outputs (grad_dir (B,N1,32,3), grad_rows
+ * (B,N1,32,256), grad_weights = dWpos (256,3) | dbpos (256) | dWmlp (256,256) | dbmlp (256): mcp_cross256_grad_floats() floats), tie
+ * rule (lowest list position among equal maxima) and errors (k != 32: MCP_ERR_UNSUPPORTED; short workspace, null or misaligned
+ * pointer: MCP_ERR_BAD_ARG; nothing is launched) as mcp_cross_grad; both index forms.  z is recomputed with the forward's own kernel
+ * arithmetic (same weight image, same MFMA order), so the arg-max neighbours are the forward's.  The gradient of z is non-zero at
+ * one neighbour per (point, channel): dx and dWmlp are exact fp32 sums over those entries, every sum in a fixed order (results repeat
+ * bit for bit, no atomics).  grad_rows doubles as scratch for the layer's hidden activations while the call runs.
+ * workspace: mcp_cross256_grad_workspace_bytes(b, n1) bytes, 16-byte aligned (2 KB per point + up to about 20 MB). */
+int mcp_cross256_grad_floats(void);
+size_t mcp_cross256_grad_workspace_bytes(int b, int n1);
+int mcp_cross256_grad(int b, int n1, int n2, int k, const float *xyz1, const float *xyz2, const float *points1, const float *points2,
+                      const int *idx, const int *idx2, const float *wpos, const float *bpos, const float *wmlp, const float *bmlp,
+                      const float *grad_out, float *grad_xyz1, float *grad_dir, float *grad_points1, float *grad_rows, float *grad_weights,
+                      void *workspace, size_t workspace_bytes, mcp_stream_t stream);
 
 /* PointConv / PointConvD up to the final Linear (mocopci.py:1218-1266, :1289-1300, :1330-1335):
  * s_xyz (B,N,3), new_xyz (B,S,3) centres, s_points (B,N,D) channel-last, idx (B,S,32) int32 into the

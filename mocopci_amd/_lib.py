@@ -43,6 +43,7 @@ SIGNATURES = {
     "mcp_group_rows": [_i, _i, _i, _i, _p, _p, _p, _p],
     "mcp_interp3": [_i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p],
     "mcp_interp3_weights": [_i, _i, _i, _p, _p, _p, _p, _p],
+    "mcp_interp3_weights_grad": [_i, _i, _i, _p, _p, _p, _p, _p, _p, _p],
     "mcp_interp3_apply": [_i, _i, _i, _i, _p, _p, _p, _p, _p],
     "mcp_interp3_apply_grad": [_i, _i, _i, _i, _p, _p, _p, _p, _p],
     "mcp_interp3_apply_grad_sorted": [_i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p],
@@ -66,6 +67,9 @@ SIGNATURES = {
     "mcp_cross_grad_floats": [_i],
     "mcp_cross_grad_workspace_bytes": [_i, _i, _i],
     "mcp_cross_grad": [_i] * 5 + [_p] * 17 + [ctypes.c_size_t, _p],
+    "mcp_cross256_grad_floats": [],
+    "mcp_cross256_grad_workspace_bytes": [_i, _i],
+    "mcp_cross256_grad": [_i] * 4 + [_p] * 17 + [ctypes.c_size_t, _p],
     "mcp_pointconv_agg": [_i] * 5 + [_p] * 12,
     "mcp_pointconv_agg_grad_floats": [],
     "mcp_pointconv_agg_grad_workspace_bytes": [_i, _i],
@@ -113,7 +117,8 @@ SIGNATURES = {
     "mcp_prof_collect": [_i, _p, _p],
 }
 _RESTYPES = {"mcp_error_string": ctypes.c_char_p, "mcp_fps_workspace_bytes": ctypes.c_size_t, "mcp_fusion_grad_workspace_bytes": ctypes.c_size_t,
-             "mcp_cross_grad_workspace_bytes": ctypes.c_size_t, "mcp_pointconv_agg_grad_workspace_bytes": ctypes.c_size_t,
+             "mcp_cross_grad_workspace_bytes": ctypes.c_size_t, "mcp_cross256_grad_workspace_bytes": ctypes.c_size_t,
+             "mcp_pointconv_agg_grad_workspace_bytes": ctypes.c_size_t,
              "mcp_fusion_bn_workspace_bytes": ctypes.c_size_t, "mcp_fusion_bn_grad_workspace_bytes": ctypes.c_size_t,
              "mcp_ptblock_grad_workspace_bytes": ctypes.c_size_t, "mcp_attention_small_grad_workspace_bytes": ctypes.c_size_t,
              "mcp_linear_wgrad_workspace_bytes": ctypes.c_size_t, "mcp_scatter_segments_workspace_bytes": ctypes.c_size_t,

@@ -5,9 +5,14 @@ three hand-written scatter-add kernels for gather / group / interpolate (K3/K6/K
 interpolate_gpu.cu:120-161, all atomicAdd).  Here
 
   * forward in training is the SAME fused HIP kernel as in inference (identical numerics);
-  * backward re-evaluates the layer in its unfused form -- the "twin" functions below, restatements of the reference layers on
-    channel-last tensors (citations on each) built from the differentiable row gather -- and lets autograd differentiate that:
-    the standard recompute-in-backward trade (nothing of size B x N x K x C is kept between forward and backward);
+  * backward re-evaluates the layer (the standard recompute-in-backward trade: nothing of size B x N x K x C is kept between
+    forward and backward).  Where a hand-written HIP backward exists it does so inside the kernel (the autograd.Functions of
+    ops.py: fusion, the cost volumes at D = 64 / 128 / 256, PointConv at feature widths that are multiples of 4, the vector-attention block, narrow-head attention,
+    the per-point Linear and MLP, the interpolation blend and its weights).  Elsewhere -- wide-head attention (head widths
+    32 / 256), the D = 3 first PointConv, shapes a kernel is not built for -- RecomputeFn evaluates the layer's unfused form, the
+    "twin" functions below (restatements of the reference layers on channel-last tensors, citations on each, built from the
+    differentiable row gather), and lets autograd differentiate that.  The twins are also the yardsticks the kernels are tested
+    against;
   * the only non-dense piece of any of these gradients, the scatter-add of the row gather, is a DETERMINISTIC segmented
     reduction (mcp_group_rows_grad_sorted: stable sort by destination row + in-order sums) instead of atomics, so a training
     step is bit-reproducible.

@@ -85,6 +85,32 @@ class _Interp3ApplyFn(torch.autograd.Function):
         return d_feat, None, d_w3
 
 
+class _Interp3WeightsFn(torch.autograd.Function):
+    """mcp_interp3_weights with its hand-written backward (mcp_interp3_weights_grad): one thread per dense point recomputes the
+    three distances; the per-neighbour gradients (B,N,3,3) reach the sparse set through the deterministic segmented scatter, with
+    the (order, seg) pair of idx3 that _Interp3ApplyFn builds for the same list inside one segments_memo() block."""
+
+    @staticmethod
+    def forward(ctx, be, dense, sparse, idx3):
+        dense, sparse = dense.detach().contiguous(), sparse.detach().contiguous()
+        ctx.save_for_backward(dense, sparse, idx3)
+        return be._interp3_weights(dense, sparse, idx3)
+
+    @staticmethod
+    def backward(ctx, grad_w3):
+        dense, sparse, idx3 = ctx.saved_tensors
+        B, N, _ = dense.shape
+        S = sparse.shape[1]
+        need_d, need_s = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        grad_w3 = grad_w3.contiguous()
+        d_dense = torch.empty_like(dense) if need_d else None
+        d_nb = torch.empty((B, N, 3, 3), dtype=torch.float32, device=dense.device) if need_s else None
+        _call("mcp_interp3_weights_grad", dense, B, N, S, _lib.fptr(dense), _lib.fptr(sparse), _lib.iptr(idx3), _lib.fptr(grad_w3),
+              None if d_dense is None else _lib.fptr(d_dense), None if d_nb is None else _lib.fptr(d_nb))
+        d_sparse = _group_rows_grad(d_nb, idx3, S) if need_s else None
+        return None, d_dense, d_sparse, None
+
+
 class _GroupRowsFn(torch.autograd.Function):
     """Row gather with its scatter-add backward (channel-last counterpart of GroupingOperation, pointnet2_utils.py:156-198)."""
 
@@ -210,8 +236,9 @@ class _PointConvAggFn(torch.autograd.Function):
 
 
 class _CrossFn(torch.autograd.Function):
-    """mcp_cross_volume with its hand-written backward (mcp_cross_grad, D = 64 / 128): recompute inside the backward kernel, the
-    per-neighbour gradients through the deterministic segmented scatter (one sort serves both), weight gradients fixed-order sums."""
+    """mcp_cross_volume with its hand-written backward (mcp_cross_grad at D = 64 / 128, mcp_cross256_grad at D = 256): recompute
+    inside the backward kernel, the per-neighbour gradients through the deterministic segmented scatter (one sort serves both),
+    weight gradients fixed-order sums."""
 
     @staticmethod
     def forward(ctx, be, ia, ib, xyz1, xyz2, points1, points2, wpos, bpos, wmlp, bmlp):
@@ -229,10 +256,15 @@ class _CrossFn(torch.autograd.Function):
         d_xyz1, d_points1 = torch.empty_like(xyz1), torch.empty_like(points1)
         d_dir = torch.empty((B, N1, 32, 3), dtype=torch.float32, device=dev)
         d_rows = torch.empty((B, N1, 32, D), dtype=torch.float32, device=dev)
-        d_w = torch.empty((lib.mcp_cross_grad_floats(D),), dtype=torch.float32, device=dev)
-        need = lib.mcp_cross_grad_workspace_bytes(B, N1, D)
+        if D == 256:   # its own entry: mcp_cross_grad keeps answering "unsupported" there
+            entry, dims = "mcp_cross256_grad", (B, N1, N2, 32)
+            floats, need = lib.mcp_cross256_grad_floats(), lib.mcp_cross256_grad_workspace_bytes(B, N1)
+        else:
+            entry, dims = "mcp_cross_grad", (B, N1, N2, D, 32)
+            floats, need = lib.mcp_cross_grad_floats(D), lib.mcp_cross_grad_workspace_bytes(B, N1, D)
+        d_w = torch.empty((floats,), dtype=torch.float32, device=dev)
         ws = torch.empty((need,), dtype=torch.uint8, device=dev)
-        _call("mcp_cross_grad", points1, B, N1, N2, D, 32, _lib.fptr(xyz1), _lib.fptr(xyz2), _lib.fptr(points1), _lib.fptr(points2), _lib.iptr(ia),
+        _call(entry, points1, *dims, _lib.fptr(xyz1), _lib.fptr(xyz2), _lib.fptr(points1), _lib.fptr(points2), _lib.iptr(ia),
               None if ib is None else _lib.iptr(ib), _lib.fptr(wpos), _lib.fptr(bpos), _lib.fptr(wmlp), _lib.fptr(bmlp), _lib.fptr(grad_out),
               _lib.fptr(d_xyz1), _lib.fptr(d_dir), _lib.fptr(d_points1), _lib.fptr(d_rows), _lib.fptr(d_w), ws.data_ptr(), need)
         d_xyz2 = d_points2 = None
@@ -797,7 +829,7 @@ class HipBackend:
         w.r.t. both coordinate sets (the reference's are: warped coordinates depend on predicted flows)."""
         dense, sparse = dense.contiguous(), sparse.contiguous()
         idx3 = self.knn(dense.detach(), sparse.detach(), 3)  # spatially pruned for the large levels, exhaustive below
-        w3 = grad.run(self._interp3_weights, lambda d, s_, i: grad.interp3_weights_twin(self.group_rows, d, s_, i), dense, sparse, idx3)
+        w3 = _Interp3WeightsFn.apply(self, dense, sparse, idx3) if grad.wants_grad(dense, sparse) else self._interp3_weights(dense, sparse, idx3)
         return idx3, w3
 
     def interp3_apply(self, feat, idx3, w3):
@@ -924,7 +956,7 @@ class HipBackend:
             return fused(xyz1, xyz2, points1, points2, idx, wpos, bpos, wmlp, bmlp)
         ia, ib = idx if isinstance(idx, (tuple, list)) else (idx, None)
         k_total = ia.shape[-1] + (0 if ib is None else ib.shape[-1])   # the backward kernel is built for the 32-neighbour lists
-        if grad.wants_grad(xyz1, xyz2, points1, points2, wpos, bpos, wmlp, bmlp) and k_total == 32 and _lib.load().mcp_cross_grad_floats(wmlp.shape[0]):
+        if grad.wants_grad(xyz1, xyz2, points1, points2, wpos, bpos, wmlp, bmlp) and k_total == 32 and wmlp.shape[0] in (64, 128, 256):
             return _CrossFn.apply(self, ia.contiguous(), None if ib is None else ib.contiguous(), xyz1, xyz2, points1, points2, wpos, bpos, wmlp, bmlp)
         return grad.run(fused, lambda *a: grad.cross_twin(self.group_rows, *a), xyz1, xyz2, points1, points2, idx, wpos, bpos, wmlp, bmlp)
 
