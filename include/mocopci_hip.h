@@ -438,6 +438,28 @@ int mcp_attention_small_grad_lse(int bf, int nq, int nk, int heads, int hd, cons
                                  int v_stride, float scale, float drop_p, unsigned seed, const float *out, const float *grad_out, const float *lse,
                                  float *grad_q, float *grad_kv, void *workspace, size_t workspace_bytes, mcp_stream_t stream);
 
+/* mcp_attention_wide (hd in {32, 64, 256}) as a training forward: the same kernels (the key-split form of head width 256 under the same
+ * dispatch rule, the same merge order) with the rows' log-sum-exp written (log2 domain; lse (BF, heads, Nq) floats) and, at drop_p > 0,
+ * attention dropout under the mask of mcp_attention_small_dropout: the same hash of (seed, (bf * heads + head) * nq + query, key), applied
+ * to P in P.V only (row sums before the mask), kept entries scaled by 1 / (1 - drop_p).  out (BF,Nq,heads*hd) is dense.  drop_p = 0: the
+ * result of mcp_attention_wide bit for bit.  mcp_attention_wide_dropout is the same call without lse.  lse (and the backward's workspace)
+ * are touched by scalar float accesses only: 4-byte alignment suffices for them, the other pointers are 16-byte aligned. */
+int mcp_attention_wide_dropout(int bf, int nq, int nk, int heads, int hd, const float *q, int q_stride, const float *k, int k_stride, const float *v,
+                               int v_stride, float scale, float drop_p, unsigned seed, float *out, mcp_stream_t stream);
+int mcp_attention_wide_lse(int bf, int nq, int nk, int heads, int hd, const float *q, int q_stride, const float *k, int k_stride, const float *v,
+                           int v_stride, float scale, float drop_p, unsigned seed, float *out, float *lse, mcp_stream_t stream);
+
+/* Backward of mcp_attention_wide_lse (hd in {32, 64, 256}); arguments and layouts as mcp_attention_small_grad_lse: out / grad_out dense,
+ * grad_q (BF,Nq,heads*hd), grad_kv (BF,Nk,2*heads*hd) laid out [dK | dV].  One elementwise pass for D = dO . O, a query-stationary dQ
+ * kernel and a key-stationary dK / dV kernel, every product on fp32 MFMA; at head width 256 the four waves of a workgroup each take
+ * 64 channels of one block of 32 rows and merge their partial score tiles through LDS in wave order.  Nothing of size Nq x Nk is written,
+ * no atomics: results repeat bit for bit.  workspace: mcp_attention_wide_grad_workspace_bytes(bf, nq, nk, heads, hd) bytes (0 for
+ * non-positive sizes). */
+size_t mcp_attention_wide_grad_workspace_bytes(int bf, int nq, int nk, int heads, int hd);
+int mcp_attention_wide_grad_lse(int bf, int nq, int nk, int heads, int hd, const float *q, int q_stride, const float *k, int k_stride, const float *v,
+                                int v_stride, float scale, float drop_p, unsigned seed, const float *out, const float *grad_out, const float *lse,
+                                float *grad_q, float *grad_kv, void *workspace, size_t workspace_bytes, mcp_stream_t stream);
+
 /* Row normalisation with the additions in front of it (nn.LayerNorm semantics: biased variance, eps inside the root):
  *     z = x[r] (+ y[r]) (+ bias);   out[r] = (z - mean z) * rsqrt(var z + eps) (* gamma + beta)
  * x, y, out (rows, c) with row strides in floats; y, bias, gamma, beta may be NULL; c <= 1024.  Replaces the LayerNorm launches

@@ -82,6 +82,10 @@ SIGNATURES = {
     "mcp_attention_small_grad": [_i] * 5 + [_p, _i, _p, _i, _p, _i, _f, _f, ctypes.c_uint, _p, _p, _p, _p, _p, ctypes.c_size_t, _p],
     "mcp_attention_small_lse": [_i] * 5 + [_p, _i, _p, _i, _p, _i, _f, _f, ctypes.c_uint, _p, _p, _p],
     "mcp_attention_small_grad_lse": [_i] * 5 + [_p, _i, _p, _i, _p, _i, _f, _f, ctypes.c_uint, _p, _p, _p, _p, _p, _p, ctypes.c_size_t, _p],
+    "mcp_attention_wide_dropout": [_i] * 5 + [_p, _i, _p, _i, _p, _i, _f, _f, ctypes.c_uint, _p, _p],
+    "mcp_attention_wide_lse": [_i] * 5 + [_p, _i, _p, _i, _p, _i, _f, _f, ctypes.c_uint, _p, _p, _p],
+    "mcp_attention_wide_grad_workspace_bytes": [_i] * 5,
+    "mcp_attention_wide_grad_lse": [_i] * 5 + [_p, _i, _p, _i, _p, _i, _f, _f, ctypes.c_uint, _p, _p, _p, _p, _p, _p, ctypes.c_size_t, _p],
     "mcp_chamfer_nn": [_i, _i, _i, _p, _p, _p, _p, _p],
     "mcp_ptblock_packed_floats": [],
     "mcp_ptblock_pack": [_p] * 10,
@@ -121,6 +125,7 @@ _RESTYPES = {"mcp_error_string": ctypes.c_char_p, "mcp_fps_workspace_bytes": cty
              "mcp_pointconv_agg_grad_workspace_bytes": ctypes.c_size_t,
              "mcp_fusion_bn_workspace_bytes": ctypes.c_size_t, "mcp_fusion_bn_grad_workspace_bytes": ctypes.c_size_t,
              "mcp_ptblock_grad_workspace_bytes": ctypes.c_size_t, "mcp_attention_small_grad_workspace_bytes": ctypes.c_size_t,
+             "mcp_attention_wide_grad_workspace_bytes": ctypes.c_size_t,
              "mcp_linear_wgrad_workspace_bytes": ctypes.c_size_t, "mcp_scatter_segments_workspace_bytes": ctypes.c_size_t,
              "mcp_prelu_dropout_grad_workspace_bytes": ctypes.c_size_t, "mcp_emd_levels_floats": ctypes.c_size_t}
 

@@ -174,6 +174,8 @@ struct WideCfg {
     static constexpr size_t LDS_BYTES = 2 * (size_t)KT * (KS + HD) * sizeof(float);
 };
 
+// NOTE: attention_wide_grad.hip restates this kernel as the training forward (attention_wide_lse_kernel: + log-sum-exp, + dropout mask) and
+// promises the same bits at drop_p = 0 -- a change to the arithmetic here is made there too (tests/test_attention_wide_grad_gpu.py).
 template <int HD>
 __global__ __launch_bounds__(64 * WAVES, 1) void attention_wide_kernel(int nq, int nk, const float *__restrict__ q, int qs,
                                                                        const float *__restrict__ k, int ks, const float *__restrict__ v,
@@ -334,6 +336,7 @@ struct WideSplitCfg {
     static_assert(TD % WAVES == 0, "output tiles shared out evenly");
 };
 
+// NOTE: restated in attention_wide_grad.hip as well (attention_wide_ksplit_lse_kernel), same bits promised: keep the two in step.
 template <int HD>
 __global__ __launch_bounds__(64 * WAVES, 1) void attention_wide_ksplit_kernel(int nq, int nk, const float *__restrict__ q, int qs,
                                                                               const float *__restrict__ k, int ks, const float *__restrict__ v,
@@ -540,6 +543,7 @@ int attention_any(int bf, int nq, int nk, int heads, int hd, const float *q, int
     } else {
         rc = hd == 32   ? launch_wide<32>(bf, nq, nk, heads, q, q_stride, k, k_stride, v, v_stride, sl2, out, out_stride, kv_shift, s)
              : hd == 64 ? launch_wide<64>(bf, nq, nk, heads, q, q_stride, k, k_stride, v, v_stride, sl2, out, out_stride, kv_shift, s)
+                        // (this dispatch rule is repeated in launch_forward of attention_wide_grad.hip: the training forward takes the same branch)
                         // head width 256: few, long problems -- when the query-stationary form would not cover the chip's 1024 SIMDs and there
                         // are key stages to share out, the waves of a workgroup split the keys instead
                         : ((long long)mcp_divup(nq, 32 * WAVES) * heads * bf * WAVES < 1024 && nk >= 32 * WAVES)

@@ -10,6 +10,7 @@
 //   dkv    key-stationary:   the same p, dp, ds per (query, key), dV += p dO_i, dK += ds Q_i.
 // Every sum has a fixed order (lane-local chains, two lane halves added once): results repeat bit for bit.
 #include "common.h"
+#include "attention_dropout.h"
 
 namespace {
 
@@ -35,15 +36,6 @@ struct Stage {
     static constexpr int KS = HD + 1;
     static constexpr int PAD = KT * KS, PLAIN = KT * HD;
 };
-
-// Attention dropout (net.train(): mocopci.py:660-662 drops entries of the softmax matrix at rate 0.05).  The keep / drop decision of
-// entry (row, key) is a counter-based hash of (seed, row, key) -- row = the query's index over (batch, head, query) -- so the forward
-// and both backward kernels regenerate the same mask without storing it.  m = 1 / (1 - p) for a kept entry, 0 for a dropped one.
-__device__ __forceinline__ float drop_scale(uint32_t seed, uint32_t row, uint32_t key, uint32_t threshold, float inv_keep) {
-    uint32_t x = seed ^ (row * 0x9E3779B1u) ^ (key * 0x85EBCA77u);
-    x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
-    return x >= threshold ? inv_keep : 0.f;
-}
 
 // ---- the forward with dropout: mcp_attention_small's kernel (attention.hip) with the mask applied to P in P.V only (the row sums
 // that normalise the softmax are taken before the mask, as softmax -> dropout -> matmul does) ----
@@ -529,14 +521,6 @@ int launch_all(int bf, int nq, int nk, int heads, const float *q, int qs, const 
     hipLaunchKernelGGL((attention_dkv_kernel<HD, DROP>), gk, dim3(64 * WAVES), 0, s, nq, nk, heads, q, qs, k, ks, v, vs, sl2, scale, seed, threshold, inv_keep,
                        gout, lse, dsum, dkv);
     return mcp_launch_status();
-}
-
-// drop probability -> (threshold of the 32-bit hash below which an entry is dropped, 1 / (1 - p))
-bool drop_params(float drop_p, uint32_t *threshold, float *inv_keep) {
-    if (!(drop_p >= 0.f && drop_p < 1.f)) return false;
-    *threshold = (uint32_t)((double)drop_p * 4294967296.0);
-    *inv_keep = (float)(1.0 / (1.0 - (double)drop_p));
-    return true;
 }
 
 }  // namespace

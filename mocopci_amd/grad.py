@@ -7,9 +7,9 @@ interpolate_gpu.cu:120-161, all atomicAdd).  Here
   * forward in training is the SAME fused HIP kernel as in inference (identical numerics);
   * backward re-evaluates the layer (the standard recompute-in-backward trade: nothing of size B x N x K x C is kept between
     forward and backward).  Where a hand-written HIP backward exists it does so inside the kernel (the autograd.Functions of
-    ops.py: fusion, the cost volumes at D = 64 / 128 / 256, PointConv at feature widths that are multiples of 4, the vector-attention block, narrow-head attention,
-    the per-point Linear and MLP, the interpolation blend and its weights).  Elsewhere -- wide-head attention (head widths
-    32 / 256), the D = 3 first PointConv, shapes a kernel is not built for -- RecomputeFn evaluates the layer's unfused form, the
+    ops.py: fusion, the cost volumes at D = 64 / 128 / 256, PointConv at feature widths that are multiples of 4, the vector-attention block, attention at head widths
+    8 / 16 / 32 / 64 / 256 (the forward keeps the rows' log-sum-exp instead: nothing is re-evaluated there), the per-point Linear and MLP,
+    the interpolation blend and its weights).  Elsewhere -- the D = 3 first PointConv, shapes a kernel is not built for -- RecomputeFn evaluates the layer's unfused form, the
     "twin" functions below (restatements of the reference layers on channel-last tensors, citations on each, built from the
     differentiable row gather), and lets autograd differentiate that.  The twins are also the yardsticks the kernels are tested
     against;

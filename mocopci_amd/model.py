@@ -289,7 +289,7 @@ class MoCoPCI(nn.Module):
     TRAIN_PYRAMID_LANE = True   # training forwards: the encoder's FPS chain on side lane 0, beside the level-0 layers
     _train_lane0 = False
     TRAIN_LANES = (0, 4, 5, 6)
-    SDPA_DROPOUT = True         # net.train() on the GPU: attention dropout inside the library's fused attention kernel
+    SDPA_DROPOUT = True         # net.train() on the GPU: attention dropout drawn inside the attention kernel (this repo's for head widths 8 / 16 / 32 / 64 / 256, the library's fused attention for any other)
     CHECKPOINT_BYTES = 1 << 30  # net.train() forwards: unfused blocks whose intermediates exceed this are recomputed in the backward, in chunks of about this size
 
     def attend(self, q, kv, heads, scale=None):
@@ -303,14 +303,14 @@ class MoCoPCI(nn.Module):
         BF, Nq, C = q.shape
         Nk, hd = kv.shape[1], C // heads
         sc = hd ** -0.5 if scale is None else scale
-        if q.is_cuda and self.SDPA_DROPOUT and hd in (8, 16):
-            # head widths 8 / 16: this repo's attention kernels with the mask generated inside (forward and backward regenerate it
-            # from one seed drawn from torch's generator); nothing of size heads x Nq x Nk exists
+        if q.is_cuda and self.SDPA_DROPOUT and hd in (8, 16, 32, 64, 256):
+            # this repo's attention kernels with the mask generated inside (forward and backward regenerate it from one seed drawn
+            # from torch's generator); nothing of size heads x Nq x Nk exists
             return ops.backend().attention(q, kv, heads, scale=sc, dropout_p=p)
         if q.is_cuda and self.SDPA_DROPOUT:
-            # the library's fused attention draws the dropout mask inside the kernel (forward and backward from one counter-based
-            # stream seeded by torch's generator): same distribution as softmax -> F.dropout -> matmul, nothing of size
-            # heads x Nq x Nk exists.  The CPU (oracle backend) path below keeps the explicit form.
+            # head widths no kernel is built for: the library's fused attention draws the dropout mask inside the kernel (forward and
+            # backward from one counter-based stream seeded by torch's generator): same distribution as softmax -> F.dropout ->
+            # matmul, nothing of size heads x Nq x Nk exists.  The CPU (oracle backend) path below keeps the explicit form.
             qh = q.reshape(BF, Nq, heads, hd).permute(0, 2, 1, 3)
             kvh = kv.reshape(BF, Nk, 2, heads, hd).permute(2, 0, 3, 1, 4)
             o = F.scaled_dot_product_attention(qh, kvh[0], kvh[1], dropout_p=p, scale=sc)

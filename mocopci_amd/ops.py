@@ -314,6 +314,39 @@ class _AttentionSmallFn(torch.autograd.Function):
         return None, dq, dkv, None, None, None, None
 
 
+class _AttentionWideFn(torch.autograd.Function):
+    """mcp_attention_wide (head widths 32 / 64 / 256) with its hand-written backward (mcp_attention_wide_grad_lse: D = dO . O, dQ, dK/dV
+    on fp32 MFMA); the forward keeps the rows' log-sum-exp, dropout is the in-kernel hash mask of the narrow heads."""
+
+    @staticmethod
+    def forward(ctx, be, q, kv, heads, scale, drop_p, seed):
+        q, kv = q.detach().contiguous(), kv.detach().contiguous()
+        BF, Nq, C = q.shape
+        Nk = kv.shape[1]
+        out = torch.empty((BF, Nq, C), dtype=torch.float32, device=q.device)
+        lse = torch.empty((BF, heads, Nq), dtype=torch.float32, device=q.device)   # kept for the backward: no second forward there
+        _call("mcp_attention_wide_lse", q, BF, Nq, Nk, heads, C // heads, _lib.fptr(q), C, _lib.fptr(kv), 2 * C, kv.data_ptr() + 4 * C, 2 * C,
+              float(scale), float(drop_p), int(seed), out.data_ptr(), lse.data_ptr())
+        ctx.heads, ctx.scale, ctx.drop_p, ctx.seed = heads, scale, drop_p, seed
+        ctx.save_for_backward(q, kv, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        q, kv, out, lse = ctx.saved_tensors
+        BF, Nq, C = q.shape
+        Nk, heads = kv.shape[1], ctx.heads
+        lib = _lib.load()
+        grad_out = grad_out.contiguous()
+        dq, dkv = torch.empty_like(q), torch.empty_like(kv)
+        need = lib.mcp_attention_wide_grad_workspace_bytes(BF, Nq, Nk, heads, C // heads)
+        ws = torch.empty((need,), dtype=torch.uint8, device=q.device)
+        _call("mcp_attention_wide_grad_lse", q, BF, Nq, Nk, heads, C // heads, q.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 4 * C, 2 * C,
+              float(ctx.scale), float(ctx.drop_p), int(ctx.seed), _lib.fptr(out), _lib.fptr(grad_out), _lib.fptr(lse), _lib.fptr(dq), _lib.fptr(dkv),
+              ws.data_ptr(), need)
+        return None, dq, dkv, None, None, None, None
+
+
 def _prelu_drop_fwd(z, slope, drop_p=0.0, seed=0):
     """m * prelu(z, slope): slope a 1-element device tensor; drop_p = 0: plain PReLU (mcp_prelu_dropout)."""
     out = torch.empty_like(z)
@@ -1036,26 +1069,27 @@ class HipBackend:
 
     def attention(self, q, kv, heads, scale=None, dropout_p=0.0):
         """softmax(q k^T * scale) v per head, reading the projection outputs in place: q (BF,Nq,C), kv (BF,Nk,2C)
-        laid out [k | v] as the reference's kv Linear produces (mocopci.py:74-75, :653-654) -> (BF,Nq,C).  dropout_p > 0 (head dims 8 /
-        16 only): attention dropout on the softmax matrix inside the kernel, the mask a counter-based hash seeded from torch's CPU
-        generator (reproducible under torch.manual_seed; see mcp_attention_small_dropout)."""
+        laid out [k | v] as the reference's kv Linear produces (mocopci.py:74-75, :653-654) -> (BF,Nq,C).  dropout_p > 0: attention
+        dropout on the softmax matrix inside the kernel (head dims 8 / 16 / 32 / 64 / 256), the mask a counter-based hash seeded from
+        torch's CPU generator (reproducible under torch.manual_seed; see mcp_attention_small_dropout, mcp_attention_wide_dropout)."""
         BF, Nq, C = q.shape
         Nk = kv.shape[1]
         hd = C // heads
         if scale is None:
             scale = hd ** -0.5
+        fn = _AttentionSmallFn if hd in (8, 16) else _AttentionWideFn
         if dropout_p > 0.0:
-            if hd not in (8, 16):
-                raise RuntimeError("attention dropout inside the kernel: head dims 8 / 16")
+            if hd not in (8, 16, 32, 64, 256):
+                raise RuntimeError("attention dropout inside the kernel: head dims 8 / 16 / 32 / 64 / 256")
             seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())  # CPU generator: no device synchronisation
             if grad.wants_grad(q, kv):
-                return _AttentionSmallFn.apply(self, q, kv, heads, float(scale), float(dropout_p), seed)
+                return fn.apply(self, q, kv, heads, float(scale), float(dropout_p), seed)
             return self._attention(q, kv, heads, float(scale), float(dropout_p), seed)
         if hd not in (8, 16, 32, 64, 256):  # head dims neither kernel is built for: the dense formulation (same arithmetic as the twin)
             return grad.attention_twin(q, kv, heads, float(scale))
-        if hd in (8, 16) and grad.wants_grad(q, kv):
-            return _AttentionSmallFn.apply(self, q, kv, heads, float(scale), 0.0, 0)
-        return grad.run(self._attention, grad.attention_twin, q, kv, heads, float(scale))
+        if grad.wants_grad(q, kv):
+            return fn.apply(self, q, kv, heads, float(scale), 0.0, 0)
+        return self._attention(q, kv, heads, float(scale))
 
     def _attention(self, q, kv, heads, scale, drop_p=0.0, seed=0):
         q, kv = q.contiguous(), kv.contiguous()
@@ -1063,7 +1097,8 @@ class HipBackend:
         Nk, hd = kv.shape[1], C // heads
         out = torch.empty((BF, Nq, C), dtype=torch.float32, device=q.device)
         if drop_p > 0.0:
-            _call("mcp_attention_small_dropout", q, BF, Nq, Nk, heads, hd, q.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 4 * C, 2 * C,
+            name = "mcp_attention_small_dropout" if hd in (8, 16) else "mcp_attention_wide_dropout"
+            _call(name, q, BF, Nq, Nk, heads, hd, q.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 4 * C, 2 * C,
                   float(scale), float(drop_p), int(seed), out.data_ptr())
             return out
         # head dims 8/16: S on MFMA, P.V on packed FMAs; 32/64/256 (ei3, Cross_Frame_Att): both products on MFMA
