@@ -145,6 +145,18 @@ int mcp_three_interpolate_grad(int b, int c, int n, int m, const float *grad_out
 int mcp_knn(int b, int q, int n, int k, int dist_form, const float *query, const float *ref, int *idx, float *dist,
             mcp_stream_t stream);
 
+/* mcp_knn on a padded batch of clouds of different sizes (pytorch3d.ops.knn_points' lengths1 / lengths2): element bb searches
+ * only the first rlen[bb] rows of ref and only its first qlen[bb] query rows are live.  qlen, rlen: (B) int32 DEVICE arrays,
+ * read by the kernel (no synchronisation) and clamped there to [0,Q] / [0,N]; either may be NULL = every row valid, and with
+ * both NULL the call IS mcp_knn (same launch, same bits).  Same distance forms, 1 <= K <= 32, any N.
+ *   live rows (i < qlen[bb]):    the K smallest under (distance, index) among references 0 .. rlen[bb]-1, ascending -- what
+ *                                mcp_knn returns for the two valid prefixes on their own; if rlen[bb] < K the tail repeats the
+ *                                last valid entry; if rlen[bb] == 0, index 0 and distance 0;
+ *   padded rows (i >= qlen[bb]): index 0, distance 0.
+ * Rows beyond a length are never read: their contents influence no output bit.  Errors as mcp_knn (nothing is launched). */
+int mcp_knn_lengths(int b, int q, int n, int k, int dist_form, const float *query, const float *ref, const int *qlen,
+                    const int *rlen, int *idx, float *dist, mcp_stream_t stream);
+
 /* Spatially pruned variant of mcp_knn for large clouds: identical results (same definition, same fp32
  * canon), but queries and references are given in Morton order and each tile of consecutive sorted references
  * has a bounding box, so a wave visits tiles by ascending lower bound and stops early.
@@ -481,6 +493,13 @@ int mcp_mfa_prepare(int rows, int n, int c, const float *fea, const int *src_sel
 /* chamfer_loss (models/utils.py:36-45 -> pytorch3d chamfer_distance defaults): per-point squared
  * nearest distance both ways.  x (B,N,3), y (B,M,3) -> dxy (B,N), dyx (B,M); the caller takes the means. */
 int mcp_chamfer_nn(int b, int n, int m, const float *x, const float *y, float *dxy, float *dyx, mcp_stream_t stream);
+
+/* mcp_chamfer_nn over the valid prefixes of a padded batch (pytorch3d chamfer_distance's x_lengths / y_lengths): xlen, ylen (B)
+ * int32 device arrays as in mcp_knn_lengths (NULL = every row valid; both NULL = mcp_chamfer_nn).  dxy[bb,i] for i < xlen[bb] is
+ * the squared distance to the nearest of y[bb, 0 .. ylen[bb]-1] (0 if there is none), and symmetrically dyx; padded rows
+ * receive 0, so the caller's sums over whole rows are sums over the valid ones. */
+int mcp_chamfer_nn_lengths(int b, int n, int m, const float *x, const float *y, const int *xlen, const int *ylen, float *dxy,
+                           float *dyx, mcp_stream_t stream);
 
 /* Per-point Linear (1x1 convolution) with fused epilogue for the tall-skinny shapes of the caller graph (Conv1d wrapper
  * mocopci.py:1111-1127, the Linear layers of :438-468 / :821-1059, and the concatenations in front of them, :186-187, :846-847):

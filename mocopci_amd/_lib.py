@@ -34,6 +34,7 @@ SIGNATURES = {
     "mcp_three_interpolate": [_i, _i, _i, _i, _p, _p, _p, _p, _p],
     "mcp_three_interpolate_grad": [_i, _i, _i, _i, _p, _p, _p, _p, _p],
     "mcp_knn": [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p],
+    "mcp_knn_lengths": [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p],
     "mcp_knn_tile_size": [],
     "mcp_build_cloud": [_i, _i, _p, _p, _p, _p, _p],
     "mcp_morton_codes": [_i, _i, _p, _p, _p, _p],
@@ -87,6 +88,7 @@ SIGNATURES = {
     "mcp_attention_wide_grad_workspace_bytes": [_i] * 5,
     "mcp_attention_wide_grad_lse": [_i] * 5 + [_p, _i, _p, _i, _p, _i, _f, _f, ctypes.c_uint, _p, _p, _p, _p, _p, _p, ctypes.c_size_t, _p],
     "mcp_chamfer_nn": [_i, _i, _i, _p, _p, _p, _p, _p],
+    "mcp_chamfer_nn_lengths": [_i, _i, _i, _p, _p, _p, _p, _p, _p, _p],
     "mcp_ptblock_packed_floats": [],
     "mcp_ptblock_pack": [_p] * 10,
     "mcp_ptblock_attention": [_i] * 5 + [_p] * 8,

@@ -55,10 +55,32 @@ def index_points_gather(points, fps_idx):
     return ops.backend().group_rows(points.contiguous(), fps_idx.int())
 
 
-def knn_points(p1, p2, K=1, **_):
-    """pytorch3d.ops.knn_points subset used at pointconv_util.py:910: returns (dists, idx, None)."""
-    idx, dist = ops.backend().knn(p1.contiguous(), p2.contiguous(), K, mode=ops.MCP_DIST_DIRECT, return_dist=True)
-    return dist, idx.long(), None
+def knn_points(p1, p2, lengths1=None, lengths2=None, K=1, return_nn=False, **_):
+    """pytorch3d.ops.knn_points as called at pointconv_util.py:910 and models/layers.py:205,287: returns (dists, idx, nn).
+    lengths1 / lengths2 (B,): only p1[b, :lengths1[b]] are queries and only p2[b, :lengths2[b]] are searched.  As in pytorch3d,
+    rows >= lengths1[b] and positions k >= lengths2[b] are zero in dists and idx (the library's own rule for fewer than K
+    references, "repeat the last valid entry", is overwritten here).  return_nn: nn = p2 gathered through idx, (B,P1,K,3);
+    otherwise None.  Every other keyword of pytorch3d's signature is accepted and ignored."""
+    be = ops.backend()
+    p1, p2 = p1.contiguous(), p2.contiguous()
+    if lengths1 is None and lengths2 is None:
+        idx, dist = be.knn(p1, p2, K, mode=ops.MCP_DIST_DIRECT, return_dist=True)
+    else:
+        B, P2 = p2.shape[0], p2.shape[1]
+        l1, l2 = ops.lengths_tensor(lengths1, B, p1.shape[1], p1.device), ops.lengths_tensor(lengths2, B, P2, p1.device)
+        idx, dist = be.knn(p1, p2, K, mode=ops.MCP_DIST_DIRECT, return_dist=True, query_lengths=l1, ref_lengths=l2)
+        if l2 is not None:
+            pad = torch.arange(K, device=p1.device).view(1, 1, K) >= l2.clamp(0, P2).view(B, 1, 1)
+            idx, dist = idx.masked_fill(pad, 0), dist.masked_fill(pad, 0.0)
+    nn = be.group_rows(p2, idx) if return_nn else None
+    return dist, idx.long(), nn
+
+
+def chamfer_distance(x, y, x_lengths=None, y_lengths=None):
+    """pytorch3d.loss.chamfer_distance as called at models/utils.py:44 (default reductions, no normals): (loss, None)."""
+    if x_lengths is None and y_lengths is None:
+        return ops.backend().chamfer(x.contiguous(), y.contiguous()), None
+    return ops.backend().chamfer(x.contiguous(), y.contiguous(), x_lengths=x_lengths, y_lengths=y_lengths), None
 
 
 def install(patch_helpers=False):

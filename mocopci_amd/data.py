@@ -13,6 +13,11 @@ np.random is used in the reference's call order, so a seeded run reproduces the 
 GPU-side resampling (NLDriveDataset(device=...)): the raw scan is uploaded once, whole, and the row selection runs on the GPU
 (mcp_group_rows); the index list still comes from np.random in the reference's call order (O(N) host work, no point data
 touched on the host), so the sample is bit-identical to the host path's and the duplicated rows are exact duplicates.
+
+Whole ground-truth frames (NLDriveDataset(raw_gt=True)): the ground-truth scans come back as recorded, every one with its own
+point count, and no random draw is made for them; collate_padded() zero-pads them per batch and returns the counts, and
+evaluate(raw_gt=True) hands those to the Chamfer distance as y_lengths -- the metric against the scan itself instead of against a
+random num_points subsample of it.  The inputs' draws come first in the reference's call order, so the inputs do not change.
 """
 import os
 
@@ -44,11 +49,13 @@ def resample_on_device(raw, pick, device):
 
 
 class NLDriveDataset(Dataset):
-    def __init__(self, data_root, scene_list, num_points=8192, interval=4, num_frames=4, device=None):
+    def __init__(self, data_root, scene_list, num_points=8192, interval=4, num_frames=4, device=None, raw_gt=False):
         """device: None = the reference's host path (numpy fancy indexing); a CUDA device = GPU-side resampling (use with
-        num_workers=0: the frames come back as tensors of that device)."""
+        num_workers=0: the frames come back as tensors of that device).  raw_gt: the ground-truth frames whole, (n_j,3) each with
+        its own n_j, instead of resampled to num_points (batch them with collate_padded)."""
         super().__init__()
         self.device = device
+        self.raw_gt = raw_gt
         self.data_root, self.scene_list = data_root, scene_list
         self.num_points, self.interval, self.num_frames = num_points, interval, num_frames
         with open(scene_list, "r") as fh:
@@ -70,7 +77,14 @@ class NLDriveDataset(Dataset):
         for i in range(self.interval - 1):
             raw = read_frame(os.path.join(self.data_root, names[3 + (i + 1) * gt_intv]))
             gts.append(raw)
-            gpicks.append(resample_indices(raw.shape[0], self.num_points))
+            if not self.raw_gt:
+                gpicks.append(resample_indices(raw.shape[0], self.num_points))
+        if self.raw_gt:
+            whole = [torch.from_numpy(np.ascontiguousarray(f, dtype=np.float32)) for f in gts]
+            if self.device is not None:
+                return ([resample_on_device(f, p, self.device) for f, p in zip(frames, picks)],
+                        [t.to(self.device, non_blocking=True) for t in whole])
+            return [torch.from_numpy(f[p, :].astype("float32")) for f, p in zip(frames, picks)], whole
         if self.device is not None:
             return ([resample_on_device(f, p, self.device) for f, p in zip(frames, picks)],
                     [resample_on_device(f, p, self.device) for f, p in zip(gts, gpicks)])
@@ -79,9 +93,27 @@ class NLDriveDataset(Dataset):
         return inp, gt
 
 
-def evaluate(net, loader, device="cuda"):
+def collate_padded(batch):
+    """collate_fn for NLDriveDataset(raw_gt=True): batch = [(inputs, gts), ...] -> (inputs, gts, gt_lengths).  inputs: num_frames
+    stacked (B,N,3) tensors, as the default collate gives.  gts[j] (B, L_j, 3): frame j of every sample, zero-padded to the longest
+    one of the batch (L_j >= 1); gt_lengths[j] (B,) int32 on the CPU: the point counts, the y_lengths of the Chamfer distance."""
+    inputs = [torch.stack([item[0][i] for item in batch]) for i in range(len(batch[0][0]))]
+    gts, lengths = [], []
+    for j in range(len(batch[0][1])):
+        frames = [item[1][j] for item in batch]
+        out = frames[0].new_zeros((len(frames), max(1, max(f.shape[0] for f in frames)), 3))
+        for b, f in enumerate(frames):
+            out[b, :f.shape[0]] = f
+        gts.append(out)
+        lengths.append(torch.tensor([f.shape[0] for f in frames], dtype=torch.int32))
+    return inputs, gts, lengths
+
+
+def evaluate(net, loader, device="cuda", raw_gt=False):
     """The evaluation loop of test.py:71-135 in its intended form (one forward -> 3 frames; test.py:84 passes
-    train=True by mistake): per-frame Chamfer distance and EMD means, forward time with device sync."""
+    train=True by mistake): per-frame Chamfer distance and EMD means, forward time with device sync.
+    raw_gt: the loader yields collate_padded batches of NLDriveDataset(raw_gt=True); the Chamfer distance is taken against the
+    whole ground-truth scans (y_lengths = their point counts) and "emd" is None (the EMD kernel has no lengths)."""
     import time
 
     from . import emd as emd_mod, ops
@@ -89,7 +121,8 @@ def evaluate(net, loader, device="cuda"):
     emd = [[], [], []]
     seconds = []
     with torch.no_grad():
-        for inp, gt in loader:
+        for sample in loader:
+            inp, gt = sample[0], sample[1]
             inp = [t.permute(0, 2, 1).to(device).contiguous().float() for t in inp]   # (B,3,N), test.py:73-74
             gt = [t.to(device).contiguous().float() for t in gt]                      # (B,N,3)
             torch.cuda.synchronize()
@@ -98,8 +131,11 @@ def evaluate(net, loader, device="cuda"):
             torch.cuda.synchronize()
             seconds.append(time.perf_counter() - t0)
             for j in range(3):
+                if raw_gt:
+                    cd[j].append(float(ops.backend().chamfer(out[j].contiguous(), gt[j], y_lengths=sample[2][j])))
+                    continue
                 cd[j].append(float(ops.backend().chamfer(out[j].contiguous(), gt[j])))
                 emd[j].append(float(emd_mod.EMD(out[j].permute(0, 2, 1).contiguous(), gt[j].permute(0, 2, 1).contiguous())))
     mean = lambda v: float(np.mean(v)) if v else float("nan")
-    return {"chamfer": [mean(c) for c in cd], "emd": [mean(e) for e in emd], "seconds_per_forward": mean(seconds),
+    return {"chamfer": [mean(c) for c in cd], "emd": None if raw_gt else [mean(e) for e in emd], "seconds_per_forward": mean(seconds),
             "sequences": len(loader.dataset)}

@@ -565,6 +565,70 @@ class _ChamferFn(torch.autograd.Function):
         return None, gx, gy
 
 
+def lengths_tensor(lengths, batch, limit, device):
+    """Per-cloud lengths as the (B,) int32 device array the length-aware kernels read.  A sequence of ints or a CPU tensor is
+    validated here (one entry per batch element, 0 <= len <= limit; RuntimeError otherwise) and uploaded from pinned memory on
+    the current stream, without a synchronisation.  A device tensor (int32 / int64) is trusted as it is: reading it back would
+    be a synchronisation, and the kernels clamp every length to [0, limit] themselves."""
+    if lengths is None:
+        return None
+    if torch.is_tensor(lengths) and lengths.is_cuda:
+        if lengths.dtype not in (torch.int32, torch.int64) or lengths.numel() != batch:
+            raise RuntimeError(f"lengths: expected {batch} int32/int64 entries, got {lengths.numel()} of {lengths.dtype}")
+        return lengths.reshape(batch).to(torch.int32).contiguous()
+    host = torch.as_tensor(lengths)
+    if host.is_floating_point() or host.is_complex() or host.dtype == torch.bool:
+        raise RuntimeError(f"lengths: expected integers, got {host.dtype}")
+    host = host.reshape(-1).to(torch.int64)
+    if host.numel() != batch:
+        raise RuntimeError(f"lengths: expected one entry per batch element ({batch}), got {host.numel()}")
+    if batch and (int(host.min()) < 0 or int(host.max()) > limit):
+        raise RuntimeError(f"lengths: every entry must lie in [0, {limit}], got {host.tolist()}")
+    return host.to(torch.int32).pin_memory().to(device, non_blocking=True)
+
+
+def _valid_counts(lens, batch, limit, device):
+    """(B,) int32 number of valid rows per element as the kernels see it (clamped; `limit` everywhere without lengths)."""
+    if lens is None:
+        return torch.full((batch,), limit, dtype=torch.int32, device=device)
+    return lens.clamp(0, limit)
+
+
+class _ChamferLengthsFn(torch.autograd.Function):
+    """_ChamferFn over the valid prefixes of a padded batch (pytorch3d's x_lengths / y_lengths with its default reductions):
+    value_b = sum_{i<xl} dxy_i / max(xl,1) + sum_{j<yl} dyx_j / max(yl,1).  Forward: the length-aware search returns 0 for every
+    padded row, so the sums run over whole rows.  Backward: the same row gather and deterministic segmented scatter as _ChamferFn;
+    the direct term of a padded row -- and of every row when the other cloud is empty -- is set to an exact zero, so what the
+    scatter adds through those rows' index 0 is zero, and no padded coordinate reaches a gradient."""
+
+    @staticmethod
+    def forward(ctx, be, x, y, xl, yl):
+        x, y = x.detach().contiguous(), y.detach().contiguous()
+        B, N, _ = x.shape
+        M = y.shape[1]
+        ixy, dxy = be.knn(x, y, 1, mode=MCP_DIST_DIRECT, return_dist=True, query_lengths=xl, ref_lengths=yl)
+        iyx, dyx = be.knn(y, x, 1, mode=MCP_DIST_DIRECT, return_dist=True, query_lengths=yl, ref_lengths=xl)
+        xe, ye = _valid_counts(xl, B, N, x.device), _valid_counts(yl, B, M, x.device)
+        xden, yden = xe.clamp(min=1).float(), ye.clamp(min=1).float()
+        both = ((xe > 0) & (ye > 0)).view(B, 1, 1)
+        xrow = (torch.arange(N, device=x.device).view(1, N, 1) < xe.view(B, 1, 1)) & both   # rows with a neighbour to point at
+        yrow = (torch.arange(M, device=x.device).view(1, M, 1) < ye.view(B, 1, 1)) & both
+        ctx.save_for_backward(x, y, ixy, iyx, xden, yden, xrow, yrow)
+        return dxy[..., 0].sum(1) / xden + dyx[..., 0].sum(1) / yden
+
+    @staticmethod
+    def backward(ctx, gv):
+        x, y, ixy, iyx, xden, yden, xrow, yrow = ctx.saved_tensors
+        B, N, _ = x.shape
+        M = y.shape[1]
+        zero = gv.new_zeros(())
+        gx_d = torch.where(xrow, (x - _group_rows_fwd(y, ixy).squeeze(2)) * (gv * 2.0 / xden).view(B, 1, 1), zero)
+        gy_d = torch.where(yrow, (y - _group_rows_fwd(x, iyx).squeeze(2)) * (gv * 2.0 / yden).view(B, 1, 1), zero)
+        gx = gx_d - _group_rows_grad(gy_d.unsqueeze(2), iyx, N) if ctx.needs_input_grad[1] else None
+        gy = gy_d - _group_rows_grad(gx_d.unsqueeze(2), ixy, M) if ctx.needs_input_grad[2] else None
+        return None, gx, gy, None, None
+
+
 class _PtblockFn(torch.autograd.Function):
     """mcp_ptblock_attention with its hand-written backward (mcp_ptblock_grad): the block re-evaluated in the backward kernel, the
     per-neighbour gradients through the deterministic segmented scatter (one sort serves xyz, k and v), weight gradients fixed-order."""
@@ -791,15 +855,23 @@ class HipBackend:
         if getattr(self._tls, "scope", None) is not None and self.PRUNE_MIN_REFS <= xyz.shape[1] <= 65536:
             self._sorted_cloud(xyz.detach())
 
-    def knn(self, query, ref, k, mode=MCP_DIST_EXPANSION, return_dist=False):
+    def knn(self, query, ref, k, mode=MCP_DIST_EXPANSION, return_dist=False, query_lengths=None, ref_lengths=None):
         """knn_point(k, ref, query) (mocopci.py:1158-1169): (B,Q,3),(B,N,3) -> (B,Q,k) int32,
-        ascending by (distance, index)."""
+        ascending by (distance, index).
+        query_lengths / ref_lengths (pytorch3d's lengths1 / lengths2; see lengths_tensor for the accepted forms): element b searches
+        only ref[b, :ref_lengths[b]] and only query[b, :query_lengths[b]] is live.  Live rows get what the search of the two prefixes
+        on their own returns (fewer than k references: the tail repeats the last valid entry; none: index 0, distance 0); padded
+        query rows get index 0 and distance 0; padded rows of either cloud are never read.  Without lengths nothing changes."""
         query, ref = query.detach(), ref.detach()  # an index-producing search: no gradient (pointnet2_utils.py:31-33)
         B, Q, _ = query.shape
         N = ref.shape[1]
         idx = torch.empty((B, Q, k), dtype=torch.int32, device=query.device)
         dist = torch.empty((B, Q, k), dtype=torch.float32, device=query.device) if return_dist else None
-        if N >= self.PRUNE_MIN_REFS and Q >= self.PRUNE_MIN_QUERIES and k <= 32 and N <= 65536:
+        if query_lengths is not None or ref_lengths is not None:   # always the exhaustive kernels: the pruned search has no lengths yet
+            ql, rl = lengths_tensor(query_lengths, B, Q, query.device), lengths_tensor(ref_lengths, B, N, query.device)
+            _call("mcp_knn_lengths", query, B, Q, N, k, mode, _lib.fptr(query), _lib.fptr(ref), None if ql is None else _lib.iptr(ql),
+                  None if rl is None else _lib.iptr(rl), _lib.iptr(idx), _lib.fptr(dist) if return_dist else None)
+        elif N >= self.PRUNE_MIN_REFS and Q >= self.PRUNE_MIN_QUERIES and k <= 32 and N <= 65536:
             _lib.fptr(query), _lib.fptr(ref)  # validate before building the sorted clouds
             rs, rperm, boxes = self._sorted_cloud(ref)
             same = query.data_ptr() == ref.data_ptr() and query.shape == ref.shape
@@ -1317,11 +1389,29 @@ class HipBackend:
 
     EXPLICIT_CHAMFER_GRAD = True
 
-    def chamfer(self, x, y, per_sample=False):
+    def chamfer(self, x, y, per_sample=False, x_lengths=None, y_lengths=None):
         """chamfer_loss (models/utils.py:36-45; pytorch3d defaults): x (B,N,3), y (B,M,3) -> 0-dim tensor.  As a training loss
         (train.py:135-160) it is differentiable w.r.t. both clouds: the nearest neighbours come from the search kernel and the
         squared distances to them are re-evaluated differentiably.  per_sample: the (B,) values whose mean that is -- several terms
-        of the objective that share a ground-truth cloud are then ONE call on a stacked batch (training.multiscale_loss)."""
+        of the objective that share a ground-truth cloud are then ONE call on a stacked batch (training.multiscale_loss).
+        x_lengths / y_lengths (forms: lengths_tensor): only x[b, :xl] and y[b, :yl] count; the value of sample b is
+        sum_{i<xl} d_i / max(xl,1) + sum_{j<yl} d_j / max(yl,1), gradient rows at or beyond a length are exact zeros, and padded
+        rows are never read.  Without lengths nothing changes."""
+        if x_lengths is not None or y_lengths is not None:
+            B, N, _ = x.shape
+            M = y.shape[1]
+            xl, yl = lengths_tensor(x_lengths, B, N, x.device), lengths_tensor(y_lengths, B, M, x.device)
+            if grad.wants_grad(x, y):
+                v = _ChamferLengthsFn.apply(self, x, y, xl, yl)
+            else:
+                x, y = x.contiguous(), y.contiguous()
+                dxy = torch.empty((B, N), dtype=torch.float32, device=x.device)
+                dyx = torch.empty((B, M), dtype=torch.float32, device=x.device)
+                _call("mcp_chamfer_nn_lengths", x, B, N, M, _lib.fptr(x), _lib.fptr(y), None if xl is None else _lib.iptr(xl),
+                      None if yl is None else _lib.iptr(yl), _lib.fptr(dxy), _lib.fptr(dyx))
+                v = (dxy.sum(1) / _valid_counts(xl, B, N, x.device).clamp(min=1).float()
+                     + dyx.sum(1) / _valid_counts(yl, B, M, x.device).clamp(min=1).float())
+            return v if per_sample else v.mean()
         if grad.wants_grad(x, y):
             if self.EXPLICIT_CHAMFER_GRAD:
                 v = _ChamferFn.apply(self, x, y)
