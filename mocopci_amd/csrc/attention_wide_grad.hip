@@ -3,10 +3,8 @@
 // cross-former (mocopci.py:72-86 at dim 256 / 8 heads) and Cross_Frame_Att (mocopci.py:499-522: 16 x 3 head slots of 256 x 256 at
 // width 256).  Every product is v_mfma_f32_32x32x2_f32 (exact fp32); nothing of size Nq x Nk is written; every sum has a fixed order.
 //
-//   forward   attention_wide_kernel / attention_wide_ksplit_kernel of attention.hip restated with two additions: the row's
-//             log-sum-exp (log2 domain) is stored, and with DROP the hash mask of attention_dropout.h multiplies P in P.V only (row
-//             sums are taken before the mask).  Same instruction sequence per (query, key) and the same dispatch rule, so at
-//             drop_p = 0 the output is mcp_attention_wide's bit for bit.
+//   forward   the bodies of attention_wide_fwd.h (shared with the inference kernels of attention.hip) with the log-sum-exp output and,
+//             with DROP, the dropout mask; at drop_p = 0 the output is mcp_attention_wide's bit for bit.
 //   dsum      D = dO . O per (batch, head, query), one elementwise pass.
 //   dq        query-stationary: a wave owns 32 queries on the MFMA column, keys stream through LDS in 32-key tiles:
 //             S^T = K Q^T, dP^T = V dO^T, p = exp2(s - L), ds = p (m dP - D), dQ^T += K^T ds  (ds stays in the accumulator layout
@@ -23,325 +21,33 @@
 // is the unsplit one (3 HD/2 for dq, 4 HD/2 for dkv), registers per wave are those of head width 64, and the 16 x 3 x 256 x 256 call of
 // the training step is 384 workgroups instead of 96.  Head widths 32 / 64: no split, a workgroup is four independent waves.
 #include "common.h"
-#include "attention_dropout.h"
+#include "attention_wide_fwd.h"  // f32x16, WAVES, chan_of, drop_scale; the forward bodies
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr int WAVES = 4;
-
-__device__ __forceinline__ int chan_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 // =====================================================================================================================================
 // forward
 // =====================================================================================================================================
-template <int HD>
-struct WideCfg {
-    static constexpr int KT = 32, KS = HD + 1, TD = HD / 32;
-    static constexpr size_t LDS_BYTES = 2 * (size_t)KT * (KS + HD) * sizeof(float);
-};
-
-// attention_wide_kernel (attention.hip) + lse + mask; out is dense (row stride heads * HD)
+// out is dense (row stride heads * HD), keys / values are the batch element's own
 template <int HD, bool DROP>
 __global__ __launch_bounds__(64 * WAVES, 1) void attention_wide_lse_kernel(int nq, int nk, int heads, const float *__restrict__ q, int qs,
                                                                            const float *__restrict__ k, int ks, const float *__restrict__ v, int vs,
                                                                            float scale_log2e, uint32_t seed, uint32_t threshold, float inv_keep,
                                                                            float *__restrict__ out, float *__restrict__ lse) {
-    using C = WideCfg<HD>;
-    constexpr int KT = C::KT, KS = C::KS, TD = C::TD;
     extern __shared__ __attribute__((aligned(16))) float lds_w[];
-    float *kt = lds_w;                   // [2][KT][KS]
-    float *vt = lds_w + 2 * KT * KS;     // [2][KT][HD]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, col = lane & 31;
-    const int head = blockIdx.y, bf = blockIdx.z;
-    const int qi = blockIdx.x * (32 * WAVES) + wave * 32 + col;
-    const bool live = qi < nq;
-    const uint32_t row = (uint32_t)(((size_t)bf * heads + head) * nq + qi);
-    q += ((size_t)bf * nq + (live ? qi : 0)) * qs + head * HD;
-    k += (size_t)bf * nk * ks + head * HD;
-    v += (size_t)bf * nk * vs + head * HD;
-
-    float qf[HD / 2];
-#pragma unroll
-    for (int s4 = 0; s4 < HD / 4; ++s4) {  // Q[query][2s + h]: one float4 holds the operands of two k-steps for both halves
-        const float4 t = *reinterpret_cast<const float4 *>(q + 4 * s4);
-        qf[2 * s4 + 0] = (h ? t.y : t.x) * scale_log2e;
-        qf[2 * s4 + 1] = (h ? t.w : t.z) * scale_log2e;
-    }
-    f32x16 o[TD];
-#pragma unroll
-    for (int d = 0; d < TD; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
-    float m = -INFINITY, l = 0.f;
-
-    constexpr int F4_ROW = HD / 4, F4_TILE = KT * F4_ROW;
-    constexpr int LOADS = (F4_TILE + 64 * WAVES - 1) / (64 * WAVES);
-    float4 pre[LOADS];
-    auto fetch = [&](int t, const float *src, int stride) {
-#pragma unroll
-        for (int u = 0; u < LOADS; ++u) {
-            const int e = tid + u * 64 * WAVES;
-            const int r_ = e / F4_ROW, c4 = e % F4_ROW, key = t * KT + r_;
-            pre[u] = make_float4(0.f, 0.f, 0.f, 0.f);  // keys past nk: zero rows (their scores are masked, 0 * 0 stays 0)
-            if (e < F4_TILE && key < nk) pre[u] = *reinterpret_cast<const float4 *>(src + (size_t)key * stride + c4 * 4);
-        }
-    };
-    auto stash_k = [&](int buf) {
-#pragma unroll
-        for (int u = 0; u < LOADS; ++u) {
-            const int e = tid + u * 64 * WAVES;
-            if (e >= F4_TILE) continue;
-            float *dst = &kt[(buf * KT + e / F4_ROW) * KS + (e % F4_ROW) * 4];
-            dst[0] = pre[u].x; dst[1] = pre[u].y; dst[2] = pre[u].z; dst[3] = pre[u].w;
-        }
-    };
-    auto stash_v = [&](int buf) {
-#pragma unroll
-        for (int u = 0; u < LOADS; ++u) {
-            const int e = tid + u * 64 * WAVES;
-            if (e < F4_TILE) *reinterpret_cast<float4 *>(&vt[(buf * KT + e / F4_ROW) * HD + (e % F4_ROW) * 4]) = pre[u];
-        }
-    };
-
-    const int stages = (nk + KT - 1) / KT;
-    fetch(0, k, ks);
-    stash_k(0);
-    fetch(0, v, vs);
-    stash_v(0);
-    for (int t = 0; t < stages; ++t) {
-        const int cur = t & 1;
-        const bool more = t + 1 < stages;
-        __syncthreads();  // stage `cur` is complete; every wave has finished reading stage cur^1 (previous iteration)
-        if (more) fetch(t + 1, k, ks);
-        const float *ka = &kt[(cur * KT + col) * KS + h];
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-        for (int s = 0; s < HD / 2; ++s) {
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[2 * s], qf[s], acc, 0, 0, 0);
-            if (HD > 64 && (s & 15) == 15) __builtin_amdgcn_sched_barrier(0);  // keep the LDS operand reads from being hoisted en bloc (registers)
-        }
-        if (more) {
-            stash_k(cur ^ 1);
-            fetch(t + 1, v, vs);
-        } else {
-            // last stage, full tile: nothing sits between the S MFMAs and the first vector read of their result; the wait states of a
-            // 16-pass MFMA result are spelled out (see the same place in attention.hip)
-            asm volatile("s_nop 15\n\ts_nop 1" ::: "memory");
-        }
-        const int kbase = t * KT;
-        if (kbase + KT > nk) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                if (kbase + chan_of(r, h) >= nk) acc[r] = -INFINITY;
-        }
-        float mt = acc[0];
-#pragma unroll
-        for (int r = 1; r < 16; ++r) mt = fmaxf(mt, acc[r]);
-        mt = fmaxf(mt, __shfl_xor(mt, 32));          // both halves of a query agree on the maximum (tile 0 always has key 0)
-        const float mn = fmaxf(m, mt);
-        const float alpha = __builtin_amdgcn_exp2f(m - mn);
-        m = mn;
-        l *= alpha;
-#pragma unroll
-        for (int d = 0; d < TD; ++d)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
-        float p[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            p[r] = __builtin_amdgcn_exp2f(acc[r] - mn);
-            l += p[r];
-            if (DROP) p[r] *= drop_scale(seed, row, (uint32_t)(kbase + chan_of(r, h)), threshold, inv_keep);
-        }
-#pragma unroll
-        for (int d = 0; d < TD; ++d) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float a = vt[(cur * KT + chan_of(r, h)) * HD + 32 * d + col];
-                o[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, p[r], o[d], 0, 0, 0);
-            }
-            if (HD > 64) __builtin_amdgcn_sched_barrier(0);
-        }
-        if (more) stash_v(cur ^ 1);
-    }
-    const float lsum = l + __shfl_xor(l, 32);
-    const float inv = 1.0f / lsum;
-    if (live) {
-        float *dst = out + ((size_t)bf * nq + qi) * (size_t)(heads * HD) + head * HD;
-#pragma unroll
-        for (int d = 0; d < TD; ++d)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)  // registers 4g..4g+3 = channels 32d + 8g + 4h .. +3
-                *reinterpret_cast<float4 *>(dst + 32 * d + 8 * g + 4 * h) =
-                    make_float4(o[d][4 * g] * inv, o[d][4 * g + 1] * inv, o[d][4 * g + 2] * inv, o[d][4 * g + 3] * inv);
-        if (lse && h == 0) lse[((size_t)bf * heads + head) * nq + qi] = m + __builtin_amdgcn_logf(lsum);  // v_log_f32 is log2
-    }
+    attention_wide_body<HD, DROP>(lds_w, nq, nk, heads, q, qs, k, ks, v, vs, (int)blockIdx.z, scale_log2e, seed, threshold, inv_keep, out, heads * HD,
+                                  lse);
 }
 
-template <int HD>
-struct WideSplitCfg {
-    static constexpr int KT = 32, KS = HD + 1, TD = HD / 32;
-    static constexpr int BUF = KT * KS;                                  // floats per wave: K tile (padded rows) or V tile or the wave's O^T
-    static constexpr size_t LDS_BYTES = (size_t)WAVES * (BUF + 2 * 64) * sizeof(float);
-    static_assert(TD * 16 * 64 <= BUF, "a wave's O^T tiles fit its staging buffer");
-    static_assert(TD % WAVES == 0, "output tiles shared out evenly");
-};
-
-// attention_wide_ksplit_kernel (attention.hip: the keys split over the waves of a workgroup) + lse + mask
+// the keys split over the waves of a workgroup
 template <int HD, bool DROP>
 __global__ __launch_bounds__(64 * WAVES, 1) void attention_wide_ksplit_lse_kernel(int nq, int nk, int heads, const float *__restrict__ q, int qs,
                                                                                   const float *__restrict__ k, int ks, const float *__restrict__ v, int vs,
                                                                                   float scale_log2e, uint32_t seed, uint32_t threshold, float inv_keep,
                                                                                   float *__restrict__ out, float *__restrict__ lse) {
-    using C = WideSplitCfg<HD>;
-    constexpr int KT = C::KT, KS = C::KS, TD = C::TD, BUF = C::BUF;
     extern __shared__ __attribute__((aligned(16))) float lds_ws[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, col = lane & 31;
-    float *buf = lds_ws + wave * BUF;                       // this wave's staging buffer
-    float *ml = lds_ws + WAVES * BUF;                       // [WAVES][2][64]: running maximum, row sum
-    const int head = blockIdx.y, bf = blockIdx.z;
-    const int qi = blockIdx.x * 32 + col;
-    const bool live = qi < nq;
-    const uint32_t row = (uint32_t)(((size_t)bf * heads + head) * nq + qi);
-    q += ((size_t)bf * nq + (live ? qi : 0)) * qs + head * HD;
-    k += (size_t)bf * nk * ks + head * HD;
-    v += (size_t)bf * nk * vs + head * HD;
-
-    float qf[HD / 2];
-#pragma unroll
-    for (int s4 = 0; s4 < HD / 4; ++s4) {
-        const float4 t = *reinterpret_cast<const float4 *>(q + 4 * s4);
-        qf[2 * s4 + 0] = (h ? t.y : t.x) * scale_log2e;
-        qf[2 * s4 + 1] = (h ? t.w : t.z) * scale_log2e;
-    }
-    f32x16 o[TD];
-#pragma unroll
-    for (int d = 0; d < TD; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
-    float m = -INFINITY, l = 0.f;
-
-    constexpr int F4_ROW = HD / 4, PER_LANE = KT * F4_ROW / 64;
-    float4 pre[PER_LANE];
-    auto issue = [&](int t, const float *src, int stride) {
-#pragma unroll
-        for (int u = 0; u < PER_LANE; ++u) {
-            const int e = u * 64 + lane;
-            const int r_ = e / F4_ROW, c4 = e % F4_ROW, key = t * KT + r_;
-            pre[u] = key < nk ? *reinterpret_cast<const float4 *>(src + (size_t)key * stride + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto commit = [&](bool padded) {
-#pragma unroll
-        for (int u = 0; u < PER_LANE; ++u) {
-            const int e = u * 64 + lane;
-            const int r_ = e / F4_ROW, c4 = e % F4_ROW;
-            if (padded) {
-                float *dst = &buf[r_ * KS + c4 * 4];
-                dst[0] = pre[u].x; dst[1] = pre[u].y; dst[2] = pre[u].z; dst[3] = pre[u].w;
-            } else {
-                *reinterpret_cast<float4 *>(&buf[r_ * HD + c4 * 4]) = pre[u];
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    };
-    const int stages = (nk + KT - 1) / KT;
-    if (wave < stages) issue(wave, k, ks);
-    for (int t = wave; t < stages; t += WAVES) {
-        commit(true);                      // this stage's K tile
-        issue(t, v, vs);                   // its V tile: in flight under the S MFMAs
-        const float *ka = &buf[col * KS + h];
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-        for (int s = 0; s < HD / 2; ++s) {
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[2 * s], qf[s], acc, 0, 0, 0);
-            if ((s & 15) == 15) __builtin_amdgcn_sched_barrier(0);
-        }
-        __builtin_amdgcn_wave_barrier();   // every lane's K reads are issued; LDS serves a wave's accesses in order: V may overwrite the buffer
-        commit(false);
-        if (t + WAVES < stages) issue(t + WAVES, k, ks);   // the next stage's K tile: in flight under the softmax and the P.V MFMAs
-        const int kbase = t * KT;
-        if (kbase + KT > nk) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                if (kbase + chan_of(r, h) >= nk) acc[r] = -INFINITY;
-        }
-        float mt = acc[0];
-#pragma unroll
-        for (int r = 1; r < 16; ++r) mt = fmaxf(mt, acc[r]);
-        mt = fmaxf(mt, __shfl_xor(mt, 32));
-        const float mn = fmaxf(m, mt);
-        const float alpha = __builtin_amdgcn_exp2f(m - mn);
-        m = mn;
-        l *= alpha;
-#pragma unroll
-        for (int d = 0; d < TD; ++d)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
-        float p[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            p[r] = __builtin_amdgcn_exp2f(acc[r] - mn);
-            l += p[r];
-            if (DROP) p[r] *= drop_scale(seed, row, (uint32_t)(kbase + chan_of(r, h)), threshold, inv_keep);
-        }
-#pragma unroll
-        for (int d = 0; d < TD; ++d) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float a = buf[chan_of(r, h) * HD + 32 * d + col];
-                o[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, p[r], o[d], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        __builtin_amdgcn_wave_barrier();   // V reads issued before the next stage's K tile is written
-    }
-    // ---- the four partial results meet in LDS ----
-    const float lq = l + __shfl_xor(l, 32);   // the query's row sum over this wave's stages (both lane halves)
-#pragma unroll
-    for (int d = 0; d < TD; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) buf[(d * 16 + r) * 64 + lane] = o[d][r];
-    ml[(wave * 2 + 0) * 64 + lane] = m;
-    ml[(wave * 2 + 1) * 64 + lane] = lq;
-    __syncthreads();
-    float mm = -INFINITY;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) mm = fmaxf(mm, ml[(w * 2 + 0) * 64 + lane]);
-    float sc[WAVES], lsum = 0.f;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) {
-        const float mw = ml[(w * 2 + 0) * 64 + lane];
-        sc[w] = mw == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(mw - mm);   // a wave without stages (nk < 32 * WAVES) contributes nothing
-        lsum += sc[w] * ml[(w * 2 + 1) * 64 + lane];
-    }
-    const float inv = 1.0f / lsum;
-    if (live) {
-        float *dst = out + ((size_t)bf * nq + qi) * (size_t)(heads * HD) + head * HD;
-        constexpr int TPW = TD / WAVES;
-#pragma unroll
-        for (int dd = 0; dd < TPW; ++dd) {
-            const int d = wave * TPW + dd;
-            float res[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                float a = 0.f;
-#pragma unroll
-                for (int w = 0; w < WAVES; ++w) a += sc[w] * lds_ws[w * BUF + (d * 16 + r) * 64 + lane];
-                res[r] = a * inv;
-            }
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-                *reinterpret_cast<float4 *>(dst + 32 * d + 8 * g + 4 * h) = make_float4(res[4 * g], res[4 * g + 1], res[4 * g + 2], res[4 * g + 3]);
-        }
-        if (lse && wave == 0 && h == 0) lse[((size_t)bf * heads + head) * nq + qi] = mm + __builtin_amdgcn_logf(lsum);
-    }
+    attention_wide_ksplit_body<HD, DROP>(lds_ws, nq, nk, heads, q, qs, k, ks, v, vs, (int)blockIdx.z, scale_log2e, seed, threshold, inv_keep, out,
+                                         heads * HD, lse);
 }
 
 // dynamic LDS above the 64 KB default: the attribute is set once per device and kernel instantiation
@@ -359,9 +65,8 @@ int allow_lds() {
 template <int HD, bool DROP>
 int launch_forward(int bf, int nq, int nk, int heads, const float *q, int qs, const float *k, int ks, const float *v, int vs, float sl2, uint32_t seed,
                    uint32_t threshold, float inv_keep, float *out, float *lse, hipStream_t s) {
-    // the dispatch rule of attention_any (attention.hip): head width 256, few long problems -> the keys split over the waves
     if constexpr (HD == 256) {
-        if ((long long)mcp_divup(nq, 32 * WAVES) * heads * bf * WAVES < 1024 && nk >= 32 * WAVES) {
+        if (wide_keys_split(bf, nq, nk, heads)) {
             constexpr auto kern = attention_wide_ksplit_lse_kernel<HD, DROP>;
             if (const int rc = allow_lds<kern>()) return rc;
             hipLaunchKernelGGL(kern, dim3(mcp_divup(nq, 32), heads, bf), dim3(64 * WAVES), WideSplitCfg<HD>::LDS_BYTES, s, nq, nk, heads, q, qs, k, ks, v, vs,

@@ -18,240 +18,45 @@
 // Result definition (same as oracle/pointset_oracle.c:orc_knn): the K smallest under the
 // lexicographic order (distance, index), ascending; distances in the canon of common.h.
 // Keys are the 64-bit (distance, index) keys of topk.h: a compare-exchange is one v_min_f64 / v_max_f64 pair.
-#include "common.h"
-#include "topk.h"
+//
+// The device code is in knn_scan.h: two kernel bodies, each instantiated without lengths (mcp_knn: knn_small_kernel, knn_queue_kernel) and
+// with per-cloud lengths (mcp_knn_lengths, mcp_chamfer_nn_lengths: knn_len_small_kernel, knn_len_queue_kernel).
+#include "knn_scan.h"
 
 namespace {
 
-typedef mcp_key u64;  // 64-bit (distance, index) key, see topk.h
-#define KEY_INF MCP_KEY_INF
-constexpr int TILE = 64;   // reference points per LDS tile (per wave); small, so that the N = 256 .. 1024 searches can be split over 2-4 waves
-
-template <int MODE>
-__device__ __forceinline__ float pair_dist(float qx, float qy, float qz, float qn, const float4 r) {
-    if (MODE == MCP_DIST_EXPANSION) return mcp_expdist(qx, qy, qz, qn, r.x, r.y, r.z, r.w);
-    return mcp_sqdist3(qx, qy, qz, r.x, r.y, r.z);
-}
-
-template <int MODE>
-__device__ __forceinline__ float4 load_ref(const float *__restrict__ ref, int i, int n) {
-    if (i < n) {
-        const float x = ref[(size_t)i * 3 + 0], y = ref[(size_t)i * 3 + 1], z = ref[(size_t)i * 3 + 2];
-        return make_float4(x, y, z, mcp_sqnorm3(x, y, z));
-    }
-    // padding: distance evaluates to +inf in both forms, so it never passes "d < tau"
-    return MODE == MCP_DIST_EXPANSION ? make_float4(0.f, 0.f, 0.f, INFINITY) : make_float4(INFINITY, 0.f, 0.f, 0.f);
-}
-
-// ---------------------------------------------------------------------------------------------
-// K <= 4: sorted 4-list in registers, insertion guarded by a wave-uniform branch.
-// ---------------------------------------------------------------------------------------------
 template <int MODE, int SPLIT>
 __global__ __launch_bounds__(64 * SPLIT) void knn_small_kernel(int q, int n, int kout, const float *__restrict__ query,
                                                                const float *__restrict__ ref, int *__restrict__ idx,
                                                                float *__restrict__ dist) {
     __shared__ float4 tiles[SPLIT][2][TILE];
     __shared__ u64 mrg[SPLIT][4][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int b = blockIdx.y;
-    const int qi = blockIdx.x * 64 + lane;
-    const bool live = qi < q;
-    const float *qp = query + ((size_t)b * q + (live ? qi : 0)) * 3;
-    const float qx = qp[0], qy = qp[1], qz = qp[2];
-    const float qn = mcp_sqnorm3(qx, qy, qz);
-    ref += (size_t)b * n * 3;
-
-    // slice of the reference set for this wave, in whole tiles
-    const int ntiles = (n + TILE - 1) / TILE;
-    const int t0 = (int)((long long)ntiles * wave / SPLIT), t1 = (int)((long long)ntiles * (wave + 1) / SPLIT);
-
-    u64 a[4] = {KEY_INF, KEY_INF, KEY_INF, KEY_INF};
-    float tau = INFINITY;
-    float4(*tile)[TILE] = tiles[wave];
-
-    if (t0 < t1) {
-#pragma unroll
-        for (int u = 0; u < TILE / 64; ++u) tile[0][lane + 64 * u] = load_ref<MODE>(ref, t0 * TILE + lane + 64 * u, n);
-    }
-    for (int t = t0; t < t1; ++t) {
-        const int cur = (t - t0) & 1;
-        float4 nxt[TILE / 64];
-        if (t + 1 < t1) {
-#pragma unroll
-            for (int u = 0; u < TILE / 64; ++u) nxt[u] = load_ref<MODE>(ref, (t + 1) * TILE + lane + 64 * u, n);
-        }
-        __builtin_amdgcn_wave_barrier();
-        const int base = t * TILE;
-        constexpr int G = 8;  // references per group: loads of group g+1 are in flight under the math of group g
-        float4 rc[G];
-#pragma unroll
-        for (int u = 0; u < G; ++u) rc[u] = tile[cur][u];
-        for (int r0 = 0; r0 < TILE; r0 += G) {
-            float4 rn[G];
-            const int rnext = r0 + G < TILE ? r0 + G : r0;
-#pragma unroll
-            for (int u = 0; u < G; ++u) rn[u] = tile[cur][rnext + u];
-            float d[G];
-            bool any = false;
-#pragma unroll
-            for (int u = 0; u < G; ++u) {
-                d[u] = pair_dist<MODE>(qx, qy, qz, qn, rc[u]);
-                any |= d[u] < tau;
-            }
-            if (__builtin_amdgcn_ballot_w64(any)) {
-#pragma unroll
-                for (int u = 0; u < G; ++u) {
-                    if (__builtin_amdgcn_ballot_w64(d[u] < tau)) {
-                        u64 key = mcp_make_key(d[u], (uint32_t)(base + r0 + u));
-                        key = d[u] < tau ? key : KEY_INF;
-                        a[3] = mcp_key_min(key, a[3]);
-                        mcp_ce_asc(a[2], a[3]);
-                        mcp_ce_asc(a[1], a[2]);
-                        mcp_ce_asc(a[0], a[1]);
-                        tau = mcp_tau_of(a[3]);
-                    }
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < G; ++u) rc[u] = rn[u];
-        }
-        if (t + 1 < t1) {
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int u = 0; u < TILE / 64; ++u) tile[cur ^ 1][lane + 64 * u] = nxt[u];
-        }
-    }
-    if (SPLIT > 1) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) mrg[wave][j][lane] = a[j];
-        __syncthreads();
-        if (wave != 0) return;
-        for (int w = 1; w < SPLIT; ++w) {
-            u64 o[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o[j] = mrg[w][j][lane];
-            mcp_merge_sorted<4, 4>(a, o);
-        }
-    }
-    if (!live) return;
-    int *oi = idx + ((size_t)b * q + qi) * kout;
-    float *od = dist ? dist + ((size_t)b * q + qi) * kout : nullptr;
-    mcp_store_list<4>(a, kout, oi, od);
+    knn_small_body<MODE, SPLIT, false>(tiles, mrg, q, n, kout, query, ref, nullptr, nullptr, idx, dist);
 }
-
-// ---------------------------------------------------------------------------------------------
-// K in {16, 32}: threshold-filtered LDS queues + register bitonic merges.
-// ---------------------------------------------------------------------------------------------
-template <int K>
-struct KnnLds {
-    static constexpr int QS = 16;                       // queue slots per lane
-    static constexpr int TILE_BYTES = 2 * TILE * 16;    // double-buffered float4 tile
-    static constexpr int QUEUE_BYTES = QS * 64 * 8;     // [QS][64] (d, idx) pairs
-    static constexpr int MERGE_BYTES = K * 64 * 8;      // [K][64] keys, aliases tile+queue after the scan
-    static constexpr int SCAN_BYTES = TILE_BYTES + QUEUE_BYTES;
-    static constexpr int WAVE_BYTES = SCAN_BYTES > MERGE_BYTES ? SCAN_BYTES : MERGE_BYTES;
-};
+template <int MODE, int SPLIT>
+__global__ __launch_bounds__(64 * SPLIT) void knn_len_small_kernel(int q, int n, int kout, const float *__restrict__ query,
+                                                                   const float *__restrict__ ref, const int *__restrict__ qlen,
+                                                                   const int *__restrict__ rlen, int *__restrict__ idx,
+                                                                   float *__restrict__ dist) {
+    __shared__ float4 tiles[SPLIT][2][TILE];
+    __shared__ u64 mrg[SPLIT][4][64];
+    knn_small_body<MODE, SPLIT, true>(tiles, mrg, q, n, kout, query, ref, qlen, rlen, idx, dist);
+}
 
 template <int K, int MODE, int SPLIT>
 __global__ __launch_bounds__(64 * SPLIT) void knn_queue_kernel(int q, int n, int kout, const float *__restrict__ query,
                                                                const float *__restrict__ ref, int *__restrict__ idx,
                                                                float *__restrict__ dist) {
-    using L = KnnLds<K>;
-    constexpr int QS = L::QS;
-    constexpr int CHK = 4;  // refs between queue-full checks
     extern __shared__ float4 smem_f4[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    char *wbase = reinterpret_cast<char *>(smem_f4) + (size_t)wave * L::WAVE_BYTES;
-    float4(*tile)[TILE] = reinterpret_cast<float4(*)[TILE]>(wbase);
-    uint2(*queue)[64] = reinterpret_cast<uint2(*)[64]>(wbase + L::TILE_BYTES);
-
-    const int b = blockIdx.y;
-    const int qi = blockIdx.x * 64 + lane;
-    const bool live = qi < q;
-    const float *qp = query + ((size_t)b * q + (live ? qi : 0)) * 3;
-    const float qx = qp[0], qy = qp[1], qz = qp[2];
-    const float qn = mcp_sqnorm3(qx, qy, qz);
-    ref += (size_t)b * n * 3;
-
-    const int ntiles = (n + TILE - 1) / TILE;
-    const int t0 = (int)((long long)ntiles * wave / SPLIT), t1 = (int)((long long)ntiles * (wave + 1) / SPLIT);
-
-    u64 a[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) a[j] = KEY_INF;
-    float tau = INFINITY;
-    int cnt = 0;
-
-    auto flush = [&]() {
-        mcp_flush_queue<K, QS>(a, queue, lane, cnt);
-        tau = mcp_tau_of(a[K - 1]);
-        cnt = 0;
-    };
-
-    if (t0 < t1) {
-#pragma unroll
-        for (int u = 0; u < TILE / 64; ++u) tile[0][lane + 64 * u] = load_ref<MODE>(ref, t0 * TILE + lane + 64 * u, n);
-    }
-    for (int t = t0; t < t1; ++t) {
-        const int cur = (t - t0) & 1;
-        float4 nxt[TILE / 64];
-        if (t + 1 < t1) {
-#pragma unroll
-            for (int u = 0; u < TILE / 64; ++u) nxt[u] = load_ref<MODE>(ref, (t + 1) * TILE + lane + 64 * u, n);
-        }
-        __builtin_amdgcn_wave_barrier();
-        const int base = t * TILE;
-        // software pipeline over groups of CHK references: the next group's float4s are in flight while this
-        // group's distances and queue pushes run (the compiler will not hoist LDS reads above the queue writes)
-        float4 rc[CHK];
-#pragma unroll
-        for (int u = 0; u < CHK; ++u) rc[u] = tile[cur][u];
-        for (int r0 = 0; r0 < TILE; r0 += CHK) {
-            float4 rn[CHK];
-            const int rnext = r0 + CHK < TILE ? r0 + CHK : r0;  // last group re-reads itself (harmless)
-#pragma unroll
-            for (int u = 0; u < CHK; ++u) rn[u] = tile[cur][rnext + u];
-            float d[CHK];
-#pragma unroll
-            for (int u = 0; u < CHK; ++u) d[u] = pair_dist<MODE>(qx, qy, qz, qn, rc[u]);
-#pragma unroll
-            for (int u = 0; u < CHK; ++u) {
-                if (d[u] < tau) {
-                    queue[cnt][lane] = make_uint2(__float_as_uint(d[u]), (uint32_t)(base + r0 + u));
-                    ++cnt;
-                }
-            }
-            if (__builtin_amdgcn_ballot_w64(cnt > QS - CHK)) flush();
-#pragma unroll
-            for (int u = 0; u < CHK; ++u) rc[u] = rn[u];
-        }
-        if (t + 1 < t1) {
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int u = 0; u < TILE / 64; ++u) tile[cur ^ 1][lane + 64 * u] = nxt[u];
-        }
-    }
-    flush();
-
-    if (SPLIT > 1) {
-        __syncthreads();  // every wave is done with its tile/queue region before it is reused for keys
-        u64(*mrg)[64] = reinterpret_cast<u64(*)[64]>(wbase);
-#pragma unroll
-        for (int j = 0; j < K; ++j) mrg[j][lane] = a[j];
-        __syncthreads();
-        if (wave != 0) return;
-        for (int w = 1; w < SPLIT; ++w) {
-            u64(*om)[64] = reinterpret_cast<u64(*)[64]>(reinterpret_cast<char *>(smem_f4) + (size_t)w * L::WAVE_BYTES);
-            u64 o[K];
-#pragma unroll
-            for (int j = 0; j < K; ++j) o[j] = om[j][lane];
-            mcp_merge_sorted<K, K>(a, o);
-        }
-    }
-    if (!live) return;
-    int *oi = idx + ((size_t)b * q + qi) * kout;
-    float *od = dist ? dist + ((size_t)b * q + qi) * kout : nullptr;
-    mcp_store_list<K>(a, kout, oi, od);
+    knn_queue_body<K, MODE, SPLIT, false>(smem_f4, q, n, kout, query, ref, nullptr, nullptr, idx, dist);
+}
+template <int K, int MODE, int SPLIT>
+__global__ __launch_bounds__(64 * SPLIT) void knn_len_queue_kernel(int q, int n, int kout, const float *__restrict__ query,
+                                                                   const float *__restrict__ ref, const int *__restrict__ qlen,
+                                                                   const int *__restrict__ rlen, int *__restrict__ idx,
+                                                                   float *__restrict__ dist) {
+    extern __shared__ float4 smem_f4[];
+    knn_queue_body<K, MODE, SPLIT, true>(smem_f4, q, n, kout, query, ref, qlen, rlen, idx, dist);
 }
 
 // Chamfer helper: nearest squared distance from every x to the set y (direct form).
@@ -275,6 +80,8 @@ __global__ __launch_bounds__(256) void nn1_kernel(int n, int m, const float *__r
     if (live) out[(size_t)b * n + p] = best;
 }
 
+// The split comes from the PADDED sizes: the host does not know the lengths (reading them would be a synchronisation).  A short
+// element leaves some of its SPLIT waves without a tile; they idle through the merge.
 int pick_split(int b, int q, int n) {
     // aim for >= 2 waves per SIMD (1024 SIMDs) while keeping at least two 64-reference tiles per wave.  (The rule used to keep
     // two tiles per wave: the N = 512 / 1024 searches of the lower pyramid levels then ran 384-768 waves of 512 sequential
@@ -286,37 +93,60 @@ int pick_split(int b, int q, int n) {
     return split;
 }
 
-template <int MODE, int SPLIT>
-int launch_small(int b, int q, int n, int k, const float *query, const float *ref, int *idx, float *dist, hipStream_t s) {
-    hipLaunchKernelGGL((knn_small_kernel<MODE, SPLIT>), dim3(mcp_divup(q, 64), b), dim3(64 * SPLIT), 0, s, q, n, k, query, ref, idx,
-                       dist);
+struct Args {
+    int b, q, n, k;
+    const float *query, *ref;
+    const int *qlen, *rlen;  // LEN only
+    int *idx;
+    float *dist;
+    hipStream_t s;
+};
+
+// one launch of either family: the plain kernels take no lengths
+template <bool LEN, typename Plain, typename Len>
+int launch(Plain plain, Len len, int split, size_t lds, const Args &a) {
+    const dim3 grid(mcp_divup(a.q, 64), a.b), block(64 * split);
+    if constexpr (LEN) hipLaunchKernelGGL(len, grid, block, lds, a.s, a.q, a.n, a.k, a.query, a.ref, a.qlen, a.rlen, a.idx, a.dist);
+    else hipLaunchKernelGGL(plain, grid, block, lds, a.s, a.q, a.n, a.k, a.query, a.ref, a.idx, a.dist);
     return mcp_launch_status();
 }
-template <int K, int MODE, int SPLIT>
-int launch_queue(int b, int q, int n, int k, const float *query, const float *ref, int *idx, float *dist, hipStream_t s) {
-    const size_t lds = (size_t)KnnLds<K>::WAVE_BYTES * SPLIT;
-    auto kern = knn_queue_kernel<K, MODE, SPLIT>;
-    static McpPerDeviceOnce attr_once;
+template <int MODE, int SPLIT, bool LEN>
+int launch_small(const Args &a) {
+    return launch<LEN>(knn_small_kernel<MODE, SPLIT>, knn_len_small_kernel<MODE, SPLIT>, SPLIT, 0, a);
+}
+template <int K, int MODE, int SPLIT, bool LEN>
+int launch_queue(const Args &a) {
+    constexpr auto plain = knn_queue_kernel<K, MODE, SPLIT>;
+    constexpr auto len = knn_len_queue_kernel<K, MODE, SPLIT>;
+    static McpPerDeviceOnce attr_once;  // one per instantiation, that is per kernel symbol
     if (attr_once.need()) {
-        { const hipError_t attr_e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); if (attr_e_ != hipSuccess) return (int)attr_e_; }
+        const void *kern = LEN ? reinterpret_cast<const void *>(len) : reinterpret_cast<const void *>(plain);
+        const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return (int)e;
         attr_once.done();
     }
-    hipLaunchKernelGGL(kern, dim3(mcp_divup(q, 64), b), dim3(64 * SPLIT), lds, s, q, n, k, query, ref, idx, dist);
-    return mcp_launch_status();
+    return launch<LEN>(plain, len, SPLIT, (size_t)KnnLds<K>::WAVE_BYTES * SPLIT, a);
 }
-template <int MODE, int SPLIT>
-int dispatch_k(int b, int q, int n, int k, const float *query, const float *ref, int *idx, float *dist, hipStream_t s) {
-    if (k <= 4) return launch_small<MODE, SPLIT>(b, q, n, k, query, ref, idx, dist, s);
-    if (k <= 16) return launch_queue<16, MODE, SPLIT>(b, q, n, k, query, ref, idx, dist, s);
-    return launch_queue<32, MODE, SPLIT>(b, q, n, k, query, ref, idx, dist, s);
+template <int MODE, int SPLIT, bool LEN>
+int dispatch_k(const Args &a) {
+    if (a.k <= 4) return launch_small<MODE, SPLIT, LEN>(a);
+    if (a.k <= 16) return launch_queue<16, MODE, SPLIT, LEN>(a);
+    return launch_queue<32, MODE, SPLIT, LEN>(a);
 }
-template <int MODE>
-int dispatch_split(int split, int b, int q, int n, int k, const float *query, const float *ref, int *idx, float *dist,
-                   hipStream_t s) {
-    if (split == 1) return dispatch_k<MODE, 1>(b, q, n, k, query, ref, idx, dist, s);
-    if (split == 2) return dispatch_k<MODE, 2>(b, q, n, k, query, ref, idx, dist, s);
-    if (split == 4) return dispatch_k<MODE, 4>(b, q, n, k, query, ref, idx, dist, s);
-    return dispatch_k<MODE, 8>(b, q, n, k, query, ref, idx, dist, s);
+template <int MODE, bool LEN>
+int dispatch_split(const Args &a) {
+    const int split = pick_split(a.b, a.q, a.n);
+    if (split == 1) return dispatch_k<MODE, 1, LEN>(a);
+    if (split == 2) return dispatch_k<MODE, 2, LEN>(a);
+    if (split == 4) return dispatch_k<MODE, 4, LEN>(a);
+    return dispatch_k<MODE, 8, LEN>(a);
+}
+template <bool LEN>
+int search(int dist_form, const Args &a) {
+    mcp_prof_begin(MCP_KERNEL_KNN, a.s);
+    const int rc = dist_form == MCP_DIST_EXPANSION ? dispatch_split<MCP_DIST_EXPANSION, LEN>(a) : dispatch_split<MCP_DIST_DIRECT, LEN>(a);
+    mcp_prof_end(MCP_KERNEL_KNN, a.s);
+    return rc;
 }
 
 }  // namespace
@@ -326,13 +156,16 @@ MCP_EXPORT int mcp_knn(int b, int q, int n, int k, int dist_form, const float *q
     MCP_CHECK_ARGS(b > 0 && q > 0 && n > 0 && k > 0 && query && ref && idx);
     MCP_CHECK_ARGS(dist_form == MCP_DIST_EXPANSION || dist_form == MCP_DIST_DIRECT);
     if (k > 32) return MCP_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    const int split = pick_split(b, q, n);
-    mcp_prof_begin(MCP_KERNEL_KNN, s);
-    const int rc = dist_form == MCP_DIST_EXPANSION ? dispatch_split<MCP_DIST_EXPANSION>(split, b, q, n, k, query, ref, idx, dist, s)
-                                                   : dispatch_split<MCP_DIST_DIRECT>(split, b, q, n, k, query, ref, idx, dist, s);
-    mcp_prof_end(MCP_KERNEL_KNN, s);
-    return rc;
+    return search<false>(dist_form, Args{b, q, n, k, query, ref, nullptr, nullptr, idx, dist, (hipStream_t)stream});
+}
+
+MCP_EXPORT int mcp_knn_lengths(int b, int q, int n, int k, int dist_form, const float *query, const float *ref, const int *qlen,
+                               const int *rlen, int *idx, float *dist, mcp_stream_t stream) {
+    if (!qlen && !rlen) return mcp_knn(b, q, n, k, dist_form, query, ref, idx, dist, stream);  // the same launch, the same bits
+    MCP_CHECK_ARGS(b > 0 && q > 0 && n > 0 && k > 0 && query && ref && idx);
+    MCP_CHECK_ARGS(dist_form == MCP_DIST_EXPANSION || dist_form == MCP_DIST_DIRECT);
+    if (k > 32) return MCP_ERR_UNSUPPORTED;
+    return search<true>(dist_form, Args{b, q, n, k, query, ref, qlen, rlen, idx, dist, (hipStream_t)stream});
 }
 
 MCP_EXPORT int mcp_chamfer_nn(int b, int n, int m, const float *x, const float *y, float *dxy, float *dyx, mcp_stream_t stream) {
@@ -341,4 +174,14 @@ MCP_EXPORT int mcp_chamfer_nn(int b, int n, int m, const float *x, const float *
     hipLaunchKernelGGL(nn1_kernel, dim3(mcp_divup(n, 256), b), dim3(256), 0, s, n, m, x, y, dxy);
     hipLaunchKernelGGL(nn1_kernel, dim3(mcp_divup(m, 256), b), dim3(256), 0, s, m, n, y, x, dyx);
     return mcp_launch_status();
+}
+
+MCP_EXPORT int mcp_chamfer_nn_lengths(int b, int n, int m, const float *x, const float *y, const int *xlen, const int *ylen, float *dxy,
+                                      float *dyx, mcp_stream_t stream) {
+    MCP_CHECK_ARGS(b > 0 && n > 0 && m > 0 && x && y && dxy && dyx);
+    if (!xlen && !ylen) return mcp_chamfer_nn(b, n, m, x, y, dxy, dyx, stream);
+    hipStream_t s = (hipStream_t)stream;
+    const int rc = search<true>(MCP_DIST_DIRECT, Args{b, n, m, 1, x, y, xlen, ylen, nullptr, dxy, s});
+    if (rc) return rc;
+    return search<true>(MCP_DIST_DIRECT, Args{b, m, n, 1, y, x, ylen, xlen, nullptr, dyx, s});
 }

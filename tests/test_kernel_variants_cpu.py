@@ -43,7 +43,7 @@ def emitted_kernels():
 
 
 def test_expected_kernel_mirrors_the_dispatch_rules():
-    # spot checks of the C conditions the mirror encodes (linear.hip:415-435, :554; mlp.hip:214-220; attention.hip:545)
+    # spot checks of the C conditions the mirror encodes (linear.hip:415-435, :554; mlp.hip:214-220; attention_wide_fwd.h: wide_keys_split)
     e = kv.expected_kernel
     assert e("linear", rows=131072, ks=(256,), n=32) == "linear_kernel<1, 4, 8>"
     assert e("linear", rows=131071, ks=(256,), n=32) == "linear_kernel<1, 4, 4>"

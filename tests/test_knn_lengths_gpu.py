@@ -1,4 +1,4 @@
-"""The length-aware exhaustive KNN search (mcp_knn_lengths, csrc/knn_lengths.hip) against the CPU oracle run on every element's
+"""The length-aware exhaustive KNN search (mcp_knn_lengths, csrc/knn.hip) against the CPU oracle run on every element's
 valid prefixes on their own.  The padding is hostile: padded reference rows are copies of live query points (an unmasked kernel
 returns them at distance 0) and padded query rows hold 1e30; a second filling (NaN / -5e29) must not move a single output bit."""
 import ctypes

@@ -219,7 +219,11 @@ def test_three_nn_and_interpolate(n, m):
 
 @pytest.mark.parametrize("q,n,k,mode", [(8192, 8192, 32, 0), (2048, 8192, 32, 0), (2048, 2048, 16, 0), (2048, 2048, 16, 1),
                                         (8192, 2048, 3, 0), (512, 256, 32, 0), (256, 64, 32, 0), (300, 1000, 7, 1), (64, 20, 32, 0),
-                                        (1000, 3000, 1, 1), (70, 5000, 16, 0)])
+                                        (1000, 3000, 1, 1), (70, 5000, 16, 0)] +
+                         # every family of the exhaustive search (K <= 4, <= 16, <= 32) at every SPLIT: with b = 2 and q = 70 (a partial
+                         # wave) n = 60 / 150 / 300 / 500 is 1 / 3 / 5 / 8 reference tiles, which pick_split turns into SPLIT 1 / 2 / 4 / 8;
+                         # both distance forms in every family and at every SPLIT
+                         [(70, n, k, (i + j) & 1) for j, k in enumerate((3, 16, 32)) for i, n in enumerate((60, 150, 300, 500))])
 def test_knn_bit_exact(q, n, k, mode):
     b = 2
     query, ref = cloud(31 + q, b, q), cloud(32 + n, b, n)
