@@ -618,6 +618,28 @@ int mcp_emd_keep(int b, int n, int m, const float *xyz1, const float *xyz2, floa
 int mcp_emd_grad(int b, int n, int m, const float *grad_cost, const float *xyz1, const float *xyz2, const float *levels, float *grad1,
                  float *grad2, mcp_stream_t stream);
 
+/* mcp_emd / mcp_emd_keep / mcp_emd_grad on a padded batch of clouds of different sizes: element bb is the metric of its two
+ * prefixes xyz1[bb, 0 .. len1[bb]-1] and xyz2[bb, 0 .. len2[bb]-1].  len1, len2: (B) int32 DEVICE arrays, read by the kernels (no
+ * synchronisation) and clamped there to [0,N] / [0,M]; either may be NULL = every row of that side valid, and with both NULL the
+ * call IS mcp_emd / mcp_emd_keep / mcp_emd_grad (same launches, same bits).  Layouts keep the padded strides: xyz1 (B,N,3),
+ * xyz2 (B,M,3), match (B,M,N), workspace B*(3N+2M) floats, levels (B,10,N+M), grad1 (B,N,3), grad2 (B,M,3).
+ *   cost[bb]: bit for bit what mcp_emd(1, len1[bb], len2[bb], ...) returns on contiguous copies of the two prefixes (the mass
+ *             ratio multiL / multiR of emd_kernel.cu:32-38 is the integer division of the element's own counts);
+ *   match:    block [0..len2[bb]) x [0..len1[bb]) of match[bb] as that call writes it, exact zeros elsewhere;
+ *   levels:   the live entries of each level's ratios; entries beyond a length are left unwritten and never read;
+ *   grad1/2:  rows below the lengths bit for bit mcp_emd_grad's on the prefixes (same wave slices, same wave-order sum); rows at
+ *             or beyond a length are exact zeros;
+ *   an element with an empty side (len1[bb] == 0 or len2[bb] == 0): cost 0, match 0, gradients 0, nothing of it is loaded.
+ * Rows beyond a length are never read: their contents influence no output bit.  The launches are those of the length-free calls
+ * (grids over the padded N / M); a workgroup whose rows are all padding returns at once.  Errors as mcp_emd / mcp_emd_keep /
+ * mcp_emd_grad (nothing is launched). */
+int mcp_emd_lengths(int b, int n, int m, const float *xyz1, const float *xyz2, const int *len1, const int *len2, float *match,
+                    float *cost, float *workspace, mcp_stream_t stream);
+int mcp_emd_keep_lengths(int b, int n, int m, const float *xyz1, const float *xyz2, const int *len1, const int *len2, float *cost,
+                         float *levels, float *workspace, mcp_stream_t stream);
+int mcp_emd_grad_lengths(int b, int n, int m, const float *grad_cost, const float *xyz1, const float *xyz2, const int *len1,
+                         const int *len2, const float *levels, float *grad1, float *grad2, mcp_stream_t stream);
+
 /* emd_cuda.matchcost_forward / matchcost_backward on a caller's match (B,M,N) (emd_kernel.cu:204-247, matchcostgrad1/2).
  * mcp_matchcost: cost[b] = sum_{l,k} match[l][k] |xyz2[l]-xyz1[k]|^2; one workgroup per batch element, lane t sums
  *   k = t, t+1024, ... each over ascending l (float products, double sums), then a fixed-shape tree over the 1024 lanes.

@@ -117,6 +117,9 @@ SIGNATURES = {
     "mcp_emd_levels_floats": [_i, _i, _i],
     "mcp_emd_keep": [_i, _i, _i, _p, _p, _p, _p, _p, _p],
     "mcp_emd_grad": [_i, _i, _i, _p, _p, _p, _p, _p, _p, _p],
+    "mcp_emd_lengths": [_i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p],
+    "mcp_emd_keep_lengths": [_i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p],
+    "mcp_emd_grad_lengths": [_i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "mcp_matchcost": [_i, _i, _i, _p, _p, _p, _p, _p],
     "mcp_matchcost_grad": [_i, _i, _i, _p, _p, _p, _p, _p, _p, _p],
     "mcp_prof_enable": [_i],

@@ -11,7 +11,12 @@
 // A workgroup is eight waves over the same 64 lane points; wave w takes entries [64w, 64w+64) of every 512-entry tile, and
 // the eight partial sums are added in wave order at the end (fixed order, no atomics: bit-reproducible).  A level whose
 // argument is below -128 for every lane of the wave is skipped: its __expf, and so its share of the match, is exactly 0.
+//
+// emd_grad_kernel is stated once with a compile-time LEN (emd_lengths.h).  LEN == true (mcp_emd_grad_lengths) bounds the lane
+// points and the streamed tiles by the element's two lengths -- the same wave slices [64w, 64w+64) of every 512-entry tile and
+// the same wave-order sum as the plain kernel on the prefixes -- and writes exact zeros to the rows beyond a length.
 #include "common.h"
+#include "emd_lengths.h"
 
 namespace {
 
@@ -37,14 +42,26 @@ struct alignas(16) GradPt {
 };
 
 // SIDE 1: lanes = xyz1 (grad1), streamed = xyz2 with ratioR.  SIDE 2: lanes = xyz2 (grad2), streamed = xyz1 with ratioL.
-template <int SIDE>
+template <int SIDE, bool LEN>
 __global__ __launch_bounds__(GBLK) void emd_grad_kernel(Levels lv, int n, int m, const float *__restrict__ grad_cost,
                                                        const float *__restrict__ xyz1, const float *__restrict__ xyz2,
-                                                       const float *__restrict__ levels, float *__restrict__ grad) {
+                                                       const float *__restrict__ levels, float *__restrict__ grad,
+                                                       const int *__restrict__ len1, const int *__restrict__ len2) {
     __shared__ GradPt tile[GTILE];
     __shared__ float part[WAVES][64][3];
     const int b = blockIdx.y;
-    const int na = SIDE == 1 ? n : m, nb = SIDE == 1 ? m : n;
+    const int na = SIDE == 1 ? n : m;
+    int nl, ml;
+    emd_counts<LEN>(len1, len2, b, n, m, nl, ml);
+    const int nal = SIDE == 1 ? nl : ml, nb = SIDE == 1 ? ml : nl;  // valid lane points, valid streamed points
+    if (LEN && (int)blockIdx.x * 64 >= nal) {  // workgroup-uniform: nothing but padding here
+        const int r = blockIdx.x * 64 + (int)threadIdx.x;
+        if (threadIdx.x < 64 && r < na) {
+            float *o = grad + ((size_t)b * na + r) * 3;
+            o[0] = o[1] = o[2] = 0.f;
+        }
+        return;
+    }
     const int offa = SIDE == 1 ? 0 : n, offb = SIDE == 1 ? n : 0;
     const size_t lstride = (size_t)n + m;
     const float *pa = SIDE == 1 ? xyz1 + (size_t)b * n * 3 : xyz2 + (size_t)b * m * 3;
@@ -52,8 +69,8 @@ __global__ __launch_bounds__(GBLK) void emd_grad_kernel(Levels lv, int n, int m,
     const float *lev = levels + (size_t)b * NLEV * lstride;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int i = blockIdx.x * 64 + lane;
-    const bool live = i < na;
-    const int ii = live ? i : 0;  // dead lanes compute on point 0 and store nothing
+    const bool live = i < nal;
+    const int ii = live ? i : 0;  // dead lanes compute on point 0 (live: nal > 0 here) and store no sum
     const float xa = pa[(size_t)ii * 3], ya = pa[(size_t)ii * 3 + 1], za = pa[(size_t)ii * 3 + 2];
     float ra[NLEV];
 #pragma unroll
@@ -106,6 +123,10 @@ __global__ __launch_bounds__(GBLK) void emd_grad_kernel(Levels lv, int n, int m,
             for (int w = 1; w < WAVES; ++w) s += part[w][lane][c];
             o[c] = s * g2;
         }
+    }
+    if (LEN && wave == 0 && !live && i < na) {  // a padded row beside live ones
+        float *o = grad + ((size_t)b * na + i) * 3;
+        o[0] = o[1] = o[2] = 0.f;
     }
 }
 
@@ -219,16 +240,33 @@ __global__ __launch_bounds__(RBLK) void matchcost_grad2_kernel(int n, int m, con
 
 }  // namespace
 
+namespace {
+template <bool LEN>
+int emd_grad_run(int b, int n, int m, const float *grad_cost, const float *xyz1, const float *xyz2, const int *len1, const int *len2,
+                 const float *levels, float *grad1, float *grad2, hipStream_t s) {
+    const Levels lv = emd_levels();
+    if (grad1)
+        hipLaunchKernelGGL((emd_grad_kernel<1, LEN>), dim3(mcp_divup(n, 64), b), dim3(GBLK), 0, s, lv, n, m, grad_cost, xyz1, xyz2, levels,
+                           grad1, len1, len2);
+    if (grad2)
+        hipLaunchKernelGGL((emd_grad_kernel<2, LEN>), dim3(mcp_divup(m, 64), b), dim3(GBLK), 0, s, lv, n, m, grad_cost, xyz1, xyz2, levels,
+                           grad2, len1, len2);
+    return mcp_launch_status();
+}
+}  // namespace
+
 MCP_EXPORT int mcp_emd_grad(int b, int n, int m, const float *grad_cost, const float *xyz1, const float *xyz2, const float *levels,
                             float *grad1, float *grad2, mcp_stream_t stream) {
     MCP_CHECK_ARGS(b > 0 && n > 0 && m > 0 && grad_cost && xyz1 && xyz2 && levels);
-    hipStream_t s = (hipStream_t)stream;
-    const Levels lv = emd_levels();
-    if (grad1)
-        hipLaunchKernelGGL(emd_grad_kernel<1>, dim3(mcp_divup(n, 64), b), dim3(GBLK), 0, s, lv, n, m, grad_cost, xyz1, xyz2, levels, grad1);
-    if (grad2)
-        hipLaunchKernelGGL(emd_grad_kernel<2>, dim3(mcp_divup(m, 64), b), dim3(GBLK), 0, s, lv, n, m, grad_cost, xyz1, xyz2, levels, grad2);
-    return mcp_launch_status();
+    return emd_grad_run<false>(b, n, m, grad_cost, xyz1, xyz2, nullptr, nullptr, levels, grad1, grad2, (hipStream_t)stream);
+}
+
+MCP_EXPORT int mcp_emd_grad_lengths(int b, int n, int m, const float *grad_cost, const float *xyz1, const float *xyz2, const int *len1,
+                                    const int *len2, const float *levels, float *grad1, float *grad2, mcp_stream_t stream) {
+    MCP_CHECK_ARGS(b > 0 && n > 0 && m > 0 && grad_cost && xyz1 && xyz2 && levels);
+    if (!len1 && !len2)
+        return emd_grad_run<false>(b, n, m, grad_cost, xyz1, xyz2, nullptr, nullptr, levels, grad1, grad2, (hipStream_t)stream);
+    return emd_grad_run<true>(b, n, m, grad_cost, xyz1, xyz2, len1, len2, levels, grad1, grad2, (hipStream_t)stream);
 }
 
 MCP_EXPORT int mcp_matchcost(int b, int n, int m, const float *xyz1, const float *xyz2, const float *match, float *cost,

@@ -18,6 +18,7 @@ Whole ground-truth frames (NLDriveDataset(raw_gt=True)): the ground-truth scans 
 point count, and no random draw is made for them; collate_padded() zero-pads them per batch and returns the counts, and
 evaluate(raw_gt=True) hands those to the Chamfer distance as y_lengths -- the metric against the scan itself instead of against a
 random num_points subsample of it.  The inputs' draws come first in the reference's call order, so the inputs do not change.
+evaluate(raw_gt=True, raw_emd=True) reports the EMD the same way: emd.EMD(lengths2=) runs the auction on each scan's own points.
 """
 import os
 
@@ -109,11 +110,14 @@ def collate_padded(batch):
     return inputs, gts, lengths
 
 
-def evaluate(net, loader, device="cuda", raw_gt=False):
+def evaluate(net, loader, device="cuda", raw_gt=False, raw_emd=False):
     """The evaluation loop of test.py:71-135 in its intended form (one forward -> 3 frames; test.py:84 passes
     train=True by mistake): per-frame Chamfer distance and EMD means, forward time with device sync.
     raw_gt: the loader yields collate_padded batches of NLDriveDataset(raw_gt=True); the Chamfer distance is taken against the
-    whole ground-truth scans (y_lengths = their point counts) and "emd" is None (the EMD kernel has no lengths)."""
+    whole ground-truth scans (y_lengths = their point counts).  "emd" is None unless raw_emd is set too: then it holds the per-frame
+    means of EMD(out_j, gt_j, lengths2 = the scans' point counts), the auction between the prediction and each whole scan.
+    raw_emd has a meaning only together with raw_gt: without raw_gt the ground truth is already resampled to full clouds, the EMD is
+    always reported and raw_emd is ignored."""
     import time
 
     from . import emd as emd_mod, ops
@@ -133,9 +137,13 @@ def evaluate(net, loader, device="cuda", raw_gt=False):
             for j in range(3):
                 if raw_gt:
                     cd[j].append(float(ops.backend().chamfer(out[j].contiguous(), gt[j], y_lengths=sample[2][j])))
+                    if raw_emd:
+                        emd[j].append(float(emd_mod.EMD(out[j].permute(0, 2, 1).contiguous(), gt[j].permute(0, 2, 1).contiguous(),
+                                                        lengths2=sample[2][j])))
                     continue
                 cd[j].append(float(ops.backend().chamfer(out[j].contiguous(), gt[j])))
                 emd[j].append(float(emd_mod.EMD(out[j].permute(0, 2, 1).contiguous(), gt[j].permute(0, 2, 1).contiguous())))
     mean = lambda v: float(np.mean(v)) if v else float("nan")
-    return {"chamfer": [mean(c) for c in cd], "emd": None if raw_gt else [mean(e) for e in emd], "seconds_per_forward": mean(seconds),
+    with_emd = raw_emd or not raw_gt
+    return {"chamfer": [mean(c) for c in cd], "emd": [mean(e) for e in emd] if with_emd else None, "seconds_per_forward": mean(seconds),
             "sequences": len(loader.dataset)}

@@ -23,6 +23,13 @@ def chamfer_loss(pred, gt, rows=None, gt_lengths=None):
     return ops.backend().chamfer(pred.contiguous(), g)
 
 
+def emd_loss(pred, gt, gt_lengths=None):
+    """models/utils.py:223-235 (EMD) on chamfer_loss's layouts: pred (B,n,3), gt (B,3,n) -> mean over the batch of cost / n,
+    differentiable.  gt_lengths: per-sample point counts of a zero-padded ground truth, passed through as the EMD's lengths2."""
+    from . import emd
+    return emd.EMD(pred.transpose(1, 2), gt, lengths2=gt_lengths)
+
+
 def multiscale_loss(frames_lst_f, frames_lst_b, gt_frame, out_lst, gt):
     """losssum of train.py:135-160: final frames vs gt, the two full-resolution warps of both directions, and the level 1..3
     frames against the FPS-downsampled ground truth with weights alpha[1:].  The 33 Chamfer terms share 12 ground-truth clouds;
