@@ -69,7 +69,28 @@ int mcp_furthest_point_sampling_ws(int b, int n, int m, const float *xyz, float 
 int mcp_furthest_point_sampling_fresh(int b, int n, int m, const float *xyz, int *idx, float *sampled_xyz, void *workspace,
                                       size_t workspace_bytes, mcp_stream_t stream);
 
-/* gather_points_wrapper(b,c,n,npoints,points,idx,out)      sampling.cpp:11-22, sampling_gpu.cu:8-44
+/* A fresh sampling of a padded batch of clouds of different sizes (pytorch3d.ops.sample_farthest_points' lengths): len (B) is an
+ * int32 DEVICE array, read by the kernel with no host synchronisation and clamped there to [0, n].  len == NULL: the call IS
+ * mcp_furthest_point_sampling_fresh (same dispatch, same launch, same bits; workspace as described there).  Otherwise, per
+ * element bb with l = len[bb]:
+ *   l >= 1:  idx[bb, 0..m-1] is bit for bit what mcp_furthest_point_sampling returns for the cloud xyz[bb, :l] alone with the same
+ *            m and temp = 1e10, including m > l, where the reference simply keeps selecting; sampled_xyz[bb, j] = xyz[bb, idx[bb, j]]
+ *            for every j (sampled_xyz (b,m,3) is optional: NULL to skip);
+ *   l == 0:  the idx row is all 0 and the sampled_xyz row is all 0.0;
+ *   rows at or beyond l are never read: their contents reach no output bit.
+ * The tie rule needs no per-element block size: the reference's order for a cloud of ANY length is the one of its 1024-thread block,
+ * (bitrev_10(k mod 1024), k div 1024) (csrc/fps_lengths.hip).
+ * n <= 16384: one workgroup per element, points and running distances in registers, register slices and waves wholly beyond l
+ * skipped; no workspace (the query returns 0).  n > 16384: a streaming kernel bounded by l that keeps its running distances in the
+ * workspace: mcp_fps_lengths_workspace_bytes returns b*n*4, and the call returns MCP_ERR_UNSUPPORTED when workspace is NULL or
+ * smaller.  The buffer is only used during the call (stream-ordered) and needs no initialisation.
+ * Error codes as for the length-free calls (MCP_ERR_BAD_ARG: b <= 0, n <= 0, NULL xyz or idx; nothing is launched); m <= 0
+ * returns MCP_OK. */
+size_t mcp_fps_lengths_workspace_bytes(int b, int n, int m);
+int mcp_furthest_point_sampling_lengths(int b, int n, int m, const float *xyz, const int *len, int *idx, float *sampled_xyz,
+                                        void *workspace, size_t workspace_bytes, mcp_stream_t stream);
+
+/* gather_points_wrapper(b,c,n,npoints,points,idx,out)     sampling.cpp:11-22, sampling_gpu.cu:8-44
  * points (B,C,N), idx (B,npoints) -> out (B,C,npoints). */
 int mcp_gather_points(int b, int c, int n, int npoints, const float *points, const int *idx, float *out, mcp_stream_t stream);
 

@@ -83,6 +83,27 @@ def chamfer_distance(x, y, x_lengths=None, y_lengths=None):
     return ops.backend().chamfer(x.contiguous(), y.contiguous(), x_lengths=x_lengths, y_lengths=y_lengths), None
 
 
+def sample_farthest_points(points, lengths=None, K=50, random_start_point=False):
+    """pytorch3d.ops.sample_farthest_points: points (B,P,3), lengths (B,) -> (sampled (B,K,3), idx (B,K) int64).  Element b samples
+    min(lengths[b], K) points of points[b, :lengths[b]], starting from row 0; as pytorch3d pads, positions j >= lengths[b] hold index
+    -1 and coordinates 0.  One launch of the length-aware sampler (HipBackend.fps(lengths=)); rows beyond a length are never read.
+    Among points at equal distance the tie rule is this library's -- the reference sampling kernel's (csrc/fps.hip) -- not
+    pytorch3d's first-index rule, so on clouds with exact ties the selections can differ from pytorch3d's.  K is one integer;
+    random_start_point=True is not supported (the sampler is deterministic) and raises."""
+    if random_start_point:
+        raise NotImplementedError("sample_farthest_points: random_start_point=True is not supported; the start point is row 0")
+    points = points.contiguous()
+    B, P = points.shape[0], points.shape[1]
+    if lengths is None:
+        idx, sampled = ops.backend().fps(points, K, with_points=True)
+        lens = None
+    else:
+        lens = ops.lengths_tensor(lengths, B, P, points.device)
+        idx, sampled = ops.backend().fps(points, K, with_points=True, lengths=lens)
+    pad = torch.arange(K, device=points.device).view(1, K) >= (P if lens is None else lens.clamp(0, P).view(B, 1))
+    return sampled.masked_fill(pad.unsqueeze(-1), 0.0), idx.long().masked_fill(pad, -1)
+
+
 def install(patch_helpers=False):
     sys.modules["pointnet2_cuda"] = pointnet2_cuda
     sys.modules["emd_cuda"] = emd_cuda                                # models/EMD/emd.py:2
@@ -102,3 +123,5 @@ def install(patch_helpers=False):
                     setattr(mod, fn.__name__, fn)
             if hasattr(mod, "knn_points"):
                 mod.knn_points = knn_points
+            if hasattr(mod, "sample_farthest_points"):
+                mod.sample_farthest_points = sample_farthest_points

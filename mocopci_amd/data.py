@@ -19,6 +19,9 @@ point count, and no random draw is made for them; collate_padded() zero-pads the
 evaluate(raw_gt=True) hands those to the Chamfer distance as y_lengths -- the metric against the scan itself instead of against a
 random num_points subsample of it.  The inputs' draws come first in the reference's call order, so the inputs do not change.
 evaluate(raw_gt=True, raw_emd=True) reports the EMD the same way: emd.EMD(lengths2=) runs the auction on each scan's own points.
+evaluate(raw_gt=True, gt_points=K) first reduces every whole scan to at most K points by furthest point sampling on the GPU
+(downsample_padded: one launch of the length-aware sampler per frame): a deterministic, coverage-preserving subset instead of a
+random draw, and a bounded size for the auction.
 """
 import os
 
@@ -110,14 +113,32 @@ def collate_padded(batch):
     return inputs, gts, lengths
 
 
-def evaluate(net, loader, device="cuda", raw_gt=False, raw_emd=False):
+def downsample_padded(clouds, lengths, num_points):
+    """A padded batch reduced to at most num_points points per cloud by furthest point sampling: clouds (B,L,3) on the GPU,
+    lengths (B,) (forms: ops.lengths_tensor) -> (points (B,num_points,3), new_lengths (B,) int32 on the clouds' device) with
+    new_lengths = min(lengths, num_points).  Row j < new_lengths[b] is the j-th furthest-point sample of clouds[b, :lengths[b]]
+    (start point: row 0; a cloud shorter than num_points comes back whole, in sampling order); rows at or beyond the new length are
+    zero.  One launch of the length-aware sampler with its coordinate output; padded rows of `clouds` are never read."""
+    from . import ops
+    clouds = clouds.contiguous()
+    B, L = clouds.shape[0], clouds.shape[1]
+    lens = ops.lengths_tensor(lengths, B, L, clouds.device)
+    _, points = ops.backend().fps(clouds, num_points, with_points=True, lengths=lens)
+    new_lengths = lens.clamp(0, min(L, num_points))
+    pad = torch.arange(num_points, device=clouds.device).view(1, num_points) >= new_lengths.view(B, 1)
+    return points.masked_fill(pad.unsqueeze(-1), 0.0), new_lengths
+
+
+def evaluate(net, loader, device="cuda", raw_gt=False, raw_emd=False, gt_points=None):
     """The evaluation loop of test.py:71-135 in its intended form (one forward -> 3 frames; test.py:84 passes
     train=True by mistake): per-frame Chamfer distance and EMD means, forward time with device sync.
     raw_gt: the loader yields collate_padded batches of NLDriveDataset(raw_gt=True); the Chamfer distance is taken against the
     whole ground-truth scans (y_lengths = their point counts).  "emd" is None unless raw_emd is set too: then it holds the per-frame
     means of EMD(out_j, gt_j, lengths2 = the scans' point counts), the auction between the prediction and each whole scan.
     raw_emd has a meaning only together with raw_gt: without raw_gt the ground truth is already resampled to full clouds, the EMD is
-    always reported and raw_emd is ignored."""
+    always reported and raw_emd is ignored.
+    gt_points (with raw_gt): every whole scan is first reduced to at most gt_points points by downsample_padded (furthest point
+    sampling on the GPU), and the new point counts are the y_lengths / lengths2 of the two metrics.  None: the scans as they are."""
     import time
 
     from . import emd as emd_mod, ops
@@ -136,10 +157,13 @@ def evaluate(net, loader, device="cuda", raw_gt=False, raw_emd=False):
             seconds.append(time.perf_counter() - t0)
             for j in range(3):
                 if raw_gt:
-                    cd[j].append(float(ops.backend().chamfer(out[j].contiguous(), gt[j], y_lengths=sample[2][j])))
+                    scan, count = gt[j], sample[2][j]
+                    if gt_points is not None:
+                        scan, count = downsample_padded(scan, count, gt_points)
+                    cd[j].append(float(ops.backend().chamfer(out[j].contiguous(), scan, y_lengths=count)))
                     if raw_emd:
-                        emd[j].append(float(emd_mod.EMD(out[j].permute(0, 2, 1).contiguous(), gt[j].permute(0, 2, 1).contiguous(),
-                                                        lengths2=sample[2][j])))
+                        emd[j].append(float(emd_mod.EMD(out[j].permute(0, 2, 1).contiguous(), scan.permute(0, 2, 1).contiguous(),
+                                                        lengths2=count)))
                     continue
                 cd[j].append(float(ops.backend().chamfer(out[j].contiguous(), gt[j])))
                 emd[j].append(float(emd_mod.EMD(out[j].permute(0, 2, 1).contiguous(), gt[j].permute(0, 2, 1).contiguous())))

@@ -758,11 +758,24 @@ class _FusionFn(torch.autograd.Function):
 class HipBackend:
     name = "hip"
 
-    def fps(self, xyz, npoint, with_points=False):
+    def fps(self, xyz, npoint, with_points=False, lengths=None):
         """furthest_point_sample (pointnet2_utils.py:10-29): xyz (B,N,3) -> (B,npoint) int32.  with_points: also the sampled
-        coordinates (B,npoint,3) -- the index_points_gather that follows in every caller -- from the same launch."""
+        coordinates (B,npoint,3) -- the index_points_gather that follows in every caller -- from the same launch.
+        lengths (pytorch3d's sample_farthest_points(points, lengths, K); forms: lengths_tensor): element b is the cloud
+        xyz[b, :lengths[b]] alone -- its row is bit for bit the sampling of that slice (the reference keeps selecting when
+        npoint > lengths[b]), an empty element gives index 0 and coordinates 0.0, and rows at or beyond a length are never read.
+        Without lengths nothing changes."""
         xyz = xyz.detach()
         B, N, _ = xyz.shape
+        if lengths is not None:
+            lens = lengths_tensor(lengths, B, N, xyz.device)
+            out = torch.empty((B, npoint), dtype=torch.int32, device=xyz.device)
+            pts = torch.empty((B, npoint, 3), dtype=torch.float32, device=xyz.device) if with_points else None
+            need = _lib.load().mcp_fps_lengths_workspace_bytes(B, N, npoint)  # the streaming form's running distances (N > 16384), else 0
+            ws = torch.empty((need,), dtype=torch.uint8, device=xyz.device) if need else None
+            _call("mcp_furthest_point_sampling_lengths", xyz, B, N, npoint, _lib.fptr(xyz), _lib.iptr(lens), _lib.iptr(out),
+                  None if pts is None else _lib.fptr(pts), ws.data_ptr() if need else None, need)
+            return (out, pts) if with_points else out
         out = torch.empty((B, npoint), dtype=torch.int32, device=xyz.device)
         need = _lib.load().mcp_fps_workspace_bytes(B, N, npoint)  # scratch for the tiled kernel (16384 < N <= 65536), else 0
         ws = torch.empty((need,), dtype=torch.uint8, device=xyz.device) if need else None
