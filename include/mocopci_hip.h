@@ -196,6 +196,32 @@ int mcp_tile_boxes(int b, int n, const float *sorted_xyz, float *boxes, mcp_stre
 int mcp_knn_pruned(int b, int q, int n, int k, int dist_form, const float *query_sorted, const int *qperm,
                    const float *ref_sorted, const int *rperm, const float *boxes, int *idx, float *dist, mcp_stream_t stream);
 
+/* The pruned search on a padded batch of clouds of different sizes: the result of mcp_knn_lengths, bit for bit (live rows: the K
+ * smallest under (distance, original index) among references 0 .. rlen[bb]-1, ascending, the tail repeating the last valid entry
+ * if rlen[bb] < K, index 0 / distance 0 if rlen[bb] == 0; rows at or beyond qlen[bb]: index 0 / distance 0), visiting only the
+ * tiles the pruning keeps.  Lengths are (B) int32 DEVICE arrays, read and clamped to [0, N] (or [0, Q]) by the kernels; grids,
+ * strides and the boxes' ceil(N/tile) rows per element keep the padded sizes.  A NULL length means every row is valid, and with
+ * every length NULL each entry point IS its original above (same launch, same bits).  Same limits and error codes as the
+ * originals; an argument error launches nothing.  No row beyond a length -- of a cloud, a sorted cloud, a perm or the boxes --
+ * is ever read.
+ *   mcp_build_cloud_lengths:  N <= 16384.  sorted_xyz[bb, :len], perm[bb, :len] and boxes[bb, :ceil(len/tile)] are what
+ *                             mcp_build_cloud returns for xyz[bb, :len] on its own; beyond them perm[bb, s] = s and the
+ *                             coordinates and boxes are zero.
+ *   mcp_morton_codes_lengths: box (B,6) = (min xyz, max xyz) over each element's LIVE rows; codes[bb, :len] are mcp_morton_codes'
+ *                             for the prefix with that box, codes[bb, len:] = 0x7fffffff (above every live code), so a STABLE
+ *                             sort by code leaves the padding where it is: perm[bb, s] = s for s >= len, which the search
+ *                             relies on.
+ *   mcp_tile_boxes_lengths:   boxes over the first len rows of sorted_xyz; tiles beyond them are zero.
+ *   mcp_knn_pruned_lengths:   clouds as built by the entry points above with the same lengths (a cloud whose length is NULL
+ *                             here: by the plain ones).  A padded query's zeros go to the row of its sorted position. */
+int mcp_build_cloud_lengths(int b, int n, const float *xyz, const int *len, float *sorted_xyz, int *perm, float *boxes,
+                            mcp_stream_t stream);
+int mcp_morton_codes_lengths(int b, int n, const float *xyz, const float *box, const int *len, int *codes, mcp_stream_t stream);
+int mcp_tile_boxes_lengths(int b, int n, const float *sorted_xyz, const int *len, float *boxes, mcp_stream_t stream);
+int mcp_knn_pruned_lengths(int b, int q, int n, int k, int dist_form, const float *query_sorted, const int *qperm,
+                           const float *ref_sorted, const int *rperm, const float *boxes, const int *qlen, const int *rlen,
+                           int *idx, float *dist, mcp_stream_t stream);
+
 /* knn_point_cosine(nsample, xyz, new_xyz) (pointconv_util.py:111-153) on channel-last features:
  * qfeat (B,Q,C), rfeat (B,N,C) -> idx (B,Q,K) (and dist if non-NULL): the K smallest of
  * d = 1 - <q^,r^>, x^ = x / sqrt(sum x^2 + 1e-8), under the order (d, index), ascending.

@@ -42,6 +42,10 @@ SIGNATURES = {
     "mcp_morton_codes": [_i, _i, _p, _p, _p, _p],
     "mcp_tile_boxes": [_i, _i, _p, _p, _p],
     "mcp_knn_pruned": [_i] * 5 + [_p] * 8,
+    "mcp_build_cloud_lengths": [_i, _i, _p, _p, _p, _p, _p, _p],
+    "mcp_morton_codes_lengths": [_i, _i, _p, _p, _p, _p, _p],
+    "mcp_tile_boxes_lengths": [_i, _i, _p, _p, _p, _p],
+    "mcp_knn_pruned_lengths": [_i] * 5 + [_p] * 10,
     "mcp_knn_cosine": [_i] * 5 + [_p] * 6,
     "mcp_group_rows": [_i, _i, _i, _i, _p, _p, _p, _p],
     "mcp_interp3": [_i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p],

@@ -16,6 +16,12 @@
 //     longer visited in index order;
 //   * results are written to the query's original row (qperm).
 // At N=8192 a wave scans ~900 of the 8192 references (64-point tiles measured 5-7 % faster than 128/256).
+//
+// Per-cloud lengths (mcp_build_cloud_lengths, mcp_morton_codes_lengths, mcp_tile_boxes_lengths, mcp_knn_pruned_lengths): every kernel
+// below takes a compile-time LEN.  LEN == false is the kernel as it always was (no length is loaded; the model's inference and
+// training paths run only these).  LEN == true: element b's cloud is its first len[b] rows; the builders sort those rows alone and
+// leave the padding behind them in place, the search kernels take their live counts from the lengths and their strides from the
+// padded sizes, and the result is mcp_knn_lengths' (knn_scan.h), bit for bit.  No row beyond a length is read by any kernel.
 #include <stdlib.h>
 
 #include <rocprim/block/block_radix_sort.hpp>
@@ -42,6 +48,21 @@ __device__ __forceinline__ float wave_maxf(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
     return v;
+}
+
+// Per-cloud lengths (LEN == true in the kernels below; the search's result definition is knn_scan.h's): (B) int32 device arrays, one
+// wave-uniform load per workgroup, clamped to [0, full]; a null pointer means every row is valid.  Strides and grids keep the padded
+// sizes; only comparisons use the clamped value, and a row at or beyond it is never loaded.
+__device__ __forceinline__ int clamped_len(const int *__restrict__ len, int b, int full) {
+    if (!len) return full;
+    const int v = len[b];
+    return v < 0 ? 0 : (v > full ? full : v);
+}
+__device__ __forceinline__ void store_zero_row(int kout, int *oi, float *od) {
+    for (int j = 0; j < kout; ++j) {
+        oi[j] = 0;
+        if (od) od[j] = 0.f;
+    }
 }
 
 // ---- preprocessing kernels ------------------------------------------------------------------
@@ -132,19 +153,34 @@ __device__ __forceinline__ uint32_t cloud_key(const float *p, const float *bbox,
     return d;
 #endif
 }
-// Morton code (30 bits over three axes, or 20 over two: cloud_code) on the per-batch box [lo, hi] (box (B,6): lo xyz, hi xyz)
+// Morton code (30 bits over three axes, or 20 over two: cloud_code) on the per-batch box [lo, hi] (box (B,6): lo xyz, hi xyz).
+// LEN: the box is that of the element's live rows, the cell size comes from their number, and a padded row gets the code above every
+// live one (0x7fffffff) without being loaded -- a stable sort by code then leaves it where it is.
+template <bool LEN>
 __global__ __launch_bounds__(256) void morton_kernel(int n, const float *__restrict__ xyz, const float *__restrict__ box,
-                                                     int *__restrict__ codes) {
+                                                     const int *__restrict__ len, int *__restrict__ codes) {
     const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
+    const int nl = LEN ? clamped_len(len, b, n) : n;
+    if (LEN && i >= nl) {
+        codes[(size_t)b * n + i] = 0x7fffffff;
+        return;
+    }
     const float *bx = box + b * 6;
-    codes[(size_t)b * n + i] = (int)cloud_key<10>(xyz + ((size_t)b * n + i) * 3, bx, cloud_code(bx, n, 10, 10), 10);
+    codes[(size_t)b * n + i] = (int)cloud_key<10>(xyz + ((size_t)b * n + i) * 3, bx, cloud_code(bx, nl, 10, 10), 10);
 }
-// one wave per tile of PT sorted points: (lo xyz, hi xyz)
-__global__ __launch_bounds__(64) void tile_box_kernel(int n, int tiles, const float *__restrict__ sorted_xyz, float *__restrict__ boxes) {
+// one wave per tile of PT sorted points: (lo xyz, hi xyz).  LEN: over the live rows only; a tile beyond them gets a zero box.
+template <bool LEN>
+__global__ __launch_bounds__(64) void tile_box_kernel(int n, int tiles, const float *__restrict__ sorted_xyz, const int *__restrict__ len,
+                                                      float *__restrict__ boxes) {
     const int b = blockIdx.y, t = blockIdx.x, lane = threadIdx.x;
+    const int nl = LEN ? clamped_len(len, b, n) : n;
+    if (LEN && t * PT >= nl) {
+        if (lane < 6) boxes[((size_t)b * tiles + t) * 6 + lane] = 0.f;
+        return;
+    }
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int i = t * PT + lane; i < min(n, (t + 1) * PT); i += 64) {
+    for (int i = t * PT + lane; i < min(nl, (t + 1) * PT); i += 64) {
         const float *p = sorted_xyz + ((size_t)b * n + i) * 3;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
@@ -184,8 +220,12 @@ struct CloudSort {
     };
 };
 
-template <int IPT>
-__global__ __launch_bounds__(BT) void build_cloud_kernel(int n, int tiles, const float *__restrict__ xyz,
+// LEN: the cloud is the element's first len[b] rows.  The box, the cell size, the keys and the tile boxes come from those rows alone
+// and no other row is loaded, so sorted_xyz[:len], perm[:len] and boxes[:ceil(len / PT)] are what the builder returns for the prefix
+// on its own (the sort is stable: the same permutation whichever IPT the padded n selects).  Beyond the length the outputs are fixed
+// values: perm[s] = s (where the stable sort leaves the padding keys anyway), zero coordinates, zero boxes.
+template <int IPT, bool LEN>
+__global__ __launch_bounds__(BT) void build_cloud_kernel(int n, int tiles, const float *__restrict__ xyz, const int *__restrict__ len,
                                                          float *__restrict__ sorted_xyz, int *__restrict__ perm,
                                                          float *__restrict__ boxes) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long dyn[];
@@ -198,12 +238,21 @@ __global__ __launch_bounds__(BT) void build_cloud_kernel(int n, int tiles, const
     sorted_xyz += (size_t)b * n * 3;
     perm += (size_t)b * n;
     boxes += (size_t)b * tiles * 6;
+    const int nl = LEN ? clamped_len(len, b, n) : n;
+    if (LEN && nl == 0) {   // an empty element: the fixed values, before any load
+        for (int s = tid; s < n; s += BT) {
+            perm[s] = s;
+            sorted_xyz[(size_t)s * 3 + 0] = 0.f; sorted_xyz[(size_t)s * 3 + 1] = 0.f; sorted_xyz[(size_t)s * 3 + 2] = 0.f;
+        }
+        for (int c = tid; c < tiles * 6; c += BT) boxes[c] = 0.f;
+        return;
+    }
     // 1. bounding box of the cloud; thread t holds points t*IPT .. t*IPT+IPT-1 (kept in registers for the keys)
     float px[IPT], py[IPT], pz[IPT];
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
 #pragma unroll
     for (int u = 0; u < IPT; ++u) {
-        const int i = min(tid * IPT + u, n - 1);   // padding repeats the last point: no effect on the box
+        const int i = min(tid * IPT + u, nl - 1);   // padding repeats the last point: no effect on the box
         px[u] = xyz[(size_t)i * 3 + 0]; py[u] = xyz[(size_t)i * 3 + 1]; pz[u] = xyz[(size_t)i * 3 + 2];
         lo[0] = fminf(lo[0], px[u]); hi[0] = fmaxf(hi[0], px[u]);
         lo[1] = fminf(lo[1], py[u]); hi[1] = fmaxf(hi[1], py[u]);
@@ -224,13 +273,13 @@ __global__ __launch_bounds__(BT) void build_cloud_kernel(int n, int tiles, const
     __syncthreads();
     // 2. keys: isotropic cells over three axes or, for a cloud flatter than a tile is wide, over two (cloud_code); padding sorts
     //    last (the bit above the codes)
-    const CloudCode cc = cloud_code(bbox, n, CELL_BITS, CELL_BITS_2D);
+    const CloudCode cc = cloud_code(bbox, nl, CELL_BITS, CELL_BITS_2D);
     uint32_t keys[IPT], vals[IPT];
 #pragma unroll
     for (int u = 0; u < IPT; ++u) {
         const int i = tid * IPT + u;
         const float p[3] = {px[u], py[u], pz[u]};
-        keys[u] = i < n ? cloud_key<CELL_BITS_2D>(p, bbox, cc, CELL_BITS) : 1u << CODE_BITS;
+        keys[u] = i < nl ? cloud_key<CELL_BITS_2D>(p, bbox, cc, CELL_BITS) : 1u << CODE_BITS;
         vals[u] = (uint32_t)i;
     }
     // 3. stable radix sort of the (code, index) pairs over the code's bits and the padding bit: points of one cell stay in index order
@@ -241,7 +290,12 @@ __global__ __launch_bounds__(BT) void build_cloud_kernel(int n, int tiles, const
 #pragma unroll
     for (int u = 0; u < IPT; ++u) {
         const int s = tid * IPT + u;
-        if (s < n) {
+        if (LEN && s >= nl) {
+            if (s < n) {
+                perm[s] = s;
+                sorted_xyz[(size_t)s * 3 + 0] = 0.f; sorted_xyz[(size_t)s * 3 + 1] = 0.f; sorted_xyz[(size_t)s * 3 + 2] = 0.f;
+            }
+        } else if (s < n) {
             const int src = (int)vals[u];
             const float x = xyz[(size_t)src * 3 + 0], y = xyz[(size_t)src * 3 + 1], z = xyz[(size_t)src * 3 + 2];
             perm[s] = src;
@@ -266,20 +320,24 @@ __global__ __launch_bounds__(BT) void build_cloud_kernel(int n, int tiles, const
     const int t = tid / TPT;
     if ((tid & (TPT - 1)) == 0 && t < tiles) {
         float *o = boxes + (size_t)t * 6;
-        o[0] = tl[0]; o[1] = tl[1]; o[2] = tl[2]; o[3] = th[0]; o[4] = th[1]; o[5] = th[2];
+        if (LEN && t * PT >= nl) {
+            o[0] = 0.f; o[1] = 0.f; o[2] = 0.f; o[3] = 0.f; o[4] = 0.f; o[5] = 0.f;
+        } else {
+            o[0] = tl[0]; o[1] = tl[1]; o[2] = tl[2]; o[3] = th[0]; o[4] = th[1]; o[5] = th[2];
+        }
     }
 }
 
-template <int IPT>
-int launch_build_cloud(int b, int n, int tiles, const float *xyz, float *sorted_xyz, int *perm, float *boxes, hipStream_t s) {
-    auto kern = build_cloud_kernel<IPT>;
+template <int IPT, bool LEN>
+int launch_build_cloud(int b, int n, int tiles, const float *xyz, const int *len, float *sorted_xyz, int *perm, float *boxes, hipStream_t s) {
+    auto kern = build_cloud_kernel<IPT, LEN>;
     const size_t lds = 512 + sizeof(typename CloudSort<IPT>::Lds);
     static McpPerDeviceOnce attr_once;
     if (attr_once.need()) {
         { const hipError_t attr_e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); if (attr_e_ != hipSuccess) return (int)attr_e_; }
         attr_once.done();
     }
-    hipLaunchKernelGGL(kern, dim3(b), dim3(BT), lds, s, n, tiles, xyz, sorted_xyz, perm, boxes);
+    hipLaunchKernelGGL(kern, dim3(b), dim3(BT), lds, s, n, tiles, xyz, len, sorted_xyz, perm, boxes);
     return mcp_launch_status();
 }
 
@@ -449,11 +507,18 @@ __device__ unsigned long long g_walk_diag[16];
 #define WALK_STAMP(slot)
 #endif
 
-template <int K, int MODE, int TPL>
+// LEN (both search kernels): element b has ql live queries and rl live references, both at the head of their SORTED clouds (the
+// builders sort padding last and leave perm[s] = s there).  Every comparison below that decides what is live -- `live`, the tile
+// count, the tail mask of the last tile, "fewer than K references" -- uses ql / rl / ceil(rl / PT); every stride keeps q / n / tiles.
+// A wave with no live query, or an element with no reference, writes index 0 / distance 0 to its rows and returns before any load of
+// a coordinate or a box; dead lanes of a partial wave write their zeros before the walk.  A padded query's row is its own sorted position,
+// so no perm row beyond a length is read either.
+template <int K, int MODE, int TPL, bool LEN>
 __global__ __launch_bounds__(64) void knn_walk_kernel(int q, int n, int tiles, int kout, const float *__restrict__ query,
                                                       const int *__restrict__ qperm, const float *__restrict__ ref,
                                                       const int *__restrict__ rperm, const float *__restrict__ boxes,
-                                                      int *__restrict__ idx, float *__restrict__ dist, int vec_rows) {
+                                                      int *__restrict__ idx, float *__restrict__ dist, int vec_rows,
+                                                      const int *__restrict__ qlen, const int *__restrict__ rlen) {
     using C = WalkCfg<K>;
     constexpr int SUB = 4, QPW = 64 / SUB, RPL = PT / SUB, KS = C::KS, CL = C::CL, NET = C::NET, CHK = C::CHK, GAP = C::GAP, NQ = C::NQ;
     extern __shared__ float4 smem_f4[];
@@ -482,7 +547,19 @@ __global__ __launch_bounds__(64) void knn_walk_kernel(int q, int n, int tiles, i
     const int sub = lane % SUB;
     const int q0 = blockIdx.x * QPW;            // first query of the wave: always < q (grid is sized from q)
     const int qi = q0 + lane / SUB;
-    const bool live = qi < q;
+    const int ql = LEN ? clamped_len(qlen, b, q) : q, rl = LEN ? clamped_len(rlen, b, n) : n;
+    if (LEN && (q0 >= ql || rl == 0)) {         // wave-uniform: nothing but padding here, or nothing to search
+        if (sub == 0 && qi < q) {
+            const int row = qi < ql && qperm ? qperm[(size_t)b * q + qi] : qi;
+            store_zero_row(kout, idx + ((size_t)b * q + row) * kout, dist ? dist + ((size_t)b * q + row) * kout : nullptr);
+        }
+        return;
+    }
+    const bool live = qi < ql;
+    if (LEN && !live && sub == 0 && qi < q)     // dead lanes of a partial wave: their zeros now, nothing kept for the end
+        store_zero_row(kout, idx + ((size_t)b * q + qi) * kout, dist ? dist + ((size_t)b * q + qi) * kout : nullptr);
+    // a tile t holds a live reference: LEN ? t * PT < rl : t < tiles
+    auto live_tile = [&](int t) -> bool { return LEN ? t * PT < rl : t < tiles; };
     // dead lanes replicate the wave's first query so they do not inflate the query box
     const float *qp = query + ((size_t)b * q + (live ? qi : q0)) * 3;
     const float qx = qp[0], qy = qp[1], qz = qp[2];
@@ -501,7 +578,7 @@ __global__ __launch_bounds__(64) void knn_walk_kernel(int q, int n, int tiles, i
     for (int u = 0; u < TPL; ++u) {
         const int t = lane + 64 * u;
         lb[u] = INFINITY;
-        if (t < tiles) {
+        if (live_tile(t)) {
             const float *bx = boxes + t * 6;
             const float g0 = fmaxf(0.f, fmaxf(bx[0] - bh0, bl0 - bx[3]));
             const float g1 = fmaxf(0.f, fmaxf(bx[1] - bh1, bl1 - bx[4]));
@@ -672,7 +749,7 @@ __global__ __launch_bounds__(64) void knn_walk_kernel(int q, int n, int tiles, i
     static_assert(PT == 64, "one reference per lane and tile");
     auto fetch = [&](int t, TileRegs &g) {
         const int gi = t * PT + lane;
-        const bool ok = gi < n;
+        const bool ok = gi < rl;
         const int gg = ok ? gi : 0;
         const float x = ref[(size_t)gg * 3 + 0], y = ref[(size_t)gg * 3 + 1], z = ref[(size_t)gg * 3 + 2];
         g.pi = ok ? rperm[gg] : 0;
@@ -701,7 +778,7 @@ __global__ __launch_bounds__(64) void knn_walk_kernel(int q, int n, int tiles, i
 #pragma unroll
         for (int u = 0; u < TPL; ++u) {
             const int tt = lane + 64 * u;
-            const float *p = boxes + (tt < tiles ? tt : 0) * 6;
+            const float *p = boxes + (live_tile(tt) ? tt : 0) * 6;
 #pragma unroll
             for (int c = 0; c < 6; ++c) bx[u][c] = p[c];
             need[u] = false;
@@ -827,7 +904,7 @@ __global__ __launch_bounds__(64) void knn_walk_kernel(int q, int n, int tiles, i
     atomicAdd(&g_walk_diag[7], (unsigned long long)((wp - lane4) / SLOT));
 #endif
     quad_sort_low<NET>(v, sub);
-    if (n < K) {
+    if (rl < K) {
         // fewer references than list entries: the missing ranks repeat the last valid one (as mcp_store_list does)
         mcp_key last = __hiloint2double((int)0xFFF00000, 0);   // -inf: below every key
 #pragma unroll
@@ -869,40 +946,50 @@ __global__ __launch_bounds__(64) void knn_walk_kernel(int q, int n, int tiles, i
 #endif
 }
 
-template <int K, int MODE, int TPL>
-int launch_walk_tpl(int b, int q, int n, int tiles, int k, const float *query, const int *qperm, const float *ref, const int *rperm,
-                    const float *boxes, int *idx, float *dist, hipStream_t s) {
+// what a search launch takes besides its sizes (LEN == false: qlen / rlen are not read)
+struct SearchArgs {
+    const float *query;
+    const int *qperm;
+    const float *ref;
+    const int *rperm;
+    const float *boxes;
+    int *idx;
+    float *dist;
+    const int *qlen, *rlen;
+};
+
+template <int K, int MODE, int TPL, bool LEN>
+int launch_walk_tpl(int b, int q, int n, int tiles, int k, const SearchArgs &a, hipStream_t s) {
     const size_t lds = (size_t)WalkCfg<K>::WAVE_BYTES;
-    auto kern = knn_walk_kernel<K, MODE, TPL>;
+    auto kern = knn_walk_kernel<K, MODE, TPL, LEN>;
     static McpPerDeviceOnce attr_once;
     if (attr_once.need()) {  // lets the CU's whole 160 KB LDS count towards residency (default budget: 64 KB)
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return (int)e;
         attr_once.done();
     }
-    const int vec_rows = (k & 3) == 0 && (reinterpret_cast<uintptr_t>(idx) & 15) == 0 && (!dist || (reinterpret_cast<uintptr_t>(dist) & 15) == 0);
-    hipLaunchKernelGGL(kern, dim3(mcp_divup(q, 16), b), dim3(64), lds, s, q, n, tiles, k, query, qperm, ref, rperm, boxes, idx, dist, vec_rows);
+    const int vec_rows = (k & 3) == 0 && (reinterpret_cast<uintptr_t>(a.idx) & 15) == 0 && (!a.dist || (reinterpret_cast<uintptr_t>(a.dist) & 15) == 0);
+    hipLaunchKernelGGL(kern, dim3(mcp_divup(q, 16), b), dim3(64), lds, s, q, n, tiles, k, a.query, a.qperm, a.ref, a.rperm, a.boxes, a.idx, a.dist,
+                       vec_rows, a.qlen, a.rlen);
     return mcp_launch_status();
 }
 
-template <int K, int MODE>
-int launch_walk(int b, int q, int n, int tiles, int k, const float *query, const int *qperm, const float *ref, const int *rperm,
-                const float *boxes, int *idx, float *dist, hipStream_t s) {
+template <int K, int MODE, bool LEN>
+int launch_walk(int b, int q, int n, int tiles, int k, const SearchArgs &a, hipStream_t s) {
     // tile bounds held per lane: sized to the cloud so the per-visit argmin stays short
-    if (tiles <= 64) return launch_walk_tpl<K, MODE, 1>(b, q, n, tiles, k, query, qperm, ref, rperm, boxes, idx, dist, s);
-    if (tiles <= 128) return launch_walk_tpl<K, MODE, 2>(b, q, n, tiles, k, query, qperm, ref, rperm, boxes, idx, dist, s);
-    if (tiles <= 256) return launch_walk_tpl<K, MODE, 4>(b, q, n, tiles, k, query, qperm, ref, rperm, boxes, idx, dist, s);
-    return launch_walk_tpl<K, MODE, MAX_TPL>(b, q, n, tiles, k, query, qperm, ref, rperm, boxes, idx, dist, s);
+    if (tiles <= 64) return launch_walk_tpl<K, MODE, 1, LEN>(b, q, n, tiles, k, a, s);
+    if (tiles <= 128) return launch_walk_tpl<K, MODE, 2, LEN>(b, q, n, tiles, k, a, s);
+    if (tiles <= 256) return launch_walk_tpl<K, MODE, 4, LEN>(b, q, n, tiles, k, a, s);
+    return launch_walk_tpl<K, MODE, MAX_TPL, LEN>(b, q, n, tiles, k, a, s);
 }
 
-template <int MODE>
-int launch_walk_k(int b, int q, int n, int tiles, int k, const float *query, const int *qperm, const float *ref, const int *rperm,
-                  const float *boxes, int *idx, float *dist, hipStream_t s) {
+template <int MODE, bool LEN>
+int launch_walk_k(int b, int q, int n, int tiles, int k, const SearchArgs &a, hipStream_t s) {
 #if defined(MCP_AB) || defined(MCP_KNN_DIAG)   // the product sends K <= 16 to round 3's kernel (below)
-    if (k <= 4) return launch_walk<4, MODE>(b, q, n, tiles, k, query, qperm, ref, rperm, boxes, idx, dist, s);
-    if (k <= 16) return launch_walk<16, MODE>(b, q, n, tiles, k, query, qperm, ref, rperm, boxes, idx, dist, s);
+    if (k <= 4) return launch_walk<4, MODE, LEN>(b, q, n, tiles, k, a, s);
+    if (k <= 16) return launch_walk<16, MODE, LEN>(b, q, n, tiles, k, a, s);
 #endif
-    return launch_walk<32, MODE>(b, q, n, tiles, k, query, qperm, ref, rperm, boxes, idx, dist, s);
+    return launch_walk<32, MODE, LEN>(b, q, n, tiles, k, a, s);
 }
 
 // ---- round 3's search kernel (per-lane sorted K-lists + threshold queue): the searches with K <= 16 ----------------------------
@@ -959,11 +1046,12 @@ __device__ unsigned long long g_knn_phase[8];  // cycles: 0 setup 1 walk 2 stagi
 #define OLD_STAMP(slot)
 #endif
 
-template <int K, int MODE, int SUB, int TPL>
+template <int K, int MODE, int SUB, int TPL, bool LEN>
 __global__ __launch_bounds__(64) void knn_pruned_kernel(int q, int n, int tiles, int kout, const float *__restrict__ query,
                                                         const int *__restrict__ qperm, const float *__restrict__ ref,
                                                         const int *__restrict__ rperm, const float *__restrict__ boxes,
-                                                        int *__restrict__ idx, float *__restrict__ dist) {
+                                                        int *__restrict__ idx, float *__restrict__ dist,
+                                                        const int *__restrict__ qlen, const int *__restrict__ rlen) {
     using L = PrunedLds<K>;
     constexpr int QS = L::QS, CHK = 4, QPW = 64 / SUB, RPL = PT / SUB;  // queries per wave, references per lane per tile
     extern __shared__ float4 smem_f4[];
@@ -982,7 +1070,19 @@ __global__ __launch_bounds__(64) void knn_pruned_kernel(int q, int n, int tiles,
     const int sub = lane % SUB;
     const int q0 = blockIdx.x * QPW;            // first query of the wave: always < q (grid is sized from q)
     const int qi = q0 + lane / SUB;
-    const bool live = qi < q;
+    const int ql = LEN ? clamped_len(qlen, b, q) : q, rl = LEN ? clamped_len(rlen, b, n) : n;
+    if (LEN && (q0 >= ql || rl == 0)) {         // wave-uniform: nothing but padding here, or nothing to search
+        if (sub == 0 && qi < q) {
+            const int row = qi < ql && qperm ? qperm[(size_t)b * q + qi] : qi;
+            store_zero_row(kout, idx + ((size_t)b * q + row) * kout, dist ? dist + ((size_t)b * q + row) * kout : nullptr);
+        }
+        return;
+    }
+    const bool live = qi < ql;
+    if (LEN && !live && sub == 0 && qi < q)     // dead lanes of a partial wave: their zeros now, nothing kept for the end
+        store_zero_row(kout, idx + ((size_t)b * q + qi) * kout, dist ? dist + ((size_t)b * q + qi) * kout : nullptr);
+    // a tile t holds a live reference: LEN ? t * PT < rl : t < tiles
+    auto live_tile = [&](int t) -> bool { return LEN ? t * PT < rl : t < tiles; };
     // dead lanes replicate the wave's first query so they do not inflate the query box
     const float *qp = query + ((size_t)b * q + (live ? qi : q0)) * 3;
     const float qx = qp[0], qy = qp[1], qz = qp[2];
@@ -1001,7 +1101,7 @@ __global__ __launch_bounds__(64) void knn_pruned_kernel(int q, int n, int tiles,
     for (int u = 0; u < TPL; ++u) {
         const int t = lane + 64 * u;
         lb[u] = INFINITY;
-        if (t < tiles) {
+        if (live_tile(t)) {
             const float *bx = boxes + t * 6;
             const float g0 = fmaxf(0.f, fmaxf(bx[0] - bh0, bl0 - bx[3]));
             const float g1 = fmaxf(0.f, fmaxf(bx[1] - bh1, bl1 - bx[4]));
@@ -1071,7 +1171,7 @@ __global__ __launch_bounds__(64) void knn_pruned_kernel(int q, int n, int tiles,
 #pragma unroll
         for (int u = 0; u < PT / 64; ++u) {
             const int gi = t * PT + lane + 64 * u;
-            const bool ok = gi < n;
+            const bool ok = gi < rl;
             const int gg = ok ? gi : 0;
             const float x = ref[(size_t)gg * 3 + 0], y = ref[(size_t)gg * 3 + 1], z = ref[(size_t)gg * 3 + 2];
             g.pi[u] = ok ? rperm[gg] : 0;
@@ -1121,8 +1221,11 @@ __global__ __launch_bounds__(64) void knn_pruned_kernel(int q, int n, int tiles,
         for (int u = 0; u < PT / 64; ++u) {
             const int r = lane + 64 * u;
             const bool pad = cur.z[u] != cur.z[u];
-            float4 v = make_float4(cur.x[u], cur.y[u], pad ? 0.f : cur.z[u], 0.f);
-            v.w = pad ? (MODE == MCP_DIST_EXPANSION ? INFINITY : 0.f) : mcp_sqnorm3(v.x, v.y, v.z);
+            // LEN: a masked reference gets a NaN distance in both forms, as in the walk kernel -- the +inf of the plain kernel passes
+            // `d <= tau` while tau is still +inf, which only a search with fewer than K live references can show.  What the plain
+            // kernel returns for n < K is what it always returned: LEN == false is untouched here
+            float4 v = make_float4(LEN && pad ? NAN : cur.x[u], cur.y[u], pad ? 0.f : cur.z[u], 0.f);
+            v.w = pad ? (LEN ? NAN : MODE == MCP_DIST_EXPANSION ? INFINITY : 0.f) : mcp_sqnorm3(v.x, v.y, v.z);
             tile[r] = v;
             tperm[(r % SUB) * RPL + r / SUB] = cur.pi[u];
         }
@@ -1204,45 +1307,41 @@ __global__ __launch_bounds__(64) void knn_pruned_kernel(int q, int n, int tiles,
 #endif
 }
 
-template <int K, int MODE, int SUB, int TPL>
-int launch_pruned_tpl(int b, int q, int n, int tiles, int k, const float *query, const int *qperm, const float *ref, const int *rperm,
-                      const float *boxes, int *idx, float *dist, hipStream_t s) {
+template <int K, int MODE, int SUB, int TPL, bool LEN>
+int launch_pruned_tpl(int b, int q, int n, int tiles, int k, const SearchArgs &a, hipStream_t s) {
     const size_t lds = (size_t)PrunedLds<K>::WAVE_BYTES;
-    auto kern = knn_pruned_kernel<K, MODE, SUB, TPL>;
+    auto kern = knn_pruned_kernel<K, MODE, SUB, TPL, LEN>;
     static McpPerDeviceOnce attr_once;
     if (attr_once.need()) {  // lets the CU's whole 160 KB LDS count towards residency (default budget: 64 KB)
         { const hipError_t attr_e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); if (attr_e_ != hipSuccess) return (int)attr_e_; }
         attr_once.done();
     }
-    hipLaunchKernelGGL(kern, dim3(mcp_divup(q, 64 / SUB), b), dim3(64), lds, s, q, n, tiles, k, query, qperm,
-                       ref, rperm, boxes, idx, dist);
+    hipLaunchKernelGGL(kern, dim3(mcp_divup(q, 64 / SUB), b), dim3(64), lds, s, q, n, tiles, k, a.query, a.qperm,
+                       a.ref, a.rperm, a.boxes, a.idx, a.dist, a.qlen, a.rlen);
     return mcp_launch_status();
 }
 
-template <int K, int MODE, int SUB>
-int launch_pruned_sub(int b, int q, int n, int tiles, int k, const float *query, const int *qperm, const float *ref, const int *rperm,
-                      const float *boxes, int *idx, float *dist, hipStream_t s) {
+template <int K, int MODE, int SUB, bool LEN>
+int launch_pruned_sub(int b, int q, int n, int tiles, int k, const SearchArgs &a, hipStream_t s) {
     // tile bounds held per lane: sized to the cloud so the per-visit argmin stays short
-    if (tiles <= 64) return launch_pruned_tpl<K, MODE, SUB, 1>(b, q, n, tiles, k, query, qperm, ref, rperm, boxes, idx, dist, s);
-    if (tiles <= 128) return launch_pruned_tpl<K, MODE, SUB, 2>(b, q, n, tiles, k, query, qperm, ref, rperm, boxes, idx, dist, s);
-    if (tiles <= 256) return launch_pruned_tpl<K, MODE, SUB, 4>(b, q, n, tiles, k, query, qperm, ref, rperm, boxes, idx, dist, s);
-    return launch_pruned_tpl<K, MODE, SUB, MAX_TPL>(b, q, n, tiles, k, query, qperm, ref, rperm, boxes, idx, dist, s);
+    if (tiles <= 64) return launch_pruned_tpl<K, MODE, SUB, 1, LEN>(b, q, n, tiles, k, a, s);
+    if (tiles <= 128) return launch_pruned_tpl<K, MODE, SUB, 2, LEN>(b, q, n, tiles, k, a, s);
+    if (tiles <= 256) return launch_pruned_tpl<K, MODE, SUB, 4, LEN>(b, q, n, tiles, k, a, s);
+    return launch_pruned_tpl<K, MODE, SUB, MAX_TPL, LEN>(b, q, n, tiles, k, a, s);
 }
 
-template <int K, int MODE>
-int launch_pruned(int b, int q, int n, int tiles, int k, const float *query, const int *qperm, const float *ref, const int *rperm,
-                  const float *boxes, int *idx, float *dist, hipStream_t s) {
+template <int K, int MODE, bool LEN>
+int launch_pruned(int b, int q, int n, int tiles, int k, const SearchArgs &a, hipStream_t s) {
     // 4 lanes per query (1 and 2 were measured slower at every shape of the pipeline)
-    return launch_pruned_sub<K, MODE, 4>(b, q, n, tiles, k, query, qperm, ref, rperm, boxes, idx, dist, s);
+    return launch_pruned_sub<K, MODE, 4, LEN>(b, q, n, tiles, k, a, s);
 }
 
-template <int MODE>
-int launch_pruned_k(int b, int q, int n, int tiles, int k, const float *query, const int *qperm, const float *ref, const int *rperm,
-                    const float *boxes, int *idx, float *dist, hipStream_t s) {
-    if (k <= 4) return launch_pruned<4, MODE>(b, q, n, tiles, k, query, qperm, ref, rperm, boxes, idx, dist, s);
-    if (k <= 16) return launch_pruned<16, MODE>(b, q, n, tiles, k, query, qperm, ref, rperm, boxes, idx, dist, s);
+template <int MODE, bool LEN>
+int launch_pruned_k(int b, int q, int n, int tiles, int k, const SearchArgs &a, hipStream_t s) {
+    if (k <= 4) return launch_pruned<4, MODE, LEN>(b, q, n, tiles, k, a, s);
+    if (k <= 16) return launch_pruned<16, MODE, LEN>(b, q, n, tiles, k, a, s);
 #if defined(MCP_AB) || defined(MCP_KNN_DIAG)
-    return launch_pruned<32, MODE>(b, q, n, tiles, k, query, qperm, ref, rperm, boxes, idx, dist, s);   // A/B builds only
+    return launch_pruned<32, MODE, LEN>(b, q, n, tiles, k, a, s);   // A/B builds only
 #else
     return MCP_ERR_UNSUPPORTED;
 #endif
@@ -1272,8 +1371,8 @@ static int g_knn_use_old = 0;
 extern "C" __attribute__((visibility("default"))) void mcp_knn_pruned_use_old(int on) { g_knn_use_old = on; }
 // resident workgroups per CU the runtime reports for the K = 32 kernels (walk, round 3)
 extern "C" __attribute__((visibility("default"))) int mcp_knn_occupancy(int *walk, int *old) {
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(walk, knn_walk_kernel<32, MCP_DIST_EXPANSION, 2>, 64, WalkCfg<32>::WAVE_BYTES);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(old, knn_pruned_kernel<32, MCP_DIST_EXPANSION, 4, 2>, 64, PrunedLds<32>::WAVE_BYTES);
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(walk, knn_walk_kernel<32, MCP_DIST_EXPANSION, 2, false>, 64, WalkCfg<32>::WAVE_BYTES);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(old, knn_pruned_kernel<32, MCP_DIST_EXPANSION, 4, 2, false>, 64, PrunedLds<32>::WAVE_BYTES);
     return (int)e;
 }
 #endif
@@ -1282,27 +1381,76 @@ MCP_EXPORT int mcp_knn_tile_size(void) { return PT; }
 
 MCP_EXPORT int mcp_morton_codes(int b, int n, const float *xyz, const float *box, int *codes, mcp_stream_t stream) {
     MCP_CHECK_ARGS(b > 0 && n > 0 && xyz && box && codes);
-    hipLaunchKernelGGL(morton_kernel, dim3(mcp_divup(n, 256), b), dim3(256), 0, (hipStream_t)stream, n, xyz, box, codes);
+    hipLaunchKernelGGL(morton_kernel<false>, dim3(mcp_divup(n, 256), b), dim3(256), 0, (hipStream_t)stream, n, xyz, box, nullptr, codes);
+    return mcp_launch_status();
+}
+
+MCP_EXPORT int mcp_morton_codes_lengths(int b, int n, const float *xyz, const float *box, const int *len, int *codes, mcp_stream_t stream) {
+    if (!len) return mcp_morton_codes(b, n, xyz, box, codes, stream);
+    MCP_CHECK_ARGS(b > 0 && n > 0 && xyz && box && codes);
+    hipLaunchKernelGGL(morton_kernel<true>, dim3(mcp_divup(n, 256), b), dim3(256), 0, (hipStream_t)stream, n, xyz, box, len, codes);
     return mcp_launch_status();
 }
 
 MCP_EXPORT int mcp_tile_boxes(int b, int n, const float *sorted_xyz, float *boxes, mcp_stream_t stream) {
     MCP_CHECK_ARGS(b > 0 && n > 0 && sorted_xyz && boxes);
     const int tiles = (n + PT - 1) / PT;
-    hipLaunchKernelGGL(tile_box_kernel, dim3(tiles, b), dim3(64), 0, (hipStream_t)stream, n, tiles, sorted_xyz, boxes);
+    hipLaunchKernelGGL(tile_box_kernel<false>, dim3(tiles, b), dim3(64), 0, (hipStream_t)stream, n, tiles, sorted_xyz, nullptr, boxes);
     return mcp_launch_status();
 }
+
+MCP_EXPORT int mcp_tile_boxes_lengths(int b, int n, const float *sorted_xyz, const int *len, float *boxes, mcp_stream_t stream) {
+    if (!len) return mcp_tile_boxes(b, n, sorted_xyz, boxes, stream);
+    MCP_CHECK_ARGS(b > 0 && n > 0 && sorted_xyz && boxes);
+    const int tiles = (n + PT - 1) / PT;
+    hipLaunchKernelGGL(tile_box_kernel<true>, dim3(tiles, b), dim3(64), 0, (hipStream_t)stream, n, tiles, sorted_xyz, len, boxes);
+    return mcp_launch_status();
+}
+
+namespace {
+// the builder and the search behind the plain entry points (LEN == false) and the _lengths ones: instantiation by the padded sizes
+template <bool LEN>
+int build_cloud_run(int b, int n, const float *xyz, const int *len, float *sorted_xyz, int *perm, float *boxes, hipStream_t s) {
+    const int tiles = (n + PT - 1) / PT;
+    if (n <= BT) return launch_build_cloud<1, LEN>(b, n, tiles, xyz, len, sorted_xyz, perm, boxes, s);
+    if (n <= 2 * BT) return launch_build_cloud<2, LEN>(b, n, tiles, xyz, len, sorted_xyz, perm, boxes, s);
+    if (n <= 4 * BT) return launch_build_cloud<4, LEN>(b, n, tiles, xyz, len, sorted_xyz, perm, boxes, s);
+    if (n <= 8 * BT) return launch_build_cloud<8, LEN>(b, n, tiles, xyz, len, sorted_xyz, perm, boxes, s);
+    return launch_build_cloud<16, LEN>(b, n, tiles, xyz, len, sorted_xyz, perm, boxes, s);
+}
+
+template <bool LEN>
+int knn_pruned_run(int b, int q, int n, int k, int dist_form, const SearchArgs &a, hipStream_t s) {
+    const int tiles = (n + PT - 1) / PT;
+    mcp_prof_begin(MCP_KERNEL_KNN, s);
+    int rc;
+    bool old = k <= 16;
+#if defined(MCP_AB) || defined(MCP_KNN_DIAG)
+    old = g_knn_use_old == 1 || (g_knn_use_old == 0 && old);
+#endif
+    if (old)
+        rc = dist_form == MCP_DIST_EXPANSION ? launch_pruned_k<MCP_DIST_EXPANSION, LEN>(b, q, n, tiles, k, a, s)
+                                             : launch_pruned_k<MCP_DIST_DIRECT, LEN>(b, q, n, tiles, k, a, s);
+    else
+        rc = dist_form == MCP_DIST_EXPANSION ? launch_walk_k<MCP_DIST_EXPANSION, LEN>(b, q, n, tiles, k, a, s)
+                                             : launch_walk_k<MCP_DIST_DIRECT, LEN>(b, q, n, tiles, k, a, s);
+    mcp_prof_end(MCP_KERNEL_KNN, s);
+    return rc;
+}
+}  // namespace
 
 MCP_EXPORT int mcp_build_cloud(int b, int n, const float *xyz, float *sorted_xyz, int *perm, float *boxes, mcp_stream_t stream) {
     MCP_CHECK_ARGS(b > 0 && n > 0 && xyz && sorted_xyz && perm && boxes);
     if (n > 16384) return MCP_ERR_UNSUPPORTED;  // larger clouds: mcp_morton_codes + an external sort + mcp_tile_boxes
-    const int tiles = (n + PT - 1) / PT;
-    hipStream_t s = (hipStream_t)stream;
-    if (n <= BT) return launch_build_cloud<1>(b, n, tiles, xyz, sorted_xyz, perm, boxes, s);
-    if (n <= 2 * BT) return launch_build_cloud<2>(b, n, tiles, xyz, sorted_xyz, perm, boxes, s);
-    if (n <= 4 * BT) return launch_build_cloud<4>(b, n, tiles, xyz, sorted_xyz, perm, boxes, s);
-    if (n <= 8 * BT) return launch_build_cloud<8>(b, n, tiles, xyz, sorted_xyz, perm, boxes, s);
-    return launch_build_cloud<16>(b, n, tiles, xyz, sorted_xyz, perm, boxes, s);
+    return build_cloud_run<false>(b, n, xyz, nullptr, sorted_xyz, perm, boxes, (hipStream_t)stream);
+}
+
+MCP_EXPORT int mcp_build_cloud_lengths(int b, int n, const float *xyz, const int *len, float *sorted_xyz, int *perm, float *boxes,
+                                       mcp_stream_t stream) {
+    if (!len) return mcp_build_cloud(b, n, xyz, sorted_xyz, perm, boxes, stream);
+    MCP_CHECK_ARGS(b > 0 && n > 0 && xyz && sorted_xyz && perm && boxes);
+    if (n > 16384) return MCP_ERR_UNSUPPORTED;  // larger clouds: the three-step route with mcp_morton_codes_lengths / mcp_tile_boxes_lengths
+    return build_cloud_run<true>(b, n, xyz, len, sorted_xyz, perm, boxes, (hipStream_t)stream);
 }
 
 MCP_EXPORT int mcp_knn_pruned(int b, int q, int n, int k, int dist_form, const float *query_sorted, const int *qperm,
@@ -1310,25 +1458,18 @@ MCP_EXPORT int mcp_knn_pruned(int b, int q, int n, int k, int dist_form, const f
                               mcp_stream_t stream) {
     MCP_CHECK_ARGS(b > 0 && q > 0 && n > 0 && k > 0 && query_sorted && ref_sorted && rperm && boxes && idx);
     MCP_CHECK_ARGS(dist_form == MCP_DIST_EXPANSION || dist_form == MCP_DIST_DIRECT);
-    const int tiles = (n + PT - 1) / PT;
-    if (k > 32 || tiles > 64 * MAX_TPL) return MCP_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    mcp_prof_begin(MCP_KERNEL_KNN, s);
-    int rc;
-    bool old = k <= 16;
-#if defined(MCP_AB) || defined(MCP_KNN_DIAG)
-    old = g_knn_use_old == 1 || (g_knn_use_old == 0 && old);
-#endif
-    if (old) {
-        rc = dist_form == MCP_DIST_EXPANSION ? launch_pruned_k<MCP_DIST_EXPANSION>(b, q, n, tiles, k, query_sorted, qperm, ref_sorted, rperm, boxes, idx, dist, s)
-                                             : launch_pruned_k<MCP_DIST_DIRECT>(b, q, n, tiles, k, query_sorted, qperm, ref_sorted, rperm, boxes, idx, dist, s);
-        mcp_prof_end(MCP_KERNEL_KNN, s);
-        return rc;
-    }
-    if (dist_form == MCP_DIST_EXPANSION)
-        rc = launch_walk_k<MCP_DIST_EXPANSION>(b, q, n, tiles, k, query_sorted, qperm, ref_sorted, rperm, boxes, idx, dist, s);
-    else
-        rc = launch_walk_k<MCP_DIST_DIRECT>(b, q, n, tiles, k, query_sorted, qperm, ref_sorted, rperm, boxes, idx, dist, s);
-    mcp_prof_end(MCP_KERNEL_KNN, s);
-    return rc;
+    if (k > 32 || (n + PT - 1) / PT > 64 * MAX_TPL) return MCP_ERR_UNSUPPORTED;
+    const SearchArgs a = {query_sorted, qperm, ref_sorted, rperm, boxes, idx, dist, nullptr, nullptr};
+    return knn_pruned_run<false>(b, q, n, k, dist_form, a, (hipStream_t)stream);
+}
+
+MCP_EXPORT int mcp_knn_pruned_lengths(int b, int q, int n, int k, int dist_form, const float *query_sorted, const int *qperm,
+                                      const float *ref_sorted, const int *rperm, const float *boxes, const int *qlen, const int *rlen,
+                                      int *idx, float *dist, mcp_stream_t stream) {
+    if (!qlen && !rlen) return mcp_knn_pruned(b, q, n, k, dist_form, query_sorted, qperm, ref_sorted, rperm, boxes, idx, dist, stream);
+    MCP_CHECK_ARGS(b > 0 && q > 0 && n > 0 && k > 0 && query_sorted && ref_sorted && rperm && boxes && idx);
+    MCP_CHECK_ARGS(dist_form == MCP_DIST_EXPANSION || dist_form == MCP_DIST_DIRECT);
+    if (k > 32 || (n + PT - 1) / PT > 64 * MAX_TPL) return MCP_ERR_UNSUPPORTED;
+    const SearchArgs a = {query_sorted, qperm, ref_sorted, rperm, boxes, idx, dist, qlen, rlen};
+    return knn_pruned_run<true>(b, q, n, k, dist_form, a, (hipStream_t)stream);
 }

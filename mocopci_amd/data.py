@@ -155,18 +155,19 @@ def evaluate(net, loader, device="cuda", raw_gt=False, raw_emd=False, gt_points=
             out = net(inp[1], inp[2])                                                  # the two middle frames, test.py:84
             torch.cuda.synchronize()
             seconds.append(time.perf_counter() - t0)
-            for j in range(3):
-                if raw_gt:
-                    scan, count = gt[j], sample[2][j]
-                    if gt_points is not None:
-                        scan, count = downsample_padded(scan, count, gt_points)
-                    cd[j].append(float(ops.backend().chamfer(out[j].contiguous(), scan, y_lengths=count)))
-                    if raw_emd:
-                        emd[j].append(float(emd_mod.EMD(out[j].permute(0, 2, 1).contiguous(), scan.permute(0, 2, 1).contiguous(),
-                                                        lengths2=count)))
-                    continue
-                cd[j].append(float(ops.backend().chamfer(out[j].contiguous(), gt[j])))
-                emd[j].append(float(emd_mod.EMD(out[j].permute(0, 2, 1).contiguous(), gt[j].permute(0, 2, 1).contiguous())))
+            with ops.backend().cloud_scope():   # a cloud the metrics search in both roles is sorted once per batch
+                for j in range(3):
+                    if raw_gt:
+                        scan, count = gt[j], sample[2][j]
+                        if gt_points is not None:
+                            scan, count = downsample_padded(scan, count, gt_points)
+                        cd[j].append(float(ops.backend().chamfer(out[j].contiguous(), scan, y_lengths=count)))
+                        if raw_emd:
+                            emd[j].append(float(emd_mod.EMD(out[j].permute(0, 2, 1).contiguous(), scan.permute(0, 2, 1).contiguous(),
+                                                            lengths2=count)))
+                        continue
+                    cd[j].append(float(ops.backend().chamfer(out[j].contiguous(), gt[j])))
+                    emd[j].append(float(emd_mod.EMD(out[j].permute(0, 2, 1).contiguous(), gt[j].permute(0, 2, 1).contiguous())))
     mean = lambda v: float(np.mean(v)) if v else float("nan")
     with_emd = raw_emd or not raw_gt
     return {"chamfer": [mean(c) for c in cd], "emd": [mean(e) for e in emd] if with_emd else None, "seconds_per_forward": mean(seconds),

@@ -606,8 +606,9 @@ class _ChamferLengthsFn(torch.autograd.Function):
         x, y = x.detach().contiguous(), y.detach().contiguous()
         B, N, _ = x.shape
         M = y.shape[1]
-        ixy, dxy = be.knn(x, y, 1, mode=MCP_DIST_DIRECT, return_dist=True, query_lengths=xl, ref_lengths=yl)
-        iyx, dyx = be.knn(y, x, 1, mode=MCP_DIST_DIRECT, return_dist=True, query_lengths=yl, ref_lengths=xl)
+        with be.cloud_scope():   # where the searches prune, a cloud that is query here and reference there is sorted once
+            ixy, dxy = be.knn(x, y, 1, mode=MCP_DIST_DIRECT, return_dist=True, query_lengths=xl, ref_lengths=yl)
+            iyx, dyx = be.knn(y, x, 1, mode=MCP_DIST_DIRECT, return_dist=True, query_lengths=yl, ref_lengths=xl)
         xe, ye = _valid_counts(xl, B, N, x.device), _valid_counts(yl, B, M, x.device)
         xden, yden = xe.clamp(min=1).float(), ye.clamp(min=1).float()
         both = ((xe > 0) & (ye > 0)).view(B, 1, 1)
@@ -796,9 +797,23 @@ class HipBackend:
     # (plain attributes: A/B tools set them on the class; the package reads no tuning variables from the environment)
     PRUNE_MIN_REFS = 2048
     PRUNE_MIN_QUERIES = 1024
+    # the same rule for a search with per-cloud lengths, on the PADDED sizes (the host never reads a length).  Its constants are the
+    # smallest class measured to win WITH both cloud builds (profiles/knn_pruned_lengths_times.json): at 8 x 8192 x 8192 the pruned
+    # route takes 0.099 ms against the exhaustive 0.144 (K = 1) and 0.113-0.145 against 0.216-0.377 (K = 32); at 8 x 2048 x 4096 it
+    # loses, 0.065 against 0.037 and 0.072 against 0.056, as at 8 x 1024 x 2048 (two builds cost more than the whole exhaustive
+    # search there).  Nothing in between is measured, so it stays exhaustive.
+    PRUNE_LENGTHS_MIN_REFS = 8192
+    PRUNE_LENGTHS_MIN_QUERIES = 8192
+
+    @classmethod
+    def prunes_with_lengths(cls, Q, N, k):
+        """Whether a search with lengths of (B,Q,3) queries in (B,N,3) references takes the pruned route: a pure function of the
+        padded shapes and k (the candidate lists hold 16-bit indices: N <= 65536)."""
+        return cls.PRUNE_LENGTHS_MIN_REFS <= N <= 65536 and Q >= cls.PRUNE_LENGTHS_MIN_QUERIES and k <= 32
 
     def __init__(self):
-        self._tls = threading.local()  # .scope: {key: (tensor, sorted cloud, stream, built-event)} while a cloud_scope is open
+        # .scope: {key: (tensor, sorted cloud, stream, built-event, lengths tensor or None)} while a cloud_scope is open
+        self._tls = threading.local()
         self._tile = None
 
     @property
@@ -823,14 +838,32 @@ class HipBackend:
         finally:
             self._tls.scope = outer
 
-    def _build_cloud(self, xyz):
+    def _build_cloud(self, xyz, lens=None):
+        """lens: (B,) int32 device lengths (lengths_tensor) -- the sorted form of each element's first lens[b] rows, padding behind
+        it in place (perm[s] = s); no padded row of xyz reaches the box, a key or a tile box."""
         B, N, _ = xyz.shape
         tiles = (N + self.TILE - 1) // self.TILE
         boxes = torch.empty((B, tiles, 6), dtype=torch.float32, device=xyz.device)
         if N <= 16384:  # one fused launch: bbox, Morton keys, in-LDS sort, gather, tile boxes
             sorted_xyz = torch.empty_like(xyz)
             perm = torch.empty((B, N), dtype=torch.int32, device=xyz.device)
-            _call("mcp_build_cloud", xyz, B, N, _lib.fptr(xyz), _lib.fptr(sorted_xyz), _lib.iptr(perm), _lib.fptr(boxes))
+            if lens is None:
+                _call("mcp_build_cloud", xyz, B, N, _lib.fptr(xyz), _lib.fptr(sorted_xyz), _lib.iptr(perm), _lib.fptr(boxes))
+            else:
+                _call("mcp_build_cloud_lengths", xyz, B, N, _lib.fptr(xyz), _lib.iptr(lens), _lib.fptr(sorted_xyz), _lib.iptr(perm),
+                      _lib.fptr(boxes))
+        elif lens is not None:
+            # the box over live rows only (a masked min / max: NaN or huge padding cannot leak), padding coded above every live point,
+            # and a STABLE sort, so that the padding stays where it is
+            live = torch.arange(N, device=xyz.device).view(1, N, 1) < lens.clamp(0, N).view(B, 1, 1)
+            lo = torch.where(live, xyz, xyz.new_tensor(float("inf"))).amin(dim=1)
+            hi = torch.where(live, xyz, xyz.new_tensor(float("-inf"))).amax(dim=1)
+            box = torch.cat([lo, hi], dim=-1).contiguous()
+            codes = torch.empty((B, N), dtype=torch.int32, device=xyz.device)
+            _call("mcp_morton_codes_lengths", xyz, B, N, _lib.fptr(xyz), _lib.fptr(box), _lib.iptr(lens), _lib.iptr(codes))
+            perm = torch.sort(codes, dim=1, stable=True)[1].int()
+            sorted_xyz = self.group_rows(xyz, perm)   # rows beyond a length: copies of the padding, which the search never reads
+            _call("mcp_tile_boxes_lengths", xyz, B, N, _lib.fptr(sorted_xyz), _lib.iptr(lens), _lib.fptr(boxes))
         else:
             box = torch.cat([xyz.amin(dim=1), xyz.amax(dim=1)], dim=-1).contiguous()
             codes = torch.empty((B, N), dtype=torch.int32, device=xyz.device)
@@ -840,25 +873,30 @@ class HipBackend:
             _call("mcp_tile_boxes", xyz, B, N, _lib.fptr(sorted_xyz), _lib.fptr(boxes))
         return sorted_xyz, perm, boxes
 
-    def _sorted_cloud(self, xyz):
-        """Morton order of a cloud: (sorted xyz, perm int32, tile boxes); cached only inside a cloud_scope."""
+    def _sorted_cloud(self, xyz, lens=None):
+        """Morton order of a cloud: (sorted xyz, perm int32, tile boxes); cached only inside a cloud_scope.  lens: see _build_cloud;
+        the lengths tensor is part of the key (and is kept alive by the entry), so a cloud sorted under lengths is served only to
+        searches with that very lengths tensor, and a length-free one only to length-free searches.  The key is the data_ptr of the
+        (B,) int32 device array the kernels read: an int32 device tensor keeps its own, but lengths_tensor makes a fresh array of a
+        list, a CPU tensor or an int64 device tensor on every call, so such lengths share a sorted cloud only when the caller
+        converts them once (as chamfer and compat.knn_points do for their own searches) and passes the result."""
         scope = getattr(self._tls, "scope", None)
         if scope is None:
-            return self._build_cloud(xyz)
+            return self._build_cloud(xyz, lens)
         cur = torch.cuda.current_stream(xyz.device)
-        key = (xyz.data_ptr(), tuple(xyz.shape), xyz.device.index)
+        key = (xyz.data_ptr(), tuple(xyz.shape), xyz.device.index, None if lens is None else lens.data_ptr())
         hit = scope.get(key)
         if hit is not None:
-            _, cloud, stream, done = hit
+            cloud, stream, done = hit[1:4]
             if stream != cur:  # built on another stream of this forward: order + lifetime
                 cur.wait_event(done)
                 for t in cloud:
                     t.record_stream(cur)
             return cloud
-        cloud = self._build_cloud(xyz)
+        cloud = self._build_cloud(xyz, lens)
         done = torch.cuda.Event()
         done.record(cur)
-        scope[key] = (xyz, cloud, cur, done)
+        scope[key] = (xyz, cloud, cur, done, lens)
         return cloud
 
     def prebuild_cloud(self, xyz):
@@ -874,16 +912,27 @@ class HipBackend:
         query_lengths / ref_lengths (pytorch3d's lengths1 / lengths2; see lengths_tensor for the accepted forms): element b searches
         only ref[b, :ref_lengths[b]] and only query[b, :query_lengths[b]] is live.  Live rows get what the search of the two prefixes
         on their own returns (fewer than k references: the tail repeats the last valid entry; none: index 0, distance 0); padded
-        query rows get index 0 and distance 0; padded rows of either cloud are never read.  Without lengths nothing changes."""
+        query rows get index 0 and distance 0; padded rows of either cloud are never read.  Without lengths nothing changes.
+        With lengths the padded sizes choose the route (prunes_with_lengths): the pruned search over clouds sorted under their
+        lengths, or the exhaustive kernels -- the same bits either way."""
         query, ref = query.detach(), ref.detach()  # an index-producing search: no gradient (pointnet2_utils.py:31-33)
         B, Q, _ = query.shape
         N = ref.shape[1]
         idx = torch.empty((B, Q, k), dtype=torch.int32, device=query.device)
         dist = torch.empty((B, Q, k), dtype=torch.float32, device=query.device) if return_dist else None
-        if query_lengths is not None or ref_lengths is not None:   # always the exhaustive kernels: the pruned search has no lengths yet
+        if query_lengths is not None or ref_lengths is not None:
             ql, rl = lengths_tensor(query_lengths, B, Q, query.device), lengths_tensor(ref_lengths, B, N, query.device)
-            _call("mcp_knn_lengths", query, B, Q, N, k, mode, _lib.fptr(query), _lib.fptr(ref), None if ql is None else _lib.iptr(ql),
-                  None if rl is None else _lib.iptr(rl), _lib.iptr(idx), _lib.fptr(dist) if return_dist else None)
+            qlp, rlp = None if ql is None else _lib.iptr(ql), None if rl is None else _lib.iptr(rl)
+            if self.prunes_with_lengths(Q, N, k):
+                _lib.fptr(query), _lib.fptr(ref)  # validate before building the sorted clouds
+                rs, rperm, boxes = self._sorted_cloud(ref, rl)   # a side without a length: the length-free cloud
+                same = query.data_ptr() == ref.data_ptr() and query.shape == ref.shape and query_lengths is ref_lengths
+                qs, qperm, _ = (rs, rperm, boxes) if same else self._sorted_cloud(query, ql)
+                _call("mcp_knn_pruned_lengths", query, B, Q, N, k, mode, _lib.fptr(qs), _lib.iptr(qperm), _lib.fptr(rs), _lib.iptr(rperm),
+                      _lib.fptr(boxes), qlp, rlp, _lib.iptr(idx), _lib.fptr(dist) if return_dist else None)
+            else:
+                _call("mcp_knn_lengths", query, B, Q, N, k, mode, _lib.fptr(query), _lib.fptr(ref), qlp, rlp, _lib.iptr(idx),
+                      _lib.fptr(dist) if return_dist else None)
         elif N >= self.PRUNE_MIN_REFS and Q >= self.PRUNE_MIN_QUERIES and k <= 32 and N <= 65536:
             _lib.fptr(query), _lib.fptr(ref)  # validate before building the sorted clouds
             rs, rperm, boxes = self._sorted_cloud(ref)
@@ -896,12 +945,17 @@ class HipBackend:
                   _lib.fptr(dist) if return_dist else None)
         return (idx, dist) if return_dist else idx
 
-    def knn_bruteforce(self, query, ref, k, mode=MCP_DIST_EXPANSION, return_dist=False):
-        """The exhaustive kernel regardless of size (tests compare both paths)."""
+    def knn_bruteforce(self, query, ref, k, mode=MCP_DIST_EXPANSION, return_dist=False, query_lengths=None, ref_lengths=None):
+        """The exhaustive kernel regardless of size (tests compare both paths), with or without per-cloud lengths."""
         B, Q, _ = query.shape
         N = ref.shape[1]
         idx = torch.empty((B, Q, k), dtype=torch.int32, device=query.device)
         dist = torch.empty((B, Q, k), dtype=torch.float32, device=query.device) if return_dist else None
+        if query_lengths is not None or ref_lengths is not None:
+            ql, rl = lengths_tensor(query_lengths, B, Q, query.device), lengths_tensor(ref_lengths, B, N, query.device)
+            _call("mcp_knn_lengths", query, B, Q, N, k, mode, _lib.fptr(query), _lib.fptr(ref), None if ql is None else _lib.iptr(ql),
+                  None if rl is None else _lib.iptr(rl), _lib.iptr(idx), _lib.fptr(dist) if return_dist else None)
+            return (idx, dist) if return_dist else idx
         _call("mcp_knn", query, B, Q, N, k, mode, _lib.fptr(query), _lib.fptr(ref), _lib.iptr(idx),
               _lib.fptr(dist) if return_dist else None)
         return (idx, dist) if return_dist else idx
@@ -1418,10 +1472,17 @@ class HipBackend:
                 v = _ChamferLengthsFn.apply(self, x, y, xl, yl)
             else:
                 x, y = x.contiguous(), y.contiguous()
-                dxy = torch.empty((B, N), dtype=torch.float32, device=x.device)
-                dyx = torch.empty((B, M), dtype=torch.float32, device=x.device)
-                _call("mcp_chamfer_nn_lengths", x, B, N, M, _lib.fptr(x), _lib.fptr(y), None if xl is None else _lib.iptr(xl),
-                      None if yl is None else _lib.iptr(yl), _lib.fptr(dxy), _lib.fptr(dyx))
+                if self.prunes_with_lengths(N, M, 1) or self.prunes_with_lengths(M, N, 1):
+                    # a direction whose padded shapes qualify takes the pruned search, the other one the exhaustive kernels (knn
+                    # decides); one scope, so a cloud that is query here and reference there is sorted once
+                    with self.cloud_scope():
+                        dxy = self.knn(x, y, 1, mode=MCP_DIST_DIRECT, return_dist=True, query_lengths=xl, ref_lengths=yl)[1][..., 0]
+                        dyx = self.knn(y, x, 1, mode=MCP_DIST_DIRECT, return_dist=True, query_lengths=yl, ref_lengths=xl)[1][..., 0]
+                else:
+                    dxy = torch.empty((B, N), dtype=torch.float32, device=x.device)
+                    dyx = torch.empty((B, M), dtype=torch.float32, device=x.device)
+                    _call("mcp_chamfer_nn_lengths", x, B, N, M, _lib.fptr(x), _lib.fptr(y), None if xl is None else _lib.iptr(xl),
+                          None if yl is None else _lib.iptr(yl), _lib.fptr(dxy), _lib.fptr(dyx))
                 v = (dxy.sum(1) / _valid_counts(xl, B, N, x.device).clamp(min=1).float()
                      + dyx.sum(1) / _valid_counts(yl, B, M, x.device).clamp(min=1).float())
             return v if per_sample else v.mean()
