@@ -138,6 +138,35 @@ int mcp_ball_query(int b, int n, int m, float radius, int nsample, const float *
 int mcp_query_and_group(int b, int n, int m, int c, float radius, int nsample, int use_xyz, const float *xyz, const float *new_xyz,
                         const float *features, float *out, mcp_stream_t stream);
 
+/* Ball query on a padded batch of clouds of different sizes.  qlen, rlen: (B) int32 DEVICE arrays, read by the kernels and clamped
+ * there to [0,M] / [0,N]; either may be NULL = every row live.  One result definition for the three entry points, with
+ * rl = clamp(rlen[bb]), ql = clamp(qlen[bb]):
+ *   live centres (p < ql):    the first nsample indices k < rl, ascending, with d2(centre, xyz[bb,k]) < radius*radius (the float
+ *                             expression and host-side radius*radius of mcp_ball_query); slots beyond the hit count hold the first
+ *                             hit; no hit, or rl == 0: zeros.  Bit for bit what mcp_ball_query returns for xyz[bb,:rl] and
+ *                             new_xyz[bb,:ql] alone on a pre-zeroed idx;
+ *   padded centres (p >= ql): zeros;
+ *   cnt (B,M) int32, may be NULL: min(hits, nsample) for live centres, 0 for padded ones -- what tells a row of zeros
+ *                             "no hit" from "only point 0 hit".
+ * Every slot of idx and cnt is written (no pre-zeroing by the caller); no row at or beyond a length -- of xyz, new_xyz, features, a
+ * sorted cloud, its perm or its boxes -- is read.  An argument error launches nothing.
+ *   mcp_ball_query_lengths:      any nsample.
+ *   mcp_query_and_group_lengths: mcp_query_and_group on the two prefixes for live centres (nsample <= 64; a live centre with no hit
+ *                                groups point 0, which is live since rl > 0); padded centres, and every centre of an element
+ *                                with rl == 0, write zeros to all their output channels.
+ *   mcp_ball_query_pruned:       the idx and cnt of mcp_ball_query_lengths, bit for bit, from a Morton-sorted cloud with tile boxes
+ *                                (ref_sorted, rperm, boxes: mcp_build_cloud / mcp_morton_codes + sort + mcp_tile_boxes below, or
+ *                                their _lengths forms under the same rlen), reading only the tiles whose box the ball reaches.
+ *                                Centres in the caller's order.  nsample <= 64 and N <= 65536 (MCP_ERR_UNSUPPORTED above). */
+int mcp_ball_query_lengths(int b, int n, int m, float radius, int nsample, const float *new_xyz, const float *xyz, const int *qlen,
+                           const int *rlen, int *idx, int *cnt, mcp_stream_t stream);
+int mcp_query_and_group_lengths(int b, int n, int m, int c, float radius, int nsample, int use_xyz, const float *xyz,
+                                const float *new_xyz, const float *features, const int *rlen, const int *qlen, float *out,
+                                mcp_stream_t stream);
+int mcp_ball_query_pruned(int b, int n, int m, float radius, int nsample, const float *new_xyz, const float *ref_sorted,
+                          const int *rperm, const float *boxes, const int *qlen, const int *rlen, int *idx, int *cnt,
+                          mcp_stream_t stream);
+
 /* three_nn_wrapper(b,n,m,unknown,known,dist2,idx)            interpolate.cpp:14-24, interpolate_gpu.cu:9-74
  * unknown (B,n,3), known (B,m,3) -> dist2 (B,n,3) SQUARED distances, idx (B,n,3). */
 int mcp_three_nn(int b, int n, int m, const float *unknown, const float *known, float *dist2, int *idx, mcp_stream_t stream);

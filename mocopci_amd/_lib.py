@@ -32,6 +32,9 @@ SIGNATURES = {
     "mcp_three_interpolate_grad_sorted": [_i, _i, _i, _i, _p, _p, _p, _p, _p, _p],
     "mcp_ball_query": [_i, _i, _i, _f, _i, _p, _p, _p, _p],
     "mcp_query_and_group": [_i, _i, _i, _i, _f, _i, _i, _p, _p, _p, _p, _p],
+    "mcp_ball_query_lengths": [_i, _i, _i, _f, _i, _p, _p, _p, _p, _p, _p, _p],
+    "mcp_query_and_group_lengths": [_i, _i, _i, _i, _f, _i, _i, _p, _p, _p, _p, _p, _p, _p],
+    "mcp_ball_query_pruned": [_i, _i, _i, _f, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "mcp_three_nn": [_i, _i, _i, _p, _p, _p, _p, _p],
     "mcp_three_interpolate": [_i, _i, _i, _i, _p, _p, _p, _p, _p],
     "mcp_three_interpolate_grad": [_i, _i, _i, _i, _p, _p, _p, _p, _p],

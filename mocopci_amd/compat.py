@@ -76,6 +76,22 @@ def knn_points(p1, p2, lengths1=None, lengths2=None, K=1, return_nn=False, **_):
     return dist, idx.long(), nn
 
 
+def ball_query(p1, p2, lengths1=None, lengths2=None, K=500, radius=0.2, return_nn=True):
+    """pytorch3d.ops.ball_query: for every point of p1 (B,P1,3) the first K points of p2 (B,P2,3), in index order, closer than
+    `radius` -> (dists, idx, nn).  lengths1 / lengths2 (B,): only p1[b, :lengths1[b]] are centres and only p2[b, :lengths2[b]] are
+    searched.  idx (B,P1,K) int64 holds -1 behind a centre's hits and in rows >= lengths1[b] (pytorch3d's padding; the library's
+    own, "repeat the first hit", is overwritten from the hit counts); dists (B,P1,K) are the SQUARED distances and nn (B,P1,K,3) the
+    gathered points (None without return_nn), both zero where idx is -1."""
+    be = ops.backend()
+    p1, p2 = p1.contiguous(), p2.contiguous()
+    idx, cnt = be.ball_query(p2, p1, radius, K, xyz_lengths=lengths2, new_xyz_lengths=lengths1, return_count=True)
+    pad = torch.arange(K, device=p1.device).view(1, 1, K) >= cnt.unsqueeze(-1)
+    nn = be.group_rows(p2.detach(), idx.masked_fill(pad, 0)).masked_fill(pad.unsqueeze(-1), 0.0)
+    diff = (nn - p1.detach().unsqueeze(2)).masked_fill(pad.unsqueeze(-1), 0.0)
+    dists = diff[..., 0] * diff[..., 0] + diff[..., 1] * diff[..., 1] + diff[..., 2] * diff[..., 2]
+    return dists, idx.long().masked_fill(pad, -1), nn if return_nn else None
+
+
 def chamfer_distance(x, y, x_lengths=None, y_lengths=None):
     """pytorch3d.loss.chamfer_distance as called at models/utils.py:44 (default reductions, no normals): (loss, None)."""
     if x_lengths is None and y_lengths is None:

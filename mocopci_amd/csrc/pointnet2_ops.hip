@@ -4,6 +4,7 @@
 // one index load is shared across channels, outputs are written coalesced, the per-query
 // scans (ball_query, three_nn) stream the reference points through LDS tiles that every
 // lane reads as a broadcast.
+#include "ball_query.h"
 #include "common.h"
 
 namespace {
@@ -220,18 +221,14 @@ __global__ __launch_bounds__(BLK) void group_rows_grad_sorted_narrow_kernel(int 
 // order -- so the scan stops, wave-uniformly, as soon as nsample hits exist.  Slots beyond the hit count are filled
 // with the first hit (the reference writes it to every slot when it is found); centres with no hit keep the
 // caller's zeros.
-constexpr int BQ_WAVES = 4;
-__global__ __launch_bounds__(64 * BQ_WAVES) void ball_query_kernel(int n, int m, float radius2, int nsample,
-                                                                   const float *__restrict__ new_xyz, const float *__restrict__ xyz,
-                                                                   int *__restrict__ idx) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int b = blockIdx.y;
-    const int p = blockIdx.x * BQ_WAVES + wave;
-    if (p >= m) return;  // whole wave; no barriers below
-    const float *q = new_xyz + ((size_t)b * m + p) * 3;
-    const float qx = q[0], qy = q[1], qz = q[2];
-    const float *rb = xyz + (size_t)b * n * 3;
-    int *o = idx + ((size_t)b * m + p) * nsample;
+//
+// The scan, stated once for ball_query_kernel and query_and_group_kernel: the first n rows of rb against the centre; store(rank, k)
+// is called by the lane that holds hit number `rank` < nsample, point k.  Returns cnt = hits seen (it may pass nsample within the
+// last step) and first = the first hit, -1 if there is none.
+struct BallHits { int cnt, first; };
+template <typename Store>
+__device__ __forceinline__ BallHits ball_scan(int n, int nsample, float radius2, float qx, float qy, float qz, const float *__restrict__ rb,
+                                              int lane, Store store) {
     int cnt = 0, first = -1;
     for (int base = 0; base < n && cnt < nsample; base += 64) {
         const int k = base + lane;
@@ -241,12 +238,44 @@ __global__ __launch_bounds__(64 * BQ_WAVES) void ball_query_kernel(int n, int m,
         if (mask) {
             if (first < 0) first = base + (int)__builtin_ctzll(mask);
             const int rank = cnt + (int)__builtin_popcountll(mask & ((1ull << lane) - 1ull));
-            if (hit && rank < nsample) o[rank] = k;
+            if (hit && rank < nsample) store(rank, k);
             cnt += (int)__builtin_popcountll(mask);
         }
     }
+    return {cnt, first};
+}
+
+// Per-cloud lengths (mcp_ball_query_lengths, mcp_query_and_group_lengths; result definition: ball_query.h): both kernels take a
+// compile-time LEN.  LEN == false is the kernel as it always was: no length is loaded, no zero is written.  LEN == true reads the two
+// lengths once per wave, bounds the scan by rl, writes the zero rows itself (the caller does not pre-zero) and returns for a padded
+// centre, or an element without a point, before any coordinate is loaded.
+template <bool LEN>
+__global__ __launch_bounds__(64 * BQ_WAVES) void ball_query_kernel(int n, int m, float radius2, int nsample,
+                                                                   const float *__restrict__ new_xyz, const float *__restrict__ xyz,
+                                                                   int *__restrict__ idx, const int *__restrict__ qlen,
+                                                                   const int *__restrict__ rlen, int *__restrict__ cnt_out) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.y;
+    const int p = blockIdx.x * BQ_WAVES + wave;
+    if (p >= m) return;  // whole wave; no barriers below
+    int *o = idx + ((size_t)b * m + p) * nsample;
+    int *co = LEN && cnt_out ? cnt_out + (size_t)b * m + p : nullptr;
+    const int rl = LEN ? bq_clamped_len(rlen, b, n) : n;
+    if (LEN && (p >= bq_clamped_len(qlen, b, m) || rl == 0)) {  // wave-uniform
+        bq_zero_row(lane, nsample, o, co);
+        return;
+    }
+    const float *q = new_xyz + ((size_t)b * m + p) * 3;
+    const float qx = q[0], qy = q[1], qz = q[2];
+    const float *rb = xyz + (size_t)b * n * 3;
+    const BallHits h = ball_scan(rl, nsample, radius2, qx, qy, qz, rb, lane, [o](int rank, int k) { o[rank] = k; });
+    const int cnt = h.cnt, first = h.first;
     if (first >= 0)
         for (int l = min(cnt, nsample) + lane; l < nsample; l += 64) o[l] = first;
+    if (LEN) {
+        if (first < 0) bq_zero_row(lane, nsample, o, co);
+        else if (co && lane == 0) *co = min(cnt, nsample);
+    }
 }
 
 // QueryAndGroup.forward (pointnet2/pointnet2_utils.py:231-264) as ONE launch: the reference runs ball_query, transposes the cloud,
@@ -254,32 +283,33 @@ __global__ __launch_bounds__(64 * BQ_WAVES) void ball_query_kernel(int n, int m,
 // wave owns a centre: the ball query above leaves its nsample hits in an LDS row, then lane (channel offset, slot) gathers
 // 64 / nsample output channels per pass -- relative coordinates first (xyz is read in its (B,N,3) layout: no transposed copy),
 // then the (B,C,N) feature rows -- and writes the (B, 3+C, M, nsample) layout directly.  nsample <= 64.
+// LEN: a padded centre, and every centre of an element without a point, writes zeros to its output channels and reads nothing; a
+// live centre without a hit groups point 0, which is live because rl > 0.
+template <bool LEN>
 __global__ __launch_bounds__(64 * BQ_WAVES) void query_and_group_kernel(int n, int m, int c, float radius2, int nsample, int xyz_ch,
                                                                         const float *__restrict__ xyz, const float *__restrict__ new_xyz,
-                                                                        const float *__restrict__ features, float *__restrict__ out) {
+                                                                        const float *__restrict__ features, float *__restrict__ out,
+                                                                        const int *__restrict__ rlen, const int *__restrict__ qlen) {
     __shared__ int s_idx[BQ_WAVES][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = blockIdx.y;
     const int p = blockIdx.x * BQ_WAVES + wave;
     if (p >= m) return;  // whole wave; no workgroup barriers below
+    const int rl = LEN ? bq_clamped_len(rlen, b, n) : n;
+    if (LEN && (p >= bq_clamped_len(qlen, b, m) || rl == 0)) {  // wave-uniform; the lane-to-output map of the gather below
+        const int cpl = 64 / nsample, slot = lane % nsample, coff = lane / nsample, ct = xyz_ch + (features ? c : 0);
+        if (coff < cpl)
+            for (int ch = coff; ch < ct; ch += cpl) out[(((size_t)b * ct + ch) * m + p) * nsample + slot] = 0.f;
+        return;
+    }
     const float *q = new_xyz + ((size_t)b * m + p) * 3;
     const float qx = q[0], qy = q[1], qz = q[2];
     const float *rb = xyz + (size_t)b * n * 3;
     s_idx[wave][lane] = 0;  // a centre with no hit groups point 0 (the reference's pre-zeroed idx, pointnet2_utils.py:218)
     __builtin_amdgcn_wave_barrier();
-    int cnt = 0, first = -1;
-    for (int base = 0; base < n && cnt < nsample; base += 64) {
-        const int k = base + lane;
-        bool hit = false;
-        if (k < n) hit = mcp_sqdist3(qx, qy, qz, rb[(size_t)k * 3 + 0], rb[(size_t)k * 3 + 1], rb[(size_t)k * 3 + 2]) < radius2;
-        const unsigned long long mask = __builtin_amdgcn_ballot_w64(hit);
-        if (mask) {
-            if (first < 0) first = base + (int)__builtin_ctzll(mask);
-            const int rank = cnt + (int)__builtin_popcountll(mask & ((1ull << lane) - 1ull));
-            if (hit && rank < nsample) s_idx[wave][rank] = k;
-            cnt += (int)__builtin_popcountll(mask);
-        }
-    }
+    int *row = s_idx[wave];
+    const BallHits h = ball_scan(rl, nsample, radius2, qx, qy, qz, rb, lane, [row](int rank, int k) { row[rank] = k; });
+    const int cnt = h.cnt, first = h.first;
     __builtin_amdgcn_wave_barrier();
     if (first >= 0 && lane >= min(cnt, nsample) && lane < nsample) s_idx[wave][lane] = first;
     __builtin_amdgcn_wave_barrier();
@@ -506,8 +536,17 @@ MCP_EXPORT int mcp_ball_query(int b, int n, int m, float radius, int nsample, co
                               mcp_stream_t stream) {
     MCP_CHECK_ARGS(b > 0 && n > 0 && m > 0 && nsample > 0 && new_xyz && xyz && idx);
     const float radius2 = radius * radius;  // ball_query_gpu.cu:20
-    hipLaunchKernelGGL(ball_query_kernel, dim3(mcp_divup(m, BQ_WAVES), b), dim3(64 * BQ_WAVES), 0, (hipStream_t)stream, n, m, radius2,
-                       nsample, new_xyz, xyz, idx);
+    hipLaunchKernelGGL(ball_query_kernel<false>, dim3(mcp_divup(m, BQ_WAVES), b), dim3(64 * BQ_WAVES), 0, (hipStream_t)stream, n, m, radius2,
+                       nsample, new_xyz, xyz, idx, nullptr, nullptr, nullptr);
+    return mcp_launch_status();
+}
+
+MCP_EXPORT int mcp_ball_query_lengths(int b, int n, int m, float radius, int nsample, const float *new_xyz, const float *xyz,
+                                      const int *qlen, const int *rlen, int *idx, int *cnt, mcp_stream_t stream) {
+    MCP_CHECK_ARGS(b > 0 && n > 0 && m > 0 && nsample > 0 && new_xyz && xyz && idx);
+    const float radius2 = radius * radius;  // as mcp_ball_query
+    hipLaunchKernelGGL(ball_query_kernel<true>, dim3(mcp_divup(m, BQ_WAVES), b), dim3(64 * BQ_WAVES), 0, (hipStream_t)stream, n, m, radius2,
+                       nsample, new_xyz, xyz, idx, qlen, rlen, cnt);
     return mcp_launch_status();
 }
 
@@ -516,8 +555,19 @@ MCP_EXPORT int mcp_query_and_group(int b, int n, int m, int c, float radius, int
     MCP_CHECK_ARGS(b > 0 && n > 0 && m > 0 && nsample > 0 && xyz && new_xyz && out && (features ? c > 0 : use_xyz != 0));
     if (nsample > 64) return MCP_ERR_UNSUPPORTED;
     const float radius2 = radius * radius;  // ball_query_gpu.cu:20
-    hipLaunchKernelGGL(query_and_group_kernel, dim3(mcp_divup(m, BQ_WAVES), b), dim3(64 * BQ_WAVES), 0, (hipStream_t)stream, n, m, c, radius2,
-                       nsample, (use_xyz || !features) ? 3 : 0, xyz, new_xyz, features, out);
+    hipLaunchKernelGGL(query_and_group_kernel<false>, dim3(mcp_divup(m, BQ_WAVES), b), dim3(64 * BQ_WAVES), 0, (hipStream_t)stream, n, m, c, radius2,
+                       nsample, (use_xyz || !features) ? 3 : 0, xyz, new_xyz, features, out, nullptr, nullptr);
+    return mcp_launch_status();
+}
+
+MCP_EXPORT int mcp_query_and_group_lengths(int b, int n, int m, int c, float radius, int nsample, int use_xyz, const float *xyz,
+                                           const float *new_xyz, const float *features, const int *rlen, const int *qlen, float *out,
+                                           mcp_stream_t stream) {
+    MCP_CHECK_ARGS(b > 0 && n > 0 && m > 0 && nsample > 0 && xyz && new_xyz && out && (features ? c > 0 : use_xyz != 0));
+    if (nsample > 64) return MCP_ERR_UNSUPPORTED;
+    const float radius2 = radius * radius;  // as mcp_query_and_group
+    hipLaunchKernelGGL(query_and_group_kernel<true>, dim3(mcp_divup(m, BQ_WAVES), b), dim3(64 * BQ_WAVES), 0, (hipStream_t)stream, n, m, c, radius2,
+                       nsample, (use_xyz || !features) ? 3 : 0, xyz, new_xyz, features, out, rlen, qlen);
     return mcp_launch_status();
 }
 

@@ -899,12 +899,18 @@ class HipBackend:
         scope[key] = (xyz, cloud, cur, done, lens)
         return cloud
 
-    def prebuild_cloud(self, xyz):
+    def _holds_cloud(self, xyz, lens=None):
+        """Whether the open cloud_scope (if any) already holds the sorted form of this cloud under these lengths."""
+        scope = getattr(self._tls, "scope", None)
+        return scope is not None and (xyz.data_ptr(), tuple(xyz.shape), xyz.device.index, None if lens is None else lens.data_ptr()) in scope
+
+    def prebuild_cloud(self, xyz, lengths=None):
         """Build the Morton-sorted form of a cloud now, on the current stream, when a later search of this cloud_scope will want
-        it (a cloud large enough for the pruned search): lets a caller put the build on a side stream, off the critical path.
-        No-op outside a scope or for small clouds."""
+        it (a cloud large enough for the pruned search): lets a caller put the build on a side stream, off the critical path --
+        and sends the scope's ball queries on this cloud through the pruned search.  lengths: the (B,) int32 device tensor the
+        later searches will pass (the sorted cloud is keyed by it).  No-op outside a scope or for small clouds."""
         if getattr(self._tls, "scope", None) is not None and self.PRUNE_MIN_REFS <= xyz.shape[1] <= 65536:
-            self._sorted_cloud(xyz.detach())
+            self._sorted_cloud(xyz.detach(), None if lengths is None else lengths_tensor(lengths, xyz.shape[0], xyz.shape[1], xyz.device))
 
     def knn(self, query, ref, k, mode=MCP_DIST_EXPANSION, return_dist=False, query_lengths=None, ref_lengths=None):
         """knn_point(k, ref, query) (mocopci.py:1158-1169): (B,Q,3),(B,N,3) -> (B,Q,k) int32,
@@ -944,6 +950,57 @@ class HipBackend:
             _call("mcp_knn", query, B, Q, N, k, mode, _lib.fptr(query), _lib.fptr(ref), _lib.iptr(idx),
                   _lib.fptr(dist) if return_dist else None)
         return (idx, dist) if return_dist else idx
+
+    # ball query: when the box-pruned search (csrc/ball_query_pruned.hip) replaces the exhaustive scan.  The search alone is 4-11 x
+    # faster than the scan at the small radii (8 x 2048 centres in 8 x 16384 points, r = 0.5 / nsample 16: 0.019 ms against 0.134;
+    # profiles/ball_query_lengths_times.json) and level with it at r = 4 / nsample 8, where the scan stops early -- but a cloud build
+    # costs 0.09 ms at N = 16384 and 0.46 ms beyond it, so build + search beats the scan only at two of that shape's four radii (0.111
+    # against 0.134 ms), ties one, loses the fourth (0.127 against 0.034) and loses everywhere at 8 x 40960.  The radius is no shape:
+    # no class of padded shapes wins with the build included, so the shape rule is off (a bound no supported cloud reaches) and the
+    # pruned route is taken where the build is already paid -- the open cloud_scope holds the cloud sorted under these lengths
+    # (prebuild_cloud, an earlier ball query that pruned, or a pruned KNN search): four radii on one prebuilt cloud take 0.177 ms
+    # against 0.418 for four scans.
+    BALL_PRUNE_MIN_REFS = 1 << 30
+    BALL_PRUNE_MIN_CENTRES = 1024
+
+    @classmethod
+    def ball_prunable(cls, N, nsample):
+        """What the pruned ball query supports: one list entry per lane (nsample <= 64), 16 tile bounds per lane (N <= 65536)."""
+        return N <= 65536 and nsample <= 64
+
+    @classmethod
+    def prunes_ball(cls, M, N, nsample):
+        """Whether a ball query of (B,M,3) centres in a (B,N,3) cloud builds the sorted cloud and takes the pruned route: a pure
+        function of the padded shapes and nsample, with the two class attributes above as its thresholds."""
+        return cls.ball_prunable(N, nsample) and N >= cls.BALL_PRUNE_MIN_REFS and M >= cls.BALL_PRUNE_MIN_CENTRES
+
+    def ball_query(self, xyz, new_xyz, radius, nsample, xyz_lengths=None, new_xyz_lengths=None, return_count=False):
+        """ball_query(radius, nsample, xyz, new_xyz) (pointnet2_utils.py:200-225) on a padded batch: xyz (B,N,3), centres new_xyz
+        (B,M,3) -> idx (B,M,nsample) int32, with return_count also cnt (B,M) int32.
+        xyz_lengths / new_xyz_lengths (forms: lengths_tensor): element b is xyz[b, :xyz_lengths[b]] with the centres
+        new_xyz[b, :new_xyz_lengths[b]].  A live centre gets the first nsample indices inside the ball in ascending order, padded with
+        the first hit, zeros without a hit -- the reference's row for the two prefixes; a padded centre gets zeros.  cnt = min(hits,
+        nsample), 0 for padded centres: it tells "no hit" from "only point 0 hit".  Rows at or beyond a length are never read.
+        Route: the box-pruned search when the padded shapes say so (prunes_ball) or when the open cloud_scope already holds this
+        cloud sorted under these lengths (inside a scope several radii on one cloud share one build); the exhaustive scan
+        otherwise -- the same bits either way.  As everywhere, lengths share a sorted cloud only as one int32 device tensor."""
+        xyz, new_xyz = xyz.detach(), new_xyz.detach()  # an index-producing search: no gradient
+        B, N, _ = xyz.shape
+        M = new_xyz.shape[1]
+        rl, ql = lengths_tensor(xyz_lengths, B, N, xyz.device), lengths_tensor(new_xyz_lengths, B, M, xyz.device)
+        rlp, qlp = None if rl is None else _lib.iptr(rl), None if ql is None else _lib.iptr(ql)
+        idx = torch.empty((B, M, nsample), dtype=torch.int32, device=xyz.device)
+        cnt = torch.empty((B, M), dtype=torch.int32, device=xyz.device) if return_count else None
+        cntp = _lib.iptr(cnt) if return_count else None
+        if self.prunes_ball(M, N, nsample) or (self.ball_prunable(N, nsample) and self._holds_cloud(xyz, rl)):
+            _lib.fptr(xyz), _lib.fptr(new_xyz)  # validate before building the sorted cloud
+            rs, rperm, boxes = self._sorted_cloud(xyz, rl)
+            _call("mcp_ball_query_pruned", xyz, B, N, M, float(radius), int(nsample), _lib.fptr(new_xyz), _lib.fptr(rs), _lib.iptr(rperm),
+                  _lib.fptr(boxes), qlp, rlp, _lib.iptr(idx), cntp)
+        else:
+            _call("mcp_ball_query_lengths", xyz, B, N, M, float(radius), int(nsample), _lib.fptr(new_xyz), _lib.fptr(xyz), qlp, rlp,
+                  _lib.iptr(idx), cntp)
+        return (idx, cnt) if return_count else idx
 
     def knn_bruteforce(self, query, ref, k, mode=MCP_DIST_EXPANSION, return_dist=False, query_lengths=None, ref_lengths=None):
         """The exhaustive kernel regardless of size (tests compare both paths), with or without per-cloud lengths."""

@@ -30,24 +30,25 @@ def parse(path):
 
 def main():
     parent, now = parse(sys.argv[1]), parse(sys.argv[2])
-    base = lambda n: re.sub(r"<false>$", "", re.sub(r", false>$", ">", n))
+    stripped = lambda n: re.sub(r"<false>$", "", re.sub(r", false>$", ">", n))
+    base = lambda n: n if n in parent else stripped(n)   # a kernel that had the argument already keeps its name
     row = lambda v: "".join(f"{v[k]:>9}" for k in FIELDS)
     head = f"{'kernel':<44}{'':8}" + "".join(f"{k:>9}" for k in FIELDS)
     moved, flagged = 0, 0
+    new = [n for n in sorted(now) if n.endswith("true>") and n not in parent]   # `true` kernels the parent has too are compared
     print("FLAG = false: parent against now\n" + head)
     for n in sorted(now):
-        if n.endswith("true>"):
+        if n in new:
             continue
         same = all(parent[base(n)][k] == now[n][k] for k in FIELDS)
         moved += not same
         print(f"{base(n):<44}{'parent':<8}{row(parent[base(n)])}\n{'':<44}{'now':<8}{row(now[n])}   {'unchanged' if same else 'MOVED'}")
-    print(f"\n{sum(not n.endswith('true>') for n in now)} kernels, {moved} moved\n\nFLAG = true: new kernels\n" + head)
-    for n in sorted(now):
-        if n.endswith("true>"):
-            bad = any(now[n][k] != "0" for k in ("scratch", "sspill", "vspill"))
-            flagged += bad
-            print(f"{n:<44}{'':<8}{row(now[n])}{'   SPILLS' if bad else ''}")
-    print(f"\n{sum(n.endswith('true>') for n in now)} kernels, {flagged} with scratch or spilled registers")
+    print(f"\n{len(now) - len(new)} kernels, {moved} moved\n\nFLAG = true: new kernels\n" + head)
+    for n in new:
+        bad = any(now[n][k] != "0" for k in ("scratch", "sspill", "vspill"))
+        flagged += bad
+        print(f"{n:<44}{'':<8}{row(now[n])}{'   SPILLS' if bad else ''}")
+    print(f"\n{len(new)} kernels, {flagged} with scratch or spilled registers")
 
 
 if __name__ == "__main__":
