@@ -1,8 +1,9 @@
-"""The dense-layer kernel variants (csrc/linear.hip, mlp.hip, attention.hip) and the parity cases that reach them.
+"""The kernel variants of the dense layers (csrc/linear.hip, mlp.hip, attention.hip) and of the fused point layers (fusion.hip,
+cross.hip, pointconv.hip, ptblock.hip), and the parity cases that reach them.
 
 expected_kernel() mirrors the C dispatch: given an entry point and a shape it names the template instantiation that runs, in
 the form c++filt prints it without namespace and arguments ("linear_kernel<3, 2, 8>").  CASES parametrises
-test_kernel_variants_gpu.py; test_kernel_variants_cpu.py checks that every instantiation in the device assembly is named by at
+test_kernel_variants_gpu.py (dense layers) and test_fused_variants_gpu.py (point layers); test_kernel_variants_cpu.py checks that every instantiation in the device assembly is named by at
 least one case, so a variant added later without a parity case fails the CPU suite.  A plain module, imported by both tests."""
 
 
@@ -59,9 +60,97 @@ def _attention(bf, nq, nk, heads, hd):
     raise ValueError(f"attention: head width {hd} is not built")      # mcp_attention, attention.hip:574
 
 
+# ---- the fused point layers.  launch_grid() mirrors the grid arithmetic beside each dispatch, so that test_kernel_variants_cpu.py can
+# check that the cases reach the loop edges their comments name ----
+POINTCONV_LOWLEVEL_MAX = 16384   # mcp_pointconv_agg, pointconv.hip:474
+FUSION_WAVES, FUSION_GRID_CAP = 4, 4096                      # fusion.hip:34, :298
+CROSS_WAVES = {64: 4, 128: 8, 256: 4}                        # CrossShape<D>::NW, cross.hip:150; X256_WAVES, cross.hip:330
+CROSS_GRID_CAP = {64: 768, 128: 256, 256: 256}               # CrossShape<D>::GRID, cross.hip:152; launch_cross256, cross.hip:439
+PTBLOCK_WAVES, PTBLOCK_GRID_CAP = 4, 768                     # ptblock.hip:19, :194
+
+
+def _fusion(b, n, nb=64):
+    if nb != 64:                                                     # mcp_fusion, fusion.hip:291
+        raise ValueError(f"fusion: {nb} neighbours are not built")
+    return "fusion_split_kernel"                                     # fusion.hip:318 (fusion_kernel only under -DMCP_AB, :306-312)
+
+
+def _cross(d, k=32):
+    if k != 32 or d not in (64, 128, 256):                           # mcp_cross_volume, cross.hip:489
+        raise ValueError(f"cross: d={d}, k={k} is not built")
+    if d == 256:                                                     # cross.hip:495-497 -> launch_cross256 :440
+        return "cross256_stream_kernel"
+    return f"cross_kernel<{d}, 1>"                                   # launch_cross<D, 1>, cross.hip:452
+
+
+def _pointconv_agg(b, s, d, aligned=True, k=32):
+    if k != 32:                                                      # mcp_pointconv_agg, pointconv.hip:462
+        raise ValueError(f"pointconv_agg: {k} neighbours are not built")
+    total = b * s
+    vec4 = d % 4 == 0 and aligned                                    # pointconv.hip:466 (aligned: s_points on a 16-byte boundary)
+    if total <= POINTCONV_LOWLEVEL_MAX or not vec4:                  # pointconv.hip:474
+        if d >= 256 and total <= 8192:                               # pointconv.hip:476-477
+            return "pointconv_agg_lowlevel_kernel<1024>"
+        return "pointconv_agg_lowlevel_kernel<256>"                  # pointconv.hip:479
+    if d <= 32:                                                      # pointconv.hip:480
+        return "pointconv_agg_kernel<256, 32>"
+    if d <= 64:                                                      # pointconv.hip:481
+        return "pointconv_agg_kernel<256, 16>"
+    return "pointconv_agg_kernel<256, 8>"                            # pointconv.hip:482
+
+
+def _pointconv_linear(d, c_out, k=32):
+    if k != 32 or (d, c_out) not in ((32, 32), (64, 64)):            # mcp_pointconv_linear, pointconv.hip:495
+        raise ValueError(f"pointconv_linear: d={d}, c_out={c_out}, k={k} is not built")
+    return "pointconv_linear_kernel<32, 1>" if d == 32 else "pointconv_linear_kernel<64, 2>"   # pointconv.hip:501-520
+
+
+def _ptblock(c=64, k=16):
+    if c != 64 or k != 16:                                           # mcp_ptblock_attention, ptblock.hip:188
+        raise ValueError(f"ptblock: c={c}, k={k} is not built")
+    return "ptblock_kernel"                                          # ptblock.hip:197
+
+
+def launch_grid(op, **shape):
+    """(workgroups, units, units per workgroup step) of the launch: `units` are what the kernel's persistent loop deals out (points,
+    or point pairs in ptblock_kernel).  mcp_units_by_xcd (common.h:101-111) and cross_kernel (cross.hip:197-204) deal units by XCD
+    when the grid is a multiple of 8; cross256_stream_kernel always deals round-robin (cross.hip:356-358)."""
+    if op == "fusion":                                               # fusion.hip:304
+        total = shape["b"] * shape["n"]
+        return min(_cdiv(total, FUSION_WAVES), FUSION_GRID_CAP), total, FUSION_WAVES
+    if op == "cross":
+        d, total = shape["d"], shape["b"] * shape["n1"]
+        nw = CROSS_WAVES[d]
+        want = _cdiv(total, nw) if d == 256 else _cdiv(total, nw * 8)   # cross.hip:438, :459
+        return max(1, min(want, CROSS_GRID_CAP[d])), total, nw          # cross.hip:439, :462
+    if op == "pointconv_agg":
+        total = shape["b"] * shape["s"]
+        name = expected_kernel(op, **shape)
+        ppb = 8 if "lowlevel" in name else int(name[:-1].split(",")[1])  # LPPB, pointconv.hip:143; PPB :480-482
+        return min(_cdiv(total, ppb), 1 << 20), total, ppb              # pointconv.hip:471, :475
+    if op == "pointconv_linear":                                     # FPPB, pointconv.hip:260, :499
+        total = shape["b"] * shape["s"]
+        return min(_cdiv(total, 32), 1 << 20), total, 32
+    if op == "ptblock":                                              # ptblock.hip:103, :193-194
+        pairs = (shape["b"] * shape["n"] + 1) // 2
+        return max(1, min(_cdiv(pairs, PTBLOCK_WAVES * 4), PTBLOCK_GRID_CAP)), pairs, PTBLOCK_WAVES
+    raise ValueError(f"unknown op {op}")
+
+
 def expected_kernel(op, **shape):
     """Demangled name of the kernel the entry point `op` launches for `shape` (extra keys of a case are ignored):
-    linear (rows, ks, n[, policy_rows]), linear_narrow (k, n), mlp2 (rows, cin, hidden, cout), attention (bf, nq, nk, heads, hd)."""
+    linear (rows, ks, n[, policy_rows]), linear_narrow (k, n), mlp2 (rows, cin, hidden, cout), attention (bf, nq, nk, heads, hd),
+    fusion (b, n), cross (d), pointconv_agg (b, s, d[, aligned]), pointconv_linear (d, c_out), ptblock ()."""
+    if op == "fusion":
+        return _fusion(shape["b"], shape["n"], shape.get("nb", 64))
+    if op == "cross":
+        return _cross(shape["d"], shape.get("k", 32))
+    if op == "pointconv_agg":
+        return _pointconv_agg(shape["b"], shape["s"], shape["d"], shape.get("aligned", True), shape.get("k", 32))
+    if op == "pointconv_linear":
+        return _pointconv_linear(shape["d"], shape["c_out"], shape.get("k", 32))
+    if op == "ptblock":
+        return _ptblock(shape.get("c", 64), shape.get("k", 16))
     if op == "linear":
         return _linear(shape["rows"], shape["ks"], shape["n"], shape.get("policy_rows"))
     if op == "linear_narrow":
@@ -85,6 +174,31 @@ def _att(bf, nq, nk, heads, hd, shift=None, logits=None, same_keys=False):
     """shift None: be.attention (kv packed as [k | v]); an int: be.attention_rot with that kv_shift.  logits: scale q so that
     max |q.k| * scale is about this.  same_keys: every key of head 0 identical."""
     return dict(op="attention", bf=bf, nq=nq, nk=nk, heads=heads, hd=hd, shift=shift, logits=logits, same_keys=same_keys)
+
+
+def _fus(tag, b, n, **kw):
+    """same: p2 is p1 (every list holds a zero-length vector); dup: the second list repeats the first; extent: coordinates of
+    test_ops_gpu.cloud's extent; mutant=False: the output does not depend on the products (no two-term check)."""
+    return dict(op="fusion", tag=tag, b=b, n=n, **kw)
+
+
+def _crs(tag, d, b, n1, n2, **kw):
+    return dict(op="cross", tag=tag, d=d, b=b, n1=n1, n2=n2, **kw)
+
+
+def _agg(tag, b, n, s, d, **kw):
+    """aligned=False: s_points is a view 4 bytes into its storage."""
+    return dict(op="pointconv_agg", tag=tag, b=b, n=n, s=s, d=d, **kw)
+
+
+def _pcl(tag, b, n, s, d, **kw):
+    return dict(op="pointconv_linear", tag=tag, b=b, n=n, s=s, d=d, c_out=d, **kw)
+
+
+def _ptb(tag, b, n, **kw):
+    """packed: q, k, v are slices of one (B, N, 192) tensor in the checked run; logits: largest |attn| / 8; same: the 16 neighbours of a
+    point are one point."""
+    return dict(op="ptblock", tag=tag, b=b, n=n, **kw)
 
 
 T8 = 131072 + 37    # 8-wave row count with a ragged last workgroup
@@ -169,6 +283,51 @@ CASES = [
     _att(2, 130, 100, 8, 16, logits=80.0),
     _att(2, 130, 70, 8, 8, same_keys=True),
     _att(2, 130, 70, 8, 16, same_keys=True),
+    # ---- fusion_split_kernel: one point per wave, 4 waves, grid = min(ceil(total / 4), 4096); by XCD when grid % 8 == 0 ----
+    _fus("one-point", 1, 1, mutant=False),                   # 3 dead waves; the 64 neighbours are the one point: the blend is that point
+    _fus("3-points", 1, 3),                                  # one workgroup, one dead wave
+    _fus("5-points", 1, 5, same=True),                       # grid 2: the second workgroup has one live wave; zero-length vectors
+    _fus("xcd-ragged", 1, 61),                               # grid 16: eighths of 8 points, the last one has 5
+    _fus("grid-750", 2, 1499, same=True, dup=True),          # grid % 8 = 6: round-robin deal; p2 = p1 and every neighbour twice
+    _fus("grid-cap-2-rounds", 3, 5483, extent=True),         # 16449 points on 4096 workgroups by XCD: 2060-point eighths, steps of 2048
+    # ---- cross_kernel<64, 1>: 4 waves, grid = min(ceil(total / 32), 768) ----
+    _crs("xcd-ragged", 64, 3, 83, 70, extent=True),          # (a, e) 249 points, grid 8: eighths of 32 cut inside batch elements, the last has 25
+    _crs("grid-cap-stride>=n1", 64, 665, 37, 41),            # (b) 24605 points, grid 768 by XCD: steps of 384 points cross 10 batch elements
+    _crs("grid-10", 64, 2, 150, 150),                        # (c) round-robin deal, steps of 40 < n1
+    _crs("3-points", 64, 1, 3, 50),                          # (d) one workgroup, one wave without a point
+    # ---- cross_kernel<128, 1>: 8 waves, grid = min(ceil(total / 64), 256) ----
+    _crs("xcd-ragged", 128, 3, 167, 150, extent=True),       # (a, e) 501 points, grid 8: eighths of 63, the last has 60
+    _crs("grid-cap-stride>=n1", 128, 443, 37, 41),           # (b) 16391 points, grid 256 by XCD: steps of 256 points cross 6 batch elements
+    _crs("grid-10", 128, 2, 300, 300),                       # (c)
+    _crs("5-points", 128, 1, 5, 50),                         # (d) three waves without a point
+    # ---- cross256_stream_kernel: 4 waves in lockstep, grid = min(ceil(total / 4), 256), round-robin rounds ----
+    _crs("ragged-workgroup", 256, 3, 83, 70, extent=True),   # (c, e) 249 points, grid 63: the last workgroup has one live wave
+    _crs("grid-cap-3-rounds", 256, 59, 37, 41),              # (b) 2183 points, grid 256: rounds of 1024 cross 27 batch elements; 3 points in the last step
+    _crs("3-points", 256, 1, 3, 50),                         # (d) the dead wave recomputes the last point and does not store
+    # ---- pointconv_agg_lowlevel_kernel<256 | 1024>: 8 points per workgroup, one channel per thread ----
+    _agg("total-16384", 4, 4096, 4096, 32),                  # the last total of the low-level route; S = N; grid 2048 by XCD
+    _agg("d%4", 5, 3300, 3277, 5),                           # 16385 centres, d = 5: no float4 gather
+    _agg("unaligned", 5, 3300, 3277, 32, aligned=False),     # 16385 centres, s_points 4 bytes off a 16-byte boundary
+    _agg("wide-few", 2, 100, 77, 256, extent=True),          # <1024>: 154 centres, grid 20, the last workgroup has 2
+    # ---- pointconv_agg_kernel<256, PPB>: PPB points per workgroup, (point, 4 channels) items ----
+    _agg("total-16385", 5, 3300, 3277, 32, extent=True),     # <256,32> the first streaming total: grid 513, the last workgroup has 1 point
+    _agg("d4=1", 5, 3327, 3327, 4),                          # <256,32> one item per point; S = N; grid 520 by XCD, the last workgroup has 27
+    _agg("d=36", 5, 3300, 3277, 36),                         # <256,16> 9 items per point (144 of 256 threads), grid 1025
+    _agg("d=64", 3, 6000, 5500, 64, extent=True),            # <256,16> grid 1032 by XCD, the last workgroup has 4 points
+    _agg("d=128", 2, 8200, 8193, 128),                       # <256,8> 256 items: one round; grid 2049, the last workgroup has 2
+    _agg("d=256", 1, 16445, 16445, 256),                     # <256,8> 512 items: two rounds; S = N; grid 2056 by XCD, the last workgroup has 5
+    # ---- pointconv_linear_kernel<32, 1> / <64, 2>: 32 centres per workgroup ----
+    _pcl("few", 1, 700, 333, 32),                            # 333 centres: the last group has 13
+    _pcl("above-16384", 3, 6000, 5463, 32, extent=True),     # 16389 centres, grid 513: the last group has 5
+    _pcl("few", 2, 515, 77, 64, extent=True),                # 154 centres: the last group has 26
+    _pcl("above-16384", 2, 8200, 8200, 64),                  # 16400 centres, grid 513: the last group has 16
+    # ---- ptblock_kernel: two points per wave, 4 waves, grid = min(ceil(pairs / 16), 768) ----
+    _ptb("one-point", 1, 1),                                 # the odd tail alone: the second half-wave recomputes point 0
+    _ptb("odd-B1", 1, 333, extent=True),                     # 167 pairs, grid 11 (round-robin), odd tail
+    _ptb("odd-B3", 3, 111, packed=True),                     # 333 points: pairs straddle batch elements; q/k/v with row stride 192
+    _ptb("grid-cap-odd", 3, 8183),                           # 24549 points, 12275 pairs on 768 workgroups by XCD: 4 rounds, ragged eighth, odd tail
+    _ptb("xcd-ragged", 2, 117, logits=80.0),                 # 117 pairs in 30 steps on 8 workgroups: eighths of 4 steps, the last has 5 pairs; large logits
+    _ptb("same-neighbour", 2, 125, same=True),               # a uniform softmax in every channel
 ]
 
 
@@ -177,6 +336,6 @@ def cases(op):
 
 
 def case_id(c):
-    """A readable pytest id: the variant and the shape."""
-    shape = ",".join(f"{k}={v}" for k, v in c.items() if k != "op" and v not in (None, False))
+    """A readable pytest id: the variant and the shape (the fused cases: their tag first)."""
+    shape = ",".join(v if k == "tag" else f"{k}={v}" for k, v in c.items() if k != "op" and v not in (None, False))
     return f"{expected_kernel(**c)}[{shape}]".replace(" ", "")
