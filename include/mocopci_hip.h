@@ -404,6 +404,31 @@ int mcp_cross_pack(int d, const float *wpos, const float *bpos, const float *wml
 int mcp_cross_volume(int b, int n1, int n2, int d, int k, const float *xyz1, const float *xyz2, const float *points1,
                      const float *points2, const int *idx, const int *idx2, const int *bmap, int shared, const float *packed, float *out, mcp_stream_t stream);
 
+/* Set-abstraction layer of pointnet2 after its neighbour search (PointnetSAModule[MSG], pointnet2_modules.py; SetConv and
+ * FlowEmbedding, models/layers.py:76-117): grouping, shared per-pair MLP and the pool over the neighbours in one kernel.
+ * xyz (B,N,3), new_xyz (B,M,3), features (B,N,C) channel-last or NULL (c = 0), idx (B,M,nsample) int32 into the N points
+ * -> out (B,M,widths[L-1]).  For a live centre p of element bb, with k_j = idx[bb,p,j]:
+ *     x_j = [xyz[bb,k_j] - new_xyz[bb,p] (if use_xyz) | features[bb,k_j]],
+ *     h1_j = ReLU(W1 x_j + b1 (+ row_bias[bb,p])),  hl_j = ReLU(Wl h(l-1)_j + bl),
+ *     out[bb,p] = max_j hL_j (pool 0) or the mean over all nsample slots (pool 1);
+ * repeated indices count as often as they appear (the ball query's "repeat the first hit" padding needs no count).
+ * W_l (widths[l], cin_l) row-major and b_l (widths[l]) -- eval-mode BatchNorm already folded in by the caller -- are packed ONCE by
+ * mcp_group_mlp_pack into the MFMA-operand image (mcp_group_mlp_packed_floats floats, 16-byte aligned, caller-owned; w and b are
+ * host arrays of `layers` device pointers, widths a host array).  row_bias (B,M,widths[0]) or NULL is added before the first ReLU:
+ * with the centre's own features sent through mcp_linear it expresses FlowEmbedding's concatenation.  qlen (B) device int32 or
+ * NULL, as in mcp_ball_query_lengths (clamped to [0, m] in the kernel, NULL = every centre live): a centre at or beyond qlen[bb]
+ * writes zeros and none of its rows of new_xyz, idx or row_bias is read.
+ * Supported: 1 <= nsample <= 64; c a multiple of 4, 0 <= c <= 128 (c = 0 needs use_xyz); 1 to 3 layers; hidden widths in
+ * {32, 64, 128}, last width in {32, 64, 128, 256}.  Anything else: MCP_ERR_UNSUPPORTED (mcp_group_mlp_packed_floats: 0), nothing
+ * is launched.  features, row_bias, packed, out 16-byte aligned (MCP_ERR_BAD_ARG).  Indices are trusted.  No allocation, no
+ * environment variable, no host read of a length. */
+int mcp_group_mlp_packed_floats(int c, int layers, const int *widths);
+int mcp_group_mlp_pack(int c, int use_xyz, int layers, const int *widths, const float *const *w, const float *const *b, float *packed,
+                       mcp_stream_t stream);
+int mcp_group_mlp(int b, int n, int m, int c, int nsample, int use_xyz, int pool, int layers, const int *widths, const float *xyz,
+                  const float *new_xyz, const float *features, const int *idx, const int *qlen, const float *row_bias, const float *packed,
+                  float *out, mcp_stream_t stream);
+
 /* Backward of mcp_cross_volume for one cross layer given by its own weights (the reference differentiates pointconv_util.py:765-781
  * with autograd over three materialised (B,D,32,N1) tensors; its hand-written backward pieces are the atomicAdd scatters of
  * group_points_gpu.cu:8-44).  xyz1, xyz2, points1, points2, idx / idx2 as mcp_cross_volume (no batch map); wpos (D,3), bpos (D),

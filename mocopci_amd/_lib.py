@@ -74,6 +74,9 @@ SIGNATURES = {
     "mcp_cross_packed_floats": [_i],
     "mcp_cross_pack": [_i, _p, _p, _p, _p, _p, _p],
     "mcp_cross_volume": [_i] * 5 + [_p] * 7 + [_i, _p, _p, _p],
+    "mcp_group_mlp_packed_floats": [_i, _i, _p],
+    "mcp_group_mlp_pack": [_i, _i, _i, _p, _p, _p, _p, _p],
+    "mcp_group_mlp": [_i] * 8 + [_p] * 10,
     "mcp_cross_grad_floats": [_i],
     "mcp_cross_grad_workspace_bytes": [_i, _i, _i],
     "mcp_cross_grad": [_i] * 5 + [_p] * 17 + [ctypes.c_size_t, _p],

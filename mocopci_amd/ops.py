@@ -594,6 +594,87 @@ def _valid_counts(lens, batch, limit, device):
     return lens.clamp(0, limit)
 
 
+# ---- set-abstraction layer (csrc/group_mlp.hip) ----
+GROUP_MLP_LDS_IMAGE_BYTES = 64 * 1024
+GROUP_MLP_POOLS = {"max": 0, "max_pool": 0, "mean": 1, "avg": 1, "avg_pool": 1}
+
+
+def group_mlp_supported(c, widths, nsample=1, use_xyz=True):
+    """The shapes mcp_group_mlp is built for: c input feature channels, layer widths, neighbours per centre."""
+    widths = list(widths)
+    if not (1 <= len(widths) <= 3 and 1 <= nsample <= 64 and 0 <= c <= 128 and c % 4 == 0 and (c > 0 or use_xyz)):
+        return False
+    return all(w in (32, 64, 128) for w in widths[:-1]) and widths[-1] in (32, 64, 128, 256)
+
+
+def group_mlp_image_bytes(c, widths):
+    """Bytes of the split-bf16 weight pieces of a supported (c, widths): per layer 32-channel output tiles x k-steps x 3 pieces x
+    64 lanes x 16 B, the feature k-steps of layer 1 rounded up to 1, 2, 4 or 8."""
+    ks0 = (c + 15) // 16
+    ks = [0 if ks0 == 0 else 1 << (ks0 - 1).bit_length()] + [w // 16 for w in widths[:-1]]
+    return sum((w // 32) * k * 3 * 64 * 16 for w, k in zip(widths, ks))
+
+
+def group_mlp_weights_in_lds(c, widths):
+    """Python mirror of the kernel's one dispatch predicate (gm_weights_in_lds): the weight image is staged in LDS once per
+    workgroup when it is at most 64 KB, and read through L2 otherwise."""
+    return group_mlp_image_bytes(c, list(widths)) <= GROUP_MLP_LDS_IMAGE_BYTES
+
+
+# Shape classes (column group 8 | 16 | 32 | 64, feature channels, widths) -> fewest centres B * M at which sampling-free
+# "ball query + mcp_group_mlp" measured faster than the composition "mcp_query_and_group + folded convs + max" by more than the
+# composition's own spread (tools/group_mlp_times.py -> profiles/group_mlp_times.json).  A class without a row keeps the composition.
+GROUP_MLP_FUSED_CLASSES = {}
+
+
+def group_mlp_class(c, widths, nsample):
+    return (8 if nsample <= 8 else 16 if nsample <= 16 else 32 if nsample <= 32 else 64, int(c), tuple(int(w) for w in widths))
+
+
+def group_mlp_routes_fused(c, widths, nsample, centres):
+    """The modules' route predicate: a pure function of the padded shapes."""
+    least = GROUP_MLP_FUSED_CLASSES.get(group_mlp_class(c, widths, nsample))
+    return least is not None and centres >= least
+
+
+def fold_conv_bn(conv, bn=None):
+    """(W (out, in), b (out,)) fp32 of a 1x1 convolution (or Linear) followed by an eval-mode BatchNorm with the layer's own eps:
+    W' = W * g / sqrt(var + eps), b' = (b - mean) * g / sqrt(var + eps) + beta, folded in float64 and rounded once."""
+    w = conv.weight.detach().double().flatten(1)
+    b = conv.bias.detach().double() if conv.bias is not None else w.new_zeros(w.shape[0])
+    if bn is not None:
+        g = bn.weight.detach().double() if bn.weight is not None else w.new_ones(w.shape[0])
+        beta = bn.bias.detach().double() if bn.bias is not None else w.new_zeros(w.shape[0])
+        scale = g / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+        w, b = w * scale[:, None], (b - bn.running_mean.detach().double()) * scale + beta
+    return w.float().contiguous(), b.float().contiguous()
+
+
+def group_mlp_pack_weights(weights, use_xyz=True):
+    """The MFMA-operand image of mcp_group_mlp from [(W (out, in), b (out,)), ...] fp32 device tensors -> (packed, widths)."""
+    widths = [int(w.shape[0]) for w, _ in weights]
+    c = int(weights[0][0].shape[1]) - (3 if use_xyz else 0)
+    lib = _lib.load()
+    wid = (ctypes.c_int * len(widths))(*widths)
+    n = lib.mcp_group_mlp_packed_floats(c, len(widths), wid) if len(widths) <= 3 else 0
+    if n == 0 or (c == 0 and not use_xyz):
+        raise _lib.Unsupported(f"group_mlp: unsupported shape c={c} widths={widths}")
+    ws = [w.contiguous() for w, _ in weights]
+    bs = [b.contiguous() for _, b in weights]
+    packed = torch.empty((n,), dtype=torch.float32, device=ws[0].device)
+    wp = (ctypes.c_void_p * len(ws))(*[_lib.fptr(w) for w in ws])
+    bp = (ctypes.c_void_p * len(bs))(*[_lib.fptr(b) for b in bs])
+    _call("mcp_group_mlp_pack", packed, c, int(bool(use_xyz)), len(widths), wid, wp, bp, _lib.fptr(packed))
+    return packed, widths
+
+
+def group_mlp_pack(convs, bns=None, use_xyz=True):
+    """Pack the shared MLP of a set-abstraction layer once: convs are its 1x1 Conv2d (or Linear) modules in order, bns the eval-mode
+    BatchNorm that follows each (None, or None entries, where there is none).  -> (packed, widths) for HipBackend.group_mlp."""
+    bns = [None] * len(convs) if bns is None else list(bns)
+    return group_mlp_pack_weights([fold_conv_bn(c, b) for c, b in zip(convs, bns)], use_xyz)
+
+
 class _ChamferLengthsFn(torch.autograd.Function):
     """_ChamferFn over the valid prefixes of a padded batch (pytorch3d's x_lengths / y_lengths with its default reductions):
     value_b = sum_{i<xl} dxy_i / max(xl,1) + sum_{j<yl} dyx_j / max(yl,1).  Forward: the length-aware search returns 0 for every
@@ -1188,6 +1269,30 @@ class HipBackend:
         if grad.wants_grad(xyz1, xyz2, points1, points2, wpos, bpos, wmlp, bmlp) and k_total == 32 and wmlp.shape[0] in (64, 128, 256):
             return _CrossFn.apply(self, ia.contiguous(), None if ib is None else ib.contiguous(), xyz1, xyz2, points1, points2, wpos, bpos, wmlp, bmlp)
         return grad.run(fused, lambda *a: grad.cross_twin(self.group_rows, *a), xyz1, xyz2, points1, points2, idx, wpos, bpos, wmlp, bmlp)
+
+    def group_mlp(self, xyz, new_xyz, features, idx, packed, widths, pool="max", use_xyz=True, new_xyz_lengths=None, row_bias=None):
+        """Set-abstraction layer after its neighbour search (PointnetSAModule[MSG]; SetConv / FlowEmbedding, models/layers.py:76-117)
+        in one launch: xyz (B,N,3), centres new_xyz (B,M,3), features (B,N,C) channel-last or None, idx (B,M,nsample) int32,
+        (packed, widths) = group_mlp_pack(...) -> (B,M,widths[-1]): the pool ("max" | "mean") over the nsample slots of the shared
+        MLP of [xyz[idx] - new_xyz (use_xyz) | features[idx]], every layer followed by ReLU.  row_bias (B,M,widths[0]) is added
+        before the first ReLU (the centre's own features through the first layer's columns for them: FlowEmbedding's concatenation).
+        new_xyz_lengths (forms: lengths_tensor): centres at or beyond the length give zeros and their rows are never read.
+        Inference only (no gradient); unsupported shapes raise _lib.Unsupported."""
+        B, N, _ = xyz.shape
+        M, nsample = new_xyz.shape[1], idx.shape[2]
+        C = 0 if features is None else features.shape[2]
+        widths = [int(w) for w in widths]
+        ql = lengths_tensor(new_xyz_lengths, B, M, xyz.device)
+        out = torch.empty((B, M, widths[-1]), dtype=torch.float32, device=xyz.device)
+        if B == 0 or M == 0:
+            return out
+        wid = (ctypes.c_int * len(widths))(*widths)
+        if row_bias is not None and tuple(row_bias.shape) != (B, M, widths[0]):
+            raise RuntimeError(f"row_bias: expected {(B, M, widths[0])}, got {tuple(row_bias.shape)}")
+        _call("mcp_group_mlp", xyz, B, N, M, C, nsample, int(bool(use_xyz)), GROUP_MLP_POOLS[pool], len(widths), wid, _lib.fptr(xyz),
+              _lib.fptr(new_xyz), None if features is None else _lib.fptr(features), _lib.iptr(idx), None if ql is None else _lib.iptr(ql),
+              None if row_bias is None else _lib.fptr(row_bias), _lib.fptr(packed), _lib.fptr(out))
+        return out
 
     def ptblock_layer(self, xyz, q, k, v, idx, weights, packed=None):
         """TransformerBlock vector attention from the block's own weights (wd1,bd1,wd2,bd2,wg1,bg1,wg2,bg2); differentiable."""

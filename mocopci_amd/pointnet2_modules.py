@@ -1,0 +1,141 @@
+"""Set-abstraction modules of pointnet2 (the reference's pointnet2/pointnet2_modules.py: PointnetSAModuleMSG, PointnetSAModule) on
+the MI355X kernels.  Same constructor arguments, tensor layouts (xyz (B,N,3), features (B,C,N) -> new_xyz (B,npoint,3),
+(B, sum of the scales' last widths, npoint)) and parameter names, so a state_dict of the reference classes loads strictly
+(tests/golden/pointnet2_sa_state_keys.json lists the names of one two-scale module).
+
+Two routes give the same layer:
+  * the composition -- QueryAndGroup, the shared Conv2d / BatchNorm2d / ReLU stack, the pool over the neighbours -- is the definition
+    and carries the gradient;
+  * the fused route -- sampling, one ball query per scale, one mcp_group_mlp launch per scale (ops.HipBackend.group_mlp) -- writes
+    nothing but the pooled features.  It is taken only under no-grad, in eval(), for a shape the kernel supports, and for a shape
+    class that the measurement of tools/group_mlp_times.py found faster (ops.GROUP_MLP_FUSED_CLASSES; `route` overrides it).
+PointnetFPModule is not provided: its per-point chain is served by the Linear kernels."""
+from typing import List
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import ops, pointnet2_utils as pu
+
+
+def _conv_unit(cin, cout, bn, instance_norm):
+    """One layer of the shared MLP under the reference's names: conv, bn.bn, activation, in."""
+    unit = nn.Sequential()
+    conv = nn.Conv2d(cin, cout, kernel_size=(1, 1), bias=not bn)
+    nn.init.kaiming_normal_(conv.weight)
+    if conv.bias is not None:
+        nn.init.zeros_(conv.bias)
+    unit.add_module("conv", conv)
+    if bn:
+        norm = nn.Sequential()
+        norm.add_module("bn", nn.BatchNorm2d(cout))
+        unit.add_module("bn", norm)
+    unit.add_module("activation", nn.ReLU(inplace=True))
+    if instance_norm and not bn:
+        unit.add_module("in", nn.InstanceNorm2d(cout, affine=False, track_running_stats=False))
+    return unit
+
+
+def _shared_mlp(spec, bn, instance_norm):
+    mlp = nn.Sequential()
+    for j in range(len(spec) - 1):
+        mlp.add_module(f"layer{j}", _conv_unit(spec[j], spec[j + 1], bn, instance_norm))
+    return mlp
+
+
+class PointnetSAModuleMSG(nn.Module):
+    """Set abstraction with multi-scale grouping: npoint centres by furthest point sampling, per scale a ball of radii[i] with
+    nsamples[i] slots, the shared MLP mlps[i] (its first entry counts the feature channels; 3 is added with use_xyz) and the pool.
+    npoint=None groups the whole cloud (GroupAll).  route: "measured" (default), "always" or "never" for the fused route."""
+
+    def __init__(self, *, npoint: int, radii: List[float], nsamples: List[int], mlps: List[List[int]], bn: bool = True, use_xyz: bool = True,
+                 pool_method="max_pool", instance_norm=False):
+        super().__init__()
+        if not (len(radii) == len(nsamples) == len(mlps)):
+            raise ValueError("radii, nsamples and mlps need one entry per scale")
+        if pool_method not in ("max_pool", "avg_pool"):
+            raise NotImplementedError(pool_method)
+        self.npoint, self.use_xyz, self.pool_method, self.bn, self.instance_norm = npoint, use_xyz, pool_method, bn, instance_norm
+        self.route = "measured"
+        self.groupers, self.mlps = nn.ModuleList(), nn.ModuleList()
+        for radius, nsample, spec in zip(radii, nsamples, mlps):
+            self.groupers.append(pu.QueryAndGroup(radius, nsample, use_xyz=use_xyz) if npoint is not None else pu.GroupAll(use_xyz))
+            spec = [spec[0] + (3 if use_xyz else 0), *spec[1:]]
+            self.mlps.append(_shared_mlp(spec, bn, instance_norm))
+        self.__dict__["_packed"] = {}
+
+    # ---- fused route -----------------------------------------------------------------------------------------------------------
+    def _layers(self, i):
+        units = list(self.mlps[i].children())
+        return [u.conv for u in units], [u.bn.bn if self.bn else None for u in units]
+
+    def _packed_weights(self, i):
+        """(packed, widths) of scale i, kept until one of its parameters or buffers is written or replaced."""
+        state = [*self.mlps[i].parameters(), *self.mlps[i].buffers()]
+        key = tuple((id(t), t._version, t.device) for t in state)
+        hit = self.__dict__["_packed"].get(i)
+        if hit is None or hit[0] != key:
+            hit = self.__dict__["_packed"][i] = (key, ops.group_mlp_pack(*self._layers(i), use_xyz=self.use_xyz))
+        return hit[1]
+
+    def fused_scale(self, i, channels, centres):
+        """Whether scale i of a call with `channels` feature channels and `centres` = B * npoint centres takes the fused route."""
+        if self.training or self.npoint is None or self.route == "never" or (self.instance_norm and not self.bn):
+            return False
+        g = self.groupers[i]
+        widths = [u.conv.out_channels for u in self.mlps[i].children()]
+        if not ops.group_mlp_supported(channels, widths, g.nsample, self.use_xyz):
+            return False
+        return self.route == "always" or ops.group_mlp_routes_fused(channels, widths, g.nsample, centres)
+
+    def forward(self, xyz: torch.Tensor, features: torch.Tensor = None, new_xyz=None, xyz_lengths=None, new_xyz_lengths=None):
+        """xyz (B,N,3), features (B,C,N) or None, new_xyz (B,npoint,3) or None (sampled here) -> new_xyz, (B, sum C_out, npoint).
+        xyz_lengths / new_xyz_lengths (forms: ops.lengths_tensor): element b is its first xyz_lengths[b] points with the centres
+        new_xyz[b, :new_xyz_lengths[b]]; padded centres, and every centre of an element without a point, give zeros."""
+        be = ops.backend()
+        B, N, _ = xyz.shape
+        if new_xyz is None and self.npoint is not None:
+            picked = be.fps(xyz.contiguous(), self.npoint, lengths=xyz_lengths)
+            new_xyz = pu.gather_operation(xyz.transpose(1, 2).contiguous(), picked).transpose(1, 2).contiguous()
+        wants_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (xyz, features, new_xyz, *self.parameters()))
+        M = 1 if self.npoint is None else new_xyz.shape[1]
+        C = 0 if features is None else features.shape[1]
+        with_lengths = self.npoint is not None and (xyz_lengths is not None or new_xyz_lengths is not None)
+        rl = ql = live = None
+        if with_lengths:
+            rl, ql = ops.lengths_tensor(xyz_lengths, B, N, xyz.device), ops.lengths_tensor(new_xyz_lengths, B, M, xyz.device)
+            count = torch.full((B,), M, dtype=torch.int32, device=xyz.device) if ql is None else ql.clamp(0, M)
+            if rl is not None:
+                count = torch.where(rl > 0, count, torch.zeros_like(count))
+            live = torch.arange(M, device=xyz.device).view(1, M) < count.view(B, 1)
+        rows = None  # features channel-last, made once for the fused scales
+        outs = []
+        for i, grouper in enumerate(self.groupers):
+            if not wants_grad and self.fused_scale(i, C, B * M):
+                packed, widths = self._packed_weights(i)
+                x, c = xyz.detach().contiguous(), new_xyz.detach().contiguous()
+                if features is not None and rows is None:
+                    rows = features.detach().transpose(1, 2).contiguous()
+                idx = be.ball_query(x, c, grouper.radius, grouper.nsample, xyz_lengths=rl, new_xyz_lengths=ql)
+                pooled = be.group_mlp(x, c, rows, idx, packed, widths, pool=self.pool_method, use_xyz=self.use_xyz,
+                                      new_xyz_lengths=count if with_lengths else None)
+                outs.append(pooled.transpose(1, 2))
+                continue
+            grouped = grouper(xyz, new_xyz, features, rl, ql) if with_lengths else grouper(xyz, new_xyz, features)
+            h = self.mlps[i](grouped)
+            pool = F.max_pool2d if self.pool_method == "max_pool" else F.avg_pool2d
+            h = pool(h, kernel_size=[1, h.size(3)]).squeeze(-1)
+            if live is not None:
+                h = torch.where(live.view(B, 1, M), h, h.new_zeros(()))
+            outs.append(h)
+        return new_xyz, torch.cat(outs, dim=1)
+
+
+class PointnetSAModule(PointnetSAModuleMSG):
+    """Set abstraction with one scale."""
+
+    def __init__(self, *, mlp: List[int], npoint: int = None, radius: float = None, nsample: int = None, bn: bool = True, use_xyz: bool = True,
+                 pool_method="max_pool", instance_norm=False):
+        super().__init__(mlps=[mlp], npoint=npoint, radii=[radius], nsamples=[nsample], bn=bn, use_xyz=use_xyz, pool_method=pool_method,
+                         instance_norm=instance_norm)

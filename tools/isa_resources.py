@@ -2,7 +2,7 @@
 commits): the compiler's own figures per kernel -- vector, accumulator and scalar registers, static LDS, scratch bytes per lane,
 spilled scalar / vector registers, waves per SIMD the registers allow.  A kernel of the second file whose last template argument is
 `false` is compared with the kernel of the first file that lacks that argument (a compile-time flag added since); kernels that end
-in `true` are listed on their own.
+in `true`, and kernels the first file does not have at all (a new unit: pass an empty file), are listed on their own.
 
     python tools/isa_resources.py PARENT.s NOW.s > profiles/NAME_resources.txt"""
 import re
@@ -23,7 +23,9 @@ def parse(path):
             out[m.group(1)]["sspill"] = re.search(r"\.sgpr_spill_count:\s*(\d+)", m.group(2)).group(1)
             out[m.group(1)]["vspill"] = re.search(r"\.vgpr_spill_count:\s*(\d+)", m.group(2)).group(1)
     names = list(out)
-    plain = subprocess.run(["c++filt"] + names, capture_output=True, text=True, check=True).stdout.split("\n")
+    if not names:   # an empty file: c++filt without arguments would wait for its standard input
+        return {}
+    plain =subprocess.run(["c++filt"] + names, capture_output=True, text=True, check=True).stdout.split("\n")
     short = [re.sub(r"\(.*", "", x.replace("void ", "").replace("(anonymous namespace)::", "")) for x in plain]
     return dict(zip(short, (out[n] for n in names)))
 
@@ -35,7 +37,8 @@ def main():
     row = lambda v: "".join(f"{v[k]:>9}" for k in FIELDS)
     head = f"{'kernel':<44}{'':8}" + "".join(f"{k:>9}" for k in FIELDS)
     moved, flagged = 0, 0
-    new = [n for n in sorted(now) if n.endswith("true>") and n not in parent]   # `true` kernels the parent has too are compared
+    # `true` kernels the parent has too are compared; a kernel the parent lacks under either name (a new unit) is listed on its own
+    new = [n for n in sorted(now) if n not in parent and (n.endswith("true>") or base(n) not in parent)]
     print("FLAG = false: parent against now\n" + head)
     for n in sorted(now):
         if n in new:
