@@ -429,6 +429,30 @@ int mcp_group_mlp(int b, int n, int m, int c, int nsample, int use_xyz, int pool
                   const float *new_xyz, const float *features, const int *idx, const int *qlen, const float *row_bias, const float *packed,
                   float *out, mcp_stream_t stream);
 
+/* Feature-propagation layer of pointnet2 after its three-neighbour search (PointnetFPModule, pointnet2_modules.py:116-156;
+ * FeaturePropagation, models/layers.py:150-178): blend of the three known rows, concatenation with the skip row and the shared
+ * per-point MLP in one kernel.  Channel-last known_feats (B,m,C2), skip (B,n,C1) or NULL (c1 = 0), idx (B,n,3) int32 into the m
+ * known points, dist (B,n,3) as three_nn returns it (square roots) -> out (B,n,widths[L-1]).  For a live row p of element bb:
+ *     weights by `rule`: 0: w = w3 (B,n,3) as given (dist is not read, may be NULL);
+ *                        1: r_j = 1 / (dist_j + 1e-8),                 w_j = r_j / ((r_0 + r_1) + r_2)   (pointnet2);
+ *                        2: r_j = 1 / max(dist_j * dist_j, 1e-10),     the same normalisation             (layers.py);
+ *     x = [(w0 f[i0] + w1 f[i1]) + w2 f[i2] | skip[bb,p]],   h1 = ReLU(W1 x + b1), ..., out[bb,p] = ReLU(WL h(L-1) + bL).
+ * Under rules 1 and 2 a slot whose dist is +inf (fewer than three known points) has weight exactly 0 and its row of known_feats
+ * is not read; three such slots give an interpolated part of exact zeros, never a NaN.  W_l (widths[l], cin_l) row-major and b_l
+ * -- eval-mode BatchNorm already folded in by the caller -- are packed ONCE by mcp_fp_mlp_pack (mcp_fp_mlp_packed_floats floats,
+ * 16-byte aligned, caller-owned; w and b are host arrays of `layers` device pointers, widths a host array).  ulen (B) device int32
+ * or NULL (clamped to [0, n] in the kernel, NULL = every row live): a row at or beyond ulen[bb] writes zeros and none of its rows
+ * of idx, dist, w3 or skip is read.  Every output element is written.
+ * Supported: c2 a multiple of 4 in 4 .. 512; 0 <= c1 <= 512 (any value); c1 + c2 <= 768; 1 to 3 layers of width 32, 64, 128 or
+ * 256.  Anything else: MCP_ERR_UNSUPPORTED (mcp_fp_mlp_packed_floats: 0), nothing is launched.  known_feats, packed, out -- and
+ * skip when c1 is a multiple of 4 -- 16-byte aligned (MCP_ERR_BAD_ARG).  Indices are trusted.  No allocation, no environment
+ * variable, no host read of a length. */
+int mcp_fp_mlp_packed_floats(int c2, int c1, int layers, const int *widths);
+int mcp_fp_mlp_pack(int c2, int c1, int layers, const int *widths, const float *const *w, const float *const *b, float *packed,
+                    mcp_stream_t stream);
+int mcp_fp_mlp(int b, int n, int m, int c2, int c1, int rule, int layers, const int *widths, const float *known_feats, const float *skip,
+               const int *idx, const float *dist, const float *w3, const int *ulen, const float *packed, float *out, mcp_stream_t stream);
+
 /* Backward of mcp_cross_volume for one cross layer given by its own weights (the reference differentiates pointconv_util.py:765-781
  * with autograd over three materialised (B,D,32,N1) tensors; its hand-written backward pieces are the atomicAdd scatters of
  * group_points_gpu.cu:8-44).  xyz1, xyz2, points1, points2, idx / idx2 as mcp_cross_volume (no batch map); wpos (D,3), bpos (D),

@@ -77,6 +77,9 @@ SIGNATURES = {
     "mcp_group_mlp_packed_floats": [_i, _i, _p],
     "mcp_group_mlp_pack": [_i, _i, _i, _p, _p, _p, _p, _p],
     "mcp_group_mlp": [_i] * 8 + [_p] * 10,
+    "mcp_fp_mlp_packed_floats": [_i, _i, _i, _p],
+    "mcp_fp_mlp_pack": [_i, _i, _i, _p, _p, _p, _p, _p],
+    "mcp_fp_mlp": [_i] * 7 + [_p] * 10,
     "mcp_cross_grad_floats": [_i],
     "mcp_cross_grad_workspace_bytes": [_i, _i, _i],
     "mcp_cross_grad": [_i] * 5 + [_p] * 17 + [ctypes.c_size_t, _p],

@@ -675,6 +675,88 @@ def group_mlp_pack(convs, bns=None, use_xyz=True):
     return group_mlp_pack_weights([fold_conv_bn(c, b) for c, b in zip(convs, bns)], use_xyz)
 
 
+# ---- feature-propagation layer (csrc/fp_mlp.hip) ----
+FP_MLP_LDS_IMAGE_BYTES = 64 * 1024
+FP_MLP_RULES = {"given": 0, "pointnet2": 1, "flownet3d": 2}
+
+
+def fp_mlp_supported(c2, c1, widths):
+    """The shapes mcp_fp_mlp is built for: c2 channels of the known (interpolated) features, c1 of the skip row, layer widths."""
+    widths = list(widths)
+    if not (1 <= len(widths) <= 3 and 4 <= c2 <= 512 and c2 % 4 == 0 and 0 <= c1 <= 512 and c1 + c2 <= 768):
+        return False
+    return all(w in (32, 64, 128, 256) for w in widths)
+
+
+def fp_mlp_image_bytes(c2, c1, widths):
+    """Bytes of the split-bf16 weight pieces of a supported shape: per layer 32-channel output tiles x k-steps x 3 pieces x 64 lanes
+    x 16 B; layer 1 has the k-steps of the interpolated part and those of the skip row, each rounded up on its own."""
+    ks = [(c2 + 15) // 16 + (c1 + 15) // 16] + [w // 16 for w in widths[:-1]]
+    return sum((w // 32) * k * 3 * 64 * 16 for w, k in zip(widths, ks))
+
+
+def fp_mlp_weights_in_lds(c2, c1, widths):
+    """Python mirror of the kernel's one staging predicate (fp_weights_in_lds): a weight image of at most 64 KB is staged whole in
+    LDS, a larger one is streamed slab by slab through two LDS buffers."""
+    return fp_mlp_image_bytes(c2, c1, list(widths)) <= FP_MLP_LDS_IMAGE_BYTES
+
+
+def fp_mlp_tmax(widths):
+    """Accumulator tiles per bank of the kernel instantiation that serves these widths (2, 4 or 8)."""
+    widest = max(widths)
+    return 2 if widest <= 64 else 4 if widest <= 128 else 8
+
+
+# Shape classes (c2, c1, widths) -> fewest rows B * n at which "three_nn + mcp_fp_mlp" measured faster than the module's composition
+# (three_nn, weights, three_interpolate, cat, folded convs) by more than the composition's own spread (tools/fp_mlp_times.py ->
+# profiles/fp_mlp_times.json).  A class without a row keeps the composition.  Measured at B = 8: 256 + 3 -> 256/256 over n = 16384
+# (0.516 against 0.807 ms, spread 0.071) enters; 256 + 128 -> 256/256 over n = 1024 (0.204 against 0.256, spread 0.075) and
+# 128 + 4 -> 128/128/128 over n = 4096 (0.248 against 0.296, spread 0.065) are faster by less than the spread and stay out.
+FP_MLP_FUSED_CLASSES = {(256, 3, (256, 256)): 8 * 16384}
+
+
+def fp_mlp_class(c2, c1, widths):
+    return (int(c2), int(c1), tuple(int(w) for w in widths))
+
+
+def fp_mlp_routes_fused(c2, c1, widths, rows):
+    """PointnetFPModule's route predicate: a pure function of the padded shapes."""
+    least = FP_MLP_FUSED_CLASSES.get(fp_mlp_class(c2, c1, widths))
+    return least is not None and rows >= least
+
+
+def fp_mlp_pack_weights(weights, c2):
+    """The MFMA-operand image of mcp_fp_mlp from [(W (out, in), b (out,)), ...] fp32 device tensors; the first c2 columns of the
+    first W meet the interpolated features, the rest the skip row -> (packed, widths)."""
+    widths = [int(w.shape[0]) for w, _ in weights]
+    c2 = int(c2)
+    c1 = int(weights[0][0].shape[1]) - c2
+    lib = _lib.load()
+    wid = (ctypes.c_int * len(widths))(*widths)
+    n = lib.mcp_fp_mlp_packed_floats(c2, c1, len(widths), wid) if len(widths) <= 3 and c1 >= 0 else 0
+    if n == 0:
+        raise _lib.Unsupported(f"fp_mlp: unsupported shape c2={c2} c1={c1} widths={widths}")
+    cin = [c2 + c1, *widths[:-1]]
+    for (w, b), k, o in zip(weights, cin, widths):
+        if tuple(w.shape) != (o, k) or tuple(b.shape) != (o,):
+            raise RuntimeError(f"fp_mlp: expected W {(o, k)} and b {(o,)}, got {tuple(w.shape)} and {tuple(b.shape)}")
+    ws = [w.contiguous() for w, _ in weights]
+    bs = [b.contiguous() for _, b in weights]
+    packed = torch.empty((n,), dtype=torch.float32, device=ws[0].device)
+    wp = (ctypes.c_void_p * len(ws))(*[_lib.fptr(w) for w in ws])
+    bp = (ctypes.c_void_p * len(bs))(*[_lib.fptr(b) for b in bs])
+    _call("mcp_fp_mlp_pack", packed, c2, c1, len(widths), wid, wp, bp, _lib.fptr(packed))
+    return packed, widths
+
+
+def fp_mlp_pack(convs, bns=None, c2=None):
+    """Pack the shared MLP of a feature-propagation layer once: convs are its 1x1 Conv2d (or Linear) modules in order, bns the
+    eval-mode BatchNorm that follows each (None, or None entries, where there is none), c2 the channels of the interpolated part
+    (the leading input columns of the first layer).  -> (packed, widths) for HipBackend.fp_mlp."""
+    bns = [None] * len(convs) if bns is None else list(bns)
+    return fp_mlp_pack_weights([fold_conv_bn(c, b) for c, b in zip(convs, bns)], c2)
+
+
 class _ChamferLengthsFn(torch.autograd.Function):
     """_ChamferFn over the valid prefixes of a padded batch (pytorch3d's x_lengths / y_lengths with its default reductions):
     value_b = sum_{i<xl} dxy_i / max(xl,1) + sum_{j<yl} dyx_j / max(yl,1).  Forward: the length-aware search returns 0 for every
@@ -1292,6 +1374,40 @@ class HipBackend:
         _call("mcp_group_mlp", xyz, B, N, M, C, nsample, int(bool(use_xyz)), GROUP_MLP_POOLS[pool], len(widths), wid, _lib.fptr(xyz),
               _lib.fptr(new_xyz), None if features is None else _lib.fptr(features), _lib.iptr(idx), None if ql is None else _lib.iptr(ql),
               None if row_bias is None else _lib.fptr(row_bias), _lib.fptr(packed), _lib.fptr(out))
+        return out
+
+    def fp_mlp(self, known_feats, skip, idx, dist, packed, widths, rule="pointnet2", w3=None, unknown_lengths=None):
+        """Feature-propagation layer after its three-neighbour search (PointnetFPModule; FeaturePropagation, models/layers.py:150-178)
+        in one launch: known_feats (B,m,C2) and skip (B,n,C1) or None channel-last, idx / dist (B,n,3) as three_nn returns them,
+        (packed, widths) = fp_mlp_pack(...) -> (B,n,widths[-1]): the shared MLP, every layer followed by ReLU, of
+        [w0 f[i0] + w1 f[i1] + w2 f[i2] | skip].  rule: "pointnet2" (1 / (dist + 1e-8), normalised), "flownet3d" (1 / max(dist^2,
+        1e-10), normalised) or "given" (w3 (B,n,3) as it is; dist may be None).  A slot with dist = +inf weighs exactly 0 under the
+        two computed rules.  unknown_lengths (forms: lengths_tensor): rows at or beyond the length give zeros and are never read.
+        Inference only (no gradient); unsupported shapes raise _lib.Unsupported."""
+        B, m, C2 = known_feats.shape
+        n = idx.shape[1]
+        C1 = 0 if skip is None else skip.shape[2]
+        widths = [int(w) for w in widths]
+        code = FP_MLP_RULES[rule]
+        if tuple(idx.shape) != (B, n, 3) or (skip is not None and tuple(skip.shape[:2]) != (B, n)):
+            raise RuntimeError(f"fp_mlp: idx {tuple(idx.shape)} / skip do not match B={B}, n={n}")
+        for name, t in (("w3", w3),) if code == 0 else (("dist", dist),):
+            if t is None or tuple(t.shape) != (B, n, 3):
+                raise RuntimeError(f"fp_mlp: rule {rule!r} needs {name} of shape {(B, n, 3)}")
+        if not fp_mlp_supported(C2, C1, widths):
+            raise _lib.Unsupported(f"fp_mlp: unsupported shape c2={C2} c1={C1} widths={widths}")
+        if packed.numel() != _lib.load().mcp_fp_mlp_packed_floats(C2, C1, len(widths), (ctypes.c_int * len(widths))(*widths)):
+            raise RuntimeError("fp_mlp: the packed image was built for another shape")
+        ul = lengths_tensor(unknown_lengths, B, n, known_feats.device)
+        out = torch.empty((B, n, widths[-1]), dtype=torch.float32, device=known_feats.device)
+        if B == 0 or n == 0:
+            return out
+        if m == 0:
+            raise RuntimeError("fp_mlp: the known cloud is empty")
+        wid = (ctypes.c_int * len(widths))(*widths)
+        _call("mcp_fp_mlp", known_feats, B, n, m, C2, C1, code, len(widths), wid, _lib.fptr(known_feats),
+              None if skip is None or C1 == 0 else _lib.fptr(skip), _lib.iptr(idx), None if code == 0 else _lib.fptr(dist),
+              _lib.fptr(w3) if code == 0 else None, None if ul is None else _lib.iptr(ul), _lib.fptr(packed), _lib.fptr(out))
         return out
 
     def ptblock_layer(self, xyz, q, k, v, idx, weights, packed=None):

@@ -1,7 +1,8 @@
-"""Set-abstraction modules of pointnet2 (the reference's pointnet2/pointnet2_modules.py: PointnetSAModuleMSG, PointnetSAModule) on
-the MI355X kernels.  Same constructor arguments, tensor layouts (xyz (B,N,3), features (B,C,N) -> new_xyz (B,npoint,3),
-(B, sum of the scales' last widths, npoint)) and parameter names, so a state_dict of the reference classes loads strictly
-(tests/golden/pointnet2_sa_state_keys.json lists the names of one two-scale module).
+"""Set-abstraction and feature-propagation modules of pointnet2 (the reference's pointnet2/pointnet2_modules.py:
+PointnetSAModuleMSG, PointnetSAModule, PointnetFPModule) on the MI355X kernels.  Same constructor arguments, tensor layouts (xyz
+(B,N,3), features (B,C,N) -> new_xyz (B,npoint,3), (B, sum of the scales' last widths, npoint)) and parameter names, so a state_dict
+of the reference classes loads strictly (tests/golden/pointnet2_sa_state_keys.json lists the names of one two-scale module,
+pointnet2_fp_state_keys.json those of a feature-propagation module).
 
 Two routes give the same layer:
   * the composition -- QueryAndGroup, the shared Conv2d / BatchNorm2d / ReLU stack, the pool over the neighbours -- is the definition
@@ -9,7 +10,9 @@ Two routes give the same layer:
   * the fused route -- sampling, one ball query per scale, one mcp_group_mlp launch per scale (ops.HipBackend.group_mlp) -- writes
     nothing but the pooled features.  It is taken only under no-grad, in eval(), for a shape the kernel supports, and for a shape
     class that the measurement of tools/group_mlp_times.py found faster (ops.GROUP_MLP_FUSED_CLASSES; `route` overrides it).
-PointnetFPModule is not provided: its per-point chain is served by the Linear kernels."""
+PointnetFPModule has the same two routes: the composition -- three_nn, the weights in torch, three_interpolate, cat, the shared
+stack -- and one mcp_fp_mlp launch after the three-neighbour search (ops.HipBackend.fp_mlp; ops.FP_MLP_FUSED_CLASSES from
+tools/fp_mlp_times.py)."""
 from typing import List
 
 import torch
@@ -139,3 +142,89 @@ class PointnetSAModule(PointnetSAModuleMSG):
                  pool_method="max_pool", instance_norm=False):
         super().__init__(mlps=[mlp], npoint=npoint, radii=[radius], nsamples=[nsample], bn=bn, use_xyz=use_xyz, pool_method=pool_method,
                          instance_norm=instance_norm)
+
+
+class PointnetFPModule(nn.Module):
+    """Feature propagation: the features of the `known` points are blended onto the `unknown` points from their three nearest
+    known points, concatenated with the unknown points' own (skip) features and sent through the shared MLP `mlp` (its first entry
+    counts C2 + C1).  weighting: "pointnet2" (weights 1 / (dist + 1e-8), normalised; the reference class) or "flownet3d"
+    (1 / max(dist^2, 1e-10), normalised; FeaturePropagation of models/layers.py).  route: "measured" (default), "always" or "never"
+    for the fused route."""
+
+    def __init__(self, *, mlp: List[int], bn: bool = True):
+        super().__init__()
+        self.bn = bn
+        self.weighting = "pointnet2"
+        self.route = "measured"
+        self.mlp = _shared_mlp(list(mlp), bn, False)
+        self.__dict__["_packed"] = None
+
+    # ---- fused route -----------------------------------------------------------------------------------------------------------
+    def _layers(self):
+        units = list(self.mlp.children())
+        return [u.conv for u in units], [u.bn.bn if self.bn else None for u in units]
+
+    def _packed_weights(self, c2):
+        """(packed, widths) for c2 interpolated channels, kept until a parameter or buffer of the stack is written or replaced."""
+        state = [*self.mlp.parameters(), *self.mlp.buffers()]
+        key = (c2, *((id(t), t._version, t.device) for t in state))
+        hit = self.__dict__["_packed"]
+        if hit is None or hit[0] != key:
+            hit = self.__dict__["_packed"] = (key, ops.fp_mlp_pack(*self._layers(), c2=c2))
+        return hit[1]
+
+    def fused(self, c2, c1, rows):
+        """Whether a call with c2 known and c1 skip channels over `rows` = B * n unknown points takes the fused route."""
+        if self.training or self.route == "never" or self.weighting not in ("pointnet2", "flownet3d"):
+            return False
+        convs = self._layers()[0]
+        widths = [c.out_channels for c in convs]
+        if not convs or convs[0].in_channels != c2 + c1 or not ops.fp_mlp_supported(c2, c1, widths):
+            return False
+        return self.route == "always" or ops.fp_mlp_routes_fused(c2, c1, widths, rows)
+
+    def weights(self, dist):
+        """(B,n,3) interpolation weights of three_nn's distances under `weighting`; a row without a finite distance gets zeros."""
+        if self.weighting == "pointnet2":
+            recip = 1.0 / (dist + 1e-8)
+        elif self.weighting == "flownet3d":
+            recip = 1.0 / (dist * dist).clamp_min(1e-10)
+        else:
+            raise NotImplementedError(self.weighting)
+        norm = torch.sum(recip, dim=2, keepdim=True)
+        return recip / torch.where(norm > 0, norm, torch.ones_like(norm))
+
+    def forward(self, unknown: torch.Tensor, known: torch.Tensor, unknow_feats: torch.Tensor, known_feats: torch.Tensor, unknown_lengths=None,
+                known_lengths=None) -> torch.Tensor:
+        """unknown (B,n,3), known (B,m,3) or None, unknow_feats (B,C1,n) or None, known_feats (B,C2,m) -> (B, mlp[-1], n).  known=None
+        broadcasts known_feats (B,C2,1) to every unknown point.  unknown_lengths / known_lengths (forms: ops.lengths_tensor):
+        element b is its first unknown_lengths[b] unknown and known_lengths[b] known points; padded rows give zeros, and an element
+        without a known point gets a zero interpolated part."""
+        B, n = unknown.shape[0], unknown.shape[1]
+        C2 = known_feats.shape[1]
+        C1 = 0 if unknow_feats is None else unknow_feats.shape[1]
+        with_lengths = known is not None and (unknown_lengths is not None or known_lengths is not None)
+        ul = kl = None
+        if with_lengths:
+            ul = ops.lengths_tensor(unknown_lengths, B, n, unknown.device)
+            kl = ops.lengths_tensor(known_lengths, B, known.shape[1], unknown.device)
+        wants_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (unknown, known, unknow_feats, known_feats,
+                                                                                                 *self.parameters()))
+        if known is not None and not wants_grad and self.fused(C2, C1, B * n):
+            packed, widths = self._packed_weights(C2)
+            dist, idx = pu.three_nn(unknown.detach().contiguous(), known.detach().contiguous(), ul, kl)
+            rows = known_feats.detach().transpose(1, 2).contiguous()
+            skip = None if unknow_feats is None else unknow_feats.detach().transpose(1, 2).contiguous()
+            out = ops.backend().fp_mlp(rows, skip, idx, dist, packed, widths, rule=self.weighting, unknown_lengths=ul)
+            return out.transpose(1, 2)
+        if known is not None:
+            dist, idx = pu.three_nn(unknown.contiguous(), known.contiguous(), ul, kl)
+            interpolated = pu.three_interpolate(known_feats.contiguous(), idx, self.weights(dist).contiguous())
+        else:
+            interpolated = known_feats.expand(*known_feats.size()[0:2], n)
+        new_features = interpolated if unknow_feats is None else torch.cat([interpolated, unknow_feats], dim=1)
+        h = self.mlp(new_features.unsqueeze(-1)).squeeze(-1)
+        if ul is not None:
+            live = torch.arange(n, device=h.device).view(1, n) < ul.clamp(0, n).view(B, 1)
+            h = torch.where(live.view(B, 1, n), h, h.new_zeros(()))
+        return h
