@@ -24,7 +24,8 @@ sel: flat indices (batch * points + point) of the points wanted, default all; th
 
 The *_inputs functions build the test data of a case (CPU fp32 tensors): clustered clouds whose neighbour lists are real
 neighbours, so that relative coordinates come from a cancellation, and features and weights with a positive mean, so that the
-truncation errors of a two-term split add up instead of cancelling (see the docstring of test_kernel_variants_gpu.py)."""
+truncation errors of a two-term split add up instead of cancelling (see the docstring of test_kernel_variants_gpu.py).  A case's
+optional "seed" is added to the seed its shape gives (the backward cases choose it, see fused_grad_reference.py)."""
 import math
 
 import torch
@@ -194,7 +195,7 @@ def fusion_inputs(case):
     """p1, p2 (b, n, 3), (ia, ib) two (b, n, 32) lists, [w1, b1, w2, b2, w3, b3].  same: p2 is p1, so every list holds its own point
     (a zero-length vector); dup: the second list repeats the first."""
     b, n = case["b"], case["n"]
-    g = torch.Generator().manual_seed(1000 * b + n)
+    g = torch.Generator().manual_seed(1000 * b + n + case.get("seed", 0))
     p1 = clustered_cloud(g, b, n, 64, case.get("extent", False))
     p2 = p1.clone() if case.get("same") else (p1 + 0.2 * torch.randn(b, n, 3, generator=g)).contiguous()
     ia = cluster_neighbours(g, b, n, n, 32, 64)
@@ -207,7 +208,7 @@ def fusion_inputs(case):
 def cross_inputs(case):
     """xyz1 (b, n1, 3), xyz2 (b, n2, 3), points1, points2, (ia, ib) two (b, n1, 16) lists into cloud 2, [wpos, bpos, wmlp, bmlp]."""
     b, n1, n2, d = case["b"], case["n1"], case["n2"], case["d"]
-    g = torch.Generator().manual_seed(b * 7919 + n1 * 31 + n2 + d)
+    g = torch.Generator().manual_seed(b * 7919 + n1 * 31 + n2 + d + case.get("seed", 0))
     xyz2 = clustered_cloud(g, b, n2, 32, case.get("extent", False))
     home = torch.arange(n1) * n2 // n1
     xyz1 = (xyz2[:, home] + 0.2 * torch.randn(b, n1, 3, generator=g)).contiguous()
@@ -220,7 +221,7 @@ def pointconv_inputs(case):
     """s_xyz (b, n, 3), new_xyz (b, s, 3) (points of s_xyz), s_points (b, n, d), idx (b, s, 32), the six WeightNet tensors and, with
     c_out, [w, b] of the Linear."""
     b, n, s, d = case["b"], case["n"], case["s"], case["d"]
-    g = torch.Generator().manual_seed(b * 7919 + n * 31 + s + d)
+    g = torch.Generator().manual_seed(b * 7919 + n * 31 + s + d + case.get("seed", 0))
     s_xyz = clustered_cloud(g, b, n, 32, case.get("extent", False))
     home = torch.arange(s) * n // s
     new_xyz = s_xyz[:, home].contiguous()
@@ -237,7 +238,7 @@ def ptblock_inputs(case):
     """xyz (b, n, 3), q, k, v (b, n, 64), idx (b, n, 16), the eight weights.  same: the 16 neighbours of a point are one point;
     logits: fc_gamma's last layer scaled so that the largest |attn| / 8 is about this."""
     b, n = case["b"], case["n"]
-    g = torch.Generator().manual_seed(b * 7919 + n)
+    g = torch.Generator().manual_seed(b * 7919 + n + case.get("seed", 0))
     xyz = clustered_cloud(g, b, n, 16, case.get("extent", False))
     q, k, v = (torch.randn(b, n, 64, generator=g) + 0.5 for _ in range(3))
     idx = cluster_neighbours(g, b, n, n, 16, 16)

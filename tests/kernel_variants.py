@@ -1,11 +1,16 @@
 """The kernel variants of the dense layers (csrc/linear.hip, mlp.hip, attention.hip) and of the fused point layers (fusion.hip,
-cross.hip, pointconv.hip, ptblock.hip), and the parity cases that reach them.
+cross.hip, pointconv.hip, ptblock.hip), the backward units of the fused point layers (fusion_grad.hip, cross_grad.hip,
+cross256_grad.hip, pointconv_grad.hip, ptblock_grad.hip), and the parity cases that reach them.
 
 expected_kernel() mirrors the C dispatch: given an entry point and a shape it names the template instantiation that runs, in
 the form c++filt prints it without namespace and arguments ("linear_kernel<3, 2, 8>").  CASES parametrises
 test_kernel_variants_gpu.py (dense layers) and test_fused_variants_gpu.py (point layers); test_kernel_variants_cpu.py checks that every instantiation in the device assembly is named by at
-least one case, so a variant added later without a parity case fails the CPU suite.  A plain module, imported by both tests."""
+least one case, so a variant added later without a parity case fails the CPU suite.
 
+expected_grad_kernels() names the set of kernels one backward call launches and grad_launch_grid() mirrors how each of them deals
+its points (or point pairs) to workgroups; GRAD_CASES parametrises test_fused_grad_variants_gpu.py, and test_kernel_variants_cpu.py
+checks that they reach every kernel the backward units emit and every edge of their persistent loops.  A plain module, imported by
+the tests."""
 
 def _cdiv(a, b):
     return (a + b - 1) // b
@@ -333,6 +338,159 @@ CASES = [
 
 def cases(op):
     return [c for c in CASES if c["op"] == op]
+
+
+# ---- the backward units of the fused point layers.  Every backward kernel is persistent: one workgroup per CU at the most, units
+# (points, or point pairs) dealt statically, weight-gradient partial vectors added by a second kernel over ALL workgroups ----
+GRAD_WAVES = 4                    # WAVES, fusion_grad.hip:30, cross_grad.hip:54, cross256_grad.hip:28, pointconv_grad.hip:18, ptblock_grad.hip
+X256_DX_GRID, X256_W_SLICES, X256_W_PTS = 512, 64, 4     # DX_GRID, W_SLICES, W_PTS, cross256_grad.hip:39
+X256_Z_GRID_CAP = 256             # plan(), cross256_grad.hip:380 (a constant there, not the CU count)
+
+
+def _deal(units, per, g, base=0, xcd_map=True):
+    """(dealt by XCD, [workgroup][round] -> list of units) for g workgroups of one role that starts at workgroup `base` of the launch.
+    mcp_units_by_xcd, common.h:101-111 (base = 0) and deal(), cross_grad.hip:419-430: by XCD when g >= 8, g % 8 == 0 and base % 8 == 0
+    -- eighths of ceil(steps / 8) whole steps, workgroup k starts at step k >> 3 of eighth k & 7 and strides g >> 3 steps --, else
+    workgroup k starts at step k and strides g steps.  Wave w of a workgroup takes unit first + w + round * stride while below the limit
+    (fusion_grad.hip:113, cross_grad.hip:167, pointconv_grad.hip:54, ptblock_grad.hip:149)."""
+    by_xcd = xcd_map and g >= 8 and g % 8 == 0 and base % 8 == 0
+    dealt = []
+    for k in range(g):
+        if by_xcd:
+            chunk = _cdiv(_cdiv(units, per), 8) * per
+            x = k & 7
+            first, stride, limit = x * chunk + (k >> 3) * per, (g >> 3) * per, min((x + 1) * chunk, units)
+        else:
+            first, stride, limit = k * per, g * per, units
+        dealt.append([list(range(f, min(f + per, limit))) for f in range(first, limit, stride)])
+    return by_xcd, dealt
+
+
+def _role(units, per, g, base=0, xcd_map=True):
+    by_xcd, dealt = _deal(units, per, g, base, xcd_map)
+    return dict(workgroups=g, units=units, per=per, by_xcd=by_xcd, dealt=dealt)
+
+
+def grad_launch_grid(op, cus=256, **shape):
+    """{role: dict(workgroups, units, per, by_xcd, dealt)} of one backward call on a device with `cus` compute units.  `units` are what
+    the role's loop deals out -- points, or pairs of points (2 u, 2 u + 1) in pointconv_agg_grad_kernel and ptblock_grad_kernel --,
+    `per` the units one workgroup takes per step, dealt[k][r] the units workgroup k takes in its round r (an empty dealt[k]: the
+    workgroup receives nothing and still writes its partial vector)."""
+    if op == "fusion":                                               # grad_grid, fusion_grad.hip:440-445
+        total = shape["b"] * shape["n"]
+        return {"points": _role(total, GRAD_WAVES, min(_cdiv(total, GRAD_WAVES), cus))}
+    if op == "cross":
+        d, total = shape["d"], shape["b"] * shape["n1"]
+        want = _cdiv(total, GRAD_WAVES)
+        if d == 64:                                                  # grad_grid<64>, cross_grad.hip:462-465 (one role), deal :432
+            return {"all": _role(total, GRAD_WAVES, min(want, cus))}
+        if d == 128:                                                 # grad_grid<128>, cross_grad.hip:462-465; roles :434-442
+            g0, g1 = min(want, max(cus // 2, 1)), min(want, max(cus // 4, 1))
+            return {"data": _role(total, GRAD_WAVES, g0, 0), "own0": _role(total, GRAD_WAVES, g1, g0), "own2": _role(total, GRAD_WAVES, g1, g0 + g1)}
+        if d == 256:                                                 # plan(), cross256_grad.hip:377-390
+            slices = min(_cdiv(total, 2 * X256_W_PTS), X256_W_SLICES)
+            per = _cdiv(total, slices)                               # cross256_grad_w_kernel, cross256_grad.hip:189: slice s takes points s per .. (s + 1) per
+            w = [[list(range(p, min(p + X256_W_PTS, total, (s + 1) * per))) for p in range(s * per, min((s + 1) * per, total), X256_W_PTS)]
+                 for s in range(slices)]                             # in stages of W_PTS points, :195
+            return {"z": _role(total, GRAD_WAVES, min(want, X256_Z_GRID_CAP), xcd_map=False),     # round-robin rounds, cross256_grad.hip:78-83
+                    "w": dict(workgroups=slices, units=total, per=X256_W_PTS, by_xcd=False, dealt=w),   # times 4 column blocks, :188, :429
+                    "dx": _role(total, 1, min(total, X256_DX_GRID), xcd_map=False)}                 # cross256_grad.hip:243, :381
+        raise ValueError(f"cross grad: d={d} is not built")          # mcp_cross_grad, cross_grad.hip:514
+    if op == "pointconv_agg":                                        # grad_grid, pointconv_grad.hip:204-208; pairs :52
+        total = shape["b"] * shape["s"]
+        return {"pairs": _role((total + 1) // 2, GRAD_WAVES, min(_cdiv(total, 2 * GRAD_WAVES), cus))}
+    if op == "ptblock":                                              # grad_grid, ptblock_grad.hip:417-421; pairs :147
+        pairs = (shape["b"] * shape["n"] + 1) // 2
+        return {"pairs": _role(pairs, GRAD_WAVES, min(_cdiv(pairs, GRAD_WAVES), cus))}
+    raise ValueError(f"unknown op {op}")
+
+
+def expected_grad_kernels(op, **shape):
+    """The demangled kernels one backward call of `op` launches (extra keys of a case are ignored)."""
+    if op == "fusion":                                               # mcp_fusion_grad, fusion_grad.hip:474-477
+        _fusion(shape["b"], shape["n"], shape.get("nb", 64))
+        return {"fusion_grad_kernel", "fusion_grad_reduce_kernel"}
+    if op == "cross":
+        d = shape["d"]
+        _cross(d, shape.get("k", 32))
+        if d == 256:                                                 # mcp_cross256_grad, cross256_grad.hip:427-433
+            return {"cross256_grad_z_kernel", "cross256_grad_w_kernel", "cross256_grad_dx_kernel", "cross256_grad_reduce_kernel"}
+        names = {f"cross_grad_kernel<{d}>", "cross_grad_reduce_kernel"}   # launch_cross_grad, cross_grad.hip:493-495
+        return names | {"transposed_image_kernel"} if d == 128 else names   # !WT_LDS, cross_grad.hip:60, :491
+    if op == "pointconv_agg":                                        # mcp_pointconv_agg_grad, pointconv_grad.hip:241-243; ops.pointconv_agg: d % 4 == 0, d <= 256
+        if shape.get("k", 32) != 32 or shape["d"] % 4 or shape["d"] > 256:
+            raise ValueError(f"pointconv_agg grad: d={shape['d']} is not built")
+        return {"pointconv_agg_grad_kernel", "pointconv_grad_reduce_kernel"}
+    if op == "ptblock":                                              # mcp_ptblock_grad, ptblock_grad.hip:456-459
+        _ptblock(shape.get("c", 64), shape.get("k", 16))
+        return {"ptblock_transposed_images_kernel", "ptblock_grad_kernel", "ptblock_grad_reduce_kernel"}
+    raise ValueError(f"unknown op {op}")
+
+
+def grad_weight_role(case):
+    """The role whose rounds decide the layer's largest weight-gradient matrix (the role a dropped or doubled point is looked for in)."""
+    if case["op"] == "cross":
+        return {64: "all", 128: "own0", 256: "z"}[case["d"]]
+    return "points" if case["op"] == "fusion" else "pairs"
+
+
+GRAD_CASES = [
+    # ---- fusion_grad_kernel: one point per wave, 4 waves, grid = min(ceil(total / 4), CUs) ----
+    _fus("one-point", 1, 1),                                 # 3 dead waves enter the wave-order sum; every gradient but p2's is zero
+    _fus("3-points", 1, 3),                                  # one workgroup, one dead wave
+    _fus("5-points", 1, 5),                                  # grid 2, round-robin: the second workgroup has one live wave
+    _fus("same-dup", 2, 19, same=True, dup=True, seed=1),    # 38 points, grid 10: zero-length vectors (|r| = 0) and every neighbour twice
+    _fus("xcd-ragged", 1, 61),                               # grid 16 by XCD: eighths of 8 points, the last one has 5
+    _fus("grid-75", 2, 149, extent=True, seed=4),            # 298 points, grid % 8 = 3: round-robin below the cap, two batch elements
+    _fus("cap+1", 5, 205),                                   # 1025 points, want 257 > 256: eighths of 132 against steps of 128, the last has 101: 6 workgroups idle
+    _fus("cap-4-rounds", 3, 1031),                           # 3093 points: eighths of 388 = 3 x 128 + 4, the last has 377
+    # ---- cross_grad_kernel<64>: one role, grid = min(ceil(total / 4), CUs) ----
+    _crs("3-points", 64, 1, 3, 50),                          # one workgroup, one dead wave
+    _crs("grid-38", 64, 2, 75, 70),                          # 150 points: round-robin below the cap
+    _crs("xcd-ragged", 64, 2, 31, 37, extent=True),          # 62 points, grid 16 by XCD: eighths of 8, the last has 6
+    _crs("cap+1", 64, 5, 205, 190),                          # 1025 points: 6 idle workgroups
+    _crs("cap-4-rounds", 64, 3, 1031, 900),                  # 3093 points
+    # ---- cross_grad_kernel<128>: roles of min(want, CUs / 2) + 2 x min(want, CUs / 4) workgroups, want = ceil(total / 4) ----
+    _crs("3-points", 128, 1, 3, 50, seed=1),                 # three workgroups, one per role
+    _crs("all-round-robin", 128, 2, 20, 50),                 # 40 points: 10 + 10 + 10
+    _crs("xcd-ragged", 128, 3, 127, 150, extent=True),       # 381 points: 96 + 64 + 64 all by XCD, the data role below its cap; eighths of 48, the last has 45
+    _crs("base%8", 128, 2, 200, 150),                        # 400 points: 100 + 64 + 64, the data role round-robin and the others too (base 100, 164)
+    _crs("cap-3-and-5-rounds", 128, 2, 515, 450),            # 1030 points: 128 + 64 + 64 by XCD, eighths of 132: 3 rounds of 64 (data), 5 of 32; the last has 106
+    # ---- cross256_grad_{z,w,dx,reduce}_kernel: z min(ceil(total / 4), 256) round-robin; w min(ceil(total / 8), 64) slices; dx min(total, 512) ----
+    _crs("3-points", 256, 1, 3, 50),                         # z: one dead wave; w: one slice; dx: 3 workgroups
+    _crs("ragged-workgroup", 256, 3, 83, 70, extent=True),   # 249 points: z grid 63, the last workgroup has one live wave; 32 slices of 8, the last has 1
+    _crs("cap+1", 256, 5, 205, 190),                         # 1025 points: z second round for one workgroup; slices of 17: 5 in slice 60, 61..63 empty; dx 3 / 2 points
+    _crs("cap-3-rounds", 256, 59, 37, 41),                   # 2183 points: z rounds of 1024 cross 27 batch elements; slices of 35: 13 in the last
+    # ---- pointconv_agg_grad_kernel: a wave takes a pair of centres, 4 waves, grid = min(ceil(total / 8), CUs) ----
+    _agg("one-centre", 1, 40, 1, 32),                        # the tail alone: the second lane half works on centre 0 with a zero gradient
+    _agg("9-centres", 3, 20, 3, 64),                         # 5 pairs, grid 2: the second workgroup has the half pair
+    _agg("xcd-ragged-odd", 3, 41, 41, 128),                  # 123 centres, 62 pairs, grid 16 by XCD: eighths of 8 pairs, the last has 6 with the odd tail; S = N
+    _agg("cap+1", 3, 700, 683, 32, extent=True),             # 2049 centres, 1025 pairs: 6 idle workgroups, odd tail
+    _agg("cap-3-rounds", 3, 1375, 1375, 64),                 # 4125 centres, 2063 pairs: eighths of 260 = 2 x 128 + 4, the last has 243; S = N
+    # ---- ptblock_grad_kernel: a wave takes a pair of points, 4 waves, grid = min(ceil(pairs / 4), CUs) ----
+    _ptb("one-point", 1, 1),                                 # the odd tail alone
+    _ptb("odd-B1", 1, 333, extent=True),                     # 167 pairs, grid 42 round-robin, odd tail
+    _ptb("odd-B3", 3, 111, packed=True),                     # 333 points: pairs straddle batch elements; q/k/v with row stride 192
+    _ptb("xcd-ragged", 2, 61, logits=80.0),                  # 61 pairs, grid 16 by XCD: eighths of 8, the last has 5; large logits
+    _ptb("same-neighbour", 2, 125, same=True),               # a uniform softmax: zero gradients for q and fc_gamma
+    _ptb("cap+1", 3, 683),                                   # 2049 points, 1025 pairs: 6 idle workgroups, odd tail
+    _ptb("cap-3-rounds", 3, 1375),                           # 4125 points, 2063 pairs
+]
+
+
+# seed: added to the seed the shape gives, where the shape's own data leaves too little of the upstream gradient clear
+# (fused_grad_reference.py) or, in grid-75, lets one layer-3 channel win at every neighbour, which makes the gradient of b3 zero
+
+
+def grad_cases(op):
+    return [c for c in GRAD_CASES if c["op"] == op]
+
+
+def grad_case_id(c):
+    """A readable pytest id: the backward's main kernel, the tag and the shape."""
+    main = sorted(n for n in expected_grad_kernels(**c) if not any(t in n for t in ("reduce", "transposed", "_w_", "_dx_")))[0]
+    shape = ",".join(v if k == "tag" else f"{k}={v}" for k, v in c.items() if k != "op" and v not in (None, False))
+    return f"{main}[{shape}]".replace(" ", "")
 
 
 def case_id(c):

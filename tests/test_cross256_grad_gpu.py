@@ -12,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 from mocopci_amd import _lib, grad, ops
+from tests.fused_grad_reference import cross_clear
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -89,10 +90,8 @@ def test_cross256_backward_matches_the_unfused_layer_and_float64_and_repeats_bit
         uniq = (idx[0] if isinstance(idx, tuple) else idx).long()
         d64 = [t.double() for t in (xyz1, xyz2, f1, f2, *w)]
         u64, z64 = layer64(*d64[:4], uniq, *d64[4:])
-        top2 = z64.topk(2, dim=2).values
-        clear = ((top2[:, :, 0] - top2[:, :, 1]) > 1e-4 * (1.0 + top2[:, :, 0].abs())) & (top2[:, :, 0].abs() > 1e-5)
-        clear &= (u64.abs().amin(dim=(2, 3)) > 1e-5).unsqueeze(-1)
-        del u64, z64, top2
+        clear = cross_clear(u64, z64)
+        del u64, z64
         kept = float(clear.float().mean())
         print(f"\n[{form} b={b} n1={n1}] kept (point, channel) pairs: {kept:.3f}")
         assert kept > 0.9

@@ -14,6 +14,7 @@ from mocopci_amd import ops, synth, training
 from oracle import pointset as orc
 from oracle.backend import OracleBackend
 from tests import harness_checks as hc
+from tests.fused_grad_reference import cross_clear, fusion_clear, ptblock_clear
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -128,8 +129,7 @@ def test_fusion_backward_kernel_matches_the_unfused_layer_and_repeats_bit_for_bi
     x64 = torch.cat([r64, r64.norm(dim=-1, keepdim=True)], dim=-1)
     for wi, bi_ in ((ws[0], ws[1]), (ws[2], ws[3]), (ws[4], ws[5])):
         x64 = torch.relu(x64 @ wi.double().to(DEV).T + bi_.double().to(DEV))
-    top2 = x64.topk(2, dim=-1).values
-    clear = ((top2[..., 0] - top2[..., 1]) > 1e-4 * (1.0 + top2[..., 0])).all(dim=-1)
+    clear = fusion_clear(x64)
     assert float(clear.float().mean()) > 0.9
     g = g * clear.unsqueeze(-1).float()
 
@@ -175,9 +175,8 @@ def test_cross_backward_kernel_matches_the_unfused_layer_and_repeats_bit_for_bit
         uniq = (idx[0] if isinstance(idx, tuple) else idx).long()
         wd = [t.double().to(DEV) for t in w]
         u64 = f2.double()[bi, uniq] + f1.double().unsqueeze(2) + (xyz2.double()[bi, uniq] - xyz1.double().unsqueeze(2)) @ wd[0].T + wd[1]
-        top2 = (F.leaky_relu(u64, 0.1) @ wd[2].T + wd[3]).topk(2, dim=2).values
-        clear = ((top2[:, :, 0] - top2[:, :, 1]) > 1e-4 * (1.0 + top2[:, :, 0].abs())) & (top2[:, :, 0].abs() > 1e-5)   # ... or sits on LeakyReLU's kink
-        clear &= (u64.abs().amin(dim=(2, 3)) > 1e-5).unsqueeze(-1)        # a point with some u_j[k] on the kink: LeakyReLU'(u) is 1 or 0.1 by rounding
+        # (the maximum on LeakyReLU's kink, or a point with some u_j[k] on it: LeakyReLU'(u) is 1 or 0.1 by rounding)
+        clear = cross_clear(u64, F.leaky_relu(u64, 0.1) @ wd[2].T + wd[3])
         g = g0 * clear.float()
         assert float(clear.float().mean()) > 0.9
         hip = grads(be.cross_layer, idx)
@@ -253,8 +252,7 @@ def test_fusion_on_batch_statistics_matches_autograd_over_the_unfused_layer_and_
         return torch.sum(wgt.unsqueeze(-1) * nb, dim=2), pre
     leaves64 = [t.detach().double().clone().requires_grad_(True) for t in (p1, p2, *conv, *aff)]
     want_out, pre = unfused(*leaves64)
-    top2 = torch.relu(pre[2][0]).topk(2, dim=-1).values
-    clear = ((top2[..., 0] - top2[..., 1]) > 1e-4 * (1.0 + top2[..., 0])).all(dim=-1)
+    clear = fusion_clear(torch.relu(pre[2][0]))
     clear &= (pre[0][0].abs().amin(dim=(2, 3)) > 1e-5) & (pre[1][0].abs().amin(dim=(2, 3)) > 1e-5)
     assert float(clear.float().mean()) > 0.8
     g = rnd(174, B, N, 3).to(DEV) * clear.unsqueeze(-1).float()
@@ -513,7 +511,7 @@ def test_ptblock_backward_kernel_matches_the_unfused_block_and_repeats_bit_for_b
     d1 = (x64.unsqueeze(2) - x64[bi, idx.long()]) @ ws[0].double().T + ws[1].double()
     gpre = (q64[..., :64].unsqueeze(2) - q64[..., 64:128][bi, idx.long()]) + torch.relu(d1) @ ws[2].double().T + ws[3].double()
     a1 = gpre @ ws[4].double().T + ws[5].double()
-    clear = (d1.abs().amin(dim=(2, 3)) > 1e-5) & (a1.abs().amin(dim=(2, 3)) > 1e-5)
+    clear = ptblock_clear(d1, a1)
     assert float(clear.float().mean()) > 0.8
     g = rnd(192, B, n, 64).to(DEV) * clear.unsqueeze(-1).float()
     names = ["xyz", "qkv", "wd1", "bd1", "wd2", "bd2", "wg1", "bg1", "wg2", "bg2"]

@@ -4,8 +4,13 @@ each one except the weight-packing kernels and the entries of NOT_LAUNCHED must 
 least one entry of kernel_variants.CASES (the cases of test_kernel_variants_gpu.py and test_fused_variants_gpu.py).  A template
 instantiation added later without a case fails here, on a machine without a GPU.
 
-fusion_bn.hip is not among the units: its 13 kernels are mostly backward passes, which have no parity cases of this form; its
-forward is compared with float64 by tests/test_grad_gpu.py."""
+The backward units of the fused point layers (fusion_grad, cross_grad, cross256_grad, pointconv_grad, ptblock_grad) are held the same
+way: every kernel they emit must be in kernel_variants.expected_grad_kernels of at least one entry of GRAD_CASES (the cases of
+test_fused_grad_variants_gpu.py) or in GRAD_NOT_LAUNCHED with its reason, and GRAD_EDGES states, as predicates on the mirrored launch
+(kernel_variants.grad_launch_grid at 256 compute units), every edge of their persistent loops that the cases must reach.
+
+Still outside: fusion_bn.hip, attention_grad.hip, attention_wide_grad.hip, linear_grad.hip, the MLP backward, emd_grad.hip and
+interp3_grad.hip have no parity cases of this form; tests/test_grad_gpu.py and its neighbours compare them at workload-like shapes."""
 import os
 import re
 import shutil
@@ -21,17 +26,19 @@ UNITS = ("linear", "mlp", "attention", "fusion", "cross", "pointconv", "ptblock"
 # Emitted kernels that the shipped dispatch cannot launch, by name, each with its reason.  Empty today: fusion_kernel (the f32-input
 # MFMA form of fusion.hip, launched only under -DMCP_AB) is not compiled into the shipped library at all.
 NOT_LAUNCHED = {}
+GRAD_UNITS = ("fusion_grad", "cross_grad", "cross256_grad", "pointconv_grad", "ptblock_grad")
+GRAD_NOT_LAUNCHED = {}   # the same for the backward units: every kernel they emit is launched by some backward call
 
 
-def emitted_kernels():
+def emitted_kernels(units=UNITS):
     """Demangled kernel names of the units' device assembly, without namespace, return type and arguments."""
     if not (os.path.exists("/opt/rocm/bin/hipcc") or shutil.which("hipcc")):
         pytest.skip("no hipcc: the device assembly cannot be generated on this machine")
     if not shutil.which("c++filt"):
         pytest.skip("no c++filt to demangle the kernel names")
-    subprocess.check_call(["make", "-C", CSRC, "-j3", "-s"] + [f"isa/{u}.s" for u in UNITS])
+    subprocess.check_call(["make", "-C", CSRC, "-j3", "-s"] + [f"isa/{u}.s" for u in units])
     mangled = []
-    for u in UNITS:
+    for u in units:
         with open(os.path.join(CSRC, "isa", f"{u}.s")) as f:
             mangled += re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", f.read(), re.M)
     out = subprocess.run(["c++filt"], input="\n".join(mangled), capture_output=True, text=True, check=True).stdout.split("\n")
@@ -184,3 +191,191 @@ def test_every_dense_kernel_instantiation_has_a_parity_case():
     assert not missing, f"kernel instantiations without a parity case in tests/kernel_variants.py CASES: {missing}"
     stale = sorted(covered - wanted)
     assert not stale, f"cases name kernels the library does not build: {stale}"
+
+
+# ---- the backward units of the fused point layers ------------------------------------------------------------------------------------
+CUS = 256   # compute units of the MI355X: the grid cap of every backward kernel
+
+
+def test_the_backward_mirror_follows_the_c_conditions():
+    # grad_grid / plan: fusion_grad.hip:440-445, cross_grad.hip:458-466, cross256_grad.hip:377-390, pointconv_grad.hip:204-208,
+    # ptblock_grad.hip:417-421; the deals: common.h:101-111, cross_grad.hip:419-430, cross256_grad.hip:78-83, :189, :243
+    g, e = kv.grad_launch_grid, kv.expected_grad_kernels
+    fus = lambda total, **kw: g("fusion", b=1, n=total, **kw)["points"]
+    assert fus(1024)["workgroups"] == 256 and fus(1024)["by_xcd"] and fus(1020)["workgroups"] == 255 and not fus(1020)["by_xcd"]
+    assert fus(100000)["workgroups"] == 256 and fus(100000, cus=304)["workgroups"] == 304 and fus(2000, cus=304)["workgroups"] == 304
+    assert fus(29)["workgroups"] == 8 and fus(29)["by_xcd"] and fus(28)["workgroups"] == 7
+    r = fus(1025)   # steps 257, eighths of 33 steps = 132 points; workgroup 8 j + x starts at 132 x + 4 j and strides 128
+    assert r["dealt"][7][0] == [924, 925, 926, 927] and r["dealt"][7 + 8 * 25] == [[1024]] and r["dealt"][7 + 8 * 26] == []
+    assert r["dealt"][0] == [[0, 1, 2, 3], [128, 129, 130, 131]] and r["dealt"][8 * 2] == [[8, 9, 10, 11]]
+    assert fus(5)["dealt"] == [[[0, 1, 2, 3]], [[4]]]
+    x128 = lambda total, **kw: g("cross", d=128, b=1, n1=total, **kw)
+    roles = lambda t: [(v["workgroups"], v["by_xcd"]) for v in x128(t).values()]
+    assert roles(400) == [(100, False), (64, False), (64, False)]      # base 100: the own-row roles cannot go by XCD
+    assert roles(384) == [(96, True), (64, True), (64, True)] and roles(288) == [(72, True), (64, True), (64, True)]
+    assert roles(272) == [(68, False), (64, False), (64, False)] and roles(40) == [(10, False)] * 3 and roles(3) == [(1, False)] * 3
+    assert roles(32) == [(8, True)] * 3 and roles(5000) == [(128, True), (64, True), (64, True)]
+    assert [v["workgroups"] for v in x128(5000, cus=304).values()] == [152, 76, 76]
+    assert x128(400)["own0"]["dealt"][1] == [[4, 5, 6, 7], [260, 261, 262, 263]]
+    assert g("cross", d=64, b=1, n1=5000)["all"]["workgroups"] == 256 and g("cross", d=64, b=2, n1=31)["all"]["by_xcd"]
+    x256 = lambda total, **kw: g("cross", d=256, b=1, n1=total, **kw)
+    sizes = lambda t: tuple(x256(t)[k]["workgroups"] for k in ("z", "w", "dx"))
+    assert sizes(3) == (1, 1, 3) and sizes(8) == (2, 1, 8) and sizes(9) == (3, 2, 9) and sizes(511) == (128, 64, 511)
+    assert sizes(513) == (129, 64, 512) and sizes(1025) == (256, 64, 512) and tuple(x256(5000, cus=304)[k]["workgroups"] for k in ("z", "w", "dx")) == (256, 64, 512)
+    assert not x256(1024)["z"]["by_xcd"] and x256(1025)["z"]["dealt"][0] == [[0, 1, 2, 3], [1024]]
+    w = x256(1025)["w"]["dealt"]    # slices of 17 points in stages of 4
+    assert w[0] == [[0, 1, 2, 3], [4, 5, 6, 7], [8, 9, 10, 11], [12, 13, 14, 15], [16]] and w[60] == [[1020, 1021, 1022, 1023], [1024]] and w[61] == w[63] == []
+    assert x256(1025)["dx"]["dealt"][0] == [[0], [512], [1024]] and x256(1025)["dx"]["dealt"][1] == [[1], [513]]
+    agg = lambda total, **kw: g("pointconv_agg", b=1, s=total, **kw)["pairs"]
+    assert (agg(2048)["workgroups"], agg(2048)["units"]) == (256, 1024) and (agg(2049)["workgroups"], agg(2049)["units"]) == (256, 1025)
+    assert agg(9)["dealt"] == [[[0, 1, 2, 3]], [[4]]] and agg(1)["dealt"] == [[[0]]] and agg(2040)["workgroups"] == 255
+    ptb = lambda total, **kw: g("ptblock", b=1, n=total, **kw)["pairs"]
+    assert (ptb(2049)["workgroups"], ptb(2049)["units"]) == (256, 1025) and ptb(1)["dealt"] == [[[0]]] and ptb(122)["workgroups"] == 16 and ptb(122)["by_xcd"]
+    assert e("cross", d=128) == {"cross_grad_kernel<128>", "transposed_image_kernel", "cross_grad_reduce_kernel"}
+    assert e("cross", d=64) == {"cross_grad_kernel<64>", "cross_grad_reduce_kernel"} and len(e("cross", d=256)) == 4
+    assert e("fusion", b=1, n=1) == {"fusion_grad_kernel", "fusion_grad_reduce_kernel"} and "ptblock_transposed_images_kernel" in e("ptblock")
+    for bad in (dict(op="cross", d=32), dict(op="pointconv_agg", b=1, s=1, d=5), dict(op="pointconv_agg", b=1, s=1, d=260), dict(op="fusion", b=1, n=1, nb=32)):
+        with pytest.raises(ValueError):
+            e(**bad)
+
+
+def test_the_backward_mirror_deals_every_unit_to_exactly_one_workgroup_of_each_role():
+    for c in kv.GRAD_CASES:
+        for name, role in kv.grad_launch_grid(cus=CUS, **c).items():
+            flat = sorted(u for wg in role["dealt"] for rnd in wg for u in rnd)
+            assert flat == list(range(role["units"])), (kv.grad_case_id(c), name)
+            assert len(role["dealt"]) == role["workgroups"] and all(len(rnd) <= role["per"] for wg in role["dealt"] for rnd in wg)
+
+
+def _rounds(role):
+    return max(len(wg) for wg in role["dealt"])
+
+
+def _idle(role):
+    return sum(1 for wg in role["dealt"] if not wg)
+
+
+def _want(role):
+    return -(-role["units"] // role["per"])
+
+
+def _ragged_eighth(role):
+    """Dealt by XCD with a last eighth shorter than the others."""
+    chunk = -(-_want(role) // 8) * role["per"]
+    return role["by_xcd"] and role["units"] % chunk != 0
+
+
+def _dead_waves(role):
+    """Some workgroup takes a step with fewer units than waves."""
+    return any(len(rnd) < role["per"] for wg in role["dealt"] for rnd in wg)
+
+
+def _points(c):
+    return c["b"] * c[{"fusion": "n", "cross": "n1", "pointconv_agg": "s", "ptblock": "n"}[c["op"]]]
+
+
+def _ladder(role_name, units_are_pairs=False):
+    """The edges every one-role kernel shares."""
+    R = lambda g: g[role_name]
+    return {
+        "by XCD below the cap with a ragged last eighth": lambda c, g: R(g)["workgroups"] < CUS and _ragged_eighth(R(g)) and (not units_are_pairs or _points(c) % 2 == 1 or c["op"] == "ptblock"),
+        "first total above the cap: a second round that few workgroups take, and workgroups that receive nothing":
+            lambda c, g: R(g)["workgroups"] == CUS and _want(R(g)) == CUS + 1 and _rounds(R(g)) == 2 and _idle(R(g)) > 0,
+        "three or more rounds at the cap with a ragged last eighth": lambda c, g: R(g)["workgroups"] == CUS and _rounds(R(g)) >= 3 and _ragged_eighth(R(g)),
+    }
+
+
+GRAD_EDGES = {
+    ("fusion", None): {
+        "one point": lambda c, g: _points(c) == 1,
+        "three points: one workgroup with a dead wave": lambda c, g: _points(c) == 3 and g["points"]["workgroups"] == 1,
+        "five points: the second of two workgroups has one live wave": lambda c, g: g["points"]["dealt"] == [[[0, 1, 2, 3]], [[4]]],
+        "round-robin below the cap, a grid that is no multiple of 8, more than one batch element":
+            lambda c, g: 8 < g["points"]["workgroups"] < CUS and g["points"]["workgroups"] % 8 and c["b"] >= 2 and not c.get("same"),
+        "same and dup at a small total": lambda c, g: c.get("same") and c.get("dup") and _points(c) <= 64,
+        "coordinates of a real cloud's extent": lambda c, g: c.get("extent"),
+        **_ladder("points"),
+    },
+    ("cross", 64): {
+        "three points: one workgroup with a dead wave": lambda c, g: _points(c) == 3,
+        "round-robin below the cap": lambda c, g: 1 < g["all"]["workgroups"] < CUS and not g["all"]["by_xcd"] and c["b"] >= 2,
+        "coordinates of a real cloud's extent": lambda c, g: c.get("extent"),
+        **_ladder("all"),
+    },
+    ("cross", 128): {
+        "three points: three workgroups, one per role": lambda c, g: _points(c) == 3 and [r["workgroups"] for r in g.values()] == [1, 1, 1],
+        "all roles round-robin with equal grids": lambda c, g: len({r["workgroups"] for r in g.values()}) == 1 and g["data"]["workgroups"] > 1 and not any(r["by_xcd"] for r in g.values()),
+        "data role by XCD below its cap, own-row roles at their cap by XCD, a ragged eighth":
+            lambda c, g: g["data"]["by_xcd"] and g["data"]["workgroups"] < CUS // 2 and g["own0"]["workgroups"] == g["own2"]["workgroups"] == CUS // 4
+            and g["own0"]["by_xcd"] and g["own2"]["by_xcd"] and _ragged_eighth(g["data"]),
+        "data role round-robin forces the own-row roles round-robin through their base":
+            lambda c, g: not g["data"]["by_xcd"] and g["own0"]["workgroups"] % 8 == 0 and g["own0"]["workgroups"] >= 8 and not g["own0"]["by_xcd"] and not g["own2"]["by_xcd"],
+        "all roles at their cap by XCD with different round counts (3 or more) and a ragged eighth":
+            lambda c, g: [r["workgroups"] for r in g.values()] == [CUS // 2, CUS // 4, CUS // 4] and all(r["by_xcd"] for r in g.values())
+            and 3 <= _rounds(g["data"]) < _rounds(g["own0"]) == _rounds(g["own2"]) and _ragged_eighth(g["data"]),
+        "coordinates of a real cloud's extent": lambda c, g: c.get("extent"),
+    },
+    ("cross", 256): {
+        "three points: a dead wave in z, one slice of w, total below DX_GRID": lambda c, g: _points(c) == 3 and g["w"]["workgroups"] == 1 and g["dx"]["workgroups"] == 3,
+        "z below its cap with a ragged last workgroup": lambda c, g: 1 < g["z"]["workgroups"] < kv.X256_Z_GRID_CAP and len(g["z"]["dealt"][-1][-1]) < 4,
+        "z: the first total above 4 x 256": lambda c, g: g["z"]["units"] == 4 * kv.X256_Z_GRID_CAP + 1 and _rounds(g["z"]) == 2,
+        "z: three rounds with dead waves in the last": lambda c, g: _rounds(g["z"]) == 3 and _dead_waves(g["z"]) and c["n1"] < 4 * kv.X256_Z_GRID_CAP,
+        "w: a last slice shorter than the others, with a partial stage": lambda c, g: g["w"]["workgroups"] > 1 and [len(s) for s in g["w"]["dealt"] if s][-1:] != [len(g["w"]["dealt"][0])]
+            and len([s for s in g["w"]["dealt"] if s][-1][-1]) < kv.X256_W_PTS,
+        "w: slices that receive nothing": lambda c, g: _idle(g["w"]) > 0,
+        "dx: total below DX_GRID": lambda c, g: 1 < g["dx"]["units"] < kv.X256_DX_GRID,
+        "dx: total above DX_GRID, workgroups with different point counts": lambda c, g: g["dx"]["units"] > kv.X256_DX_GRID and len({len(wg) for wg in g["dx"]["dealt"]}) > 1,
+        "coordinates of a real cloud's extent": lambda c, g: c.get("extent"),
+    },
+    ("pointconv_agg", None): {
+        "one centre: the tail alone": lambda c, g: _points(c) == 1,
+        "nine centres: the second of two workgroups has the half pair": lambda c, g: _points(c) == 9 and g["pairs"]["dealt"] == [[[0, 1, 2, 3]], [[4]]],
+        "an odd tail with more than one batch element at the cap": lambda c, g: _points(c) % 2 == 1 and c["b"] >= 2 and g["pairs"]["workgroups"] == CUS,
+        "S = N": lambda c, g: c["s"] == c["n"],
+        "S < N": lambda c, g: c["s"] < c["n"],
+        "d = 32": lambda c, g: c["d"] == 32,
+        "d = 64": lambda c, g: c["d"] == 64,
+        "d = 128": lambda c, g: c["d"] == 128,
+        "coordinates of a real cloud's extent": lambda c, g: c.get("extent"),
+        **_ladder("pairs", units_are_pairs=True),
+    },
+    ("ptblock", None): {
+        "one point: the tail alone": lambda c, g: _points(c) == 1,
+        "an odd total in one batch element": lambda c, g: _points(c) % 2 == 1 and c["b"] == 1 and c["n"] > 1,
+        "an odd total in three batch elements: pairs straddle them": lambda c, g: _points(c) % 2 == 1 and c["b"] == 3 and c["n"] % 2 == 1,
+        "q, k, v packed with row stride 192": lambda c, g: c.get("packed"),
+        "a uniform softmax": lambda c, g: c.get("same"),
+        "logits of 80": lambda c, g: c.get("logits") == 80.0,
+        "coordinates of a real cloud's extent": lambda c, g: c.get("extent"),
+        **_ladder("pairs", units_are_pairs=True),
+    },
+}
+
+
+def grad_cases_reaching(key, edge):
+    op, d = key
+    mine = [c for c in kv.grad_cases(op) if d is None or c["d"] == d]
+    return [kv.grad_case_id(c) for c in mine if GRAD_EDGES[key][edge](c, kv.grad_launch_grid(cus=CUS, **c))]
+
+
+def test_the_backward_cases_reach_the_loop_edges():
+    """Every edge of GRAD_EDGES is reached by at least one case on the mirrored launch at 256 compute units; n1 != n2 in every cross case."""
+    missing = [f"{key}: {edge}" for key, edges in GRAD_EDGES.items() for edge in edges if not grad_cases_reaching(key, edge)]
+    assert not missing, missing
+    assert all(c["n1"] != c["n2"] for c in kv.grad_cases("cross"))
+    assert {c["op"] for c in kv.GRAD_CASES} == {key[0] for key in GRAD_EDGES}
+    ids = [kv.grad_case_id(c) for c in kv.GRAD_CASES]
+    assert len(set(ids)) == len(ids)
+
+
+def test_every_backward_kernel_of_the_fused_layers_has_a_parity_case():
+    emitted = emitted_kernels(GRAD_UNITS)
+    assert "cross_grad_kernel<128>" in emitted and "fusion_grad_kernel" in emitted, sorted(emitted)   # the demangling worked
+    unknown = sorted(set(GRAD_NOT_LAUNCHED) - emitted)
+    assert not unknown, f"GRAD_NOT_LAUNCHED names kernels the library does not build: {unknown}"
+    wanted = emitted - set(GRAD_NOT_LAUNCHED)
+    covered = set().union(*(kv.expected_grad_kernels(**c) for c in kv.GRAD_CASES))
+    missing = sorted(wanted - covered)
+    assert not missing, f"backward kernels without a parity case in tests/kernel_variants.py GRAD_CASES: {missing}"
+    stale = sorted(covered - wanted)
+    assert not stale, f"backward cases name kernels the library does not build: {stale}"
