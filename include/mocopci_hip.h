@@ -453,6 +453,32 @@ int mcp_fp_mlp_pack(int c2, int c1, int layers, const int *widths, const float *
 int mcp_fp_mlp(int b, int n, int m, int c2, int c1, int rule, int layers, const int *widths, const float *known_feats, const float *skip,
                const int *idx, const float *dist, const float *w3, const int *ulen, const float *packed, float *out, mcp_stream_t stream);
 
+/* Backward of mcp_fp_mlp (csrc/fp_mlp_grad.hip).  Inputs, rules, ulen and infinite slots as mcp_fp_mlp; grad_out (B,n,widths[L-1]) =
+ * dL/dout.  With gz_L = grad_out . [out > 0], gz_(l-1) = (W_l^T gz_l) . [h_(l-1) > 0] and dx = W_1^T gz_1 it writes
+ *   grad_skip (B,n,C1) = dx[C2:] (NULL with c1 = 0);
+ *   grad_known_feats (B,m,C2) += w_j dx[:C2] at idx_j, every destination row's addends in ascending position 3 p + j -- (order
+ *       (B,3n), seg (B,m+1)) = mcp_scatter_segments of idx viewed as (B,3n) with n = m; NULL: not computed, order / seg not read;
+ *   grad_w[l] (widths[l], cin_l) and grad_b[l] (widths[l]): host arrays of `layers` device pointers, of the FOLDED weights' shapes;
+ *   out (B,n,widths[L-1]) or NULL: the forward's result again, bit for bit.
+ * dist, w3 and the coordinates get NO gradient, as in the reference (its ThreeNN and ThreeInterpolate return none for them).
+ * A padded row has none of its float inputs read, grad_out included, writes zeros to grad_skip and adds nothing anywhere else; its
+ * row of idx must be readable (mcp_scatter_segments and the scatter walk every position; out-of-range values are left out).  Rows of
+ * known_feats that no live slot gathers get exactly zero; an infinite slot weighs exactly 0.  No atomics: every sum runs in a fixed
+ * order (mcp_interp3_apply_grad_sorted, mcp_linear_wgrad), two calls give identical bits.  packed: the image of
+ * mcp_fp_mlp_grad_pack (mcp_fp_mlp_grad_packed_floats floats: mcp_fp_mlp_pack's image followed by the slabs of the transposed
+ * weights), rebuilt whenever a weight changes.  workspace: mcp_fp_mlp_grad_workspace_bytes(b, n, ...) caller-owned bytes; it receives
+ * x (rows, C2+C1), h_l for l < L, gz_l for every l, dx[:C2] and the weights the blend used.  Supported shapes: those of mcp_fp_mlp;
+ * anything else MCP_ERR_UNSUPPORTED (sizes: 0), nothing launched.  known_feats, packed, grad_out, out, workspace -- and skip,
+ * grad_skip when c1 is a multiple of 4 -- 16-byte aligned.  No allocation, no environment variable, no host read of a length. */
+int mcp_fp_mlp_grad_packed_floats(int c2, int c1, int layers, const int *widths);
+int mcp_fp_mlp_grad_pack(int c2, int c1, int layers, const int *widths, const float *const *w, const float *const *b, float *packed,
+                         mcp_stream_t stream);
+size_t mcp_fp_mlp_grad_workspace_bytes(int b, int n, int c2, int c1, int layers, const int *widths);
+int mcp_fp_mlp_grad(int b, int n, int m, int c2, int c1, int rule, int layers, const int *widths, const float *known_feats,
+                    const float *skip, const int *idx, const float *dist, const float *w3, const int *ulen, const float *packed,
+                    const float *grad_out, const int *order, const int *seg, float *grad_known_feats, float *grad_skip,
+                    float *const *grad_w, float *const *grad_b, float *out, void *workspace, size_t workspace_bytes, mcp_stream_t stream);
+
 /* Backward of mcp_cross_volume for one cross layer given by its own weights (the reference differentiates pointconv_util.py:765-781
  * with autograd over three materialised (B,D,32,N1) tensors; its hand-written backward pieces are the atomicAdd scatters of
  * group_points_gpu.cu:8-44).  xyz1, xyz2, points1, points2, idx / idx2 as mcp_cross_volume (no batch map); wpos (D,3), bpos (D),

@@ -80,6 +80,10 @@ SIGNATURES = {
     "mcp_fp_mlp_packed_floats": [_i, _i, _i, _p],
     "mcp_fp_mlp_pack": [_i, _i, _i, _p, _p, _p, _p, _p],
     "mcp_fp_mlp": [_i] * 7 + [_p] * 10,
+    "mcp_fp_mlp_grad_packed_floats": [_i, _i, _i, _p],
+    "mcp_fp_mlp_grad_pack": [_i, _i, _i, _p, _p, _p, _p, _p],
+    "mcp_fp_mlp_grad_workspace_bytes": [_i, _i, _i, _i, _i, _p],
+    "mcp_fp_mlp_grad": [_i] * 7 + [_p] * 17 + [ctypes.c_size_t, _p],
     "mcp_cross_grad_floats": [_i],
     "mcp_cross_grad_workspace_bytes": [_i, _i, _i],
     "mcp_cross_grad": [_i] * 5 + [_p] * 17 + [ctypes.c_size_t, _p],
@@ -147,7 +151,8 @@ _RESTYPES = {"mcp_error_string": ctypes.c_char_p, "mcp_fps_workspace_bytes": cty
              "mcp_ptblock_grad_workspace_bytes": ctypes.c_size_t, "mcp_attention_small_grad_workspace_bytes": ctypes.c_size_t,
              "mcp_attention_wide_grad_workspace_bytes": ctypes.c_size_t,
              "mcp_linear_wgrad_workspace_bytes": ctypes.c_size_t, "mcp_scatter_segments_workspace_bytes": ctypes.c_size_t,
-             "mcp_prelu_dropout_grad_workspace_bytes": ctypes.c_size_t, "mcp_emd_levels_floats": ctypes.c_size_t}
+             "mcp_prelu_dropout_grad_workspace_bytes": ctypes.c_size_t, "mcp_emd_levels_floats": ctypes.c_size_t,
+             "mcp_fp_mlp_grad_workspace_bytes": ctypes.c_size_t}
 
 _lib = None
 

@@ -650,6 +650,20 @@ def fold_conv_bn(conv, bn=None):
     return w.float().contiguous(), b.float().contiguous()
 
 
+def fold_conv_bn_grad(conv, bn=None):
+    """fold_conv_bn as an autograd function of conv.weight, conv.bias, bn.weight and bn.bias (the running statistics are constants):
+    the same float64 expressions and the same single rounding, so the values have fold_conv_bn's bits; the gradient of (W', b')
+    reaches the four parameters through autograd's chain rule.  For the differentiable fused layers (HipBackend.fp_mlp_layer)."""
+    w = conv.weight.double().flatten(1)
+    b = conv.bias.double() if conv.bias is not None else w.new_zeros(w.shape[0])
+    if bn is not None:
+        g = bn.weight.double() if bn.weight is not None else w.new_ones(w.shape[0])
+        beta = bn.bias.double() if bn.bias is not None else w.new_zeros(w.shape[0])
+        scale = g / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+        w, b = w * scale[:, None], (b - bn.running_mean.detach().double()) * scale + beta
+    return w.float().contiguous(), b.float().contiguous()
+
+
 def group_mlp_pack_weights(weights, use_xyz=True):
     """The MFMA-operand image of mcp_group_mlp from [(W (out, in), b (out,)), ...] fp32 device tensors -> (packed, widths)."""
     widths = [int(w.shape[0]) for w, _ in weights]
@@ -755,6 +769,101 @@ def fp_mlp_pack(convs, bns=None, c2=None):
     (the leading input columns of the first layer).  -> (packed, widths) for HipBackend.fp_mlp."""
     bns = [None] * len(convs) if bns is None else list(bns)
     return fp_mlp_pack_weights([fold_conv_bn(c, b) for c, b in zip(convs, bns)], c2)
+
+
+# ---- backward of the feature-propagation layer (csrc/fp_mlp_grad.hip) ----
+def fp_mlp_grad_supported(c2, c1, widths):
+    """The shapes mcp_fp_mlp_grad is built for: every shape of mcp_fp_mlp (no register class was narrowed)."""
+    return fp_mlp_supported(c2, c1, widths)
+
+
+def fp_mlp_grad_image_bytes(c2, c1, widths):
+    """Bytes of the backward slabs (the transposed weights) of a supported shape: for l = L .. 2 the two k-steps per tile of gz_l into
+    the tiles of layer l - 1, then the k-steps of gz_1 into the ceil((c2 + c1) / 32) tiles of dx."""
+    tiles = [w // 32 for w in widths]
+    slabs = sum(2 * tiles[l] * tiles[l - 1] for l in range(1, len(tiles))) + 2 * tiles[0] * ((c2 + c1 + 31) // 32)
+    return slabs * 3 * 64 * 16
+
+
+def fp_mlp_grad_packed_floats(c2, c1, widths):
+    """Floats of mcp_fp_mlp_grad_pack's image: the forward image (slabs, biases), then the backward slabs."""
+    return (fp_mlp_image_bytes(c2, c1, widths) + fp_mlp_grad_image_bytes(c2, c1, widths)) // 4 + sum(widths)
+
+
+def fp_mlp_grad_weights_in_lds(c2, c1, widths):
+    """Python mirror of the backward kernel's one staging predicate (fg_whole): both halves of the image at most 64 KB."""
+    return fp_mlp_weights_in_lds(c2, c1, widths) and fp_mlp_grad_image_bytes(c2, c1, list(widths)) <= FP_MLP_LDS_IMAGE_BYTES
+
+
+# Shape classes (c2, c1, widths) -> fewest rows B * n at which the module's fused differentiable route (three_nn, transpositions,
+# mcp_fp_mlp forward, mcp_fp_mlp_grad backward) measured faster, forward + backward, than the composition's forward + backward by
+# more than the composition's own spread (tools/fp_mlp_grad_times.py -> profiles/fp_mlp_grad_times.json).  A class without a row
+# keeps the composition.  Measured at B = 8 (ms, forward + backward): 256 + 3 -> 256/256 over n = 16384 (3.225 against 3.651, spread
+# 0.055) enters; 256 + 128 -> 256/256 over n = 1024 (1.052 against 0.873) and 128 + 4 -> 128/128/128 over n = 4096 (0.998 against
+# 0.903) are slower and stay out.
+FP_MLP_GRAD_FUSED_CLASSES = {(256, 3, (256, 256)): 8 * 16384}
+
+
+def fp_mlp_grad_routes_fused(c2, c1, widths, rows):
+    """PointnetFPModule's route predicate when a gradient is wanted: a pure function of the padded shapes."""
+    least = FP_MLP_GRAD_FUSED_CLASSES.get(fp_mlp_class(c2, c1, widths))
+    return least is not None and rows >= least
+
+
+def _grad_empty(shape, dtype, device):
+    """Every buffer the fused backward allocates (the tests refill them with NaN: each must be written before it is read)."""
+    return torch.empty(shape, dtype=dtype, device=device)
+
+
+def fp_mlp_grad_pack_weights(weights, c2):
+    """mcp_fp_mlp_grad_pack's image from [(W (out, in), b (out,)), ...] fp32 device tensors -> (packed, widths)."""
+    widths = [int(w.shape[0]) for w, _ in weights]
+    c2 = int(c2)
+    c1 = int(weights[0][0].shape[1]) - c2
+    lib = _lib.load()
+    wid = (ctypes.c_int * len(widths))(*widths)
+    n = lib.mcp_fp_mlp_grad_packed_floats(c2, c1, len(widths), wid) if len(widths) <= 3 and c1 >= 0 else 0
+    if n == 0:
+        raise _lib.Unsupported(f"fp_mlp_grad: unsupported shape c2={c2} c1={c1} widths={widths}")
+    cin = [c2 + c1, *widths[:-1]]
+    for (w, b), k, o in zip(weights, cin, widths):
+        if tuple(w.shape) != (o, k) or tuple(b.shape) != (o,):
+            raise RuntimeError(f"fp_mlp_grad: expected W {(o, k)} and b {(o,)}, got {tuple(w.shape)} and {tuple(b.shape)}")
+    ws = [w.contiguous() for w, _ in weights]
+    bs = [b.contiguous() for _, b in weights]
+    packed = _grad_empty((n,), torch.float32, ws[0].device)
+    wp = (ctypes.c_void_p * len(ws))(*[_lib.fptr(w) for w in ws])
+    bp = (ctypes.c_void_p * len(bs))(*[_lib.fptr(b) for b in bs])
+    _call("mcp_fp_mlp_grad_pack", packed, c2, c1, len(widths), wid, wp, bp, _lib.fptr(packed))
+    return packed, widths
+
+
+class _FpMlpLayerFn(torch.autograd.Function):
+    """mcp_fp_mlp with its hand-written backward (mcp_fp_mlp_grad): the layer is re-evaluated inside the backward kernel, so only
+    the inputs are kept (not even the output: the kernel takes the last ReLU mask from its own recompute) -- autograd over the composition keeps (B, C2, n), (B, C2 + C1, n) and one (B, C, n) per layer.
+    Gradients: known_feats, skip, every W and b; dist, w3 and the lengths get none (as the reference's ThreeNN / ThreeInterpolate)."""
+
+    @staticmethod
+    def forward(ctx, be, rule, idx, dist, w3, ulen, known_feats, skip, *wb):
+        known_feats = known_feats.detach().contiguous()
+        skip = None if skip is None else skip.detach().contiguous()
+        wb = [t.detach().contiguous() for t in wb]
+        weights = list(zip(wb[0::2], wb[1::2]))
+        packed, widths = fp_mlp_pack_weights(weights, known_feats.shape[-1])
+        out = be.fp_mlp(known_feats, skip, idx, dist, packed, widths, rule=rule, w3=w3, unknown_lengths=ulen)
+        ctx.be, ctx.rule, ctx.has_skip = be, rule, skip is not None
+        ctx.save_for_backward(idx, dist, w3, ulen, known_feats, skip, *wb)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        idx, dist, w3, ulen, known_feats, skip, *wb = ctx.saved_tensors
+        weights = list(zip(wb[0::2], wb[1::2]))
+        d_known, d_skip, d_w, d_b, _ = ctx.be.fp_mlp_grad(known_feats, skip, idx, dist, weights, grad_out, rule=ctx.rule, w3=w3, unknown_lengths=ulen,
+                                                          want_known=ctx.needs_input_grad[6])
+        pieces = [t for pair in zip(d_w, d_b) for t in pair]
+        return (None, None, None, None, None, None, d_known, d_skip if ctx.needs_input_grad[7] else None, *pieces)
 
 
 class _ChamferLengthsFn(torch.autograd.Function):
@@ -1409,6 +1518,66 @@ class HipBackend:
               None if skip is None or C1 == 0 else _lib.fptr(skip), _lib.iptr(idx), None if code == 0 else _lib.fptr(dist),
               _lib.fptr(w3) if code == 0 else None, None if ul is None else _lib.iptr(ul), _lib.fptr(packed), _lib.fptr(out))
         return out
+
+    def fp_mlp_grad(self, known_feats, skip, idx, dist, weights, grad_out, rule="pointnet2", w3=None, unknown_lengths=None, want_known=True,
+                    recompute_out=False):
+        """Backward of fp_mlp for weights = [(W, b), ...] (folded, fp32) and grad_out (B,n,widths[-1]) in one kernel launch plus the
+        deterministic scatter and one weight-gradient product per layer (mcp_fp_mlp_grad) -> (grad_known_feats (B,m,C2) or None,
+        grad_skip (B,n,C1) or None, [dW_l], [db_l], the recomputed out or None).  Bit-reproducible; unsupported shapes raise."""
+        B, m, C2 = known_feats.shape
+        n = idx.shape[1]
+        C1 = 0 if skip is None else skip.shape[2]
+        code = FP_MLP_RULES[rule]
+        dev = known_feats.device
+        if tuple(idx.shape) != (B, n, 3) or (skip is not None and tuple(skip.shape[:2]) != (B, n)):
+            raise RuntimeError(f"fp_mlp_grad: idx {tuple(idx.shape)} / skip do not match B={B}, n={n}")
+        for name, t in (("w3", w3),) if code == 0 else (("dist", dist),):
+            if t is None or tuple(t.shape) != (B, n, 3):
+                raise RuntimeError(f"fp_mlp_grad: rule {rule!r} needs {name} of shape {(B, n, 3)}")
+        widths = [int(w.shape[0]) for w, _ in weights]
+        if not fp_mlp_grad_supported(C2, C1, widths) or int(weights[0][0].shape[1]) != C2 + C1:
+            raise _lib.Unsupported(f"fp_mlp_grad: unsupported shape c2={C2} c1={C1} widths={widths}")
+        if tuple(grad_out.shape) != (B, n, widths[-1]):
+            raise RuntimeError(f"fp_mlp_grad: grad_out {tuple(grad_out.shape)}, expected {(B, n, widths[-1])}")
+        if B == 0 or n == 0 or m == 0:
+            raise RuntimeError("fp_mlp_grad: empty batch, unknown or known cloud")
+        lib = _lib.load()
+        ul = lengths_tensor(unknown_lengths, B, n, dev)
+        grad_out = grad_out.contiguous()
+        packed, _ = fp_mlp_grad_pack_weights(weights, C2)
+        wid = (ctypes.c_int * len(widths))(*widths)
+        need = lib.mcp_fp_mlp_grad_workspace_bytes(B, n, C2, C1, len(widths), wid)
+        if need == 0:
+            raise _lib.Unsupported(f"fp_mlp_grad: unsupported shape c2={C2} c1={C1} widths={widths} rows={B * n}")
+        ws = _grad_empty((need,), torch.uint8, dev)
+        d_known = _grad_empty((B, m, C2), torch.float32, dev) if want_known else None
+        d_skip = _grad_empty((B, n, C1), torch.float32, dev) if C1 else None
+        d_w = [_grad_empty(tuple(w.shape), torch.float32, dev) for w, _ in weights]
+        d_b = [_grad_empty(tuple(b.shape), torch.float32, dev) for _, b in weights]
+        out = _grad_empty((B, n, widths[-1]), torch.float32, dev) if recompute_out else None
+        order, seg = _scatter_segments(idx, m) if want_known else (None, None)
+        gw = (ctypes.c_void_p * len(d_w))(*[_lib.fptr(t) for t in d_w])
+        gb = (ctypes.c_void_p * len(d_b))(*[_lib.fptr(t) for t in d_b])
+        _call("mcp_fp_mlp_grad", known_feats, B, n, m, C2, C1, code, len(widths), wid, _lib.fptr(known_feats),
+              None if C1 == 0 else _lib.fptr(skip), _lib.iptr(idx), None if code == 0 else _lib.fptr(dist), _lib.fptr(w3) if code == 0 else None,
+              None if ul is None else _lib.iptr(ul), _lib.fptr(packed), _lib.fptr(grad_out), None if order is None else _lib.iptr(order),
+              None if seg is None else _lib.iptr(seg), None if d_known is None else _lib.fptr(d_known), None if d_skip is None else _lib.fptr(d_skip),
+              gw, gb, None if out is None else _lib.fptr(out), ws.data_ptr(), need)
+        return d_known, d_skip, d_w, d_b, out
+
+    def fp_mlp_layer(self, known_feats, skip, idx, dist, weights, rule="pointnet2", w3=None, unknown_lengths=None):
+        """The feature-propagation layer from its own weights [(W (out, in), b (out,)), ...] (BatchNorm folded in: fold_conv_bn_grad
+        keeps the parameters in the graph); arguments as fp_mlp.  Without a wanted gradient it is fp_mlp on a pack of `weights`;
+        with one it is an autograd function -- mcp_fp_mlp forward, mcp_fp_mlp_grad backward -- that returns gradients for
+        known_feats, skip and every W and b, and keeps only its inputs."""
+        flat = [t for pair in weights for t in pair]
+        if not grad.wants_grad(known_feats, skip, *flat):
+            packed, widths = fp_mlp_pack_weights([(w.detach(), b.detach()) for w, b in weights], known_feats.shape[-1])
+            return self.fp_mlp(known_feats.detach(), None if skip is None else skip.detach(), idx, dist, packed, widths, rule=rule, w3=w3,
+                               unknown_lengths=unknown_lengths)
+        B, n = idx.shape[0], idx.shape[1]
+        ul = lengths_tensor(unknown_lengths, B, n, known_feats.device)
+        return _FpMlpLayerFn.apply(self, rule, idx.contiguous(), dist, w3, ul, known_feats, skip, *flat)
 
     def ptblock_layer(self, xyz, q, k, v, idx, weights, packed=None):
         """TransformerBlock vector attention from the block's own weights (wd1,bd1,wd2,bd2,wg1,bg1,wg2,bg2); differentiable."""

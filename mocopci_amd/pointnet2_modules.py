@@ -12,7 +12,9 @@ Two routes give the same layer:
     class that the measurement of tools/group_mlp_times.py found faster (ops.GROUP_MLP_FUSED_CLASSES; `route` overrides it).
 PointnetFPModule has the same two routes: the composition -- three_nn, the weights in torch, three_interpolate, cat, the shared
 stack -- and one mcp_fp_mlp launch after the three-neighbour search (ops.HipBackend.fp_mlp; ops.FP_MLP_FUSED_CLASSES from
-tools/fp_mlp_times.py)."""
+tools/fp_mlp_times.py).  When a gradient is wanted its fused route is the differentiable layer ops.HipBackend.fp_mlp_layer
+(mcp_fp_mlp_grad backward), taken in eval() or without BatchNorm for a class of ops.FP_MLP_GRAD_FUSED_CLASSES
+(tools/fp_mlp_grad_times.py; `grad_route` overrides it)."""
 from typing import List
 
 import torch
@@ -149,13 +151,16 @@ class PointnetFPModule(nn.Module):
     known points, concatenated with the unknown points' own (skip) features and sent through the shared MLP `mlp` (its first entry
     counts C2 + C1).  weighting: "pointnet2" (weights 1 / (dist + 1e-8), normalised; the reference class) or "flownet3d"
     (1 / max(dist^2, 1e-10), normalised; FeaturePropagation of models/layers.py).  route: "measured" (default), "always" or "never"
-    for the fused route."""
+    for the fused route when no gradient is wanted; grad_route: the same three values, independently, for the fused differentiable
+    route (mcp_fp_mlp forward, mcp_fp_mlp_grad backward) when one is -- eligible in eval() or with bn=False; a training-mode
+    BatchNorm keeps the composition."""
 
     def __init__(self, *, mlp: List[int], bn: bool = True):
         super().__init__()
         self.bn = bn
         self.weighting = "pointnet2"
         self.route = "measured"
+        self.grad_route = "measured"
         self.mlp = _shared_mlp(list(mlp), bn, False)
         self.__dict__["_packed"] = None
 
@@ -182,6 +187,16 @@ class PointnetFPModule(nn.Module):
         if not convs or convs[0].in_channels != c2 + c1 or not ops.fp_mlp_supported(c2, c1, widths):
             return False
         return self.route == "always" or ops.fp_mlp_routes_fused(c2, c1, widths, rows)
+
+    def fused_grad(self, c2, c1, rows):
+        """Whether a call that wants a gradient takes the fused differentiable route: BatchNorm folded (eval mode) or absent."""
+        if (self.training and self.bn) or self.grad_route == "never" or self.weighting not in ("pointnet2", "flownet3d"):
+            return False
+        convs = self._layers()[0]
+        widths = [c.out_channels for c in convs]
+        if not convs or convs[0].in_channels != c2 + c1 or not ops.fp_mlp_grad_supported(c2, c1, widths):
+            return False
+        return self.grad_route == "always" or ops.fp_mlp_grad_routes_fused(c2, c1, widths, rows)
 
     def weights(self, dist):
         """(B,n,3) interpolation weights of three_nn's distances under `weighting`; a row without a finite distance gets zeros."""
@@ -216,6 +231,13 @@ class PointnetFPModule(nn.Module):
             rows = known_feats.detach().transpose(1, 2).contiguous()
             skip = None if unknow_feats is None else unknow_feats.detach().transpose(1, 2).contiguous()
             out = ops.backend().fp_mlp(rows, skip, idx, dist, packed, widths, rule=self.weighting, unknown_lengths=ul)
+            return out.transpose(1, 2)
+        if known is not None and wants_grad and self.fused_grad(C2, C1, B * n):
+            dist, idx = pu.three_nn(unknown.detach().contiguous(), known.detach().contiguous(), ul, kl)   # no gradient reaches the coordinates
+            rows = known_feats.transpose(1, 2).contiguous()
+            skip = None if unknow_feats is None else unknow_feats.transpose(1, 2).contiguous()
+            folded = [ops.fold_conv_bn_grad(c, b) for c, b in zip(*self._layers())]
+            out = ops.backend().fp_mlp_layer(rows, skip, idx, dist, folded, rule=self.weighting, unknown_lengths=ul)
             return out.transpose(1, 2)
         if known is not None:
             dist, idx = pu.three_nn(unknown.contiguous(), known.contiguous(), ul, kl)
