@@ -12,13 +12,6 @@
 
 constexpr int BQ_WAVES = 4;   // centres (waves) per workgroup
 
-// (B) int32 device array, one wave-uniform load, clamped to [0, full]; a null pointer means every row is live
-__device__ __forceinline__ int bq_clamped_len(const int *__restrict__ len, int b, int full) {
-    if (!len) return full;
-    const int v = len[b];
-    return v < 0 ? 0 : (v > full ? full : v);
-}
-
 // the row of a centre without a hit, or of a padded centre
 __device__ __forceinline__ void bq_zero_row(int lane, int nsample, int *__restrict__ o, int *__restrict__ cnt_slot) {
     for (int l = lane; l < nsample; l += 64) o[l] = 0;

@@ -43,7 +43,7 @@ __global__ __launch_bounds__(64 * BQ_WAVES) void ball_query_pruned_kernel(int n,
     const int b = blockIdx.y;
     const int p = blockIdx.x * BQ_WAVES + wave;
     if (p >= m) return;  // whole wave; no workgroup barriers below
-    const int ql = bq_clamped_len(qlen, b, m), rl = bq_clamped_len(rlen, b, n);
+    const int ql = mcp_clamped_len(qlen, b, m), rl = mcp_clamped_len(rlen, b, n);
     int *o = idx + ((size_t)b * m + p) * nsample;
     int *co = cnt_out ? cnt_out + (size_t)b * m + p : nullptr;
     if (p >= ql || rl == 0) {  // wave-uniform: a padded centre, or nothing to search -- before any load of a coordinate or a box

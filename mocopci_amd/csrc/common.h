@@ -31,6 +31,15 @@ __device__ __forceinline__ float mcp_unord(uint32_t u) {
     return __uint_as_float(u);
 }
 
+// Per-cloud lengths: a (B) int32 device array, one wave-uniform load per workgroup (b comes from the block index), clamped to
+// [0, full]; a null pointer means every row is valid.  Strides and grids keep the padded sizes; only comparisons use the clamped
+// value, and a row at or beyond it is never loaded.
+__device__ __forceinline__ int mcp_clamped_len(const int *__restrict__ len, int b, int full) {
+    if (!len) return full;
+    const int v = len[b];
+    return v < 0 ? 0 : (v > full ? full : v);
+}
+
 // ---- DPP helpers (wave64; row = 16 lanes) ----
 template <int CTRL>
 __device__ __forceinline__ uint32_t mcp_dpp(uint32_t v) {

@@ -50,12 +50,6 @@ __device__ __forceinline__ float4 load_ref(const float *__restrict__ ref, int i,
     return MODE == MCP_DIST_EXPANSION ? make_float4(0.f, 0.f, 0.f, INFINITY) : make_float4(INFINITY, 0.f, 0.f, 0.f);
 }
 
-__device__ __forceinline__ int clamped_len(const int *__restrict__ len, int b, int full) {
-    if (!len) return full;
-    const int v = len[b];  // b = blockIdx.y: one scalar load per workgroup
-    return v < 0 ? 0 : (v > full ? full : v);
-}
-
 // mcp_store_list with an optional index output
 template <int K>
 __device__ __forceinline__ void store_list(const u64 (&a)[K], int kout, int *oi, float *od) {
@@ -87,7 +81,7 @@ __device__ __forceinline__ void knn_small_body(float4 (&tiles)[SPLIT][2][TILE], 
                                                float *__restrict__ dist) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = blockIdx.y;
-    const int ql = LEN ? clamped_len(qlen, b, q) : q, nl = LEN ? clamped_len(rlen, b, n) : n;
+    const int ql = LEN ? mcp_clamped_len(qlen, b, q) : q, nl = LEN ? mcp_clamped_len(rlen, b, n) : n;
     const int qi = blockIdx.x * 64 + lane;
     int *oi = !LEN || idx ? idx + ((size_t)b * q + qi) * kout : nullptr;
     float *od = dist ? dist + ((size_t)b * q + qi) * kout : nullptr;
@@ -202,7 +196,7 @@ __device__ __forceinline__ void knn_queue_body(float4 *smem, int q, int n, int k
     uint2(*queue)[64] = reinterpret_cast<uint2(*)[64]>(wbase + L::TILE_BYTES);
 
     const int b = blockIdx.y;
-    const int ql = LEN ? clamped_len(qlen, b, q) : q, nl = LEN ? clamped_len(rlen, b, n) : n;
+    const int ql = LEN ? mcp_clamped_len(qlen, b, q) : q, nl = LEN ? mcp_clamped_len(rlen, b, n) : n;
     const int qi = blockIdx.x * 64 + lane;
     int *oi = !LEN || idx ? idx + ((size_t)b * q + qi) * kout : nullptr;
     float *od = dist ? dist + ((size_t)b * q + qi) * kout : nullptr;

@@ -260,8 +260,8 @@ __global__ __launch_bounds__(64 * BQ_WAVES) void ball_query_kernel(int n, int m,
     if (p >= m) return;  // whole wave; no barriers below
     int *o = idx + ((size_t)b * m + p) * nsample;
     int *co = LEN && cnt_out ? cnt_out + (size_t)b * m + p : nullptr;
-    const int rl = LEN ? bq_clamped_len(rlen, b, n) : n;
-    if (LEN && (p >= bq_clamped_len(qlen, b, m) || rl == 0)) {  // wave-uniform
+    const int rl = LEN ? mcp_clamped_len(rlen, b, n) : n;
+    if (LEN && (p >= mcp_clamped_len(qlen, b, m) || rl == 0)) {  // wave-uniform
         bq_zero_row(lane, nsample, o, co);
         return;
     }
@@ -295,8 +295,8 @@ __global__ __launch_bounds__(64 * BQ_WAVES) void query_and_group_kernel(int n, i
     const int b = blockIdx.y;
     const int p = blockIdx.x * BQ_WAVES + wave;
     if (p >= m) return;  // whole wave; no workgroup barriers below
-    const int rl = LEN ? bq_clamped_len(rlen, b, n) : n;
-    if (LEN && (p >= bq_clamped_len(qlen, b, m) || rl == 0)) {  // wave-uniform; the lane-to-output map of the gather below
+    const int rl = LEN ? mcp_clamped_len(rlen, b, n) : n;
+    if (LEN && (p >= mcp_clamped_len(qlen, b, m) || rl == 0)) {  // wave-uniform; the lane-to-output map of the gather below
         const int cpl = 64 / nsample, slot = lane % nsample, coff = lane / nsample, ct = xyz_ch + (features ? c : 0);
         if (coff < cpl)
             for (int ch = coff; ch < ct; ch += cpl) out[(((size_t)b * ct + ch) * m + p) * nsample + slot] = 0.f;

@@ -101,16 +101,17 @@ def test_three_step_route_under_lengths():
 
 # ---- the search, through the C entry point ----------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
-def pruned(B, Q, N, K, mode, qlen, rlen, filling=0):
-    """mcp_knn_pruned_lengths on clouds built under the same lengths; CPU copies of (idx, dist), pre-filled with a sentinel."""
+def pruned(B, Q, N, K, mode, qlen, rlen, filling=0, null_lengths=False):
+    """mcp_knn_pruned_lengths on clouds built under the same lengths; CPU copies of (idx, dist), pre-filled with a sentinel.
+    null_lengths: both length arrays NULL (clouds built length-free), so the call lands in mcp_knn_pruned."""
     be = ops.backend()
     query, ref = (t.to(DEV) for t in padded_pair(B, Q, N, qlen, rlen, filling))
-    ql, rl = dev_lengths(qlen), dev_lengths(rlen)
+    ql, rl = (None, None) if null_lengths else (dev_lengths(qlen), dev_lengths(rlen))
     qs, qperm, _ = be._build_cloud(query, ql)
     rs, rperm, boxes = be._build_cloud(ref, rl)
     idx, dist = torch.full((B, Q, K), -7, dtype=torch.int32, device=DEV), torch.full((B, Q, K), -7.0, device=DEV)
     ops._call("mcp_knn_pruned_lengths", query, B, Q, N, K, mode, _lib.fptr(qs), _lib.iptr(qperm), _lib.fptr(rs), _lib.iptr(rperm),
-              _lib.fptr(boxes), _lib.iptr(ql), _lib.iptr(rl), _lib.iptr(idx), _lib.fptr(dist))
+              _lib.fptr(boxes), None if ql is None else _lib.iptr(ql), None if rl is None else _lib.iptr(rl), _lib.iptr(idx), _lib.fptr(dist))
     return idx.cpu(), dist.cpu()
 
 
@@ -136,10 +137,21 @@ def test_both_kernels_against_the_oracle(K, mode):
 
 
 @pytest.mark.parametrize("mode", [0, 1])
-@pytest.mark.parametrize("K", [1, 32])
+@pytest.mark.parametrize("K", [1, 16, 32])           # round 3's kernel in its K <= 4 and K <= 16 classes, the walk kernel
 @pytest.mark.parametrize("N", [5000, 9000, 20000])   # 2, 4 and 16 tile bounds per lane; 20000 through the external sort
 def test_every_tile_count_instantiation(N, K, mode):
     check(2, 130, N, K, mode, (130, 130), (N, N // 2 + 1))
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+@pytest.mark.parametrize("K", [1, 16, 32])
+@pytest.mark.parametrize("N", [5000, 9000, 20000])
+def test_every_tile_count_instantiation_without_lengths(N, K, mode):
+    """The same shapes with both length arrays NULL: the length-free kernels (mcp_knn_pruned), every row live, against the oracle."""
+    B, Q = 2, 130
+    idx, dist = pruned(B, Q, N, K, mode, (Q,) * B, (N,) * B, null_lengths=True)
+    want_i, want_d = expected(B, Q, N, K, mode, (Q,) * B, (N,) * B)
+    assert torch.equal(idx, want_i) and torch.equal(dist, want_d)
 
 
 @pytest.mark.parametrize("K,mode", [(4, 1), (16, 0), (32, 1)])

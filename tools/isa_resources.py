@@ -4,7 +4,10 @@ spilled scalar / vector registers, waves per SIMD the registers allow.  A kernel
 `false` is compared with the kernel of the first file that lacks that argument (a compile-time flag added since); kernels that end
 in `true`, and kernels the first file does not have at all (a new unit: pass an empty file), are listed on their own.
 
-    python tools/isa_resources.py PARENT.s NOW.s > profiles/NAME_resources.txt"""
+    python tools/isa_resources.py PARENT.s NOW.s > profiles/NAME_resources.txt
+
+`--same-names PARENT.s NOW.s`: both files hold the same kernels (a refactor).  Every kernel is compared name to name, with its static
+instruction count (the lines of its body that are neither labels, directives nor comments) and that count's movement."""
 import re
 import subprocess
 import sys
@@ -30,7 +33,39 @@ def parse(path):
     return dict(zip(short, (out[n] for n in names)))
 
 
+def with_instruction_counts(path):
+    """parse(path) with an `insns` figure per kernel"""
+    res, txt = parse(path), open(path).read()
+    for name, v in res.items():
+        v["insns"] = None
+    bodies = {m.group(1): m.group(2) for m in re.finditer(r"^(_Z\w+):[^\n]*\n(.*?)^\.Lfunc_end\d+:", txt, re.S | re.M)}
+    plain = subprocess.run(["c++filt"] + list(bodies), capture_output=True, text=True, check=True).stdout.split("\n")
+    for mangled, full in zip(bodies, plain):
+        short = re.sub(r"\(.*", "", full.replace("void ", "").replace("(anonymous namespace)::", ""))
+        lines = (x.strip() for x in bodies[mangled].split("\n"))
+        if short in res:
+            res[short]["insns"] = sum(1 for x in lines if x and not x.startswith((";", ".")) and not x.endswith(":"))
+    return res
+
+
+def same_names(parent_path, now_path):
+    parent, now = with_instruction_counts(parent_path), with_instruction_counts(now_path)
+    assert set(parent) == set(now), sorted(set(parent) ^ set(now))
+    fields = FIELDS + ("insns",)
+    row = lambda v: "".join(f"{v[k]:>9}" for k in fields)
+    print(f"{'kernel':<44}{'':8}" + "".join(f"{k:>9}" for k in fields))
+    moved = 0
+    for n in sorted(now):
+        same = all(parent[n][k] == now[n][k] for k in FIELDS)
+        moved += not same
+        d = 100.0 * (now[n]["insns"] - parent[n]["insns"]) / parent[n]["insns"]
+        print(f"{n:<44}{'parent':<8}{row(parent[n])}\n{'':<44}{'now':<8}{row(now[n])}   {'unchanged' if same else 'MOVED'}, instructions {d:+.2f} %")
+    print(f"\n{len(now)} kernels, {moved} with a resource figure that moved")
+
+
 def main():
+    if sys.argv[1] == "--same-names":
+        return same_names(sys.argv[2], sys.argv[3])
     parent, now = parse(sys.argv[1]), parse(sys.argv[2])
     stripped = lambda n: re.sub(r"<false>$", "", re.sub(r", false>$", ">", n))
     base = lambda n: n if n in parent else stripped(n)   # a kernel that had the argument already keeps its name

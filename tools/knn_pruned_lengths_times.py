@@ -9,6 +9,8 @@ Shapes (B, Q, N, K, distance form, query lengths, reference lengths):
   full_k32, half_k32  8 x  8192 x  8192, K = 32 expansion, both lengths 8192 / 4096
   min_k1, min_k32     8 x  1024 x  2048, the smallest shape of the size rule, about half lengths (513 / 1000); K = 1 direct, K = 32 expansion
   mid_k1, mid_k32     8 x  2048 x  4096 likewise (1030 / 2000)
+  full_k16           48 x  2048 x  2048, K = 16 expansion, both lengths 2048: round 3's kernel in its K <= 16 class, the shape
+                      tools/knn_ab.py quotes
 Rows per shape:
   a  exhaustive_lengths   mcp_knn_lengths (HipBackend.knn_bruteforce with the lengths): the baseline, code this search does not share
   b  pruned_with_builds   HipBackend.knn with the lengths outside a cloud_scope: both clouds sorted under their lengths + the search
@@ -45,6 +47,7 @@ SHAPES = [
     ("min_k32", 8, 1024, 2048, 32, 0, 513, 1000),
     ("mid_k1", 8, 2048, 4096, 1, 1, 1030, 2000),
     ("mid_k32", 8, 2048, 4096, 32, 0, 1030, 2000),
+    ("full_k16", 48, 2048, 2048, 16, 0, 2048, 2048),
 ]
 LENGTH_ENTRY_POINTS = ("mcp_build_cloud_lengths", "mcp_morton_codes_lengths", "mcp_tile_boxes_lengths", "mcp_knn_pruned_lengths")
 DEV = "cuda:0"
