@@ -479,6 +479,41 @@ int mcp_fp_mlp_grad(int b, int n, int m, int c2, int c1, int rule, int layers, c
                     const float *grad_out, const int *order, const int *seg, float *grad_known_feats, float *grad_skip,
                     float *const *grad_w, float *const *grad_b, float *out, void *workspace, size_t workspace_bytes, mcp_stream_t stream);
 
+/* Backward of mcp_group_mlp (csrc/group_mlp_grad.hip).  Inputs, use_xyz, pool, row_bias and qlen as mcp_group_mlp; grad_out
+ * (B,M,widths[L-1]) = dL/dout.  For a live centre p, slots j < nsample, k_j = idx[p,j]:
+ *     max:  gy_j[ch] = grad_out[p,ch] for the lowest j with hL_j[ch] == out[p,ch], 0 for every other slot (F.max_pool2d's rule);
+ *     mean: gy_j = grad_out[p] / nsample;
+ *     gz_L = gy . [hL > 0],  gz_l = (W_(l+1)^T gz_(l+1)) . [h_l > 0],  dx_j = W_1^T gz_(1,j).
+ * It writes, each only when its pointer is not NULL,
+ *   grad_features (B,N,c) += dx_j[3:] and grad_xyz (B,N,3) += dx_j[:3] at row k_j, every destination row's addends in ascending
+ *       position p nsample + j -- (order (B, M nsample), seg (B, N+1)) = mcp_scatter_segments of idx viewed as (B, M nsample) with
+ *       n = N; rows that no slot gathers get exact zeros; order / seg are read only when one of the two is wanted;
+ *   grad_new_xyz (B,M,3) = -sum_j dx_j[:3];   grad_row_bias (B,M,widths[0]) = sum_j gz_(1,j) (needs row_bias);
+ *   grad_w[l] (widths[l], cin_l) and grad_b[l] (widths[l]): host arrays of `layers` device pointers (required), of the FOLDED
+ *       weights' shapes; grad_w[0] covers the three position columns when use_xyz;
+ *   out (B,M,widths[L-1]): the forward's result again, bit for bit.
+ * idx gets no gradient.  The columns of a group beyond nsample take part in no sum.  A padded centre has none of its float inputs
+ * read, grad_out included; it writes zeros to its rows of grad_new_xyz and grad_row_bias and adds nothing anywhere else; its row of
+ * idx must be readable (mcp_scatter_segments and the scatter walk every position; out-of-range values are left out).  With
+ * nsample > 32 the two column tiles of a centre agree on the winner through a first pooling pass over the recomputed values: the
+ * forward's out is not an input.  No atomics: every sum runs in a fixed order (mcp_group_rows_grad_sorted, mcp_linear_wgrad, the
+ * forward's butterfly inside a group), two calls give identical bits.  packed: the image of mcp_group_mlp_grad_pack
+ * (mcp_group_mlp_grad_packed_floats floats: mcp_group_mlp_pack's image followed by the pieces of the transposed weights), rebuilt
+ * whenever a weight changes.  workspace: mcp_group_mlp_grad_workspace_bytes(b, m, ...) caller-owned bytes; it receives, per
+ * (centre, slot) pair, x, h_l for l < L, gz_l for every l and dx -- the dense intermediate the forward avoids -- and the partial
+ * sums of mcp_linear_wgrad.  Supported shapes: those of mcp_group_mlp; anything else MCP_ERR_UNSUPPORTED (sizes: 0), nothing
+ * launched.  features, row_bias, packed, grad_out, out, grad_features, grad_row_bias, workspace 16-byte aligned.  No allocation, no
+ * environment variable, no host read of a length. */
+int mcp_group_mlp_grad_packed_floats(int c, int use_xyz, int layers, const int *widths);
+int mcp_group_mlp_grad_pack(int c, int use_xyz, int layers, const int *widths, const float *const *w, const float *const *b, float *packed,
+                            mcp_stream_t stream);
+size_t mcp_group_mlp_grad_workspace_bytes(int b, int m, int c, int nsample, int use_xyz, int layers, const int *widths);
+int mcp_group_mlp_grad(int b, int n, int m, int c, int nsample, int use_xyz, int pool, int layers, const int *widths, const float *xyz,
+                       const float *new_xyz, const float *features, const int *idx, const int *qlen, const float *row_bias,
+                       const float *packed, const float *grad_out, const int *order, const int *seg, float *grad_features, float *grad_xyz,
+                       float *grad_new_xyz, float *grad_row_bias, float *const *grad_w, float *const *grad_b, float *out, void *workspace,
+                       size_t workspace_bytes, mcp_stream_t stream);
+
 /* Backward of mcp_cross_volume for one cross layer given by its own weights (the reference differentiates pointconv_util.py:765-781
  * with autograd over three materialised (B,D,32,N1) tensors; its hand-written backward pieces are the atomicAdd scatters of
  * group_points_gpu.cu:8-44).  xyz1, xyz2, points1, points2, idx / idx2 as mcp_cross_volume (no batch map); wpos (D,3), bpos (D),

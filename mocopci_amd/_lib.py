@@ -77,6 +77,10 @@ SIGNATURES = {
     "mcp_group_mlp_packed_floats": [_i, _i, _p],
     "mcp_group_mlp_pack": [_i, _i, _i, _p, _p, _p, _p, _p],
     "mcp_group_mlp": [_i] * 8 + [_p] * 10,
+    "mcp_group_mlp_grad_packed_floats": [_i, _i, _i, _p],
+    "mcp_group_mlp_grad_pack": [_i, _i, _i, _p, _p, _p, _p, _p],
+    "mcp_group_mlp_grad_workspace_bytes": [_i, _i, _i, _i, _i, _i, _p],
+    "mcp_group_mlp_grad": [_i] * 8 + [_p] * 19 + [ctypes.c_size_t, _p],
     "mcp_fp_mlp_packed_floats": [_i, _i, _i, _p],
     "mcp_fp_mlp_pack": [_i, _i, _i, _p, _p, _p, _p, _p],
     "mcp_fp_mlp": [_i] * 7 + [_p] * 10,
@@ -152,7 +156,7 @@ _RESTYPES = {"mcp_error_string": ctypes.c_char_p, "mcp_fps_workspace_bytes": cty
              "mcp_attention_wide_grad_workspace_bytes": ctypes.c_size_t,
              "mcp_linear_wgrad_workspace_bytes": ctypes.c_size_t, "mcp_scatter_segments_workspace_bytes": ctypes.c_size_t,
              "mcp_prelu_dropout_grad_workspace_bytes": ctypes.c_size_t, "mcp_emd_levels_floats": ctypes.c_size_t,
-             "mcp_fp_mlp_grad_workspace_bytes": ctypes.c_size_t}
+             "mcp_fp_mlp_grad_workspace_bytes": ctypes.c_size_t, "mcp_group_mlp_grad_workspace_bytes": ctypes.c_size_t}
 
 _lib = None
 

@@ -624,6 +624,9 @@ def group_mlp_weights_in_lds(c, widths):
 # Shape classes (column group 8 | 16 | 32 | 64, feature channels, widths) -> fewest centres B * M at which sampling-free
 # "ball query + mcp_group_mlp" measured faster than the composition "mcp_query_and_group + folded convs + max" by more than the
 # composition's own spread (tools/group_mlp_times.py -> profiles/group_mlp_times.json).  A class without a row keeps the composition.
+# Measured at B = 8 (ms): 16384 -> 1024 / ns 16 / 4 -> 32/32/64 0.154 against 0.292 (spread 0.022) and 1024 -> 256 / ns 16 / 64 ->
+# 64/64/128 0.060 against 0.134 (spread 0.018) qualify, 256 -> 64 / ns 8 / 128 -> 128/128/256 (0.103 against 0.113, spread 0.057) does
+# not.  The table is still empty: filling it changes what existing callers run and is a change of its own.
 GROUP_MLP_FUSED_CLASSES = {}
 
 
@@ -687,6 +690,108 @@ def group_mlp_pack(convs, bns=None, use_xyz=True):
     BatchNorm that follows each (None, or None entries, where there is none).  -> (packed, widths) for HipBackend.group_mlp."""
     bns = [None] * len(convs) if bns is None else list(bns)
     return group_mlp_pack_weights([fold_conv_bn(c, b) for c, b in zip(convs, bns)], use_xyz)
+
+
+# ---- backward of the set-abstraction layer (csrc/group_mlp_grad.hip) ----
+GROUP_MLP_GRAD_LDS_IMAGE_BYTES = 128 * 1024
+
+
+def group_mlp_grad_supported(c, widths, nsample=1, use_xyz=True):
+    """The shapes mcp_group_mlp_grad is built for: every shape of mcp_group_mlp (the kernel has one register class; nothing was
+    narrowed)."""
+    return group_mlp_supported(c, widths, nsample, use_xyz)
+
+
+def group_mlp_grad_image_bytes(c, widths, use_xyz=True):
+    """Bytes of the transposed-weight pieces of a supported shape: for l = L .. 2 the two k-steps per tile of gz_l into the tiles of
+    layer l - 1, then the k-steps of gz_1 into the ceil((c + 3) / 32) tiles of dx (c without use_xyz)."""
+    tiles = [w // 32 for w in widths]
+    cin = c + (3 if use_xyz else 0)
+    pieces = sum(2 * tiles[l] * tiles[l - 1] for l in range(1, len(tiles))) + 2 * tiles[0] * ((cin + 31) // 32)
+    return pieces * 3 * 64 * 16
+
+
+def group_mlp_grad_packed_floats(c, widths, use_xyz=True):
+    """Floats of mcp_group_mlp_grad_pack's image: the forward image (pieces, position columns, biases), then the transposed pieces."""
+    return (group_mlp_image_bytes(c, widths) + group_mlp_grad_image_bytes(c, widths, use_xyz)) // 4 + widths[0] // 32 * 128 + sum(widths)
+
+
+def group_mlp_grad_weights_in_lds(c, widths, use_xyz=True):
+    """Python mirror of the backward kernel's one staging predicate (gg_weights_in_lds): both parts of the image are staged in LDS
+    once per workgroup when together they are at most 128 KB, and read through L2 otherwise."""
+    widths = list(widths)
+    return group_mlp_image_bytes(c, widths) + group_mlp_grad_image_bytes(c, widths, use_xyz) <= GROUP_MLP_GRAD_LDS_IMAGE_BYTES
+
+
+# Shape classes (column group 8 | 16 | 32 | 64, feature channels, widths) -> fewest centres B * M at which the module's fused
+# differentiable route (ball query, transposition, mcp_group_mlp forward, mcp_group_mlp_grad backward) measured faster, forward +
+# backward, than the composition's forward + backward by more than the composition's own spread (tools/group_mlp_grad_times.py ->
+# profiles/group_mlp_grad_times.json).  A class without a row keeps the composition.  Measured at B = 8 (ms, forward + backward):
+# 16384 -> 1024 / ns 16 / 4 -> 32/32/64 1.533 against 1.329, 1024 -> 256 / ns 16 / 64 -> 64/64/128 1.119 against 0.930, 256 -> 64 / ns 8 /
+# 128 -> 128/128/256 1.217 against 0.918: slower fused at all three, no class enters; grad_route = "always" takes the kernel.
+GROUP_MLP_GRAD_FUSED_CLASSES = {}
+
+
+def group_mlp_grad_routes_fused(c, widths, nsample, centres):
+    """PointnetSAModuleMSG's route predicate when a gradient is wanted: a pure function of the padded shapes."""
+    least = GROUP_MLP_GRAD_FUSED_CLASSES.get(group_mlp_class(c, widths, nsample))
+    return least is not None and centres >= least
+
+
+def group_mlp_grad_pack_weights(weights, use_xyz=True):
+    """mcp_group_mlp_grad_pack's image from [(W (out, in), b (out,)), ...] fp32 device tensors -> (packed, widths)."""
+    widths = [int(w.shape[0]) for w, _ in weights]
+    c = int(weights[0][0].shape[1]) - (3 if use_xyz else 0)
+    lib = _lib.load()
+    wid = (ctypes.c_int * len(widths))(*widths)
+    n = lib.mcp_group_mlp_grad_packed_floats(c, int(bool(use_xyz)), len(widths), wid) if len(widths) <= 3 and c >= 0 else 0
+    if n == 0:
+        raise _lib.Unsupported(f"group_mlp_grad: unsupported shape c={c} widths={widths}")
+    cin = [c + (3 if use_xyz else 0), *widths[:-1]]
+    for (w, b), k, o in zip(weights, cin, widths):
+        if tuple(w.shape) != (o, k) or tuple(b.shape) != (o,):
+            raise RuntimeError(f"group_mlp_grad: expected W {(o, k)} and b {(o,)}, got {tuple(w.shape)} and {tuple(b.shape)}")
+    ws = [w.contiguous() for w, _ in weights]
+    bs = [b.contiguous() for _, b in weights]
+    packed = _grad_empty((n,), torch.float32, ws[0].device)
+    wp = (ctypes.c_void_p * len(ws))(*[_lib.fptr(w) for w in ws])
+    bp = (ctypes.c_void_p * len(bs))(*[_lib.fptr(b) for b in bs])
+    _call("mcp_group_mlp_grad_pack", packed, c, int(bool(use_xyz)), len(widths), wid, wp, bp, _lib.fptr(packed))
+    return packed, widths
+
+
+class _GroupMlpLayerFn(torch.autograd.Function):
+    """mcp_group_mlp with its hand-written backward (mcp_group_mlp_grad): the layer is re-evaluated inside the backward kernel, so
+    only the inputs are kept (not the output: the kernel takes the winner slots and the last ReLU mask from its own recompute) --
+    autograd over the composition keeps the (B, 3 + C, M, nsample) grouped tensor and one (B, C_l, M, nsample) per layer.
+    Gradients: xyz, new_xyz, features, row_bias, every W and b; idx and the lengths get none."""
+
+    @staticmethod
+    def forward(ctx, be, pool, use_xyz, idx, ql, xyz, new_xyz, features, row_bias, *wb):
+        xyz, new_xyz = xyz.detach().contiguous(), new_xyz.detach().contiguous()
+        features = None if features is None else features.detach().contiguous()
+        row_bias = None if row_bias is None else row_bias.detach().contiguous()
+        wb = [t.detach().contiguous() for t in wb]
+        packed, widths = group_mlp_pack_weights(list(zip(wb[0::2], wb[1::2])), use_xyz)
+        out = be._group_mlp(xyz, new_xyz, features, idx, packed, widths, pool, use_xyz, ql, row_bias)
+        ctx.be, ctx.pool, ctx.use_xyz = be, pool, use_xyz
+        ctx.save_for_backward(idx, ql, xyz, new_xyz, features, row_bias, *wb)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        idx, ql, xyz, new_xyz, features, row_bias, *wb = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        d_feat, d_xyz, d_new, d_rb, d_w, d_b, _ = ctx.be.group_mlp_grad(
+            xyz, new_xyz, features, idx, list(zip(wb[0::2], wb[1::2])), grad_out, pool=ctx.pool, use_xyz=ctx.use_xyz, new_xyz_lengths=ql,
+            row_bias=row_bias, want_features=need[7] and features is not None, want_xyz=need[5] and ctx.use_xyz,
+            want_new_xyz=need[6] and ctx.use_xyz, want_row_bias=need[8] and row_bias is not None)
+        zeros = lambda t, wanted: torch.zeros_like(t) if wanted and t is not None else None   # coordinates that never enter the layer
+        if not ctx.use_xyz:
+            d_xyz, d_new = zeros(xyz, need[5]), zeros(new_xyz, need[6])
+        pieces = [t for pair in zip(d_w, d_b) for t in pair]
+        return (None, None, None, None, None, d_xyz, d_new, d_feat, d_rb, *pieces)
 
 
 # ---- feature-propagation layer (csrc/fp_mlp.hip) ----
@@ -1468,7 +1573,11 @@ class HipBackend:
         MLP of [xyz[idx] - new_xyz (use_xyz) | features[idx]], every layer followed by ReLU.  row_bias (B,M,widths[0]) is added
         before the first ReLU (the centre's own features through the first layer's columns for them: FlowEmbedding's concatenation).
         new_xyz_lengths (forms: lengths_tensor): centres at or beyond the length give zeros and their rows are never read.
-        Inference only (no gradient); unsupported shapes raise _lib.Unsupported."""
+        No gradient here: group_mlp_layer is the differentiable form.  Unsupported shapes raise _lib.Unsupported."""
+        return self._group_mlp(xyz, new_xyz, features, idx, packed, widths, pool, use_xyz, new_xyz_lengths, row_bias)
+
+    def _group_mlp(self, xyz, new_xyz, features, idx, packed, widths, pool, use_xyz, new_xyz_lengths, row_bias):
+        """The launch of group_mlp, shared with the differentiable layer's forward."""
         B, N, _ = xyz.shape
         M, nsample = new_xyz.shape[1], idx.shape[2]
         C = 0 if features is None else features.shape[2]
@@ -1484,6 +1593,71 @@ class HipBackend:
               _lib.fptr(new_xyz), None if features is None else _lib.fptr(features), _lib.iptr(idx), None if ql is None else _lib.iptr(ql),
               None if row_bias is None else _lib.fptr(row_bias), _lib.fptr(packed), _lib.fptr(out))
         return out
+
+    def group_mlp_grad(self, xyz, new_xyz, features, idx, weights, grad_out, pool="max", use_xyz=True, new_xyz_lengths=None, row_bias=None,
+                       want_features=True, want_xyz=True, want_new_xyz=True, want_row_bias=True, recompute_out=False):
+        """Backward of group_mlp for weights = [(W, b), ...] (folded, fp32) and grad_out (B,M,widths[-1]): one per-pair kernel, the
+        deterministic scatters and one weight-gradient product per layer (mcp_group_mlp_grad) -> (grad_features (B,N,C), grad_xyz
+        (B,N,3), grad_new_xyz (B,M,3), grad_row_bias (B,M,widths[0]) -- each None when not wanted or not part of the layer --, [dW_l],
+        [db_l], the recomputed out or None).  Bit-reproducible; unsupported shapes raise _lib.Unsupported."""
+        B, N, _ = xyz.shape
+        M, nsample = new_xyz.shape[1], idx.shape[2]
+        C = 0 if features is None else features.shape[2]
+        dev = xyz.device
+        widths = [int(w.shape[0]) for w, _ in weights]
+        if tuple(idx.shape[:2]) != (B, M):
+            raise RuntimeError(f"group_mlp_grad: idx {tuple(idx.shape)} does not match B={B}, M={M}")
+        if not group_mlp_grad_supported(C, widths, nsample, use_xyz) or int(weights[0][0].shape[1]) != C + (3 if use_xyz else 0):
+            raise _lib.Unsupported(f"group_mlp_grad: unsupported shape c={C} widths={widths} nsample={nsample}")
+        if tuple(grad_out.shape) != (B, M, widths[-1]):
+            raise RuntimeError(f"group_mlp_grad: grad_out {tuple(grad_out.shape)}, expected {(B, M, widths[-1])}")
+        if row_bias is not None and tuple(row_bias.shape) != (B, M, widths[0]):
+            raise RuntimeError(f"row_bias: expected {(B, M, widths[0])}, got {tuple(row_bias.shape)}")
+        if B == 0 or M == 0 or N == 0:
+            raise RuntimeError("group_mlp_grad: empty batch, cloud or centre list")
+        lib = _lib.load()
+        ql = lengths_tensor(new_xyz_lengths, B, M, dev)
+        grad_out = grad_out.contiguous()
+        packed, _ = group_mlp_grad_pack_weights(weights, use_xyz)
+        wid = (ctypes.c_int * len(widths))(*widths)
+        need = lib.mcp_group_mlp_grad_workspace_bytes(B, M, C, nsample, int(bool(use_xyz)), len(widths), wid)
+        if need == 0:
+            raise _lib.Unsupported(f"group_mlp_grad: unsupported shape c={C} widths={widths} pairs={B * M * nsample}")
+        want_features, want_xyz, want_new_xyz = bool(want_features) and C > 0, bool(want_xyz) and use_xyz, bool(want_new_xyz) and use_xyz
+        want_row_bias = bool(want_row_bias) and row_bias is not None
+        ws = _grad_empty((need,), torch.uint8, dev)
+        d_feat = _grad_empty((B, N, C), torch.float32, dev) if want_features else None
+        d_xyz = _grad_empty((B, N, 3), torch.float32, dev) if want_xyz else None
+        d_new = _grad_empty((B, M, 3), torch.float32, dev) if want_new_xyz else None
+        d_rb = _grad_empty((B, M, widths[0]), torch.float32, dev) if want_row_bias else None
+        d_w = [_grad_empty(tuple(w.shape), torch.float32, dev) for w, _ in weights]
+        d_b = [_grad_empty(tuple(b.shape), torch.float32, dev) for _, b in weights]
+        out = _grad_empty((B, M, widths[-1]), torch.float32, dev) if recompute_out else None
+        order, seg = _scatter_segments(idx.reshape(B, M * nsample), N) if (want_features or want_xyz) else (None, None)
+        gw = (ctypes.c_void_p * len(d_w))(*[_lib.fptr(t) for t in d_w])
+        gb = (ctypes.c_void_p * len(d_b))(*[_lib.fptr(t) for t in d_b])
+        opt = lambda t, ptr=_lib.fptr: None if t is None else ptr(t)
+        _call("mcp_group_mlp_grad", xyz, B, N, M, C, nsample, int(bool(use_xyz)), GROUP_MLP_POOLS[pool], len(widths), wid, _lib.fptr(xyz),
+              _lib.fptr(new_xyz), opt(features), _lib.iptr(idx), opt(ql, _lib.iptr), opt(row_bias), _lib.fptr(packed), _lib.fptr(grad_out),
+              opt(order, _lib.iptr), opt(seg, _lib.iptr), opt(d_feat), opt(d_xyz), opt(d_new), opt(d_rb), gw, gb, opt(out), ws.data_ptr(), need)
+        return d_feat, d_xyz, d_new, d_rb, d_w, d_b, out
+
+    def group_mlp_layer(self, xyz, new_xyz, features, idx, weights, pool="max", use_xyz=True, new_xyz_lengths=None, row_bias=None):
+        """The set-abstraction layer from its own weights [(W (out, in), b (out,)), ...] (BatchNorm folded in: fold_conv_bn_grad keeps
+        the parameters in the graph); arguments as group_mlp.  Without a wanted gradient it is group_mlp on a pack of `weights`; with
+        one it is an autograd function -- mcp_group_mlp forward, mcp_group_mlp_grad backward -- that returns gradients for xyz,
+        new_xyz, features, row_bias and every W and b, each only when needed, and keeps only its inputs."""
+        flat = [t for pair in weights for t in pair]
+        if not grad.wants_grad(xyz, new_xyz, features, row_bias, *flat):
+            packed, widths = group_mlp_pack_weights([(w.detach(), b.detach()) for w, b in weights], use_xyz)
+            det = lambda t: None if t is None else t.detach()
+            return self._group_mlp(xyz.detach(), new_xyz.detach(), det(features), idx, packed, widths, pool, use_xyz, new_xyz_lengths, det(row_bias))
+        B, M = new_xyz.shape[0], new_xyz.shape[1]
+        C = 0 if features is None else features.shape[2]
+        if not group_mlp_grad_supported(C, [int(w.shape[0]) for w, _ in weights], idx.shape[2], use_xyz):
+            raise _lib.Unsupported(f"group_mlp_layer: unsupported shape c={C} widths={[int(w.shape[0]) for w, _ in weights]} nsample={idx.shape[2]}")
+        ql = lengths_tensor(new_xyz_lengths, B, M, xyz.device)
+        return _GroupMlpLayerFn.apply(self, pool, bool(use_xyz), idx.contiguous(), ql, xyz, new_xyz, features, row_bias, *flat)
 
     def fp_mlp(self, known_feats, skip, idx, dist, packed, widths, rule="pointnet2", w3=None, unknown_lengths=None):
         """Feature-propagation layer after its three-neighbour search (PointnetFPModule; FeaturePropagation, models/layers.py:150-178)

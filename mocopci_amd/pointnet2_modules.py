@@ -10,6 +10,10 @@ Two routes give the same layer:
   * the fused route -- sampling, one ball query per scale, one mcp_group_mlp launch per scale (ops.HipBackend.group_mlp) -- writes
     nothing but the pooled features.  It is taken only under no-grad, in eval(), for a shape the kernel supports, and for a shape
     class that the measurement of tools/group_mlp_times.py found faster (ops.GROUP_MLP_FUSED_CLASSES; `route` overrides it).
+    When a gradient is wanted a scale's fused route is the differentiable layer ops.HipBackend.group_mlp_layer (mcp_group_mlp
+    forward, mcp_group_mlp_grad backward: the ball query on detached coordinates, gradients for xyz, new_xyz, the features and the
+    stack's parameters through ops.fold_conv_bn_grad), taken in eval() or without BatchNorm for a class of
+    ops.GROUP_MLP_GRAD_FUSED_CLASSES (tools/group_mlp_grad_times.py; `grad_route` overrides it).
 PointnetFPModule has the same two routes: the composition -- three_nn, the weights in torch, three_interpolate, cat, the shared
 stack -- and one mcp_fp_mlp launch after the three-neighbour search (ops.HipBackend.fp_mlp; ops.FP_MLP_FUSED_CLASSES from
 tools/fp_mlp_times.py).  When a gradient is wanted its fused route is the differentiable layer ops.HipBackend.fp_mlp_layer
@@ -52,7 +56,10 @@ def _shared_mlp(spec, bn, instance_norm):
 class PointnetSAModuleMSG(nn.Module):
     """Set abstraction with multi-scale grouping: npoint centres by furthest point sampling, per scale a ball of radii[i] with
     nsamples[i] slots, the shared MLP mlps[i] (its first entry counts the feature channels; 3 is added with use_xyz) and the pool.
-    npoint=None groups the whole cloud (GroupAll).  route: "measured" (default), "always" or "never" for the fused route."""
+    npoint=None groups the whole cloud (GroupAll).  route: "measured" (default), "always" or "never" for the fused route when no
+    gradient is wanted; grad_route: the same three values, independently, for the fused differentiable route (mcp_group_mlp forward,
+    mcp_group_mlp_grad backward) when one is -- eligible in eval() or with bn=False; a training-mode BatchNorm keeps the
+    composition."""
 
     def __init__(self, *, npoint: int, radii: List[float], nsamples: List[int], mlps: List[List[int]], bn: bool = True, use_xyz: bool = True,
                  pool_method="max_pool", instance_norm=False):
@@ -63,6 +70,7 @@ class PointnetSAModuleMSG(nn.Module):
             raise NotImplementedError(pool_method)
         self.npoint, self.use_xyz, self.pool_method, self.bn, self.instance_norm = npoint, use_xyz, pool_method, bn, instance_norm
         self.route = "measured"
+        self.grad_route = "measured"
         self.groupers, self.mlps = nn.ModuleList(), nn.ModuleList()
         for radius, nsample, spec in zip(radii, nsamples, mlps):
             self.groupers.append(pu.QueryAndGroup(radius, nsample, use_xyz=use_xyz) if npoint is not None else pu.GroupAll(use_xyz))
@@ -94,6 +102,17 @@ class PointnetSAModuleMSG(nn.Module):
             return False
         return self.route == "always" or ops.group_mlp_routes_fused(channels, widths, g.nsample, centres)
 
+    def fused_scale_grad(self, i, channels, centres):
+        """Whether scale i of a call that wants a gradient takes the fused differentiable route: BatchNorm folded (eval mode) or
+        absent."""
+        if (self.training and self.bn) or self.npoint is None or self.grad_route == "never" or (self.instance_norm and not self.bn):
+            return False
+        g = self.groupers[i]
+        widths = [u.conv.out_channels for u in self.mlps[i].children()]
+        if not ops.group_mlp_grad_supported(channels, widths, g.nsample, self.use_xyz):
+            return False
+        return self.grad_route == "always" or ops.group_mlp_grad_routes_fused(channels, widths, g.nsample, centres)
+
     def forward(self, xyz: torch.Tensor, features: torch.Tensor = None, new_xyz=None, xyz_lengths=None, new_xyz_lengths=None):
         """xyz (B,N,3), features (B,C,N) or None, new_xyz (B,npoint,3) or None (sampled here) -> new_xyz, (B, sum C_out, npoint).
         xyz_lengths / new_xyz_lengths (forms: ops.lengths_tensor): element b is its first xyz_lengths[b] points with the centres
@@ -115,6 +134,7 @@ class PointnetSAModuleMSG(nn.Module):
                 count = torch.where(rl > 0, count, torch.zeros_like(count))
             live = torch.arange(M, device=xyz.device).view(1, M) < count.view(B, 1)
         rows = None  # features channel-last, made once for the fused scales
+        rows_grad = None  # the same, attached to the graph, for the differentiable fused scales
         outs = []
         for i, grouper in enumerate(self.groupers):
             if not wants_grad and self.fused_scale(i, C, B * M):
@@ -125,6 +145,17 @@ class PointnetSAModuleMSG(nn.Module):
                 idx = be.ball_query(x, c, grouper.radius, grouper.nsample, xyz_lengths=rl, new_xyz_lengths=ql)
                 pooled = be.group_mlp(x, c, rows, idx, packed, widths, pool=self.pool_method, use_xyz=self.use_xyz,
                                       new_xyz_lengths=count if with_lengths else None)
+                outs.append(pooled.transpose(1, 2))
+                continue
+            if wants_grad and self.fused_scale_grad(i, C, B * M):
+                if features is not None and rows_grad is None:
+                    rows_grad = features.transpose(1, 2).contiguous()
+                # the neighbour list is a constant of the layer: no gradient reaches the search
+                idx = be.ball_query(xyz.detach().contiguous(), new_xyz.detach().contiguous(), grouper.radius, grouper.nsample, xyz_lengths=rl,
+                                    new_xyz_lengths=ql)
+                folded = [ops.fold_conv_bn_grad(c, b) for c, b in zip(*self._layers(i))]
+                pooled = be.group_mlp_layer(xyz.contiguous(), new_xyz.contiguous(), rows_grad, idx, folded, pool=self.pool_method, use_xyz=self.use_xyz,
+                                            new_xyz_lengths=count if with_lengths else None)
                 outs.append(pooled.transpose(1, 2))
                 continue
             grouped = grouper(xyz, new_xyz, features, rl, ql) if with_lengths else grouper(xyz, new_xyz, features)
