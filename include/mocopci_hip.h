@@ -479,6 +479,41 @@ int mcp_fp_mlp_grad(int b, int n, int m, int c2, int c1, int rule, int layers, c
                     const float *grad_out, const int *order, const int *seg, float *grad_known_feats, float *grad_skip,
                     float *const *grad_w, float *const *grad_b, float *out, void *workspace, size_t workspace_bytes, mcp_stream_t stream);
 
+/* mcp_fp_mlp's layer with TRAINING-MODE BatchNorm behind every product (csrc/fp_mlp_bn.hip).  Inputs, rules, ulen and infinite slots
+ * as mcp_fp_mlp.  Over the live rows R (count m), for l = 1 .. L:  z_l = W_l h_(l-1) + b_l,  mu_l = mean_R z_l,  v_l = mean_R (z_l -
+ * mu_l)^2 (biased),  rstd_l = 1 / sqrt(v_l + eps_l),  y_l = gamma_l (z_l - mu_l) rstd_l + beta_l,  h_l = ReLU(y_l),  out = h_L.
+ * mcp_fp_mlp_bn_forward writes out (B,n,widths[L-1]; zeros in padded rows), mean[l], var[l], rstd[l] (widths[l] floats each: host
+ * arrays of `layers` device pointers) and the live count m as one device int32.  gamma / beta: host arrays of `layers` device
+ * pointers, a NULL entry is ones / zeros; eps: a host array of `layers` floats, each > 0.  packed: mcp_fp_mlp_pack's image of the
+ * UNFOLDED (W_l, b_l) (zeros for an absent bias), or mcp_fp_mlp_grad_pack's, which begins with it.
+ * mcp_fp_mlp_bn_backward takes the forward's inputs again, mean and rstd as the forward wrote them, grad_out = dL/dout and
+ * mcp_fp_mlp_grad_pack's image, and writes -- with gy_L = grad_out . [y_L > 0], dbeta_l = sum_R gy_l, dgamma_l = sum_R gy_l zhat_l,
+ * gz_l = gamma_l rstd_l (gy_l - dbeta_l / m - zhat_l dgamma_l / m), gy_(l-1) = (W_l^T gz_l) . [y_(l-1) > 0], dx = W_1^T gz_1 --
+ *   grad_skip (B,n,C1) = dx[C2:] (NULL with c1 = 0), zeros in padded rows;
+ *   grad_known_feats (B,m,C2) through (order, seg) as mcp_fp_mlp_grad (NULL: not computed);
+ *   grad_w[l] (widths[l], cin_l); grad_b[l], grad_gamma[l], grad_beta[l] (widths[l]): host arrays of `layers` device pointers, a NULL
+ *       entry of the last three is not written (grad_b is zero in exact arithmetic: the statistics absorb a bias).
+ * It keeps no activation: the forward passes run again with the statistics given, so every ReLU mask is the forward's.  dist, w3,
+ * the coordinates and the lengths get no gradient.  A padded row has none of its float inputs read (grad_out included), takes part
+ * in no statistic and adds nothing to any sum.  No atomics: every per-channel sum is a fixed butterfly over a wave's rows, waves in
+ * wave order, workgroups in workgroup order; two calls give identical bits.  The variance is merged from (count, mean, M2) triples,
+ * never formed as E[z^2] - E[z]^2.  With m < 2 every division is by max(m, 1): nothing is NaN or Inf, the statistics are meaningless.
+ * workspace: mcp_fp_mlp_bn_workspace_bytes(b, n, ..., backward) caller-owned bytes (backward = 0: z_l and the partials; 1: also x, h_l,
+ * gy_l, gz_l, dx[:C2], the blend's weights and mcp_linear_wgrad's sums).  Supported shapes: those of mcp_fp_mlp; anything else
+ * MCP_ERR_UNSUPPORTED (size: 0), nothing launched.  known_feats, packed, out, grad_out, workspace -- and skip, grad_skip when c1 is a
+ * multiple of 4 -- 16-byte aligned.  No allocation, no environment variable, no host read of a length. */
+size_t mcp_fp_mlp_bn_workspace_bytes(int b, int n, int c2, int c1, int layers, const int *widths, int backward);
+int mcp_fp_mlp_bn_forward(int b, int n, int m, int c2, int c1, int rule, int layers, const int *widths, const float *known_feats,
+                          const float *skip, const int *idx, const float *dist, const float *w3, const int *ulen, const float *packed,
+                          const float *const *gamma, const float *const *beta, const float *eps, float *out, float *const *mean,
+                          float *const *var, float *const *rstd, int *count, void *workspace, size_t workspace_bytes, mcp_stream_t stream);
+int mcp_fp_mlp_bn_backward(int b, int n, int m, int c2, int c1, int rule, int layers, const int *widths, const float *known_feats,
+                           const float *skip, const int *idx, const float *dist, const float *w3, const int *ulen, const float *packed,
+                           const float *const *gamma, const float *const *beta, const float *const *mean, const float *const *rstd,
+                           const float *grad_out, const int *order, const int *seg, float *grad_known_feats, float *grad_skip,
+                           float *const *grad_w, float *const *grad_b, float *const *grad_gamma, float *const *grad_beta, void *workspace,
+                           size_t workspace_bytes, mcp_stream_t stream);
+
 /* Backward of mcp_group_mlp (csrc/group_mlp_grad.hip).  Inputs, use_xyz, pool, row_bias and qlen as mcp_group_mlp; grad_out
  * (B,M,widths[L-1]) = dL/dout.  For a live centre p, slots j < nsample, k_j = idx[p,j]:
  *     max:  gy_j[ch] = grad_out[p,ch] for the lowest j with hL_j[ch] == out[p,ch], 0 for every other slot (F.max_pool2d's rule);

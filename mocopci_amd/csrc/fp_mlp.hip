@@ -46,8 +46,6 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-// the staging predicate, a function of (c2, c1, widths) alone (ops.fp_mlp_weights_in_lds mirrors it)
-inline bool fp_weights_in_lds(const FpShape &s) { return (size_t)s.w_u4 * 16 <= (size_t)LDS_IMAGE_BYTES; }
 
 // One layer of the image: slab s (k-step s of the layer's input) holds, for every output tile t, the three pieces of the 8 values
 // per lane W[32t + (lane&31)][column of (s, i, lane>>5)].  Input k-steps 0 .. ksa-1 cover columns 0 .. va-1 (zero beyond), the next

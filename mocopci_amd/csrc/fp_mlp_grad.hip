@@ -58,27 +58,6 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-struct FgShape {
-    FpShape f;
-    int cin, dxt;        // C2 + C1 and its 32-channel tiles
-    int bwd_u4;          // uint4 of the backward slabs
-};
-
-inline bool fg_shape(int c2, int c1, int layers, const int *widths, FgShape *s) {
-    if (!fp_shape(c2, c1, layers, widths, &s->f)) return false;
-    const FpShape &f = s->f;
-    s->cin = c2 + c1;
-    s->dxt = (s->cin + 31) / 32;
-    int u4 = 0;
-    for (int l = layers - 1; l >= 1; --l) u4 += 2 * f.tiles[l] * f.tiles[l - 1] * TILE_U4;   // gz_l (two k-steps per tile) into the tiles of layer l - 1
-    u4 += s->dxt * 2 * f.tiles[0] * TILE_U4;                                                 // gz_1 into the tiles of dx
-    s->bwd_u4 = u4;
-    return true;
-}
-// the staging predicate, a function of (c2, c1, widths) alone (ops.fp_mlp_grad_weights_in_lds mirrors it)
-inline bool fg_whole(const FgShape &s) {
-    return (size_t)s.f.w_u4 * 16 <= (size_t)LDS_IMAGE_BYTES && (size_t)s.bwd_u4 * 16 <= (size_t)LDS_IMAGE_BYTES;
-}
 inline size_t fg_image_floats(const FgShape &s) { return ((size_t)s.f.w_u4 + s.bwd_u4) * 4 + s.f.small_floats; }
 
 // Slabs of A = W^T for output tiles tile0 .. tile0 + tiles - 1 (32 rows m of A each) over the ks k-steps of W's rows: entry

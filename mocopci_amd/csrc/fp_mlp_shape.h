@@ -1,5 +1,5 @@
-// fp_mlp_shape.h -- the shape arithmetic of the fused feature-propagation layer, shared by its forward (fp_mlp.hip) and its backward
-// (fp_mlp_grad.hip): which shapes are built, the k-steps and output tiles of every layer, the size of the forward weight image and
+// fp_mlp_shape.h -- the shape arithmetic of the fused feature-propagation layer, shared by its forward (fp_mlp.hip), its backward
+// (fp_mlp_grad.hip) and its training-mode BatchNorm form (fp_mlp_bn.hip): which shapes are built, the k-steps and output tiles of every layer, the size of the forward weight image and
 // the register class.  Host code only.
 #pragma once
 
@@ -49,4 +49,29 @@ inline bool fp_shape(int c2, int c1, int layers, const int *widths, FpShape *s) 
     return true;
 }
 
+// the staging predicate, a function of (c2, c1, widths) alone (ops.fp_mlp_weights_in_lds mirrors it)
+inline bool fp_weights_in_lds(const FpShape &s) { return (size_t)s.w_u4 * 16 <= (size_t)LDS_IMAGE_BYTES; }
+
+// ---- the backward: the forward's shape with the slabs of the transposed weights ----
+struct FgShape {
+    FpShape f;
+    int cin, dxt;        // C2 + C1 and its 32-channel tiles
+    int bwd_u4;          // uint4 of the backward slabs
+};
+
+inline bool fg_shape(int c2, int c1, int layers, const int *widths, FgShape *s) {
+    if (!fp_shape(c2, c1, layers, widths, &s->f)) return false;
+    const FpShape &f = s->f;
+    s->cin = c2 + c1;
+    s->dxt = (s->cin + 31) / 32;
+    int u4 = 0;
+    for (int l = layers - 1; l >= 1; --l) u4 += 2 * f.tiles[l] * f.tiles[l - 1] * TILE_U4;   // gz_l (two k-steps per tile) into the tiles of layer l - 1
+    u4 += s->dxt * 2 * f.tiles[0] * TILE_U4;                                                 // gz_1 into the tiles of dx
+    s->bwd_u4 = u4;
+    return true;
+}
+// the staging predicate, a function of (c2, c1, widths) alone (ops.fp_mlp_grad_weights_in_lds mirrors it)
+inline bool fg_whole(const FgShape &s) {
+    return (size_t)s.f.w_u4 * 16 <= (size_t)LDS_IMAGE_BYTES && (size_t)s.bwd_u4 * 16 <= (size_t)LDS_IMAGE_BYTES;
+}
 }  // namespace

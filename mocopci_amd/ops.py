@@ -971,6 +971,65 @@ class _FpMlpLayerFn(torch.autograd.Function):
         return (None, None, None, None, None, None, d_known, d_skip if ctx.needs_input_grad[7] else None, *pieces)
 
 
+# ---- feature-propagation layer with training-mode BatchNorm (csrc/fp_mlp_bn.hip) ----
+def fp_mlp_bn_supported(c2, c1, widths):
+    """The shapes mcp_fp_mlp_bn_forward / _backward are built for: every shape of mcp_fp_mlp."""
+    return fp_mlp_supported(c2, c1, widths)
+
+
+# Shape classes (c2, c1, widths) -> fewest rows B * n at which the module's fused training-mode route (three_nn, transpositions,
+# mcp_fp_mlp_bn_forward, mcp_fp_mlp_bn_backward, the running-statistics update) measured faster, forward + backward, than the
+# composition's forward + backward by more than the composition's own spread (tools/fp_mlp_bn_times.py ->
+# profiles/fp_mlp_bn_times.json).  A class without a row keeps the composition.  Measured at B = 8 in train() (ms, forward +
+# backward): 256 + 3 -> 256/256 over n = 16384 (3.304 against 3.692, spread 0.076) enters; 256 + 128 -> 256/256 over n = 1024 (1.139
+# against 0.922) and 128 + 4 -> 128/128/128 over n = 4096 (1.483 against 1.334) are slower and stay out.
+FP_MLP_BN_FUSED_CLASSES = {(256, 3, (256, 256)): 8 * 16384}
+
+
+def fp_mlp_bn_routes_fused(c2, c1, widths, rows):
+    """PointnetFPModule's route predicate under a training-mode BatchNorm: a pure function of the padded shapes."""
+    least = FP_MLP_BN_FUSED_CLASSES.get(fp_mlp_class(c2, c1, widths))
+    return least is not None and rows >= least
+
+
+def _ptr_array(tensors, ptr=None):
+    """A host array of device pointers, NULL for None."""
+    ptr = _lib.fptr if ptr is None else ptr
+    return (ctypes.c_void_p * len(tensors))(*[None if t is None else ptr(t) for t in tensors])
+
+
+class _FpMlpBnLayerFn(torch.autograd.Function):
+    """mcp_fp_mlp_bn_forward with its hand-written backward (mcp_fp_mlp_bn_backward).  Kept between the two: the inputs and the
+    per-layer (mean, rstd) -- no activation; the backward runs the forward passes again with the statistics given.  Outputs: out, then
+    per layer (mean, biased variance), then the live count; all but out are marked non-differentiable.  Gradients: known_feats, skip,
+    every W, b, gamma and beta; dist, w3 and the lengths get none."""
+
+    @staticmethod
+    def forward(ctx, be, rule, idx, dist, w3, ulen, eps, known_feats, skip, *params):
+        known_feats = known_feats.detach().contiguous()
+        skip = None if skip is None else skip.detach().contiguous()
+        params = [None if t is None else t.detach().contiguous() for t in params]
+        layers = list(zip(params[0::4], params[1::4], params[2::4], params[3::4]))
+        out, mean, var, rstd, count = be.fp_mlp_bn_forward(known_feats, skip, idx, dist, layers, eps, rule=rule, w3=w3, unknown_lengths=ulen)
+        ctx.be, ctx.rule, ctx.layers = be, rule, len(layers)
+        ctx.save_for_backward(idx, dist, w3, ulen, known_feats, skip, *params, *mean, *rstd)
+        stats = [t for pair in zip(mean, var) for t in pair]
+        ctx.mark_non_differentiable(*stats, count)
+        return (out, *stats, count)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out, *_):
+        idx, dist, w3, ulen, known_feats, skip, *rest = ctx.saved_tensors
+        L = ctx.layers
+        params, mean, rstd = rest[:4 * L], rest[4 * L:5 * L], rest[5 * L:]
+        layers = list(zip(params[0::4], params[1::4], params[2::4], params[3::4]))
+        d_known, d_skip, d_layers = ctx.be.fp_mlp_bn_backward(known_feats, skip, idx, dist, layers, mean, rstd, grad_out, rule=ctx.rule, w3=w3,
+                                                              unknown_lengths=ulen, want_known=ctx.needs_input_grad[7])
+        pieces = [t for quad in d_layers for t in quad]
+        return (None, None, None, None, None, None, None, d_known, d_skip if ctx.needs_input_grad[8] else None, *pieces)
+
+
 class _ChamferLengthsFn(torch.autograd.Function):
     """_ChamferFn over the valid prefixes of a padded batch (pytorch3d's x_lengths / y_lengths with its default reductions):
     value_b = sum_{i<xl} dxy_i / max(xl,1) + sum_{j<yl} dyx_j / max(yl,1).  Forward: the length-aware search returns 0 for every
@@ -1752,6 +1811,95 @@ class HipBackend:
         B, n = idx.shape[0], idx.shape[1]
         ul = lengths_tensor(unknown_lengths, B, n, known_feats.device)
         return _FpMlpLayerFn.apply(self, rule, idx.contiguous(), dist, w3, ul, known_feats, skip, *flat)
+
+    def _fp_mlp_bn_check(self, name, known_feats, skip, idx, dist, layers, rule, w3):
+        B, m, C2 = known_feats.shape
+        n = idx.shape[1]
+        C1 = 0 if skip is None else skip.shape[2]
+        code = FP_MLP_RULES[rule]
+        if tuple(idx.shape) != (B, n, 3) or (skip is not None and tuple(skip.shape[:2]) != (B, n)):
+            raise RuntimeError(f"{name}: idx {tuple(idx.shape)} / skip do not match B={B}, n={n}")
+        for what, t in (("w3", w3),) if code == 0 else (("dist", dist),):
+            if t is None or tuple(t.shape) != (B, n, 3):
+                raise RuntimeError(f"{name}: rule {rule!r} needs {what} of shape {(B, n, 3)}")
+        widths = [int(l[0].shape[0]) for l in layers]
+        if not fp_mlp_bn_supported(C2, C1, widths) or int(layers[0][0].shape[1]) != C2 + C1:
+            raise _lib.Unsupported(f"{name}: unsupported shape c2={C2} c1={C1} widths={widths}")
+        for (w, b, gamma, beta), k, o in zip(layers, [C2 + C1, *widths[:-1]], widths):
+            if tuple(w.shape) != (o, k) or any(t is not None and tuple(t.shape) != (o,) for t in (b, gamma, beta)):
+                raise RuntimeError(f"{name}: expected W {(o, k)} and b, gamma, beta {(o,)}")
+        if B == 0 or n == 0 or m == 0:
+            raise RuntimeError(f"{name}: empty batch, unknown or known cloud")
+        return B, n, m, C2, C1, code, widths
+
+    def fp_mlp_bn_forward(self, known_feats, skip, idx, dist, layers, eps, rule="pointnet2", w3=None, unknown_lengths=None):
+        """The feature-propagation layer with batch statistics (mcp_fp_mlp_bn_forward): arguments as fp_mlp, layers = [(W (out, in),
+        b or None, gamma or None, beta or None), ...] fp32, eps one float per layer -> (out (B,n,widths[-1]), [mean_l], [biased
+        var_l], [rstd_l], count (1,) int32: the live rows, on the device).  Padded rows give zeros and enter no statistic."""
+        B, n, m, C2, C1, code, widths = self._fp_mlp_bn_check("fp_mlp_bn_forward", known_feats, skip, idx, dist, layers, rule, w3)
+        if len(eps) != len(layers) or not all(float(e) > 0 for e in eps):
+            raise RuntimeError("fp_mlp_bn_forward: one eps > 0 per layer")
+        dev = known_feats.device
+        lib = _lib.load()
+        ul = lengths_tensor(unknown_lengths, B, n, dev)
+        packed, _ = fp_mlp_pack_weights([(w, torch.zeros_like(w[:, 0]) if b is None else b) for w, b, _, _ in layers], C2)
+        wid = (ctypes.c_int * len(widths))(*widths)
+        need = lib.mcp_fp_mlp_bn_workspace_bytes(B, n, C2, C1, len(widths), wid, 0)
+        if need == 0:
+            raise _lib.Unsupported(f"fp_mlp_bn_forward: unsupported shape c2={C2} c1={C1} widths={widths} rows={B * n}")
+        ws = _grad_empty((need,), torch.uint8, dev)
+        out = _grad_empty((B, n, widths[-1]), torch.float32, dev)
+        mean, var, rstd = ([_grad_empty((o,), torch.float32, dev) for o in widths] for _ in range(3))
+        count = _grad_empty((1,), torch.int32, dev)
+        _call("mcp_fp_mlp_bn_forward", known_feats, B, n, m, C2, C1, code, len(widths), wid, _lib.fptr(known_feats),
+              None if C1 == 0 else _lib.fptr(skip), _lib.iptr(idx), None if code == 0 else _lib.fptr(dist), _lib.fptr(w3) if code == 0 else None,
+              None if ul is None else _lib.iptr(ul), _lib.fptr(packed), _ptr_array([g for _, _, g, _ in layers]), _ptr_array([bt for _, _, _, bt in layers]),
+              (ctypes.c_float * len(eps))(*[float(e) for e in eps]), _lib.fptr(out), _ptr_array(mean), _ptr_array(var), _ptr_array(rstd),
+              _lib.iptr(count), ws.data_ptr(), need)
+        return out, mean, var, rstd, count
+
+    def fp_mlp_bn_backward(self, known_feats, skip, idx, dist, layers, mean, rstd, grad_out, rule="pointnet2", w3=None, unknown_lengths=None,
+                           want_known=True):
+        """Backward of fp_mlp_bn_forward (mcp_fp_mlp_bn_backward) from the forward's inputs, its per-layer (mean, rstd) and grad_out
+        (B,n,widths[-1]) -> (grad_known_feats (B,m,C2) or None, grad_skip (B,n,C1) or None, [(dW, db or None, dgamma or None, dbeta
+        or None), ...]; a parameter that is None gets None).  Bit-reproducible; unsupported shapes raise."""
+        B, n, m, C2, C1, code, widths = self._fp_mlp_bn_check("fp_mlp_bn_backward", known_feats, skip, idx, dist, layers, rule, w3)
+        if tuple(grad_out.shape) != (B, n, widths[-1]):
+            raise RuntimeError(f"fp_mlp_bn_backward: grad_out {tuple(grad_out.shape)}, expected {(B, n, widths[-1])}")
+        dev = known_feats.device
+        lib = _lib.load()
+        ul = lengths_tensor(unknown_lengths, B, n, dev)
+        grad_out = grad_out.contiguous()
+        packed, _ = fp_mlp_grad_pack_weights([(w, torch.zeros_like(w[:, 0]) if b is None else b) for w, b, _, _ in layers], C2)
+        wid = (ctypes.c_int * len(widths))(*widths)
+        need = lib.mcp_fp_mlp_bn_workspace_bytes(B, n, C2, C1, len(widths), wid, 1)
+        if need == 0:
+            raise _lib.Unsupported(f"fp_mlp_bn_backward: unsupported shape c2={C2} c1={C1} widths={widths} rows={B * n}")
+        ws = _grad_empty((need,), torch.uint8, dev)
+        d_known = _grad_empty((B, m, C2), torch.float32, dev) if want_known else None
+        d_skip = _grad_empty((B, n, C1), torch.float32, dev) if C1 else None
+        like = lambda t: None if t is None else _grad_empty(tuple(t.shape), torch.float32, dev)
+        d_layers = [tuple(like(t) for t in layer) for layer in layers]
+        order, seg = _scatter_segments(idx, m) if want_known else (None, None)
+        _call("mcp_fp_mlp_bn_backward", known_feats, B, n, m, C2, C1, code, len(widths), wid, _lib.fptr(known_feats),
+              None if C1 == 0 else _lib.fptr(skip), _lib.iptr(idx), None if code == 0 else _lib.fptr(dist), _lib.fptr(w3) if code == 0 else None,
+              None if ul is None else _lib.iptr(ul), _lib.fptr(packed), _ptr_array([g for _, _, g, _ in layers]), _ptr_array([bt for _, _, _, bt in layers]),
+              _ptr_array(list(mean)), _ptr_array(list(rstd)), _lib.fptr(grad_out), None if order is None else _lib.iptr(order),
+              None if seg is None else _lib.iptr(seg), None if d_known is None else _lib.fptr(d_known), None if d_skip is None else _lib.fptr(d_skip),
+              *[_ptr_array([d[i] for d in d_layers]) for i in range(4)], ws.data_ptr(), need)
+        return d_known, d_skip, d_layers
+
+    def fp_mlp_bn_layer(self, known_feats, skip, idx, dist, layers, rule="pointnet2", w3=None, unknown_lengths=None):
+        """The feature-propagation layer under a training-mode BatchNorm from its own parameters: layers = [(W (out, in), b or None,
+        gamma or None, beta or None, eps), ...]; other arguments as fp_mlp -> (out (B,n,widths[-1]), [(mean_l, biased var_l), ...],
+        count (1,) int32 on the device).  An autograd function -- mcp_fp_mlp_bn_forward, mcp_fp_mlp_bn_backward -- with gradients for
+        known_feats, skip and every W, b, gamma, beta; the statistics and the count are not differentiable.  It runs with or without
+        a wanted gradient (the caller's running statistics need the batch statistics either way)."""
+        B, n = idx.shape[0], idx.shape[1]
+        ul = lengths_tensor(unknown_lengths, B, n, known_feats.device)
+        flat = [t for layer in layers for t in layer[:4]]
+        out, *rest = _FpMlpBnLayerFn.apply(self, rule, idx.contiguous(), dist, w3, ul, tuple(float(layer[4]) for layer in layers), known_feats, skip, *flat)
+        return out, list(zip(rest[0:-1:2], rest[1:-1:2])), rest[-1]
 
     def ptblock_layer(self, xyz, q, k, v, idx, weights, packed=None):
         """TransformerBlock vector attention from the block's own weights (wd1,bd1,wd2,bd2,wg1,bg1,wg2,bg2); differentiable."""

@@ -18,7 +18,10 @@ PointnetFPModule has the same two routes: the composition -- three_nn, the weigh
 stack -- and one mcp_fp_mlp launch after the three-neighbour search (ops.HipBackend.fp_mlp; ops.FP_MLP_FUSED_CLASSES from
 tools/fp_mlp_times.py).  When a gradient is wanted its fused route is the differentiable layer ops.HipBackend.fp_mlp_layer
 (mcp_fp_mlp_grad backward), taken in eval() or without BatchNorm for a class of ops.FP_MLP_GRAD_FUSED_CLASSES
-(tools/fp_mlp_grad_times.py; `grad_route` overrides it)."""
+(tools/fp_mlp_grad_times.py; `grad_route` overrides it).  Under train() with BatchNorm it has a third route of its own: the layer
+with batch statistics, ops.HipBackend.fp_mlp_bn_layer (mcp_fp_mlp_bn_forward / mcp_fp_mlp_bn_backward), after which the module
+updates every BatchNorm2d's running statistics as torch does -- taken with or without a wanted gradient, never with lengths, for a
+class of ops.FP_MLP_BN_FUSED_CLASSES (tools/fp_mlp_bn_times.py; `bn_route` overrides it)."""
 from typing import List
 
 import torch
@@ -183,8 +186,10 @@ class PointnetFPModule(nn.Module):
     counts C2 + C1).  weighting: "pointnet2" (weights 1 / (dist + 1e-8), normalised; the reference class) or "flownet3d"
     (1 / max(dist^2, 1e-10), normalised; FeaturePropagation of models/layers.py).  route: "measured" (default), "always" or "never"
     for the fused route when no gradient is wanted; grad_route: the same three values, independently, for the fused differentiable
-    route (mcp_fp_mlp forward, mcp_fp_mlp_grad backward) when one is -- eligible in eval() or with bn=False; a training-mode
-    BatchNorm keeps the composition."""
+    route (mcp_fp_mlp forward, mcp_fp_mlp_grad backward) when one is -- eligible in eval() or with bn=False.  bn_route: the same
+    three values, independently, for the route with batch statistics (mcp_fp_mlp_bn_forward / mcp_fp_mlp_bn_backward) under train()
+    with bn=True, with or without a wanted gradient; a call with lengths keeps the composition there (its batch statistics count the
+    padded rows, the kernel's do not)."""
 
     def __init__(self, *, mlp: List[int], bn: bool = True):
         super().__init__()
@@ -192,6 +197,7 @@ class PointnetFPModule(nn.Module):
         self.weighting = "pointnet2"
         self.route = "measured"
         self.grad_route = "measured"
+        self.bn_route = "measured"
         self.mlp = _shared_mlp(list(mlp), bn, False)
         self.__dict__["_packed"] = None
 
@@ -229,6 +235,29 @@ class PointnetFPModule(nn.Module):
             return False
         return self.grad_route == "always" or ops.fp_mlp_grad_routes_fused(c2, c1, widths, rows)
 
+    def fused_bn(self, c2, c1, rows, with_lengths=False):
+        """Whether a call under train() with BatchNorm takes the fused route with batch statistics (a batch of one row is left to
+        torch, which refuses it)."""
+        if not (self.training and self.bn) or with_lengths or rows < 2 or self.bn_route == "never" or self.weighting not in ("pointnet2", "flownet3d"):
+            return False
+        convs = self._layers()[0]
+        widths = [c.out_channels for c in convs]
+        if not convs or convs[0].in_channels != c2 + c1 or not ops.fp_mlp_bn_supported(c2, c1, widths):
+            return False
+        return self.bn_route == "always" or ops.fp_mlp_bn_routes_fused(c2, c1, widths, rows)
+
+    @staticmethod
+    def _track(bn, mean, var, rows):
+        """nn.BatchNorm2d's update of its running statistics from the batch mean and the biased batch variance over `rows` rows."""
+        if not bn.track_running_stats or bn.running_mean is None:
+            return
+        with torch.no_grad():
+            if bn.num_batches_tracked is not None:
+                bn.num_batches_tracked += 1
+            f = bn.momentum if bn.momentum is not None else 1.0 / bn.num_batches_tracked.to(torch.float32)
+            bn.running_mean.mul_(1.0 - f).add_(f * mean)
+            bn.running_var.mul_(1.0 - f).add_(f * (var * (rows / (rows - 1.0))))
+
     def weights(self, dist):
         """(B,n,3) interpolation weights of three_nn's distances under `weighting`; a row without a finite distance gets zeros."""
         if self.weighting == "pointnet2":
@@ -256,6 +285,16 @@ class PointnetFPModule(nn.Module):
             kl = ops.lengths_tensor(known_lengths, B, known.shape[1], unknown.device)
         wants_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (unknown, known, unknow_feats, known_feats,
                                                                                                  *self.parameters()))
+        if known is not None and self.fused_bn(C2, C1, B * n, with_lengths):
+            dist, idx = pu.three_nn(unknown.detach().contiguous(), known.detach().contiguous())   # no gradient reaches the coordinates
+            rows = known_feats.transpose(1, 2).contiguous()
+            skip = None if unknow_feats is None else unknow_feats.transpose(1, 2).contiguous()
+            convs, bns = self._layers()
+            layers = [(c.weight.flatten(1), c.bias, b.weight, b.bias, b.eps) for c, b in zip(convs, bns)]
+            out, stats, _ = ops.backend().fp_mlp_bn_layer(rows, skip, idx, dist, layers, rule=self.weighting)
+            for b, (mean, var) in zip(bns, stats):
+                self._track(b, mean, var, B * n)
+            return out.transpose(1, 2)
         if known is not None and not wants_grad and self.fused(C2, C1, B * n):
             packed, widths = self._packed_weights(C2)
             dist, idx = pu.three_nn(unknown.detach().contiguous(), known.detach().contiguous(), ul, kl)
