@@ -36,16 +36,11 @@
 // fp_weights_in_lds(shape) is the one dispatch predicate: an image of at most 64 KB is staged whole in LDS; a larger one (up to 1.5 MB)
 // is streamed as mlp.hip streams its chunks -- the workgroup holds two slabs in LDS and fetches slab q + 1 while slab q is multiplied,
 // one barrier per slab.
-#include <math.h>
-
-#include "common.h"
-#include "mfma_split.h"
-#include "fp_mlp_shape.h"
+//
+// The row, the gather, the slab sequence and the tile helpers are fp_mlp_tile.h's, shared with fp_mlp_grad.hip and fp_mlp_bn.hip.
+#include "fp_mlp_tile.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // One layer of the image: slab s (k-step s of the layer's input) holds, for every output tile t, the three pieces of the 8 values
 // per lane W[32t + (lane&31)][column of (s, i, lane>>5)].  Input k-steps 0 .. ksa-1 cover columns 0 .. va-1 (zero beyond), the next
@@ -78,13 +73,9 @@ __global__ __launch_bounds__(256) void fp_mlp_pack_kernel(const float *__restric
 struct FpArgs {
     long long total;  // B * n rows
     int n, m, c2, c1, rule, layers;
-    int ksb, kss;
-    int ks0, ks1, ks2, t0, t1, t2, b0, b1, b2;  // per layer: k-steps, output tiles, bias offset (named: never indexed at run time)
+    int ksb, ks0;                // k-steps of the blend, and of all of layer 1's input
+    int t0, t1, t2, b0, b1, b2;  // per layer: output tiles, bias offset (named: never indexed at run time)
     int w_u4, small_floats;
-};
-
-struct FpRaw {  // what one input k-step of layer 1 reads: the two float4 of each of the three known rows, or of the skip row (in a*)
-    float4 a0, a1, b0, b1, c0, c1;
 };
 
 template <int TMAX, bool STREAM>
@@ -92,190 +83,28 @@ __global__ __launch_bounds__(THREADS, TMAX == 8 ? 1 : 2) void fp_mlp_kernel(cons
                                                                          const int *__restrict__ idx, const float *__restrict__ dist,
                                                                          const float *__restrict__ w3, const int *__restrict__ ulen,
                                                                          const float *__restrict__ packed, float *__restrict__ out) {
-    constexpr int LOADS = (TMAX * TILE_U4 + THREADS - 1) / THREADS;
-    constexpr int BUF = LOADS * THREADS;  // uint4 of one LDS slab buffer: the widest slab rounded up to whole passes of the workgroup
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float *small = lds;                                               // biases
-    u32x4 *wl = reinterpret_cast<u32x4 *>(lds + a.small_floats);      // whole image, or [2][BUF]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, col = lane & 31;
-    const u32x4 *gimg = reinterpret_cast<const u32x4 *>(packed);
-
-    auto tiles_of = [&](int l) { return l == 0 ? a.t0 : l == 1 ? a.t1 : l == 2 ? a.t2 : 0; };
-    auto ks_of = [&](int l) { return l == 0 ? a.ks0 : l == 1 ? a.ks1 : l == 2 ? a.ks2 : 0; };
-
-    // ---- the slab sequence: begin_slab(l) gives this lane's entry of the next slab (a slab of layer l), end_slab() releases it ----
-    u32x4 pre[LOADS];                 // staging registers of the slab after the one being multiplied
-    const u32x4 *nxt_src = gimg;      // streamed: where the next slab to fetch starts, its layer, and that layer's slabs still to fetch
-    int nxt_layer = 0, nxt_left = a.ks0, cur = 0;
-    const u32x4 *wcur = wl;           // staged whole: the next slab in LDS
-#pragma unroll
-    for (int u = 0; u < LOADS; ++u) pre[u] = u32x4{0u, 0u, 0u, 0u};
-    auto fetch_slab = [&]() {
-        if (nxt_layer < a.layers) {
-            const int n4 = tiles_of(nxt_layer) * TILE_U4;
-#pragma unroll
-            for (int u = 0; u < LOADS; ++u) pre[u] = nxt_src[min(tid + u * THREADS, n4 - 1)];  // entries past the slab repeat its last one, never used
-            nxt_src += n4;
-            if (--nxt_left == 0) {
-                ++nxt_layer;
-                nxt_left = ks_of(nxt_layer);
-            }
-        }
-    };
-    auto stash = [&](int buf) {
-#pragma unroll
-        for (int u = 0; u < LOADS; ++u) wl[buf * BUF + tid + u * THREADS] = pre[u];
-    };
-    auto begin_slab = [&](int l) -> const uint4 * {
-        if constexpr (STREAM) {
-            fetch_slab();
-            __syncthreads();  // the slab is complete in buffer cur; nobody reads buffer cur ^ 1 any more
-            return reinterpret_cast<const uint4 *>(wl + cur * BUF) + lane;
-        } else {
-            const u32x4 *w = wcur;
-            wcur += tiles_of(l) * TILE_U4;
-            return reinterpret_cast<const uint4 *>(w) + lane;
-        }
-    };
-    auto end_slab = [&]() {
-        if constexpr (STREAM) {
-            stash(cur ^ 1);
-            cur ^= 1;
-        }
-    };
-
+    float *small = lds;                                               // biases, then the whole image or two slab buffers
+    const int tid = threadIdx.x, h = (tid & 63) >> 5;
+    FpSlabs<TMAX, STREAM> slabs;
     {
         const float4 *src = reinterpret_cast<const float4 *>(packed) + a.w_u4;
         for (int e = tid; e < a.small_floats / 4; e += THREADS) reinterpret_cast<float4 *>(small)[e] = src[e];
-        if constexpr (STREAM) {
-            fetch_slab();
-            stash(0);
-        } else {
-            for (int e = tid; e < a.w_u4; e += THREADS) wl[e] = gimg[e];
-        }
+        slabs.begin(reinterpret_cast<u32x4 *>(lds + a.small_floats), reinterpret_cast<const u32x4 *>(packed), a.t0, a.w_u4);
     }
     __syncthreads();
 
-    // ---- this column's row: liveness, the three weights, the three known rows ----
-    const long long p = ((long long)blockIdx.x * WAVES + wave) * 32 + col;
-    const bool inr = p < a.total;
-    const long long bb = inr ? mcp_div(p, a.n, mcp_fits32(a.total)) : 0;
-    bool live = inr;
-    if (inr && ulen) {
-        const int ul = min(max(ulen[bb], 0), a.n);
-        live = (int)(p - bb * a.n) < ul;
-    }
-    float w0 = 0.f, w1 = 0.f, w2 = 0.f;
-    bool u0 = false, u1 = false, u2 = false;  // the slot's row is read
-    const float *f0 = known_feats, *f1 = known_feats, *f2 = known_feats;
-    const float *srow = skip;
-    if (live) {
-        const int *ip = idx + p * 3;
-        const long long base = bb * a.m;
-        f0 = known_feats + (base + ip[0]) * a.c2;
-        f1 = known_feats + (base + ip[1]) * a.c2;
-        f2 = known_feats + (base + ip[2]) * a.c2;
-        if (a.c1) srow = skip + p * a.c1;
-        if (a.rule == 0) {
-            w0 = w3[p * 3 + 0]; w1 = w3[p * 3 + 1]; w2 = w3[p * 3 + 2];
-            u0 = u1 = u2 = true;
-        } else {
-            float d0 = dist[p * 3 + 0], d1 = dist[p * 3 + 1], d2 = dist[p * 3 + 2];
-            u0 = d0 < INFINITY; u1 = d1 < INFINITY; u2 = d2 < INFINITY;
-            if (a.rule == 1) {
-                d0 = d0 + 1e-8f; d1 = d1 + 1e-8f; d2 = d2 + 1e-8f;
-            } else {
-                d0 = d0 * d0; d1 = d1 * d1; d2 = d2 * d2;
-                d0 = d0 < 1e-10f ? 1e-10f : d0; d1 = d1 < 1e-10f ? 1e-10f : d1; d2 = d2 < 1e-10f ? 1e-10f : d2;
-            }
-            const float r0 = u0 ? 1.0f / d0 : 0.f, r1 = u1 ? 1.0f / d1 : 0.f, r2 = u2 ? 1.0f / d2 : 0.f;
-            const float sum = (r0 + r1) + r2;
-            const bool any = sum > 0.f;  // false: no known point at all -- zeros, not 0 / 0
-            w0 = any ? r0 / sum : 0.f; w1 = any ? r1 / sum : 0.f; w2 = any ? r2 / sum : 0.f;
-        }
-    }
-    const bool skip_q = (a.c1 & 3) == 0;  // skip rows are 16-byte aligned
-
-    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    auto fetch = [&](int s) {
-        FpRaw r{z4, z4, z4, z4, z4, z4};
-        if (s < a.ksb) {
-            const int ch0 = 16 * s + 4 * h, ch1 = ch0 + 8;
-            if (ch0 < a.c2) {
-                if (u0) r.a0 = *reinterpret_cast<const float4 *>(f0 + ch0);
-                if (u1) r.b0 = *reinterpret_cast<const float4 *>(f1 + ch0);
-                if (u2) r.c0 = *reinterpret_cast<const float4 *>(f2 + ch0);
-            }
-            if (ch1 < a.c2) {
-                if (u0) r.a1 = *reinterpret_cast<const float4 *>(f0 + ch1);
-                if (u1) r.b1 = *reinterpret_cast<const float4 *>(f1 + ch1);
-                if (u2) r.c1 = *reinterpret_cast<const float4 *>(f2 + ch1);
-            }
-        } else if (live) {
-            const int ch0 = 16 * (s - a.ksb) + 4 * h, ch1 = ch0 + 8;
-            if (skip_q) {
-                if (ch0 < a.c1) r.a0 = *reinterpret_cast<const float4 *>(srow + ch0);
-                if (ch1 < a.c1) r.a1 = *reinterpret_cast<const float4 *>(srow + ch1);
-            } else {
-                if (ch0 + 0 < a.c1) r.a0.x = srow[ch0 + 0];
-                if (ch0 + 1 < a.c1) r.a0.y = srow[ch0 + 1];
-                if (ch0 + 2 < a.c1) r.a0.z = srow[ch0 + 2];
-                if (ch0 + 3 < a.c1) r.a0.w = srow[ch0 + 3];
-                if (ch1 + 0 < a.c1) r.a1.x = srow[ch1 + 0];
-                if (ch1 + 1 < a.c1) r.a1.y = srow[ch1 + 1];
-                if (ch1 + 2 < a.c1) r.a1.z = srow[ch1 + 2];
-                if (ch1 + 3 < a.c1) r.a1.w = srow[ch1 + 3];
-            }
-        }
-        return r;
-    };
-    auto blend = [&](float fa, float fb, float fc) { return (w0 * fa + w1 * fb) + w2 * fc; };
-    auto finish = [&](const FpRaw &r, int s) {
-        float v[8];
-        if (s < a.ksb) {
-            v[0] = blend(r.a0.x, r.b0.x, r.c0.x); v[1] = blend(r.a0.y, r.b0.y, r.c0.y);
-            v[2] = blend(r.a0.z, r.b0.z, r.c0.z); v[3] = blend(r.a0.w, r.b0.w, r.c0.w);
-            v[4] = blend(r.a1.x, r.b1.x, r.c1.x); v[5] = blend(r.a1.y, r.b1.y, r.c1.y);
-            v[6] = blend(r.a1.z, r.b1.z, r.c1.z); v[7] = blend(r.a1.w, r.b1.w, r.c1.w);
-        } else {
-            v[0] = r.a0.x; v[1] = r.a0.y; v[2] = r.a0.z; v[3] = r.a0.w;
-            v[4] = r.a1.x; v[5] = r.a1.y; v[6] = r.a1.z; v[7] = r.a1.w;
-        }
-        return mcp_split8(v);
-    };
+    const FpRow row(a.total, a.n, ulen);
+    FpGather g;
+    g.begin(row, a.m, a.c2, a.c1, a.rule, a.ksb, known_feats, skip, idx, dist, w3);
 
     auto bias_bank = [&](f32x16(&bank)[TMAX], int boff, int tiles) {
 #pragma unroll
-        for (int o = 0; o < TMAX; ++o) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) bank[o][r] = 0.f;
-            if (o < tiles) {
-                const float4 *bq = reinterpret_cast<const float4 *>(small + boff + (o * 2 + h) * 16);
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const float4 v = bq[g];
-                    bank[o][4 * g + 0] = v.x; bank[o][4 * g + 1] = v.y; bank[o][4 * g + 2] = v.z; bank[o][4 * g + 3] = v.w;
-                }
-            }
-        }
+        for (int o = 0; o < TMAX; ++o) fp_bias_tile(bank[o], o, tiles, small + boff);
     };
-    // one k-step slab into every output tile of a bank
-    auto slab_into = [&](f32x16(&bank)[TMAX], int l, int tiles, const McpSplit3 &xs) {
-        const uint4 *w = begin_slab(l);
-#pragma unroll
-        for (int o = 0; o < TMAX; ++o)
-            if (o < tiles) bank[o] = mcp_mfma_split(w + o * TILE_U4, xs, bank[o]);
-        // The wave-uniform branches around absent tiles leave paths on which this compiler moves a finished tile between register
-        // files 8 .. 11 wait states after its last MFMA (12 are needed; its hazard pass does not follow those branch chains, and
-        // tools/isa_lint.py finds them).  16 idle issue slots after the slab's last MFMA cover every such path; they pass while the
-        // matrix pipe is still busy with that MFMA.
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_nop 15");
-        __builtin_amdgcn_sched_barrier(0);
-        end_slab();
-    };
-    // layer l >= 1: the previous bank tile by tile through ReLU and the operand split into every output tile of the other bank
-    auto next_layer = [&](f32x16(&src)[TMAX], f32x16(&dst)[TMAX], int l, int tin, int tout, int boff) {
+    // layer l >= 1: the previous bank tile by tile through ReLU and the operand split into every output tile of the other bank;
+    // `after`: the output tiles of the layer behind this one (0: none)
+    auto next_layer = [&](f32x16(&src)[TMAX], f32x16(&dst)[TMAX], int tin, int tout, int boff, int after) {
         bias_bank(dst, boff, tout);
 #pragma unroll
         for (int t = 0; t < TMAX; ++t) {
@@ -283,23 +112,24 @@ __global__ __launch_bounds__(THREADS, TMAX == 8 ? 1 : 2) void fp_mlp_kernel(cons
                 f32x16 r = src[t];
 #pragma unroll
                 for (int i = 0; i < 16; ++i) r[i] = fmaxf(r[i], 0.f);
-#pragma unroll
-                for (int half = 0; half < 2; ++half) slab_into(dst, l, tout, mcp_split_kstep(r, half));
+                slabs.into(dst, tout, mcp_split_kstep(r, 0), tout);
+                slabs.into(dst, tout, mcp_split_kstep(r, 1), t + 1 == tin ? after : tout);
             }
         }
     };
     auto store_bank = [&](f32x16(&bank)[TMAX], int tiles) {
-        if (!inr) return;
-        float *orow = out + p * (tiles * 32) + 4 * h;
+        if (!row.inr) return;
+        const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        float *orow = out + row.p * (tiles * 32) + 4 * h;
 #pragma unroll
         for (int o = 0; o < TMAX; ++o) {
             if (o < tiles) {
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    float4 v = make_float4(fmaxf(bank[o][4 * g + 0], 0.f), fmaxf(bank[o][4 * g + 1], 0.f), fmaxf(bank[o][4 * g + 2], 0.f),
-                                           fmaxf(bank[o][4 * g + 3], 0.f));
-                    if (!live) v = z4;
-                    *reinterpret_cast<float4 *>(orow + 32 * o + 8 * g) = v;
+                for (int g4 = 0; g4 < 4; ++g4) {
+                    float4 v = make_float4(fmaxf(bank[o][4 * g4 + 0], 0.f), fmaxf(bank[o][4 * g4 + 1], 0.f), fmaxf(bank[o][4 * g4 + 2], 0.f),
+                                           fmaxf(bank[o][4 * g4 + 3], 0.f));
+                    if (!row.live) v = z4;
+                    *reinterpret_cast<float4 *>(orow + 32 * o + 8 * g4) = v;
                 }
             }
         }
@@ -308,44 +138,19 @@ __global__ __launch_bounds__(THREADS, TMAX == 8 ? 1 : 2) void fp_mlp_kernel(cons
     f32x16 bank_a[TMAX], bank_b[TMAX];
     // ---- layer 1: input k-steps from memory ----
     bias_bank(bank_a, a.b0, a.t0);
-    {
-        FpRaw now = fetch(0);
-#pragma unroll 1
-        for (int s = 0; s < a.ks0; ++s) {
-            const FpRaw nxt = fetch(min(s + 1, a.ks0 - 1));  // the last k-step fetches itself again: no branch in the loop body
-            slab_into(bank_a, 0, a.t0, finish(now, s));
-            now = nxt;
-        }
-    }
+    fp_ksteps(a.ks0, [&](int s) { return g.fetch(s); },
+              [&](const FpGatherRaw &now, int s, bool last) { slabs.into(bank_a, a.t0, g.finish(now, s, nullptr, 0), last ? a.t1 : a.t0); });
     if (a.layers == 1) {
         store_bank(bank_a, a.t0);
     } else {
-        next_layer(bank_a, bank_b, 1, a.t0, a.t1, a.b1);
+        next_layer(bank_a, bank_b, a.t0, a.t1, a.b1, a.t2);
         if (a.layers == 2) {
             store_bank(bank_b, a.t1);
         } else {
-            next_layer(bank_b, bank_a, 2, a.t1, a.t2, a.b2);
+            next_layer(bank_b, bank_a, a.t1, a.t2, a.b2, 0);
             store_bank(bank_a, a.t2);
         }
     }
-}
-
-template <int TMAX, bool STREAM>
-int launch_fp_mlp(const FpArgs &a, const float *known_feats, const float *skip, const int *idx, const float *dist, const float *w3, const int *ulen,
-                  const float *packed, float *out, hipStream_t s) {
-    auto kern = fp_mlp_kernel<TMAX, STREAM>;
-    static McpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_once.done();
-    }
-    constexpr int LOADS = (TMAX * TILE_U4 + THREADS - 1) / THREADS;
-    const size_t lds = (size_t)a.small_floats * sizeof(float) + (STREAM ? (size_t)2 * LOADS * THREADS * 16 : (size_t)a.w_u4 * 16);
-    const long long grid = (a.total + 32 * WAVES - 1) / (32 * WAVES);
-    if (grid > 0x7FFFFFFFLL) return MCP_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(THREADS), lds, s, a, known_feats, skip, idx, dist, w3, ulen, packed, out);
-    return mcp_launch_status();
 }
 
 }  // namespace
@@ -390,19 +195,15 @@ MCP_EXPORT int mcp_fp_mlp(int b, int n, int m, int c2, int c1, int rule, int lay
     FpArgs a;
     a.total = (long long)b * n;
     a.n = n; a.m = m; a.c2 = c2; a.c1 = c1; a.rule = rule; a.layers = layers;
-    a.ksb = sh.ksb; a.kss = sh.kss;
-    a.ks0 = sh.ks[0]; a.ks1 = sh.ks[1]; a.ks2 = sh.ks[2];
+    a.ksb = sh.ksb; a.ks0 = sh.ks[0];
     a.t0 = sh.tiles[0]; a.t1 = sh.tiles[1]; a.t2 = sh.tiles[2];
     a.b0 = sh.boff[0]; a.b1 = sh.boff[1]; a.b2 = sh.boff[2];
     a.w_u4 = sh.w_u4;
     a.small_floats = sh.small_floats;
-    hipStream_t s = (hipStream_t)stream;
-    const bool whole = fp_weights_in_lds(sh);
-#define FP_LAUNCH(T)                                                                                                       \
-    return whole ? launch_fp_mlp<T, false>(a, known_feats, skip, idx, dist, w3, ulen, packed, out, s)                      \
-                 : launch_fp_mlp<T, true>(a, known_feats, skip, idx, dist, w3, ulen, packed, out, s)
-    if (sh.tmax == 2) FP_LAUNCH(2);
-    if (sh.tmax == 4) FP_LAUNCH(4);
-    FP_LAUNCH(8);
-#undef FP_LAUNCH
+    return fp_dispatch(sh.tmax, !fp_weights_in_lds(sh), [&](auto tmax, auto stream_w) {
+        constexpr int T = decltype(tmax)::value;
+        constexpr bool S = decltype(stream_w)::value;
+        return fp_launch<fp_mlp_kernel<T, S>, T, S>(a.total, a.small_floats, a.w_u4, (hipStream_t)stream, a, known_feats, skip, idx, dist, w3, ulen,
+                                                    packed, out);
+    });
 }

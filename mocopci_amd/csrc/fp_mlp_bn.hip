@@ -6,7 +6,7 @@
 //
 // A pass ends where the next quantity needs a sum over all rows.  One kernel template, fpbn_pass_kernel<TMAX, STREAM, MODE>, is one
 // layer's product with what surrounds it:
-//   FWD_GATHER  h_0 from the gathered rows (fp_mlp_kernel's layer 1), z_1 = W_1 h_0 + b_1 to the workspace;
+//   FWD_GATHER  h_0 from the gathered rows (FpGather of fp_mlp_tile.h: the forward's layer 1), z_1 = W_1 h_0 + b_1 to the workspace;
 //   FWD_ROWS    h_(l-1) = ReLU(a z_(l-1) + c) formed ON LOAD from the stored z_(l-1) (a = gamma rstd, c = beta - mu a), z_l to the
 //               workspace;
 //     both accumulate, in their epilogue, one (count, mean, M2) triple per channel and workgroup;
@@ -40,16 +40,12 @@
 // slabs streamed through two LDS buffers.
 //
 // Built WITHOUT -fno-honor-nans, as fp_mlp_grad.hip: masks and ReLU are comparisons and selections, a diverged run shows its NaN.
-#include <math.h>
-
-#include "common.h"
-#include "mfma_split.h"
-#include "fp_mlp_shape.h"
+//
+// The row, the gather, the slab sequence, the tile helpers and the dx epilogue are fp_mlp_tile.h's, shared with fp_mlp.hip and
+// fp_mlp_grad.hip.
+#include "fp_mlp_tile.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 enum { FWD_GATHER = 0, FWD_ROWS = 1, BWD_MID = 2, BWD_DX = 3 };
 constexpr int COEF = 8;   // per-channel coefficient rows of one layer in the workspace: a, c, mu, rstd | p, k1, q, mu
@@ -104,209 +100,49 @@ struct BnPtrs {
     int *part_cnt;               // (workgroups): live rows
 };
 
-struct BnGather {  // what one input k-step of layer 1 reads: the two float4 of each of the three known rows, or of the skip row (in a*)
-    float4 a0, a1, b0, b1, c0, c1;
-};
 struct BnRows {    // what one k-step of a stored row reads: two quads of in0, two of in1
-    float4 a0, a1, b0, b1;
+    FpQuads a, b;
 };
 
 template <int TMAX, bool STREAM, int MODE>
 __global__ __launch_bounds__(THREADS, TMAX == 8 ? 1 : 2) void fpbn_pass_kernel(const BnArgs a, const BnPtrs q) {
-    constexpr int LOADS = (TMAX * TILE_U4 + THREADS - 1) / THREADS;
-    constexpr int BUF = LOADS * THREADS;  // uint4 of one LDS slab buffer: the widest slab rounded up to whole passes of the workgroup
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *coef = lds;                                                           // the input channels' coefficients
     float *stat = lds + a.coef_floats;                                           // [wave][2][output channels], then the waves' live rows
     int *wave_cnt = reinterpret_cast<int *>(lds + a.coef_floats + a.stat_floats) - WAVES;   // (all of the LDS is dynamic: the whole 160 KB may be asked for)
-    u32x4 *wl = reinterpret_cast<u32x4 *>(lds + a.coef_floats + a.stat_floats);  // this pass's slabs, or [2][BUF]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, col = lane & 31;
-    const u32x4 *gimg = reinterpret_cast<const u32x4 *>(q.packed) + a.slab_u4;
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
 
-    // ---- the slab sequence, as fp_mlp_grad_kernel: begin_slab gives this lane's entry of the next slab, end_slab() releases it; a
-    // streamed slab is fetched one slab ahead, so every call names the output tiles of the slab AFTER its own (0: none) ----
-    u32x4 pre[LOADS];
-    const u32x4 *nxt_src = gimg;
-    int cur = 0;
-    const u32x4 *wcur = wl;
-#pragma unroll
-    for (int u = 0; u < LOADS; ++u) pre[u] = u32x4{0u, 0u, 0u, 0u};
-    auto fetch_slab = [&](int tiles) {
-        if (tiles > 0) {
-            const int n4 = tiles * TILE_U4;
-#pragma unroll
-            for (int u = 0; u < LOADS; ++u) pre[u] = nxt_src[min(tid + u * THREADS, n4 - 1)];  // entries past the slab repeat its last one, never used
-            nxt_src += n4;
-        }
-    };
-    auto stash = [&](int buf) {
-#pragma unroll
-        for (int u = 0; u < LOADS; ++u) wl[buf * BUF + tid + u * THREADS] = pre[u];
-    };
-    auto begin_slab = [&](int tiles, int next_tiles) -> const uint4 * {
-        if constexpr (STREAM) {
-            fetch_slab(next_tiles);
-            __syncthreads();  // the slab is complete in buffer cur; nobody reads buffer cur ^ 1 any more
-            return reinterpret_cast<const uint4 *>(wl + cur * BUF) + lane;
-        } else {
-            const u32x4 *w = wcur;
-            wcur += tiles * TILE_U4;
-            return reinterpret_cast<const uint4 *>(w) + lane;
-        }
-    };
-    auto end_slab = [&]() {
-        if constexpr (STREAM) {
-            stash(cur ^ 1);
-            cur ^= 1;
-        }
-    };
-
-    const int first_tiles = MODE == BWD_DX ? min(TMAX, a.tiles) : a.tiles;
+    FpSlabs<TMAX, STREAM> slabs;   // behind coef and stat: this pass's slabs, or two slab buffers
     {
         if constexpr (MODE != FWD_GATHER)
             for (int e = tid; e < a.coef_floats / 4; e += THREADS) reinterpret_cast<float4 *>(coef)[e] = reinterpret_cast<const float4 *>(q.coef_in)[e];
-        if constexpr (STREAM) {
-            fetch_slab(first_tiles);
-            stash(0);
-        } else {
-            for (int e = tid; e < a.pass_u4; e += THREADS) wl[e] = gimg[e];
-        }
+        slabs.begin(reinterpret_cast<u32x4 *>(lds + a.coef_floats + a.stat_floats), reinterpret_cast<const u32x4 *>(q.packed) + a.slab_u4,
+                    MODE == BWD_DX ? min(TMAX, a.tiles) : a.tiles, a.pass_u4);
     }
     __syncthreads();
 
-    // ---- this column's row and its liveness ----
-    const long long p = ((long long)blockIdx.x * WAVES + wave) * 32 + col;
-    const bool inr = p < a.total;
-    const long long bb = inr ? mcp_div(p, a.n, mcp_fits32(a.total)) : 0;
-    bool live = inr;
-    if (inr && q.ulen) {
-        const int ul = min(max(q.ulen[bb], 0), a.n);
-        live = (int)(p - bb * a.n) < ul;
-    }
-
-    // ---- FWD_GATHER: the three weights and the three known rows (as fp_mlp_kernel) ----
-    float w0 = 0.f, w1 = 0.f, w2 = 0.f;
-    bool u0 = false, u1 = false, u2 = false;  // the slot's row is read
-    const float *f0 = q.known_feats, *f1 = q.known_feats, *f2 = q.known_feats;
-    const float *srow = q.skip;
-    const bool skip_q = (a.c1 & 3) == 0;  // skip rows (and so the rows of x and grad_skip) are 16-byte aligned
-    const int cx = a.c2 + a.c1;
+    const FpRow me(a.total, a.n, q.ulen);
+    const long long p = me.p;
+    const bool inr = me.inr, live = me.live;
+    FpGather gather;   // FWD_GATHER: the three weights and the three known rows
     if constexpr (MODE == FWD_GATHER) {
-        if (live) {
-            const int *ip = q.idx + p * 3;
-            const long long base = bb * a.m;
-            f0 = q.known_feats + (base + ip[0]) * a.c2;
-            f1 = q.known_feats + (base + ip[1]) * a.c2;
-            f2 = q.known_feats + (base + ip[2]) * a.c2;
-            if (a.c1) srow = q.skip + p * a.c1;
-            if (a.rule == 0) {
-                w0 = q.w3[p * 3 + 0]; w1 = q.w3[p * 3 + 1]; w2 = q.w3[p * 3 + 2];
-                u0 = u1 = u2 = true;
-            } else {
-                float d0 = q.dist[p * 3 + 0], d1 = q.dist[p * 3 + 1], d2 = q.dist[p * 3 + 2];
-                u0 = d0 < INFINITY; u1 = d1 < INFINITY; u2 = d2 < INFINITY;
-                if (a.rule == 1) {
-                    d0 = d0 + 1e-8f; d1 = d1 + 1e-8f; d2 = d2 + 1e-8f;
-                } else {
-                    d0 = d0 * d0; d1 = d1 * d1; d2 = d2 * d2;
-                    d0 = d0 < 1e-10f ? 1e-10f : d0; d1 = d1 < 1e-10f ? 1e-10f : d1; d2 = d2 < 1e-10f ? 1e-10f : d2;
-                }
-                const float r0 = u0 ? 1.0f / d0 : 0.f, r1 = u1 ? 1.0f / d1 : 0.f, r2 = u2 ? 1.0f / d2 : 0.f;
-                const float sum = (r0 + r1) + r2;
-                const bool any = sum > 0.f;  // false: no known point at all -- zeros, not 0 / 0
-                w0 = any ? r0 / sum : 0.f; w1 = any ? r1 / sum : 0.f; w2 = any ? r2 / sum : 0.f;
-            }
-        }
-        if (q.w_used && inr && h == 0) {  // the weights the blend uses: an infinite slot holds an exact 0, a padded row three
-            float *wu = q.w_used + p * 3;
-            wu[0] = u0 ? w0 : 0.f; wu[1] = u1 ? w1 : 0.f; wu[2] = u2 ? w2 : 0.f;
-        }
+        gather.begin(me, a.m, a.c2, a.c1, a.rule, a.ksb, q.known_feats, q.skip, q.idx, q.dist, q.w3);
+        if (q.w_used) gather.store_w_used(q.w_used, p);
     }
-    auto gather = [&](int s) {
-        BnGather r{z4, z4, z4, z4, z4, z4};
-        if (s < a.ksb) {
-            const int ch0 = 16 * s + 4 * h, ch1 = ch0 + 8;
-            if (ch0 < a.c2) {
-                if (u0) r.a0 = *reinterpret_cast<const float4 *>(f0 + ch0);
-                if (u1) r.b0 = *reinterpret_cast<const float4 *>(f1 + ch0);
-                if (u2) r.c0 = *reinterpret_cast<const float4 *>(f2 + ch0);
-            }
-            if (ch1 < a.c2) {
-                if (u0) r.a1 = *reinterpret_cast<const float4 *>(f0 + ch1);
-                if (u1) r.b1 = *reinterpret_cast<const float4 *>(f1 + ch1);
-                if (u2) r.c1 = *reinterpret_cast<const float4 *>(f2 + ch1);
-            }
-        } else if (live) {
-            const int ch0 = 16 * (s - a.ksb) + 4 * h, ch1 = ch0 + 8;
-            if (skip_q) {
-                if (ch0 < a.c1) r.a0 = *reinterpret_cast<const float4 *>(srow + ch0);
-                if (ch1 < a.c1) r.a1 = *reinterpret_cast<const float4 *>(srow + ch1);
-            } else {
-                if (ch0 + 0 < a.c1) r.a0.x = srow[ch0 + 0];
-                if (ch0 + 1 < a.c1) r.a0.y = srow[ch0 + 1];
-                if (ch0 + 2 < a.c1) r.a0.z = srow[ch0 + 2];
-                if (ch0 + 3 < a.c1) r.a0.w = srow[ch0 + 3];
-                if (ch1 + 0 < a.c1) r.a1.x = srow[ch1 + 0];
-                if (ch1 + 1 < a.c1) r.a1.y = srow[ch1 + 1];
-                if (ch1 + 2 < a.c1) r.a1.z = srow[ch1 + 2];
-                if (ch1 + 3 < a.c1) r.a1.w = srow[ch1 + 3];
-            }
-        }
-        return r;
-    };
-    auto blend = [&](float fa, float fb, float fc) { return (w0 * fa + w1 * fb) + w2 * fc; };
-    // the 8 values of k-step s of x, written to the workspace on the way when the backward asks for them
-    auto finish_gather = [&](const BnGather &r, int s) {
-        float v[8];
-        const bool blended = s < a.ksb;
-        if (blended) {
-            v[0] = blend(r.a0.x, r.b0.x, r.c0.x); v[1] = blend(r.a0.y, r.b0.y, r.c0.y);
-            v[2] = blend(r.a0.z, r.b0.z, r.c0.z); v[3] = blend(r.a0.w, r.b0.w, r.c0.w);
-            v[4] = blend(r.a1.x, r.b1.x, r.c1.x); v[5] = blend(r.a1.y, r.b1.y, r.c1.y);
-            v[6] = blend(r.a1.z, r.b1.z, r.c1.z); v[7] = blend(r.a1.w, r.b1.w, r.c1.w);
-        } else {
-            v[0] = r.a0.x; v[1] = r.a0.y; v[2] = r.a0.z; v[3] = r.a0.w;
-            v[4] = r.a1.x; v[5] = r.a1.y; v[6] = r.a1.z; v[7] = r.a1.w;
-        }
-        if (q.side && inr) {
-            const int lim = blended ? a.c2 : a.c1;
-            const int loc = 16 * (blended ? s : s - a.ksb) + 4 * h;
-            float *xr = q.side + p * cx + (blended ? 0 : a.c2);
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                const int lc = loc + 8 * half;
-                if (skip_q) {   // C2 and C1 multiples of 4: whole quads
-                    if (lc < lim) *reinterpret_cast<float4 *>(xr + lc) = make_float4(v[4 * half], v[4 * half + 1], v[4 * half + 2], v[4 * half + 3]);
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        if (lc + i < lim) xr[lc + i] = v[4 * half + i];
-                }
-            }
-        }
-        return mcp_split8(v);
-    };
 
     // ---- FWD_ROWS, BWD_*: k-step s of the lane's own stored row is the two quads at 16 s and 16 s + 8 (from channel 4 h) ----
     const long long in_at = p * a.cin + 4 * h;
     auto load_rows = [&](int s) {
-        BnRows r{z4, z4, z4, z4};
-        if (live) {
-            r.a0 = *reinterpret_cast<const float4 *>(q.in0 + in_at + 16 * s);
-            r.a1 = *reinterpret_cast<const float4 *>(q.in0 + in_at + 16 * s + 8);
-            if constexpr (MODE >= BWD_MID) {
-                r.b0 = *reinterpret_cast<const float4 *>(q.in1 + in_at + 16 * s);
-                r.b1 = *reinterpret_cast<const float4 *>(q.in1 + in_at + 16 * s + 8);
-            }
-        }
+        BnRows r{fp_row_kstep(q.in0 + in_at, s, live), FpQuads{z4, z4}};
+        if constexpr (MODE >= BWD_MID) r.b = fp_row_kstep(q.in1 + in_at, s, live);
         return r;
     };
     // the operand of k-step s formed on load: h_(l-1) = ReLU(a z + c), or gz_l = p (gy - k1) + q (z - mu); zeros in a padded row;
     // written to the workspace (the weight sums read it) when `keep`
     auto finish_rows = [&](const BnRows &r, int s, bool keep) {
         float v[8];
-        const float in0[8] = {r.a0.x, r.a0.y, r.a0.z, r.a0.w, r.a1.x, r.a1.y, r.a1.z, r.a1.w};
+        const float in0[8] = {r.a.a0.x, r.a.a0.y, r.a.a0.z, r.a.a0.w, r.a.a1.x, r.a.a1.y, r.a.a1.z, r.a.a1.w};
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             const int ch = 16 * s + 8 * half + 4 * h;
@@ -319,7 +155,7 @@ __global__ __launch_bounds__(THREADS, TMAX == 8 ? 1 : 2) void fpbn_pass_kernel(c
                     v[4 * half + i] = (live && y > 0.f) ? y : 0.f;
                 }
             } else {
-                const float in1[8] = {r.b0.x, r.b0.y, r.b0.z, r.b0.w, r.b1.x, r.b1.y, r.b1.z, r.b1.w};
+                const float in1[8] = {r.b.a0.x, r.b.a0.y, r.b.a0.z, r.b.a0.w, r.b.a1.x, r.b.a1.y, r.b.a1.z, r.b.a1.w};
                 const float4 k2 = *reinterpret_cast<const float4 *>(coef + 2 * a.cin + ch), k3 = *reinterpret_cast<const float4 *>(coef + 3 * a.cin + ch);
                 const float c2[4] = {k2.x, k2.y, k2.z, k2.w}, c3[4] = {k3.x, k3.y, k3.z, k3.w};
 #pragma unroll
@@ -332,38 +168,14 @@ __global__ __launch_bounds__(THREADS, TMAX == 8 ? 1 : 2) void fpbn_pass_kernel(c
         }
         return mcp_split8(v);
     };
-
-    // one k-step slab into every output tile of the bank
-    auto slab_into = [&](f32x16(&bank)[TMAX], int tiles, const McpSplit3 &xs, int next_tiles) {
-        const uint4 *w = begin_slab(tiles, next_tiles);
-#pragma unroll
-        for (int t = 0; t < TMAX; ++t)
-            if (t < tiles) bank[t] = mcp_mfma_split(w + t * TILE_U4, xs, bank[t]);
-        // As in fp_mlp_kernel: the wave-uniform branches around absent tiles leave paths on which a finished tile is moved between
-        // register files fewer than 12 wait states after its last MFMA; 16 idle issue slots after the slab's last MFMA cover them.
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_nop 15");
-        __builtin_amdgcn_sched_barrier(0);
-        end_slab();
-    };
-    // bank += image . rows over the pass's k-steps, the next k-step's quads in flight while this one is multiplied
+    // bank += image . rows over the pass's k-steps; `after`: the output tiles of the slab behind the product's last (0: none); in
+    // FWD_GATHER x is written on the way when the backward asks for it (q.side)
     auto product = [&](f32x16(&bank)[TMAX], int tiles, int after, bool keep) {
         if constexpr (MODE == FWD_GATHER) {
-            BnGather now = gather(0);
-#pragma unroll 1
-            for (int s = 0; s < a.ks; ++s) {
-                const BnGather nxt = gather(min(s + 1, a.ks - 1));  // the last k-step fetches itself again: no branch in the loop body
-                slab_into(bank, tiles, finish_gather(now, s), s + 1 == a.ks ? after : tiles);
-                now = nxt;
-            }
+            fp_ksteps(a.ks, [&](int s) { return gather.fetch(s); },
+                      [&](const FpGatherRaw &now, int s, bool last) { slabs.into(bank, tiles, gather.finish(now, s, q.side, p), last ? after : tiles); });
         } else {
-            BnRows now = load_rows(0);
-#pragma unroll 1
-            for (int s = 0; s < a.ks; ++s) {
-                const BnRows nxt = load_rows(min(s + 1, a.ks - 1));
-                slab_into(bank, tiles, finish_rows(now, s, keep), s + 1 == a.ks ? after : tiles);
-                now = nxt;
-            }
+            fp_ksteps(a.ks, load_rows, [&](const BnRows &now, int s, bool last) { slabs.into(bank, tiles, finish_rows(now, s, keep), last ? after : tiles); });
         }
     };
     // the workgroup's partials: the waves' entries of stat in wave order
@@ -374,18 +186,7 @@ __global__ __launch_bounds__(THREADS, TMAX == 8 ? 1 : 2) void fpbn_pass_kernel(c
     if constexpr (MODE == FWD_GATHER || MODE == FWD_ROWS) {
         // ---- z_l = W_l h_(l-1) + b_l; the statistics' partials ----
 #pragma unroll
-        for (int t = 0; t < TMAX; ++t) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) bank[t][r] = 0.f;
-            if (t < a.tiles) {
-                const float4 *bq = reinterpret_cast<const float4 *>(q.packed + a.bias_at + (t * 2 + h) * 16);
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const float4 v = bq[g];
-                    bank[t][4 * g + 0] = v.x; bank[t][4 * g + 1] = v.y; bank[t][4 * g + 2] = v.z; bank[t][4 * g + 3] = v.w;
-                }
-            }
-        }
+        for (int t = 0; t < TMAX; ++t) fp_bias_tile(bank[t], t, a.tiles, q.packed + a.bias_at);
         product(bank, a.tiles, 0, true);
         const int cnt = __popcll(__ballot(live) & 0xFFFFFFFFull);   // live rows of this wave
         const float inv = 1.0f / (float)max(cnt, 1);
@@ -430,11 +231,9 @@ __global__ __launch_bounds__(THREADS, TMAX == 8 ? 1 : 2) void fpbn_pass_kernel(c
         }
     } else if constexpr (MODE == BWD_MID) {
         // ---- gy_(l-1) = (W_l^T gz_l) . [y_(l-1) > 0]; the partials of sum gy_(l-1), sum gy_(l-1) zhat_(l-1) and sum (z_(l-1) - mu) ----
-#pragma unroll
-        for (int t = 0; t < TMAX; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) bank[t][r] = 0.f;
+        fp_zero_bank(bank);
         product(bank, a.tiles, 0, true);
+        fp_pin_bank(bank);
         const long long at = p * cout + 4 * h;
 #pragma unroll
         for (int t = 0; t < TMAX; ++t) {
@@ -473,37 +272,9 @@ __global__ __launch_bounds__(THREADS, TMAX == 8 ? 1 : 2) void fpbn_pass_kernel(c
 #pragma unroll 1
         for (int c0 = 0; c0 < a.tiles; c0 += TMAX) {
             const int tc = min(TMAX, a.tiles - c0);
-#pragma unroll
-            for (int t = 0; t < TMAX; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) bank[t][r] = 0.f;
+            fp_zero_bank(bank);
             product(bank, tc, min(TMAX, a.tiles - c0 - TMAX), c0 == 0);
-            if (inr) {
-#pragma unroll
-                for (int t = 0; t < TMAX; ++t) {
-                    if (t < tc) {
-#pragma unroll
-                        for (int g = 0; g < 4; ++g) {
-                            const int ch = 32 * (c0 + t) + 8 * g + 4 * h;
-                            const float v0 = bank[t][4 * g + 0], v1 = bank[t][4 * g + 1], v2 = bank[t][4 * g + 2], v3 = bank[t][4 * g + 3];
-                            if (ch < a.c2) {   // C2 is a multiple of 4: a quad lies on one side
-                                *reinterpret_cast<float4 *>(q.grad_blend + p * a.c2 + ch) = make_float4(v0, v1, v2, v3);
-                            } else {
-                                const int cs = ch - a.c2;
-                                float *gs = q.grad_skip + p * a.c1 + cs;
-                                if (skip_q) {
-                                    if (cs < a.c1) *reinterpret_cast<float4 *>(gs) = make_float4(v0, v1, v2, v3);
-                                } else {
-                                    if (cs + 0 < a.c1) gs[0] = v0;
-                                    if (cs + 1 < a.c1) gs[1] = v1;
-                                    if (cs + 2 < a.c1) gs[2] = v2;
-                                    if (cs + 3 < a.c1) gs[3] = v3;
-                                }
-                            }
-                        }
-                    }
-                }
-            }
+            if (inr) fp_store_dx(bank, c0, tc, p, a.c2, a.c1, q.grad_blend, q.grad_skip);
         }
     }
 }
@@ -662,27 +433,13 @@ __global__ __launch_bounds__(256) void fpbn_gy_last_kernel(long long total, int 
     }
 }
 
-template <int TMAX, bool STREAM, int MODE>
-int launch_pass(const BnArgs &a, const BnPtrs &q, hipStream_t s) {
-    auto kern = fpbn_pass_kernel<TMAX, STREAM, MODE>;
-    static McpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_once.done();
-    }
-    constexpr int LOADS = (TMAX * TILE_U4 + THREADS - 1) / THREADS;
-    const size_t lds = (size_t)(a.coef_floats + a.stat_floats) * sizeof(float) + (STREAM ? (size_t)2 * LOADS * THREADS * 16 : (size_t)a.pass_u4 * 16);
-    hipLaunchKernelGGL(kern, dim3((unsigned)((a.total + 32 * WAVES - 1) / (32 * WAVES))), dim3(THREADS), lds, s, a, q);
-    return mcp_launch_status();
-}
 template <int MODE>
 int launch_mode(int tmax, bool stream, const BnArgs &a, const BnPtrs &q, hipStream_t s) {
-#define BN_LAUNCH(T) return stream ? launch_pass<T, true, MODE>(a, q, s) : launch_pass<T, false, MODE>(a, q, s)
-    if (tmax == 2) BN_LAUNCH(2);
-    if (tmax == 4) BN_LAUNCH(4);
-    BN_LAUNCH(8);
-#undef BN_LAUNCH
+    return fp_dispatch(tmax, stream, [&](auto tm, auto stream_w) {
+        constexpr int T = decltype(tm)::value;
+        constexpr bool S = decltype(stream_w)::value;
+        return fp_launch<fpbn_pass_kernel<T, S, MODE>, T, S>(a.total, a.coef_floats + a.stat_floats, a.pass_u4, s, a, q);
+    });
 }
 
 // The caller-owned workspace: byte offsets of its parts, each 256-byte aligned.
@@ -691,12 +448,9 @@ struct BnLayout {
     size_t x, h1, h2, gy[MAX_LAYERS], gz[MAX_LAYERS], grad_blend, w_used, dw_slice, wgrad, wgrad_bytes;   // backward only
     size_t bytes;
 };
-constexpr int WGRAD_COLS = 256;   // mcp_linear_wgrad takes at most 256 x 256 outputs: layer 1 goes in column slices of x
-inline size_t bn_up(size_t v) { return (v + 255) & ~(size_t)255; }
 // false: mcp_linear_wgrad does not take one of the layers' products
 inline bool bn_layout(long long total, const FgShape &s, const int *widths, bool backward, BnLayout *l) {
-    size_t at = 0;
-    auto take = [&](size_t floats) { const size_t here = at; at += bn_up(floats * sizeof(float)); return here; };
+    FpTake take;
     const size_t rows = (size_t)total, groups = (size_t)((total + 32 * WAVES - 1) / (32 * WAVES));
     const int layers = s.f.layers;
     int widest = 0;
@@ -706,7 +460,7 @@ inline bool bn_layout(long long total, const FgShape &s, const int *widths, bool
     l->part = take(groups * 3 * widest);
     l->part_cnt = take(groups);
     l->count = take(1);
-    l->wgrad = at;
+    l->wgrad = take.at;
     l->wgrad_bytes = 0;
     if (backward) {
         l->x = take(rows * s.cin);
@@ -717,19 +471,11 @@ inline bool bn_layout(long long total, const FgShape &s, const int *widths, bool
         l->grad_blend = take(rows * s.f.c2);
         l->w_used = take(rows * 3);
         l->dw_slice = take(s.cin > WGRAD_COLS ? (size_t)widths[0] * WGRAD_COLS : 0);
-        size_t need = 0;
-        for (int i = 0; i < layers; ++i) {
-            const int k = i == 0 ? (s.cin < WGRAD_COLS ? s.cin : WGRAD_COLS) : widths[i - 1];
-            const size_t b = mcp_linear_wgrad_workspace_bytes(total, widths[i], k);
-            if (b == 0) return false;
-            if (b > need) need = b;
-        }
-        if (s.cin > WGRAD_COLS && s.cin % WGRAD_COLS && !mcp_linear_wgrad_workspace_bytes(total, widths[0], s.cin % WGRAD_COLS)) return false;
-        l->wgrad = at;
-        l->wgrad_bytes = need;
-        at += bn_up(need);
+        if (!fp_wgrad_bytes(total, s, widths, &l->wgrad_bytes)) return false;
+        l->wgrad = take.at;
+        take.at += FpTake::up(l->wgrad_bytes);
     }
-    l->bytes = at;
+    l->bytes = take.at;
     return true;
 }
 

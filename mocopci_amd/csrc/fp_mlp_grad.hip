@@ -28,7 +28,7 @@
 // the read.  Every layer is therefore the layer-1 loop again (layer_from_rows): a rolled loop over k-steps, the next k-step's two
 // quads in flight while this one is multiplied.
 //   Phase 1 is the forward: layer 1 from the gathered rows (x written on the way), then per layer ReLU(bank) -> h_l, biases into the
-//   bank, the k-steps of h_l back in.  Same image, same slab order, same six-product split as fp_mlp_kernel.
+//   bank, the k-steps of h_l back in.  Same image, same slab order, same six-product split as the forward (fp_mlp.hip).
 //   Phase 2: gz_L = g selected by [out > 0] in place of the last bank (the recomputed out written on the way); per layer the bank is
 //   zeroed, the k-steps of gz_l are multiplied with the image of W_l^T, and the result is selected by [h_(l-1) > 0] with h_(l-1) read
 //   back from the workspace -- no mask is kept in registers -- and written as gz_(l-1).  dx = W_1^T gz_1 has up to 24 output tiles:
@@ -47,16 +47,12 @@
 //
 // Built WITHOUT -fno-honor-nans: the masks and the ReLU are comparisons and selections, which need no canonicalisation, and a training
 // kernel should not be compiled under the assumption that no NaN arrives (a diverged run must show its NaN, not hide it).
-#include <math.h>
-
-#include "common.h"
-#include "mfma_split.h"
-#include "fp_mlp_shape.h"
+//
+// The row, the gather, the slab sequence, the tile helpers and the dx epilogue are fp_mlp_tile.h's, shared with fp_mlp.hip and
+// fp_mlp_bn.hip.
+#include "fp_mlp_tile.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 inline size_t fg_image_floats(const FgShape &s) { return ((size_t)s.f.w_u4 + s.bwd_u4) * 4 + s.f.small_floats; }
 
@@ -97,115 +93,27 @@ struct FgOut {
     float *x, *h1, *h2, *gz1, *gz2, *gz3, *grad_blend, *w_used, *grad_skip, *out;
 };
 
-struct FgRaw {  // what one input k-step of layer 1 reads: the two float4 of each of the three known rows, or of the skip row (in a*)
-    float4 a0, a1, b0, b1, c0, c1;
-};
-
 template <int TMAX, bool STREAM>
 __global__ __launch_bounds__(THREADS, 1) void fp_mlp_grad_kernel(const FgArgs a, const FgIn in, const FgOut o) {
-    constexpr int LOADS = (TMAX * TILE_U4 + THREADS - 1) / THREADS;
-    constexpr int BUF = LOADS * THREADS;  // uint4 of one LDS slab buffer: the widest slab rounded up to whole passes of the workgroup
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float *small = lds;                                               // biases
-    u32x4 *wl = reinterpret_cast<u32x4 *>(lds + a.small_floats);      // one phase's slabs, or [2][BUF]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, col = lane & 31;
+    float *small = lds;                                               // biases, then one phase's slabs or two slab buffers
+    const int tid = threadIdx.x, h = (tid & 63) >> 5;
     const u32x4 *gimg = reinterpret_cast<const u32x4 *>(in.packed);
-    const int small_u4 = a.small_floats / 4;
-
-    // ---- the slab sequence: begin_slab gives this lane's entry of the next slab, end_slab() releases it.  A streamed slab is fetched
-    // one slab ahead, so every call names the output tiles of the slab AFTER its own (0: none) and whether the biases, which lie
-    // between the forward and the backward slabs, come before it: both are known where the call stands, no walk of a table. ----
-    u32x4 pre[LOADS];                 // staging registers of the slab after the one being multiplied
-    const u32x4 *nxt_src = gimg;      // streamed: where the next slab to fetch starts
-    int cur = 0;
-    const u32x4 *wcur = wl;           // staged whole: the next slab in LDS
-#pragma unroll
-    for (int u = 0; u < LOADS; ++u) pre[u] = u32x4{0u, 0u, 0u, 0u};
-    auto fetch_slab = [&](int tiles, bool past_biases) {
-        if (tiles > 0) {
-            if (past_biases) nxt_src += small_u4;
-            const int n4 = tiles * TILE_U4;
-#pragma unroll
-            for (int u = 0; u < LOADS; ++u) pre[u] = nxt_src[min(tid + u * THREADS, n4 - 1)];  // entries past the slab repeat its last one, never used
-            nxt_src += n4;
-        }
-    };
-    auto stash = [&](int buf) {
-#pragma unroll
-        for (int u = 0; u < LOADS; ++u) wl[buf * BUF + tid + u * THREADS] = pre[u];
-    };
-    auto begin_slab = [&](int tiles, int next_tiles, bool past_biases) -> const uint4 * {
-        if constexpr (STREAM) {
-            fetch_slab(next_tiles, past_biases);
-            __syncthreads();  // the slab is complete in buffer cur; nobody reads buffer cur ^ 1 any more
-            return reinterpret_cast<const uint4 *>(wl + cur * BUF) + lane;
-        } else {
-            const u32x4 *w = wcur;
-            wcur += tiles * TILE_U4;
-            return reinterpret_cast<const uint4 *>(w) + lane;
-        }
-    };
-    auto end_slab = [&]() {
-        if constexpr (STREAM) {
-            stash(cur ^ 1);
-            cur ^= 1;
-        }
-    };
-
+    const int small_u4 = a.small_floats / 4;   // the biases lie between the forward and the backward slabs
+    FpSlabs<TMAX, STREAM> slabs;
     {
         const float4 *src = reinterpret_cast<const float4 *>(in.packed) + a.w_u4;
         for (int e = tid; e < small_u4; e += THREADS) reinterpret_cast<float4 *>(small)[e] = src[e];
-        if constexpr (STREAM) {
-            fetch_slab(a.t0, false);
-            stash(0);
-        } else {
-            for (int e = tid; e < a.w_u4; e += THREADS) wl[e] = gimg[e];
-        }
+        slabs.begin(reinterpret_cast<u32x4 *>(lds + a.small_floats), gimg, a.t0, a.w_u4);
     }
     __syncthreads();
 
-    // ---- this column's row: liveness, the three weights, the three known rows (as fp_mlp_kernel) ----
-    const long long p = ((long long)blockIdx.x * WAVES + wave) * 32 + col;
-    const bool inr = p < a.total;
-    const long long bb = inr ? mcp_div(p, a.n, mcp_fits32(a.total)) : 0;
-    bool live = inr;
-    if (inr && in.ulen) {
-        const int ul = min(max(in.ulen[bb], 0), a.n);
-        live = (int)(p - bb * a.n) < ul;
-    }
-    float w0 = 0.f, w1 = 0.f, w2 = 0.f;
-    bool u0 = false, u1 = false, u2 = false;  // the slot's row is read
-    const float *f0 = in.known_feats, *f1 = in.known_feats, *f2 = in.known_feats;
-    const float *srow = in.skip;
-    if (live) {
-        const int *ip = in.idx + p * 3;
-        const long long base = bb * a.m;
-        f0 = in.known_feats + (base + ip[0]) * a.c2;
-        f1 = in.known_feats + (base + ip[1]) * a.c2;
-        f2 = in.known_feats + (base + ip[2]) * a.c2;
-        if (a.c1) srow = in.skip + p * a.c1;
-        if (a.rule == 0) {
-            w0 = in.w3[p * 3 + 0]; w1 = in.w3[p * 3 + 1]; w2 = in.w3[p * 3 + 2];
-            u0 = u1 = u2 = true;
-        } else {
-            float d0 = in.dist[p * 3 + 0], d1 = in.dist[p * 3 + 1], d2 = in.dist[p * 3 + 2];
-            u0 = d0 < INFINITY; u1 = d1 < INFINITY; u2 = d2 < INFINITY;
-            if (a.rule == 1) {
-                d0 = d0 + 1e-8f; d1 = d1 + 1e-8f; d2 = d2 + 1e-8f;
-            } else {
-                d0 = d0 * d0; d1 = d1 * d1; d2 = d2 * d2;
-                d0 = d0 < 1e-10f ? 1e-10f : d0; d1 = d1 < 1e-10f ? 1e-10f : d1; d2 = d2 < 1e-10f ? 1e-10f : d2;
-            }
-            const float r0 = u0 ? 1.0f / d0 : 0.f, r1 = u1 ? 1.0f / d1 : 0.f, r2 = u2 ? 1.0f / d2 : 0.f;
-            const float sum = (r0 + r1) + r2;
-            const bool any = sum > 0.f;  // false: no known point at all -- zeros, not 0 / 0
-            w0 = any ? r0 / sum : 0.f; w1 = any ? r1 / sum : 0.f; w2 = any ? r2 / sum : 0.f;
-        }
-    }
-    if (inr && h == 0) {  // the weights the blend uses: an infinite slot holds an exact 0, a padded row three
-        float *wu = o.w_used + p * 3;
-        wu[0] = u0 ? w0 : 0.f; wu[1] = u1 ? w1 : 0.f; wu[2] = u2 ? w2 : 0.f;
-    }
+    const FpRow me(a.total, a.n, in.ulen);
+    const long long p = me.p;
+    const bool inr = me.inr, live = me.live;
+    FpGather g;
+    g.begin(me, a.m, a.c2, a.c1, a.rule, a.ksb, in.known_feats, in.skip, in.idx, in.dist, in.w3);
+    g.store_w_used(o.w_used, p);
     // The row index behind a compiler barrier: an address formed from it is formed where it is used.  Without it the compiler
     // forms the 64-bit row addresses of all eleven arrays at the top of the kernel and keeps them beside the bank.
     auto row = [&]() {
@@ -213,130 +121,15 @@ __global__ __launch_bounds__(THREADS, 1) void fp_mlp_grad_kernel(const FgArgs a,
         asm volatile("" : "+v"(q));
         return q;
     };
-    const bool skip_q = (a.c1 & 3) == 0;  // skip rows (and so the rows of x and grad_skip) are 16-byte aligned
-    const int cin = a.c2 + a.c1;
 
-    auto fetch = [&](int s) {
-        const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        FgRaw r{z4, z4, z4, z4, z4, z4};
-        if (s < a.ksb) {
-            const int ch0 = 16 * s + 4 * h, ch1 = ch0 + 8;
-            if (ch0 < a.c2) {
-                if (u0) r.a0 = *reinterpret_cast<const float4 *>(f0 + ch0);
-                if (u1) r.b0 = *reinterpret_cast<const float4 *>(f1 + ch0);
-                if (u2) r.c0 = *reinterpret_cast<const float4 *>(f2 + ch0);
-            }
-            if (ch1 < a.c2) {
-                if (u0) r.a1 = *reinterpret_cast<const float4 *>(f0 + ch1);
-                if (u1) r.b1 = *reinterpret_cast<const float4 *>(f1 + ch1);
-                if (u2) r.c1 = *reinterpret_cast<const float4 *>(f2 + ch1);
-            }
-        } else if (live) {
-            const int ch0 = 16 * (s - a.ksb) + 4 * h, ch1 = ch0 + 8;
-            if (skip_q) {
-                if (ch0 < a.c1) r.a0 = *reinterpret_cast<const float4 *>(srow + ch0);
-                if (ch1 < a.c1) r.a1 = *reinterpret_cast<const float4 *>(srow + ch1);
-            } else {
-                if (ch0 + 0 < a.c1) r.a0.x = srow[ch0 + 0];
-                if (ch0 + 1 < a.c1) r.a0.y = srow[ch0 + 1];
-                if (ch0 + 2 < a.c1) r.a0.z = srow[ch0 + 2];
-                if (ch0 + 3 < a.c1) r.a0.w = srow[ch0 + 3];
-                if (ch1 + 0 < a.c1) r.a1.x = srow[ch1 + 0];
-                if (ch1 + 1 < a.c1) r.a1.y = srow[ch1 + 1];
-                if (ch1 + 2 < a.c1) r.a1.z = srow[ch1 + 2];
-                if (ch1 + 3 < a.c1) r.a1.w = srow[ch1 + 3];
-            }
-        }
-        return r;
-    };
-    auto blend = [&](float fa, float fb, float fc) { return (w0 * fa + w1 * fb) + w2 * fc; };
-    // the 8 values of k-step s of x, written to the workspace on the way
-    auto finish = [&](const FgRaw &r, int s) {
-        float v[8];
-        const bool blended = s < a.ksb;
-        if (blended) {
-            v[0] = blend(r.a0.x, r.b0.x, r.c0.x); v[1] = blend(r.a0.y, r.b0.y, r.c0.y);
-            v[2] = blend(r.a0.z, r.b0.z, r.c0.z); v[3] = blend(r.a0.w, r.b0.w, r.c0.w);
-            v[4] = blend(r.a1.x, r.b1.x, r.c1.x); v[5] = blend(r.a1.y, r.b1.y, r.c1.y);
-            v[6] = blend(r.a1.z, r.b1.z, r.c1.z); v[7] = blend(r.a1.w, r.b1.w, r.c1.w);
-        } else {
-            v[0] = r.a0.x; v[1] = r.a0.y; v[2] = r.a0.z; v[3] = r.a0.w;
-            v[4] = r.a1.x; v[5] = r.a1.y; v[6] = r.a1.z; v[7] = r.a1.w;
-        }
-        if (inr) {
-            const int lim = blended ? a.c2 : a.c1;
-            const int loc = 16 * (blended ? s : s - a.ksb) + 4 * h;
-            float *xr = o.x + row() * cin + (blended ? 0 : a.c2);
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                const int lc = loc + 8 * half;
-                if (skip_q) {   // C2 and C1 multiples of 4: whole quads
-                    if (lc < lim) *reinterpret_cast<float4 *>(xr + lc) = make_float4(v[4 * half], v[4 * half + 1], v[4 * half + 2], v[4 * half + 3]);
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        if (lc + i < lim) xr[lc + i] = v[4 * half + i];
-                }
-            }
-        }
-        return mcp_split8(v);
-    };
-
-    auto zero_bank = [&](f32x16(&bank)[TMAX]) {
-#pragma unroll
-        for (int t = 0; t < TMAX; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) bank[t][r] = 0.f;
-    };
-    // tile t of the bank = its bias (zeros for an absent tile)
-    auto bias_tile = [&](f32x16 &tile, int t, int boff, int tiles) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) tile[r] = 0.f;
-        if (t < tiles) {
-            const float4 *bq = reinterpret_cast<const float4 *>(small + boff + (t * 2 + h) * 16);
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const float4 v = bq[g];
-                tile[4 * g + 0] = v.x; tile[4 * g + 1] = v.y; tile[4 * g + 2] = v.z; tile[4 * g + 3] = v.w;
-            }
-        }
-    };
-    // one k-step slab into every output tile of the bank
-    auto slab_into = [&](f32x16(&bank)[TMAX], int tiles, const McpSplit3 &xs, int next_tiles, bool past_biases) {
-        const uint4 *w = begin_slab(tiles, next_tiles, past_biases);
-#pragma unroll
-        for (int t = 0; t < TMAX; ++t)
-            if (t < tiles) bank[t] = mcp_mfma_split(w + t * TILE_U4, xs, bank[t]);
-        // As in fp_mlp_kernel: the wave-uniform branches around absent tiles leave paths on which a finished tile is moved between
-        // register files fewer than 12 wait states after its last MFMA; 16 idle issue slots after the slab's last MFMA cover them.
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_nop 15");
-        __builtin_amdgcn_sched_barrier(0);
-        end_slab();
-    };
-    // Rows of a (rows, 32 * tiles) array in accumulator order: register 4 g + j of tile t is channel 32 t + 8 g + 4 h + j (`row`
-    // points at channel 4 h of the lane's row).  K-step s of such a row -- registers 8 (s & 1) .. + 7 of tile s >> 1, what
-    // mcp_split_kstep takes -- is therefore the two quads at 16 s and 16 s + 8, written by this very lane.
-    auto store_tile = [&](float *row, int t, const f32x16 &v) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) *reinterpret_cast<float4 *>(row + 32 * t + 8 * g) = make_float4(v[4 * g + 0], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
-    };
     // bank += W . rows over `ks` k-steps of the lane's own row of a workspace array (h_l or gz_l, just written by this lane): the
-    // layer-1 loop again, the next k-step's two quads in flight while this one is multiplied.  Only one bank is ever live.
-    auto layer_from_rows = [&](f32x16(&bank)[TMAX], const float *row, int ks, int tiles, int after, bool past_biases) {
-        const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        float4 n0 = z4, n1 = z4;
-        if (inr) { n0 = *reinterpret_cast<const float4 *>(row); n1 = *reinterpret_cast<const float4 *>(row + 8); }
-#pragma unroll 1
-        for (int s = 0; s < ks; ++s) {
-            const int s2 = min(s + 1, ks - 1);   // the last k-step fetches itself again: no branch in the loop body
-            float4 m0 = z4, m1 = z4;
-            if (inr) { m0 = *reinterpret_cast<const float4 *>(row + 16 * s2); m1 = *reinterpret_cast<const float4 *>(row + 16 * s2 + 8); }
-            const float v[8] = {n0.x, n0.y, n0.z, n0.w, n1.x, n1.y, n1.z, n1.w};
-            const bool last = s + 1 == ks;
-            slab_into(bank, tiles, mcp_split8(v), last ? after : tiles, last && past_biases);
-            n0 = m0; n1 = m1;
-        }
+    // layer-1 loop again.  Only one bank is ever live.  `after`, `skip_u4`: the slab behind the last one of this product.
+    auto layer_from_rows = [&](f32x16(&bank)[TMAX], const float *rows, int ks, int tiles, int after, int skip_u4) {
+        fp_ksteps(ks, [&](int s) { return fp_row_kstep(rows, s, inr); },
+                  [&](const FpQuads &n, int, bool last) {
+                      const float v[8] = {n.a0.x, n.a0.y, n.a0.z, n.a0.w, n.a1.x, n.a1.y, n.a1.z, n.a1.w};
+                      slabs.into(bank, tiles, mcp_split8(v), last ? after : tiles, last ? skip_u4 : 0);
+                  });
     };
     // forward layer l >= 2: h_(l-1) = ReLU(bank) to the workspace, then the bank is the next layer's
     auto next_layer = [&](f32x16(&bank)[TMAX], int tin, int tout, int boff, float *hl, int after, bool last_forward) {
@@ -347,12 +140,12 @@ __global__ __launch_bounds__(THREADS, 1) void fp_mlp_grad_kernel(const FgArgs a,
                 f32x16 r = bank[t];
 #pragma unroll
                 for (int i = 0; i < 16; ++i) r[i] = r[i] > 0.f ? r[i] : 0.f;
-                store_tile(hrow, t, r);
+                fp_store_tile(hrow, t, r);
             }
         }
 #pragma unroll
-        for (int t = 0; t < TMAX; ++t) bias_tile(bank[t], t, boff, tout);
-        layer_from_rows(bank, hrow, 2 * tin, tout, after, last_forward);
+        for (int t = 0; t < TMAX; ++t) fp_bias_tile(bank[t], t, tout, small + boff);
+        layer_from_rows(bank, hrow, 2 * tin, tout, after, last_forward ? small_u4 : 0);
     };
     // gz_L = g selected by [out > 0], written to the workspace; the recomputed out on the way
     auto grad_last = [&](f32x16(&bank)[TMAX], int tiles, float *gz) {
@@ -362,72 +155,59 @@ __global__ __launch_bounds__(THREADS, 1) void fp_mlp_grad_kernel(const FgArgs a,
             if (t < tiles && inr) {
                 f32x16 outv, gzv;
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
+                for (int g4 = 0; g4 < 4; ++g4) {
                     float4 gv = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (live) gv = *reinterpret_cast<const float4 *>(in.grad_out + at + 32 * t + 8 * g);
+                    if (live) gv = *reinterpret_cast<const float4 *>(in.grad_out + at + 32 * t + 8 * g4);
                     const float gq[4] = {gv.x, gv.y, gv.z, gv.w};
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        const float v = bank[t][4 * g + j];
+                        const float v = bank[t][4 * g4 + j];
                         const bool pos = v > 0.f;
-                        outv[4 * g + j] = (pos && live) ? v : 0.f;
-                        gzv[4 * g + j] = pos ? gq[j] : 0.f;
+                        outv[4 * g4 + j] = (pos && live) ? v : 0.f;
+                        gzv[4 * g4 + j] = pos ? gq[j] : 0.f;
                     }
                 }
-                store_tile(gz + at, t, gzv);
-                if (o.out) store_tile(o.out + at, t, outv);
+                fp_store_tile(gz + at, t, gzv);
+                if (o.out) fp_store_tile(o.out + at, t, outv);
                 __builtin_amdgcn_sched_barrier(0);   // one tile's rows of g in flight, not the whole bank's
             }
         }
     };
     // gz_(l-1) = (W_l^T gz_l) selected by [h_(l-1) > 0] (h_(l-1) read back from the workspace), written to the workspace
     auto back_layer = [&](f32x16(&bank)[TMAX], const float *gz_in, int tin, int tout, const float *hl, float *gz_out, int after) {
-        zero_bank(bank);
-        layer_from_rows(bank, gz_in + row() * (tin * 32) + 4 * h, 2 * tin, tout, after, false);
+        fp_zero_bank(bank);
+        layer_from_rows(bank, gz_in + row() * (tin * 32) + 4 * h, 2 * tin, tout, after, 0);
         const long long at = row() * (tout * 32) + 4 * h;
 #pragma unroll
         for (int t = 0; t < TMAX; ++t) {
             if (t < tout && inr) {
                 f32x16 v = bank[t];
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const float4 hv = *reinterpret_cast<const float4 *>(hl + at + 32 * t + 8 * g);
-                    v[4 * g + 0] = hv.x > 0.f ? v[4 * g + 0] : 0.f;
-                    v[4 * g + 1] = hv.y > 0.f ? v[4 * g + 1] : 0.f;
-                    v[4 * g + 2] = hv.z > 0.f ? v[4 * g + 2] : 0.f;
-                    v[4 * g + 3] = hv.w > 0.f ? v[4 * g + 3] : 0.f;
+                for (int g4 = 0; g4 < 4; ++g4) {
+                    const float4 hv = *reinterpret_cast<const float4 *>(hl + at + 32 * t + 8 * g4);
+                    v[4 * g4 + 0] = hv.x > 0.f ? v[4 * g4 + 0] : 0.f;
+                    v[4 * g4 + 1] = hv.y > 0.f ? v[4 * g4 + 1] : 0.f;
+                    v[4 * g4 + 2] = hv.z > 0.f ? v[4 * g4 + 2] : 0.f;
+                    v[4 * g4 + 3] = hv.w > 0.f ? v[4 * g4 + 3] : 0.f;
                 }
-                store_tile(gz_out + at, t, v);
+                fp_store_tile(gz_out + at, t, v);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
     };
 
     f32x16 bank[TMAX];
-    // ---- phase 1, layer 1: input k-steps from memory ----
+    // ---- phase 1, layer 1: input k-steps from memory, x written to the workspace on the way ----
     const int dx_first = min(TMAX, a.dxt);   // output tiles of the first chunk of dx
     const int after1 = a.layers == 1 ? dx_first : a.t1;
 #pragma unroll
-    for (int t = 0; t < TMAX; ++t) bias_tile(bank[t], t, 0, a.t0);
-    {
-        FgRaw now = fetch(0);
-#pragma unroll 1
-        for (int s = 0; s < a.ks0; ++s) {
-            const FgRaw nxt = fetch(min(s + 1, a.ks0 - 1));  // the last k-step fetches itself again: no branch in the loop body
-            const bool last = s + 1 == a.ks0;
-            slab_into(bank, a.t0, finish(now, s), last ? after1 : a.t0, last && a.layers == 1);
-            now = nxt;
-        }
-    }
-    auto phase_two = [&]() {
-        if constexpr (!STREAM) {  // the backward slabs take the forward slabs' place
-            __syncthreads();
-            const u32x4 *gb = gimg + a.w_u4 + small_u4;
-            for (int e = tid; e < a.bwd_u4; e += THREADS) wl[e] = gb[e];
-            __syncthreads();
-            wcur = wl;
-        }
-    };
+    for (int t = 0; t < TMAX; ++t) fp_bias_tile(bank[t], t, a.t0, small);
+    fp_ksteps(a.ks0, [&](int s) { return g.fetch(s); },
+              [&](const FpGatherRaw &now, int s, bool last) {
+                  slabs.into(bank, a.t0, g.finish(now, s, o.x, row()), last ? after1 : a.t0, last && a.layers == 1 ? small_u4 : 0);
+              });
+    // the backward slabs take the forward slabs' place
+    auto phase_two = [&]() { slabs.restage(gimg + a.w_u4 + small_u4, a.bwd_u4); };
     // ---- the rest of phase 1, then phase 2: gz_L, back through the layers to gz_1 ----
     if (a.layers == 1) {
         phase_two();
@@ -446,71 +226,24 @@ __global__ __launch_bounds__(THREADS, 1) void fp_mlp_grad_kernel(const FgArgs a,
         back_layer(bank, o.gz2, a.t1, a.t0, o.h1, o.gz1, dx_first);
     }
 
-    // ---- dx = W_1^T gz_1 in chunks of TMAX output tiles: grad_blend | grad_skip ----
+    // ---- dx = W_1^T gz_1 in chunks of TMAX output tiles, each from the k-steps of gz_1 again ----
     const float *g1row = o.gz1 + row() * (a.t0 * 32) + 4 * h;
 #pragma unroll 1
     for (int c0 = 0; c0 < a.dxt; c0 += TMAX) {
         const int tc = min(TMAX, a.dxt - c0);
-        zero_bank(bank);
-        layer_from_rows(bank, g1row, 2 * a.t0, tc, min(TMAX, a.dxt - c0 - TMAX), false);
-        if (inr) {
-            const long long q = row();
-#pragma unroll
-            for (int t = 0; t < TMAX; ++t) {
-                if (t < tc) {
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const int ch = 32 * (c0 + t) + 8 * g + 4 * h;
-                        const float v0 = bank[t][4 * g + 0], v1 = bank[t][4 * g + 1], v2 = bank[t][4 * g + 2], v3 = bank[t][4 * g + 3];
-                        if (ch < a.c2) {   // C2 is a multiple of 4: a quad lies on one side
-                            *reinterpret_cast<float4 *>(o.grad_blend + q * a.c2 + ch) = make_float4(v0, v1, v2, v3);
-                        } else {
-                            const int cs = ch - a.c2;
-                            float *gs = o.grad_skip + q * a.c1 + cs;
-                            if (skip_q) {
-                                if (cs < a.c1) *reinterpret_cast<float4 *>(gs) = make_float4(v0, v1, v2, v3);
-                            } else {
-                                if (cs + 0 < a.c1) gs[0] = v0;
-                                if (cs + 1 < a.c1) gs[1] = v1;
-                                if (cs + 2 < a.c1) gs[2] = v2;
-                                if (cs + 3 < a.c1) gs[3] = v3;
-                            }
-                        }
-                    }
-                }
-            }
-        }
+        fp_zero_bank(bank);
+        layer_from_rows(bank, g1row, 2 * a.t0, tc, min(TMAX, a.dxt - c0 - TMAX), 0);
+        if (inr) fp_store_dx(bank, c0, tc, row(), a.c2, a.c1, o.grad_blend, o.grad_skip);
     }
-}
-
-template <int TMAX, bool STREAM>
-int launch_fp_mlp_grad(const FgArgs &a, const FgIn &in, const FgOut &o, hipStream_t s) {
-    auto kern = fp_mlp_grad_kernel<TMAX, STREAM>;
-    static McpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_once.done();
-    }
-    constexpr int LOADS = (TMAX * TILE_U4 + THREADS - 1) / THREADS;
-    const int widest_u4 = a.w_u4 > a.bwd_u4 ? a.w_u4 : a.bwd_u4;
-    const size_t lds = (size_t)a.small_floats * sizeof(float) + (STREAM ? (size_t)2 * LOADS * THREADS * 16 : (size_t)widest_u4 * 16);
-    const long long grid = (a.total + 32 * WAVES - 1) / (32 * WAVES);
-    if (grid > 0x7FFFFFFFLL) return MCP_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(THREADS), lds, s, a, in, o);
-    return mcp_launch_status();
 }
 
 // The caller-owned workspace: byte offsets of its parts, each 256-byte aligned.
 struct FgLayout {
     size_t x, h1, h2, gz[MAX_LAYERS], grad_blend, w_used, dw_slice, wgrad, wgrad_bytes, bytes;
 };
-constexpr int WGRAD_COLS = 256;   // mcp_linear_wgrad takes at most 256 x 256 outputs: layer 1 goes in column slices of x
-inline size_t fg_up(size_t v) { return (v + 255) & ~(size_t)255; }
 // false: mcp_linear_wgrad does not take one of the layers' products
 inline bool fg_layout(long long total, const FgShape &s, const int *widths, FgLayout *l) {
-    size_t at = 0;
-    auto take = [&](size_t floats) { const size_t here = at; at += fg_up(floats * sizeof(float)); return here; };
+    FpTake take;
     const size_t rows = (size_t)total;
     l->x = take(rows * s.cin);
     l->h1 = take(s.f.layers >= 2 ? rows * widths[0] : 0);
@@ -519,17 +252,9 @@ inline bool fg_layout(long long total, const FgShape &s, const int *widths, FgLa
     l->grad_blend = take(rows * s.f.c2);
     l->w_used = take(rows * 3);
     l->dw_slice = take(s.cin > WGRAD_COLS ? (size_t)widths[0] * WGRAD_COLS : 0);
-    size_t need = 0;
-    for (int i = 0; i < s.f.layers; ++i) {
-        const int k = i == 0 ? (s.cin < WGRAD_COLS ? s.cin : WGRAD_COLS) : widths[i - 1];
-        const size_t b = mcp_linear_wgrad_workspace_bytes(total, widths[i], k);
-        if (b == 0) return false;
-        if (b > need) need = b;
-    }
-    if (s.cin > WGRAD_COLS && s.cin % WGRAD_COLS && !mcp_linear_wgrad_workspace_bytes(total, widths[0], s.cin % WGRAD_COLS)) return false;
-    l->wgrad = at;
-    l->wgrad_bytes = need;
-    l->bytes = at + fg_up(need);
+    if (!fp_wgrad_bytes(total, s, widths, &l->wgrad_bytes)) return false;
+    l->wgrad = take.at;
+    l->bytes = take.at + FpTake::up(l->wgrad_bytes);
     return true;
 }
 
@@ -606,13 +331,11 @@ MCP_EXPORT int mcp_fp_mlp_grad(int b, int n, int m, int c2, int c1, int rule, in
     const FgIn in{known_feats, skip, dist, w3, packed, grad_out, idx, ulen};
     const FgOut o{x, hid[0], hid[1], gz[0], gz[1], gz[2], grad_blend, w_used, grad_skip, out};
     hipStream_t s = (hipStream_t)stream;
-    const bool whole = fg_whole(sh);
-    int rc;
-#define FG_LAUNCH(T) rc = whole ? launch_fp_mlp_grad<T, false>(a, in, o, s) : launch_fp_mlp_grad<T, true>(a, in, o, s)
-    if (f.tmax == 2) FG_LAUNCH(2);
-    else if (f.tmax == 4) FG_LAUNCH(4);
-    else FG_LAUNCH(8);
-#undef FG_LAUNCH
+    int rc = fp_dispatch(f.tmax, !fg_whole(sh), [&](auto tmax, auto stream_w) {
+        constexpr int T = decltype(tmax)::value;
+        constexpr bool S = decltype(stream_w)::value;
+        return fp_launch<fp_mlp_grad_kernel<T, S>, T, S>(total, a.small_floats, a.w_u4 > a.bwd_u4 ? a.w_u4 : a.bwd_u4, s, a, in, o);
+    });
     if (rc != MCP_OK) return rc;
 
     // the blend's scatter: every destination row's addends in ascending position 3 p + j

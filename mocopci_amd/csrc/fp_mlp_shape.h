@@ -1,7 +1,9 @@
 // fp_mlp_shape.h -- the shape arithmetic of the fused feature-propagation layer, shared by its forward (fp_mlp.hip), its backward
-// (fp_mlp_grad.hip) and its training-mode BatchNorm form (fp_mlp_bn.hip): which shapes are built, the k-steps and output tiles of every layer, the size of the forward weight image and
-// the register class.  Host code only.
+// (fp_mlp_grad.hip) and its training-mode BatchNorm form (fp_mlp_bn.hip): which shapes are built, the k-steps and output tiles of
+// every layer, the size of the forward weight image, the register class, and how a caller-owned workspace is laid out.  Host code
+// only; the device code and the launch code the three units share are in fp_mlp_tile.h, which includes this header.
 #pragma once
+#include "common.h"
 
 namespace {
 
@@ -73,5 +75,31 @@ inline bool fg_shape(int c2, int c1, int layers, const int *widths, FgShape *s) 
 // the staging predicate, a function of (c2, c1, widths) alone (ops.fp_mlp_grad_weights_in_lds mirrors it)
 inline bool fg_whole(const FgShape &s) {
     return (size_t)s.f.w_u4 * 16 <= (size_t)LDS_IMAGE_BYTES && (size_t)s.bwd_u4 * 16 <= (size_t)LDS_IMAGE_BYTES;
+}
+
+// ---- the caller-owned workspace of the training entry points: take(floats) gives the byte offset of the next part, each part
+// 256-byte aligned; `at` is the offset behind the parts taken so far ----
+struct FpTake {
+    size_t at = 0;
+    static size_t up(size_t v) { return (v + 255) & ~(size_t)255; }
+    size_t operator()(size_t floats) {
+        const size_t here = at;
+        at += up(floats * sizeof(float));
+        return here;
+    }
+};
+constexpr int WGRAD_COLS = 256;   // mcp_linear_wgrad takes at most 256 x 256 outputs: layer 1 goes in column slices of x
+// the largest workspace mcp_linear_wgrad asks for over the layers' products; false: it does not take one of them
+inline bool fp_wgrad_bytes(long long total, const FgShape &s, const int *widths, size_t *bytes) {
+    size_t need = 0;
+    for (int i = 0; i < s.f.layers; ++i) {
+        const int k = i == 0 ? (s.cin < WGRAD_COLS ? s.cin : WGRAD_COLS) : widths[i - 1];
+        const size_t b = mcp_linear_wgrad_workspace_bytes(total, widths[i], k);
+        if (b == 0) return false;
+        if (b > need) need = b;
+    }
+    if (s.cin > WGRAD_COLS && s.cin % WGRAD_COLS && !mcp_linear_wgrad_workspace_bytes(total, widths[0], s.cin % WGRAD_COLS)) return false;
+    *bytes = need;
+    return true;
 }
 }  // namespace

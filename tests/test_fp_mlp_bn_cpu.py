@@ -17,11 +17,16 @@ from tests.test_fp_mlp_grad_cpu import C_CAP, case, case_id
 # the GPU cases (tests/test_fp_mlp_bn_gpu.py): an image staged whole in LDS, three layers, a streamed wide shape
 CASES = [case(64, 3, [64, 64]), case(128, 4, [128, 128, 128]), case(256, 64, [256, 128])]
 SMALL = [case(64, 3, [64, 64], b, n) for b, n in ((1, 5), (2, 64))]
+# The instantiations fpbn_pass_kernel<TMAX, STREAM, MODE> that the cases above do not reach (they run <2, false>, <4, true> and
+# <8, true> in all four modes): <4, false>, <8, false> and <2, true>.  Each case has two layers, so that it runs all four modes
+# (FWD_ROWS and BWD_MID need a second layer), at 2 x 65 rows (two workgroups, a tile that straddles two elements).
+CLASSES = [case(4, 3, [64, 128], 2, 65), case(4, 3, [32, 256], 2, 65), case(512, 256, [64, 64], 2, 65)]
 LENGTHS = (70, 33, 0)
 OFFSET = 100.0
 # every (case, rule, offset, biased, lengths) the GPU tests pick
 PICKS = ([(k, "pointnet2", 0.0, True, None) for k in CASES + SMALL] + [(CASES[0], r, 0.0, True, None) for r in ("flownet3d", "given")] +
-         [(CASES[0], "pointnet2", OFFSET, False, None), (CASES[0], "pointnet2", 0.0, True, LENGTHS)])
+         [(CASES[0], "pointnet2", OFFSET, False, None), (CASES[0], "pointnet2", 0.0, True, LENGTHS)] +
+         [(k, "pointnet2", 0.0, True, None) for k in CLASSES])
 
 
 def composed(prep, l64):

@@ -22,7 +22,7 @@ import torch
 from mocopci_amd import _lib, ops, pointnet2_utils as pu
 from tests import fp_mlp_bn_reference as fbr
 from tests import fused_reference as fr
-from tests.test_fp_mlp_bn_cpu import CASES, LENGTHS, OFFSET, SMALL, composed
+from tests.test_fp_mlp_bn_cpu import CASES, CLASSES, LENGTHS, OFFSET, SMALL, composed
 from tests.test_fp_mlp_grad_cpu import B, C_CAP, N, case_id
 
 pytestmark = pytest.mark.gpu
@@ -33,6 +33,9 @@ NAN = float("nan")
 # rows, grad_skip; the fp32 composition on the same inputs: 1.08e-06), 6.38e-07 through the module against its composition; twice
 # that is 1.58e-06, between 2^-20 = 9.5e-07 and 2^-19 = 1.9e-06.  The cancellation case (|mu_1| about 127 sigma_1) measures 4.13e-05
 # at its worst (w2; the fp32 composition: 7.15e-04 on w1, 6.51e-05 on gamma2): twice that lies between 2^-14 and 2^-13, the cap.
+# The cases added later for the instantiations no other case runs (CLASSES) are held to the same 2^-19, which was not widened for them:
+# their worst is 9.73e-07 (c512+256-64x64 at 2 x 65 rows, w2, 768 input channels; the fp32 composition there: 1.32e-06), 1.96 x below;
+# c4+3-32x256 has the largest db against the floor 2e-5: 1.96e-05 (b1).
 C_FP_MLP_BN = 2.0 ** -19
 C_FP_MLP_BN_CANCELLATION = 2.0 ** -13
 assert C_FP_MLP_BN <= C_FP_MLP_BN_CANCELLATION <= C_CAP
@@ -124,7 +127,7 @@ def test_fp_mlp_bn_matches_float64(case_, nan_buffers):
     check_case(case_, "pointnet2")
 
 
-@pytest.mark.parametrize("case_", SMALL, ids=case_id)
+@pytest.mark.parametrize("case_", SMALL + CLASSES, ids=case_id)   # CLASSES: the instantiations that CASES and SMALL do not reach
 def test_fp_mlp_bn_partial_wave_and_full_workgroup(case_, nan_buffers):
     check_case(case_, "pointnet2")
 
