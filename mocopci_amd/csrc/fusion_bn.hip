@@ -6,8 +6,8 @@
 // model.py:fusion_batch_stats) materialises the (rows, 64 | 64 | 128) activations -- 1 / 1 / 2 GiB per tensor per call at B = 8,
 // N = 8192.  Here every pass re-evaluates what it needs in the fused forward's MFMA layout (one wave per point, neighbours on the MFMA
 // column), and a pass ends where the next quantity needs a reduction over all rows:
-//   forward    S1, S2, S3: statistics of z1, z2, z3 (sums of W h and (W h)^2: the conv bias is the shift that keeps the variance's
-//              cancellation small); F: the layer with all three (mean, 1/sigma) known -> out.
+//   forward    S1, S2, S3: statistics of z1, z2, z3 (sums of z - s and (z - s)^2: the shift s, the layer's conv output at the call's first
+//              row, keeps the variance's cancellation small); F: the layer with all three (mean, 1/sigma) known -> out.
 //   backward   B1: the forward with arg-max channel, softmax and ds per neighbour -> per-row (c*, dy3', a_j) and sum dy3', sum dy3' zhat3;
 //              B2: dz3 (dense: the mean terms reach every channel), dW3, dh2 -> dy2' (stored), sum dy2', sum dy2' zhat2;
 //              B3: dz2, dW2, dh1 -> dy1' (stored), its two sums;   B4: dz1, dW1, dx0 -> d_nb, d_p1.
@@ -92,25 +92,70 @@ __device__ __forceinline__ void bn_tile(const float *at, const f32x16 &z, f32x16
     }
 }
 
-// layer 1 pre-activation tile t: W1 [r, |r|] (+ conv bias unless RAW)
-template <bool RAW>
+// layer 1 pre-activation tile t: W1 [r, |r|] + what is staged as its conv bias
 __device__ __forceinline__ f32x16 layer1_tile(const float *lds, int t, int h, int lane, float in0, float in1) {
     f32x16 acc;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = RAW ? 0.f : lds[L_B1 + (t * 2 + h) * 16 + r];
+    for (int r = 0; r < 16; ++r) acc[r] = lds[L_B1 + (t * 2 + h) * 16 + r];
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(lds[L_W1 + (t * 2 + 0) * 64 + lane], in0, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(lds[L_W1 + (t * 2 + 1) * 64 + lane], in1, acc, 0, 0, 0);
     return acc;
 }
-template <bool RAW>
 __device__ __forceinline__ f32x16 bias_tile(const float *lds, int off) {
     f32x16 acc;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = RAW ? 0.f : lds[off + r];
+    for (int r = 0; r < 16; ++r) acc[r] = lds[off + r];
     return acc;
 }
 
-// MODE 1 / 2 / 3: sums of W h and (W h)^2 of layer MODE over all rows (partial[blockIdx][2 C]); MODE 0: the layer -> out (B,N,3).
+// The conv output z of layer L (bias included) of one 32-neighbour tile, through the BatchNorms of the layers before it: z[0 .. 1]
+// (L = 1, 2) or z[0 .. 3] (L = 3).  What a statistics pass evaluates once, at the call's first row, for its shift.
+template <int L>
+__device__ __forceinline__ void conv_tiles(const float *lds, const uint4 *w2s, const uint4 *w3s, int lane, int h, float in0, float in1, f32x16 *z) {
+    McpSplit3 x1[4], x2[4];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const f32x16 z1 = layer1_tile(lds, t, h, lane, in0, in1);
+        if (L == 1) {
+            z[t] = z1;
+            continue;
+        }
+        f32x16 zh, v;
+        bn_tile<C1>(lds + L_BN1 + (t * 2 + h) * 16, z1, zh, v);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) v[r] = fmaxf(v[r], 0.f);
+        x1[2 * t + 0] = mcp_split_kstep(v, 0);
+        x1[2 * t + 1] = mcp_split_kstep(v, 1);
+    }
+    if (L == 1) return;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        f32x16 z2 = bias_tile(lds, L_B2 + (t * 2 + h) * 16);
+        z2 = mcp_tile_split<4>(w2s + (size_t)t * 4 * 3 * 64 + lane, x1, z2);
+        if (L == 2) {
+            z[t] = z2;
+            continue;
+        }
+        f32x16 zh, v;
+        bn_tile<C2>(lds + L_BN2 + (t * 2 + h) * 16, z2, zh, v);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) v[r] = fmaxf(v[r], 0.f);
+        x2[2 * t + 0] = mcp_split_kstep(v, 0);
+        x2[2 * t + 1] = mcp_split_kstep(v, 1);
+    }
+    if (L == 2) return;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        f32x16 z3 = bias_tile(lds, L_B3 + (t * 2 + h) * 16);
+        z[t] = mcp_tile_split<4>(w3s + (size_t)t * 4 * 3 * 64 + lane, x2, z3);
+    }
+}
+
+// MODE 1 / 2 / 3: sums of z - s and (z - s)^2 of layer MODE over all rows (partial[blockIdx][2 C]), s = the layer's conv output at the
+// call's first row (point 0, its first neighbour): every workgroup evaluates that row itself, with the same instructions on the same
+// data and so to the same bits, puts b - s where the conv bias was staged, and workgroup 0 leaves s in shift_out for
+// fusion_bn_stats_kernel.  A row of the data is a few standard deviations from the mean wherever the conv bias is, so the variance's
+// cancellation S2 / R - (S1 / R)^2 stays small.  MODE 0: the layer -> out (B,N,3).
 // SAVE (MODE 0): also every neighbour's score (the maximum over the channels of the layer-3 output, floored at 0), the channel it sits at
 // and zhat3 there -- what the backward's first pass (fusion_bn_b1_kernel) re-evaluates the whole layer for; with them it is a light
 // kernel (fusion_bn_b1_saved_kernel).  The maximum is tracked exactly as that pass does (strict >, lowest channel among equals).
@@ -121,7 +166,8 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fusion_bn_fwd_kernel(long long 
                                                                    const float *__restrict__ w2, const float *__restrict__ b2,
                                                                    const float *__restrict__ w3, const float *__restrict__ b3,
                                                                    const float *__restrict__ bn, float *__restrict__ out, int *__restrict__ save_c,
-                                                                   float *__restrict__ save_z, float *__restrict__ save_s) {
+                                                                   float *__restrict__ save_z, float *__restrict__ save_s,
+                                                                   float *__restrict__ shift_out) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     uint4 *w2s = reinterpret_cast<uint4 *>(lds + L_F32);
     uint4 *w3s = w2s + W2_U4;
@@ -133,6 +179,28 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fusion_bn_fwd_kernel(long long 
 
     const int lane = tid & 63, wave = tid >> 6, h = lane >> 5, col = lane & 31;
     constexpr int ST = MODE == 3 ? 4 : (MODE == 0 ? 1 : 2);  // statistics tiles
+    if constexpr (MODE != 0) {
+        // the shift: wave 0 evaluates the first tile of point 0 (total >= 1) and its column 0 replaces the staged conv bias b by b - s
+        constexpr int L_BM = MODE == 1 ? L_B1 : (MODE == 2 ? L_B2 : L_B3);
+        if (wave == 0) {
+            const float *q = p2 + (long long)idx[col] * 3;  // row col of point 0's first list, in batch element 0
+            const float rx = q[0] - p1[0], ry = q[1] - p1[1], rz = q[2] - p1[2];
+            const float dist = sqrtf((rx * rx + ry * ry) + rz * rz);
+            f32x16 z[ST];
+            conv_tiles<MODE>(lds, w2s, w3s, lane, h, h ? ry : rx, h ? dist : rz, z);
+            if (col == 0) {
+#pragma unroll
+                for (int t = 0; t < ST; ++t)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int e = (t * 2 + h) * 16 + r;
+                        lds[L_BM + e] -= z[t][r];
+                        if (blockIdx.x == 0) shift_out[acc_to_channel(e)] = z[t][r];
+                    }
+            }
+        }
+        __syncthreads();
+    }
     f32x16 s1[ST], s2[ST];
 #pragma unroll
     for (int t = 0; t < ST; ++t)
@@ -156,7 +224,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fusion_bn_fwd_kernel(long long 
             McpSplit3 x1[4];
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                const f32x16 z1 = layer1_tile<MODE == 1>(lds, t, h, lane, in0, in1);
+                const f32x16 z1 = layer1_tile(lds, t, h, lane, in0, in1);
                 if (MODE == 1) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) { s1[MODE == 1 ? t : 0][r] += z1[r]; s2[MODE == 1 ? t : 0][r] = __builtin_fmaf(z1[r], z1[r], s2[MODE == 1 ? t : 0][r]); }
@@ -173,7 +241,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fusion_bn_fwd_kernel(long long 
             McpSplit3 x2[4];
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                f32x16 z2 = bias_tile<MODE == 2>(lds, L_B2 + (t * 2 + h) * 16);
+                f32x16 z2 = bias_tile(lds, L_B2 + (t * 2 + h) * 16);
                 z2 = mcp_tile_split<4>(w2s + (size_t)t * 4 * 3 * 64 + lane, x1, z2);
                 if (MODE == 2) {
 #pragma unroll
@@ -192,7 +260,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fusion_bn_fwd_kernel(long long 
             int mr = 0;
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
-                f32x16 z3 = bias_tile<MODE == 3>(lds, L_B3 + (t * 2 + h) * 16);
+                f32x16 z3 = bias_tile(lds, L_B3 + (t * 2 + h) * 16);
                 z3 = mcp_tile_split<4>(w3s + (size_t)t * 4 * 3 * 64 + lane, x2, z3);
                 if (MODE == 3) {
 #pragma unroll
@@ -270,13 +338,14 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fusion_bn_fwd_kernel(long long 
     }
 }
 
-// mean = b + S1 / R, var = S2 / R - (S1 / R)^2 (biased), rstd = 1 / sqrt(var + eps): written into the bn vector; var also to var_out.
-// S1, S2 are sums of (z - b) and (z - b)^2 (the conv bias is the shift).  The workgroup partials (fp32, each lane's own short chain)
-// are added HERE in double, in fixed order, and the subtraction is done in double: the error of var is then the fp32 rounding of
-// the partials, ~1e-7 (mean - b)^2 -- a channel whose conv output sits 300 standard deviations away from its bias still gets its
-// variance to 1 %; beyond ~3000 the estimate degrades (torch's two-pass var does not).  (the partial sums used to be
-// added in fp32 as well, which lost another factor of the number of workgroups.)
-__global__ __launch_bounds__(256) void fusion_bn_stats_kernel(const float *__restrict__ partial, int parts, int c, double rows, const float *__restrict__ bias,
+// mean = s + S1 / R, var = S2 / R - (S1 / R)^2 (biased), rstd = 1 / sqrt(var + eps): written into the bn vector; var also to var_out.
+// S1, S2 are sums of (z - s) and (z - s)^2 with the shift s = the conv output at the call's first row (fusion_bn_fwd_kernel).  The
+// workgroup partials (fp32, each lane's own short chain) are added HERE in double, in fixed order, and the subtraction is done in
+// double: the error of var is then the fp32 rounding of the partials, ~1e-7 (mean - s)^2, and a row of the data is a few standard
+// deviations from the mean however far the conv bias is.  (The conv bias used to be the shift: a layer-2 output 77 standard deviations
+// from its bias then lost 2.6e-4 of its rstd, tests/test_fusion_bn_variants_gpu.py `far`.  ADVICE r4: the partial sums used to be added
+// in fp32 as well, which lost another factor of the number of workgroups.)
+__global__ __launch_bounds__(256) void fusion_bn_stats_kernel(const float *__restrict__ partial, int parts, int c, double rows, const float *__restrict__ shift,
                                                              float eps, float *__restrict__ bn_layer, float *__restrict__ var_out) {
     // 16 channels per block, 16 chains per channel (workgroups ch, ch + 16, ... in order), chains added in chain order
     __shared__ double ca[16][17], cb[16][17];
@@ -300,7 +369,7 @@ __global__ __launch_bounds__(256) void fusion_bn_stats_kernel(const float *__res
     const double m = a / rows;
     double var = b / rows - m * m;
     if (var < 0.0) var = 0.0;
-    bn_layer[e] = (float)((double)bias[e] + m);
+    bn_layer[e] = (float)((double)shift[e] + m);
     bn_layer[c + e] = (float)(1.0 / sqrt(var + (double)eps));
     var_out[e] = (float)var;
 }
@@ -315,7 +384,7 @@ unsigned fwd_grid(long long total) {
 template <int MODE, bool SAVE = false>
 int launch_fwd(long long total, int n, const float *p1, const float *p2, const int *idx, const int *idx2, const float *w1, const float *b1, const float *w2,
                const float *b2, const float *w3, const float *b3, const float *bn, float *out, unsigned grid, hipStream_t s, int *save_c = nullptr,
-               float *save_z = nullptr, float *save_s = nullptr) {
+               float *save_z = nullptr, float *save_s = nullptr, float *shift = nullptr) {
     auto kern = fusion_bn_fwd_kernel<MODE, SAVE>;
     static McpPerDeviceOnce attr_once;
     if (attr_once.need()) {
@@ -324,7 +393,7 @@ int launch_fwd(long long total, int n, const float *p1, const float *p2, const i
         attr_once.done();
     }
     const size_t lds = (size_t)L_F32 * 4 + (size_t)(W2_U4 + W3_U4) * 16;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WAVES), lds, s, total, n, p1, p2, idx, idx2, w1, b1, w2, b2, w3, b3, bn, out, save_c, save_z, save_s);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WAVES), lds, s, total, n, p1, p2, idx, idx2, w1, b1, w2, b2, w3, b3, bn, out, save_c, save_z, save_s, shift);
     return mcp_launch_status();
 }
 
@@ -438,7 +507,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fusion_bn_b1_kernel(long long t
             McpSplit3 x1[4], x2[4];
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                const f32x16 z1 = layer1_tile<false>(lds, t, h, lane, in0, in1);
+                const f32x16 z1 = layer1_tile(lds, t, h, lane, in0, in1);
                 f32x16 zh, v;
                 bn_tile<C1>(lds + L_BN1 + (t * 2 + h) * 16, z1, zh, v);
 #pragma unroll
@@ -448,7 +517,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fusion_bn_b1_kernel(long long t
             }
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                f32x16 z2 = bias_tile<false>(lds, L_B2 + (t * 2 + h) * 16);
+                f32x16 z2 = bias_tile(lds, L_B2 + (t * 2 + h) * 16);
                 z2 = mcp_tile_split<4>(w2s + (size_t)t * 4 * 3 * 64 + lane, x1, z2);
                 f32x16 zh, v;
                 bn_tile<C2>(lds + L_BN2 + (t * 2 + h) * 16, z2, zh, v);
@@ -461,7 +530,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fusion_bn_b1_kernel(long long t
             int mr = 0;
 #pragma unroll 1
             for (int t = 0; t < 4; ++t) {
-                f32x16 z3 = bias_tile<false>(lds, L_B3 + (t * 2 + h) * 16);
+                f32x16 z3 = bias_tile(lds, L_B3 + (t * 2 + h) * 16);
                 z3 = mcp_tile_split<4>(w3s + (size_t)t * 4 * 3 * 64 + lane, x2, z3);
                 f32x16 zh, v;
                 bn_tile<C3>(lds + L_BN3 + (t * 2 + h) * 16, z3, zh, v);
@@ -695,7 +764,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void fusion_bn_b2_kernel(long long t
                 McpSplit3 x1[4];
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
-                    const f32x16 z1 = layer1_tile<false>(lds, t, h, lane, in0, in1);
+                    const f32x16 z1 = layer1_tile(lds, t, h, lane, in0, in1);
                     f32x16 zh, v;
                     bn_tile<C1>(lds + L_BN1 + (t * 2 + h) * 16, z1, zh, v);
 #pragma unroll
@@ -706,7 +775,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void fusion_bn_b2_kernel(long long t
                 __builtin_amdgcn_wave_barrier();
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
-                    f32x16 z2 = bias_tile<false>(lds, L_B2 + (t * 2 + h) * 16);
+                    f32x16 z2 = bias_tile(lds, L_B2 + (t * 2 + h) * 16);
                     z2 = mcp_tile_split<4>(w2s + (size_t)t * 4 * 3 * 64 + lane, x1, z2);
                     f32x16 v;
                     bn_tile<C2>(lds + L_BN2 + (t * 2 + h) * 16, z2, zh2[t], v);
@@ -740,7 +809,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void fusion_bn_b2_kernel(long long t
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 __builtin_amdgcn_sched_barrier(0);  // a tile's loads are not hoisted above the previous tile (registers)
-                f32x16 z3 = bias_tile<false>(lds, L_B3 + (t * 2 + h) * 16);
+                f32x16 z3 = bias_tile(lds, L_B3 + (t * 2 + h) * 16);
                 z3 = mcp_tile_split<4>(w3s + (size_t)t * 4 * 3 * 64 + lane, x2, z3);
                 f32x16 zh, v, dy, dz;
                 bn_tile<C3>(lds + L_BN3 + (t * 2 + h) * 16, z3, zh, v);
@@ -871,7 +940,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void fusion_bn_b3_kernel(long long t
                 McpSplit3 x1[4];
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
-                    const f32x16 z1 = layer1_tile<false>(lds, t, h, lane, in0, in1);
+                    const f32x16 z1 = layer1_tile(lds, t, h, lane, in0, in1);
                     f32x16 v;
                     bn_tile<C1>(lds + L_BN1 + (t * 2 + h) * 16, z1, zh1[t], v);
 #pragma unroll
@@ -883,7 +952,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void fusion_bn_b3_kernel(long long t
                 load_row64(dy2 + row * C2, h, dy);
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
-                    f32x16 z2 = bias_tile<false>(lds, L_B2 + (t * 2 + h) * 16);
+                    f32x16 z2 = bias_tile(lds, L_B2 + (t * 2 + h) * 16);
                     z2 = mcp_tile_split<4>(w2s + (size_t)t * 4 * 3 * 64 + lane, x1, z2);
                     f32x16 zh, v;
                     bn_tile<C2>(lds + L_BN2 + (t * 2 + h) * 16, z2, zh, v);
@@ -1012,7 +1081,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fusion_bn_b4_kernel(long long t
             load_row64(dy1 + row * C1, h, dy);
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                const f32x16 z1 = layer1_tile<false>(lds, t, h, lane, in0, in1);
+                const f32x16 z1 = layer1_tile(lds, t, h, lane, in0, in1);
                 f32x16 zh, v;
                 bn_tile<C1>(lds + L_BN1 + (t * 2 + h) * 16, z1, zh, v);
                 dz_tile<C1>(lds + B4_L_DZ + (t * 2 + h) * 16, dy[t], zh, dz1[t]);
@@ -1126,7 +1195,7 @@ MCP_EXPORT int mcp_fusion_bn_floats(void) { return BN_FLOATS; }
 
 MCP_EXPORT size_t mcp_fusion_bn_workspace_bytes(int b, int n) {
     if (b <= 0 || n <= 0) return 0;
-    return (size_t)fwd_grid((long long)b * n) * 2 * C3 * sizeof(float);
+    return ((size_t)fwd_grid((long long)b * n) * 2 * C3 + C3) * sizeof(float);  // the partial rows | the statistics' shift
 }
 
 // The layer on BATCH statistics, forward.  bn (1024 floats): per layer mean | rstd | gamma | beta, natural channel order, layers
@@ -1163,20 +1232,20 @@ int bn_forward(int b, int n, int nb, const float *p1, const float *p2, const int
     if (nb != NB) return MCP_ERR_UNSUPPORTED;
     const long long total = (long long)b * n;
     const unsigned grid = fwd_grid(total);
-    if (workspace_bytes < (size_t)grid * 2 * C3 * sizeof(float)) return MCP_ERR_BAD_ARG;
+    if (workspace_bytes < ((size_t)grid * 2 * C3 + C3) * sizeof(float)) return MCP_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
-    float *partial = static_cast<float *>(workspace);
+    float *partial = static_cast<float *>(workspace), *shift = partial + (size_t)grid * 2 * C3;
     const double rows = (double)total * NB;
     mcp_prof_begin(MCP_KERNEL_FUSION, s);
-    int rc = launch_fwd<1>(total, n, p1, p2, idx, idx2, w1, b1, w2, b2, w3, b3, bn, partial, grid, s);
+    int rc = launch_fwd<1>(total, n, p1, p2, idx, idx2, w1, b1, w2, b2, w3, b3, bn, partial, grid, s, nullptr, nullptr, nullptr, shift);
     if (rc) return rc;
-    hipLaunchKernelGGL(fusion_bn_stats_kernel, dim3(C1 / 16), dim3(256), 0, s, partial, (int)grid, C1, rows, b1, eps, bn + BN_L1, var);
-    rc = launch_fwd<2>(total, n, p1, p2, idx, idx2, w1, b1, w2, b2, w3, b3, bn, partial, grid, s);
+    hipLaunchKernelGGL(fusion_bn_stats_kernel, dim3(C1 / 16), dim3(256), 0, s, partial, (int)grid, C1, rows, shift, eps, bn + BN_L1, var);
+    rc = launch_fwd<2>(total, n, p1, p2, idx, idx2, w1, b1, w2, b2, w3, b3, bn, partial, grid, s, nullptr, nullptr, nullptr, shift);
     if (rc) return rc;
-    hipLaunchKernelGGL(fusion_bn_stats_kernel, dim3(C2 / 16), dim3(256), 0, s, partial, (int)grid, C2, rows, b2, eps, bn + BN_L2, var + C1);
-    rc = launch_fwd<3>(total, n, p1, p2, idx, idx2, w1, b1, w2, b2, w3, b3, bn, partial, grid, s);
+    hipLaunchKernelGGL(fusion_bn_stats_kernel, dim3(C2 / 16), dim3(256), 0, s, partial, (int)grid, C2, rows, shift, eps, bn + BN_L2, var + C1);
+    rc = launch_fwd<3>(total, n, p1, p2, idx, idx2, w1, b1, w2, b2, w3, b3, bn, partial, grid, s, nullptr, nullptr, nullptr, shift);
     if (rc) return rc;
-    hipLaunchKernelGGL(fusion_bn_stats_kernel, dim3(C3 / 16), dim3(256), 0, s, partial, (int)grid, C3, rows, b3, eps, bn + BN_L3, var + C1 + C2);
+    hipLaunchKernelGGL(fusion_bn_stats_kernel, dim3(C3 / 16), dim3(256), 0, s, partial, (int)grid, C3, rows, shift, eps, bn + BN_L3, var + C1 + C2);
     rc = save_c ? launch_fwd<0, true>(total, n, p1, p2, idx, idx2, w1, b1, w2, b2, w3, b3, bn, out, grid, s, save_c, save_z, save_s)
                 : launch_fwd<0>(total, n, p1, p2, idx, idx2, w1, b1, w2, b2, w3, b3, bn, out, grid, s);
     mcp_prof_end(MCP_KERNEL_FUSION, s);

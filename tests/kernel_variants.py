@@ -9,8 +9,9 @@ least one case, so a variant added later without a parity case fails the CPU sui
 
 expected_grad_kernels() names the set of kernels one backward call launches and grad_launch_grid() mirrors how each of them deals
 its points (or point pairs) to workgroups; GRAD_CASES parametrises test_fused_grad_variants_gpu.py, and test_kernel_variants_cpu.py
-checks that they reach every kernel the backward units emit and every edge of their persistent loops.  A plain module, imported by
-the tests."""
+checks that they reach every kernel the backward units emit and every edge of their persistent loops.  BN_CASES,
+expected_bn_kernels() and bn_launch_grid() do the same for the train-mode fusion layer (fusion_bn.hip, forward and backward in one
+unit, two grid caps in one call) and parametrise test_fusion_bn_variants_gpu.py.  A plain module, imported by the tests."""
 
 def _cdiv(a, b):
     return (a + b - 1) // b
@@ -484,6 +485,61 @@ GRAD_CASES = [
 
 def grad_cases(op):
     return [c for c in GRAD_CASES if c["op"] == op]
+
+
+# ---- the fusion layer on batch statistics (fusion_bn.hip): one call launches persistent passes under TWO grid caps, every pass deals
+# points through mcp_units_by_xcd, and every pass but the layer itself leaves one partial row per workgroup that
+# fusion_bn_stats_kernel / sum_partials_kernel add over ALL workgroups ----
+BN_WAVES = 4                      # WAVES, fusion_bn.hip:24
+
+
+def bn_launch_grid(cus=256, **shape):
+    """{role: dict(workgroups, units, per, by_xcd, dealt)} of one forward + backward call on a device with `cus` compute units, as
+    grad_launch_grid gives it.  "wide": min(ceil(total / 4), 2 CUs) workgroups -- the three statistics passes and the layer (fwd_grid,
+    fusion_bn.hip:377-382; the loop :210-211), B1 in both forms and B4 (bwd_grid(total, 2), :1179-1184, :1326, :1351; loops :491-492,
+    :631-632, :1065-1066).  "narrow": min(ceil(total / 4), CUs) -- B2 and B3 (bwd_grid(total, 1), :1337, :1344; loops :746-747, :926-927)."""
+    total = shape["b"] * shape["n"]
+    want = _cdiv(total, BN_WAVES)
+    return {"wide": _role(total, BN_WAVES, min(want, 2 * cus)), "narrow": _role(total, BN_WAVES, min(want, cus))}
+
+
+def expected_bn_kernels(**shape):
+    """The demangled kernels that test_fusion_bn_variants_gpu.py launches for a case (extra keys are ignored): the public path
+    (be.fusion_bn: mcp_fusion_bn_forward_save, mcp_fusion_bn_backward_saved), the forward that keeps nothing (be.fusion_bn_forward) and,
+    unless the case is forward-only, the backward that re-evaluates the layer (mcp_fusion_bn_backward)."""
+    if shape.get("nb", 64) != 64:                                    # bn_forward, fusion_bn.hip:1232; bn_backward :1300
+        raise ValueError(f"fusion_bn: {shape['nb']} neighbours are not built")
+    names = {f"fusion_bn_fwd_kernel<{m}, false>" for m in (1, 2, 3, 0)} | {"fusion_bn_fwd_kernel<0, true>", "fusion_bn_stats_kernel"}   # bn_forward, :1240-1250
+    if not shape.get("forward_only"):                                # bn_backward, fusion_bn.hip:1324-1354
+        names |= {"transposed_image_kernel", "fusion_bn_b1_saved_kernel", "fusion_bn_b1_kernel", "fusion_bn_b2_kernel", "fusion_bn_b3_kernel",
+                  "fusion_bn_b4_kernel", "sum_partials_kernel"}
+    return names
+
+
+def _fbn(tag, b, n, **kw):
+    """same / dup / extent / seed as _fus (the data is fused_reference.fusion_inputs'); far: the weights that put the layer-2 conv output
+    more than 30 sigma from its bias; forward_only: statistics and out only."""
+    return dict(op="fusion_bn", tag=tag, b=b, n=n, **kw)
+
+
+# at 256 CUs: the wide passes are capped at 512 workgroups, B2 / B3 at 256
+BN_CASES = [
+    _fbn("one-point", 1, 1),                                 # three dead waves; every channel of every layer has zero variance; every gradient but p2's is zero
+    _fbn("3-points", 1, 3),                                  # one workgroup, one dead wave; dead neighbours (no positive layer-3 channel)
+    _fbn("5-points", 1, 5),                                  # grid 2 round-robin: the second workgroup has one live wave; dead neighbours
+    _fbn("same-dup", 2, 19, same=True, dup=True, seed=1),    # 38 points, grid 10: |r| = 0 and every neighbour twice
+    _fbn("xcd-ragged", 1, 61),                               # grid 16 by XCD in every pass: eighths of 8 points, the last has 5
+    _fbn("grid-75", 2, 149, extent=True, seed=4),            # 298 points: round-robin below both caps, two batch elements
+    _fbn("narrow-cap+1", 5, 205),                            # 1025 points: B2 / B3 want 257 > 256 -- eighths of 132 against steps of 128, the last has 101, 6 idle workgroups; the wide passes: grid 257 round-robin
+    _fbn("wide-cap+1", 3, 683),                              # 2049 points: the wide passes want 513 > 512 -- eighths of 260 against steps of 256, the last has 229, 6 idle workgroups, one workgroup per eighth in a second round; B2 / B3: three rounds
+    _fbn("cap-rounds", 3, 1031),                             # 3093 points: eighths of 388, the last has 377; two rounds wide, four narrow
+    _fbn("far", 2, 149, far=True, forward_only=True),        # the layer-2 conv output sits more than 30 sigma from its bias: statistics and out only
+]
+
+
+def bn_case_id(c):
+    shape = ",".join(v if k == "tag" else f"{k}={v}" for k, v in c.items() if k != "op" and v not in (None, False))
+    return f"fusion_bn[{shape}]".replace(" ", "")
 
 
 def grad_case_id(c):

@@ -9,7 +9,11 @@ way: every kernel they emit must be in kernel_variants.expected_grad_kernels of 
 test_fused_grad_variants_gpu.py) or in GRAD_NOT_LAUNCHED with its reason, and GRAD_EDGES states, as predicates on the mirrored launch
 (kernel_variants.grad_launch_grid at 256 compute units), every edge of their persistent loops that the cases must reach.
 
-Still outside: fusion_bn.hip, attention_grad.hip, attention_wide_grad.hip, linear_grad.hip, the MLP backward, emd_grad.hip and
+The train-mode fusion layer (fusion_bn: forward and backward passes in one unit) likewise: every kernel it emits must be in
+kernel_variants.expected_bn_kernels of at least one entry of BN_CASES (the cases of test_fusion_bn_variants_gpu.py, which hold the unit
+to float64 at its loop edges) or in BN_NOT_LAUNCHED, and BN_EDGES states the edges of its two grid caps on kernel_variants.bn_launch_grid.
+
+Still outside: attention_grad.hip, attention_wide_grad.hip, linear_grad.hip, the MLP backward, emd_grad.hip and
 interp3_grad.hip have no parity cases of this form; tests/test_grad_gpu.py and its neighbours compare them at workload-like shapes."""
 import os
 import re
@@ -28,6 +32,8 @@ UNITS = ("linear", "mlp", "attention", "fusion", "cross", "pointconv", "ptblock"
 NOT_LAUNCHED = {}
 GRAD_UNITS = ("fusion_grad", "cross_grad", "cross256_grad", "pointconv_grad", "ptblock_grad")
 GRAD_NOT_LAUNCHED = {}   # the same for the backward units: every kernel they emit is launched by some backward call
+BN_UNITS = ("fusion_bn",)
+BN_NOT_LAUNCHED = {}     # and for the train-mode fusion layer: all 13 kernels are launched by a forward or a backward entry point
 
 
 def emitted_kernels(units=UNITS):
@@ -379,3 +385,87 @@ def test_every_backward_kernel_of_the_fused_layers_has_a_parity_case():
     assert not missing, f"backward kernels without a parity case in tests/kernel_variants.py GRAD_CASES: {missing}"
     stale = sorted(covered - wanted)
     assert not stale, f"backward cases name kernels the library does not build: {stale}"
+
+
+# ---- the fusion layer on batch statistics: two grid caps in one call --------------------------------------------------------------------
+def test_the_batch_statistics_mirror_follows_the_c_conditions():
+    # fwd_grid, fusion_bn.hip:377-382; bwd_grid :1179-1184 with per_cu 2 (B1, B4: :1326, :1351) and 1 (B2, B3: :1337, :1344); the deal: common.h:101-120
+    g, e = kv.bn_launch_grid, kv.expected_bn_kernels
+    sizes = lambda total, **kw: tuple((r["workgroups"], r["by_xcd"]) for r in g(b=1, n=total, **kw).values())
+    assert sizes(1) == ((1, False), (1, False)) and sizes(5) == ((2, False), (2, False)) and sizes(61) == ((16, True), (16, True))
+    assert sizes(1024) == ((256, True), (256, True)) and sizes(1025) == ((257, False), (256, True)) and sizes(2048) == ((512, True), (256, True))
+    assert sizes(2049) == ((512, True), (256, True)) and sizes(100000) == ((512, True), (256, True)) and sizes(100000, cus=304) == ((608, True), (304, True))
+    at1402 = g(b=2, n=701)   # the one shape test_grad_gpu.py runs: only B2 / B3 exceed their cap, nothing is dealt by XCD in the wide passes, nobody idles
+    assert sizes(1402) == ((351, False), (256, True)) and not any(not wg for r in at1402.values() for wg in r["dealt"])
+    n = g(b=5, n=205)["narrow"]    # 257 steps, eighths of 33 steps = 132 points; workgroup 8 j + x starts at 132 x + 4 j and strides 128
+    assert n["dealt"][0] == [[0, 1, 2, 3], [128, 129, 130, 131]] and n["dealt"][7 + 8 * 25] == [[1024]] and n["dealt"][7 + 8 * 26] == [] and n["dealt"][255] == []
+    w = g(b=3, n=683)["wide"]      # 513 steps, eighths of 65 steps = 260 points; workgroup 8 j + x starts at 260 x + 4 j and strides 256
+    assert w["dealt"][0] == [[0, 1, 2, 3], [256, 257, 258, 259]] and w["dealt"][8] == [[4, 5, 6, 7]] and w["dealt"][7] == [[1820, 1821, 1822, 1823]]
+    assert w["dealt"][7 + 8 * 57] == [[2048]] and w["dealt"][7 + 8 * 58] == [] and w["dealt"][511] == []
+    assert g(b=1, n=5)["wide"]["dealt"] == [[[0, 1, 2, 3]], [[4]]]
+    assert len(e(b=1, n=1)) == 13 and len(e(b=1, n=1, forward_only=True)) == 6
+    with pytest.raises(ValueError):
+        e(b=1, n=1, nb=32)
+
+
+def test_the_batch_statistics_mirror_deals_every_point_to_exactly_one_workgroup_of_each_role():
+    for c in kv.BN_CASES:
+        for name, role in kv.bn_launch_grid(cus=CUS, **c).items():
+            flat = sorted(u for wg in role["dealt"] for rnd in wg for u in rnd)
+            assert flat == list(range(c["b"] * c["n"])), (kv.bn_case_id(c), name)
+            assert len(role["dealt"]) == role["workgroups"] and all(len(rnd) <= role["per"] for wg in role["dealt"] for rnd in wg)
+
+
+def _bn_ladder(role_name, cap, rounds):
+    """The edges of one grid cap: the role's passes all launch min(ceil(total / 4), cap) workgroups."""
+    R = lambda g: g[role_name]
+    return {
+        f"{role_name}: a launch with fewer points than a workgroup has waves": lambda c, g: R(g)["units"] < R(g)["per"],
+        f"{role_name}: a round-robin grid of more than one workgroup": lambda c, g: R(g)["workgroups"] > 1 and not R(g)["by_xcd"],
+        f"{role_name}: by XCD below the cap with a ragged last eighth": lambda c, g: R(g)["workgroups"] < cap and _ragged_eighth(R(g)),
+        f"{role_name}: the first total above the cap, with workgroups that receive nothing and must still write a zero partial row":
+            lambda c, g: R(g)["workgroups"] == cap and _want(R(g)) == cap + 1 and _idle(R(g)) > 0 and _rounds(R(g)) == 2,
+        f"{role_name}: {rounds} or more rounds at the cap with a ragged last eighth":
+            lambda c, g: R(g)["workgroups"] == cap and _rounds(R(g)) >= rounds and _ragged_eighth(R(g)),
+    }
+
+
+BN_EDGES = {
+    **_bn_ladder("wide", 2 * CUS, 2),
+    **_bn_ladder("narrow", CUS, 4),
+    "only B2 / B3 above their cap: idle workgroups there, a round-robin grid in the wide passes of the same call":
+        lambda c, g: _idle(g["narrow"]) > 0 and not g["wide"]["by_xcd"] and g["wide"]["workgroups"] == CUS + 1,
+    "the wide passes above their cap with idle workgroups while B2 / B3 run three rounds": lambda c, g: _idle(g["wide"]) > 0 and _rounds(g["narrow"]) == 3,
+    "one point": lambda c, g: c["b"] * c["n"] == 1,
+    "five points: the second of two workgroups has one live wave": lambda c, g: g["wide"]["dealt"] == g["narrow"]["dealt"] == [[[0, 1, 2, 3]], [[4]]],
+    "round-robin below both caps with more than one batch element": lambda c, g: not g["wide"]["by_xcd"] and g["wide"]["workgroups"] < CUS and c["b"] >= 2 and not c.get("same"),
+    "same and dup at a small total": lambda c, g: c.get("same") and c.get("dup") and c["b"] * c["n"] <= 64,
+    "coordinates of a real cloud's extent": lambda c, g: c.get("extent"),
+    "a conv output far from its bias, forward only": lambda c, g: c.get("far") and c.get("forward_only"),
+}
+
+
+def bn_cases_reaching(edge):
+    return [kv.bn_case_id(c) for c in kv.BN_CASES if BN_EDGES[edge](c, kv.bn_launch_grid(cus=CUS, **c))]
+
+
+def test_the_batch_statistics_cases_reach_the_loop_edges():
+    """Every edge of BN_EDGES is reached by at least one case on the mirrored launch at 256 compute units."""
+    missing = [edge for edge in BN_EDGES if not bn_cases_reaching(edge)]
+    assert not missing, missing
+    ids = [kv.bn_case_id(c) for c in kv.BN_CASES]
+    assert len(set(ids)) == len(ids)
+    assert sum(1 for c in kv.BN_CASES if not c.get("forward_only")) >= 9      # the backward runs at every case but `far`
+
+
+def test_every_kernel_of_the_batch_statistics_fusion_layer_has_a_parity_case():
+    emitted = emitted_kernels(BN_UNITS)
+    assert "fusion_bn_fwd_kernel<0, true>" in emitted and "sum_partials_kernel" in emitted, sorted(emitted)   # the demangling worked
+    unknown = sorted(set(BN_NOT_LAUNCHED) - emitted)
+    assert not unknown, f"BN_NOT_LAUNCHED names kernels the library does not build: {unknown}"
+    wanted = emitted - set(BN_NOT_LAUNCHED)
+    covered = set().union(*(kv.expected_bn_kernels(**c) for c in kv.BN_CASES))
+    missing = sorted(wanted - covered)
+    assert not missing, f"fusion_bn kernels without a parity case in tests/kernel_variants.py BN_CASES: {missing}"
+    stale = sorted(covered - wanted)
+    assert not stale, f"cases name kernels the library does not build: {stale}"
