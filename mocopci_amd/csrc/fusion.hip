@@ -185,6 +185,44 @@ constexpr int SP_W1 = 0, SP_B1 = 256, SP_B2 = SP_B1 + 64, SP_B3 = SP_B2 + 64, SP
 constexpr int SP_W2_U4 = 2 * 4 * 3 * 64, SP_W3_U4 = 4 * 4 * 3 * 64;                                         // uint4 counts
 constexpr size_t SP_LDS_BYTES = SP_F32_FLOATS * 4 + (size_t)(SP_W2_U4 + SP_W3_U4) * 16;
 
+// running channel max over registers 4q..4q+3 of a tile, in register order (two v_max3_f32).  The empty asm keeps the value where it is
+// computed: without it the compiler sinks the whole chain of a point to its one use behind the last MFMA, tiles kept alive until then.
+__device__ __forceinline__ float max4(float m, const f32x16 &a, int q) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) m = fmaxf(m, a[4 * q + i]);
+    asm volatile("" : "+v"(m));
+    return m;
+}
+// TILES output tiles of one split-bf16 layer with 64 input channels: out[t] = bias(t) + sum over k-steps s = 0..3 of W(t, s) . X(s), the
+// k-steps ascending.  wl points at this lane's entry of the layer's weight image, bias at this lane half's 16 floats of tile 0 (tiles are
+// 32 floats apart).  fill(r) is the filler batch of k-step r = 4 t + s (mcp_kstep_fill), NF0 vector instructions for r < 8 and NF1 from
+// there; the weight pieces of k-step r + 1 and the bias of the next tile are read while k-step r runs.
+constexpr int NF_SPLIT = 26, NF_MAX = 2;  // mcp_relu_split4, max4
+template <int TILES, int NF0, int NF1, class Fill>
+__device__ __forceinline__ void split_layer(const uint4 *wl, const float *bias, const McpSplit3 *xs, f32x16 *out, Fill fill) {
+    uint4 w1 = wl[0], w2 = wl[64], w3 = wl[128];
+    f32x16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = bias[i];
+#pragma unroll
+    for (int r = 0; r < 4 * TILES; ++r) {
+        uint4 n1 = w1, n2 = w2, n3 = w3;
+        f32x16 nacc = acc;
+        if (r + 1 < 4 * TILES) {
+            const uint4 *nx = wl + (size_t)(r + 1) * 3 * 64;
+            n1 = nx[0]; n2 = nx[64]; n3 = nx[128];
+            if ((r & 3) == 3) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) nacc[i] = bias[32 * ((r >> 2) + 1) + i];
+            }
+        }
+        if (r < 8) acc = mcp_kstep_fill<NF0>(w1, w2, w3, xs[r & 3], acc, [&] { fill(r); });
+        else acc = mcp_kstep_fill<NF1>(w1, w2, w3, xs[r & 3], acc, [&] { fill(r); });
+        if ((r & 3) == 3) { out[r >> 2] = acc; acc = nacc; }
+        w1 = n1; w2 = n2; w3 = n3;
+    }
+}
+
 __global__ __launch_bounds__(64 * WAVES, 2) void fusion_split_kernel(long long total, int n, const float *__restrict__ p1,
                                                                   const float *__restrict__ p2, const int *__restrict__ idx, const int *__restrict__ idx2,
                                                                   const float *__restrict__ w1, const float *__restrict__ b1,
@@ -214,10 +252,17 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fusion_split_kernel(long long t
 
     const int lane = tid & 63, wave = tid >> 6, h = lane >> 5, col = lane & 31;
     const McpUnits units = mcp_units_by_xcd(total, WAVES);   // XCD x takes the x-th eighth of the points (common.h)
+    const uint4 *w2l = w2s + lane, *w3l = w3s + lane;
     for (long long p = units.first + wave; p < units.limit; p += units.stride) {
         const long long bb = mcp_div(p, n, mcp_fits32(total));
         const float cx = p1[p * 3 + 0], cy = p1[p * 3 + 1], cz = p1[p * 3 + 2];
         float score[2], nbx[2], nby[2], nbz[2];
+        // The point's two 32-neighbour column tiles are two independent chains, A (ct = 0) and B (ct = 1).  They run as a software
+        // pipeline: the ReLU + operand split (and the channel max) of one chain is the filler work under the MFMAs of the other, a
+        // quarter tile (26 vector instructions) per six-MFMA k-step, and a quarter tile is first touched at least one whole k-step
+        // after the MFMA that finished it.  Every accumulator still starts from its bias and takes its k-steps in ascending order.
+        //   layer 1 of A and B | split A1 | A: layer 2 under it split B1 | B: layer 2, split A2 | A: layer 3, split B2 + max A | B: layer 3, max A, B
+        f32x16 l1[2][2];
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct) {
             // idx2 != NULL: the two 32-neighbour halves come as separate (B,N,32) lists (no concatenation pass by the caller)
@@ -228,8 +273,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fusion_split_kernel(long long t
             const float rx = x - cx, ry = y - cy, rz = z - cz;
             const float dist = sqrtf((rx * rx + ry * ry) + rz * rz);
             const float in0 = h ? ry : rx, in1 = h ? dist : rz;
-            // ---- layer 1: 4 -> 64 on the f32-input MFMA (K = 4: two k-steps), split for layer 2 as it is produced ----
-            McpSplit3 x1[4];
+            // ---- layer 1: 4 -> 64 on the f32-input MFMA (K = 4: two k-steps) ----
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 f32x16 acc;
@@ -237,37 +281,33 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fusion_split_kernel(long long t
                 for (int r = 0; r < 16; ++r) acc[r] = lds[SP_B1 + (t * 2 + h) * 16 + r];
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(lds[SP_W1 + (t * 2 + 0) * 64 + lane], in0, acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(lds[SP_W1 + (t * 2 + 1) * 64 + lane], in1, acc, 0, 0, 0);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = fmaxf(acc[r], 0.f);
-                x1[2 * t + 0] = mcp_split_kstep(acc, 0);
-                x1[2 * t + 1] = mcp_split_kstep(acc, 1);
+                l1[ct][t] = acc;
             }
-            // ---- layer 2: 64 -> 64 ----
-            McpSplit3 x2[4];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                f32x16 acc;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = lds[SP_B2 + (t * 2 + h) * 16 + r];
-                acc = mcp_tile_split<4>(w2s + (size_t)t * 4 * 3 * 64 + lane, x1, acc);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = fmaxf(acc[r], 0.f);
-                x2[2 * t + 0] = mcp_split_kstep(acc, 0);
-                x2[2 * t + 1] = mcp_split_kstep(acc, 1);
-            }
-            // ---- layer 3: 64 -> 128, consumed into the channel max ----
-            float m = 0.f;
-#pragma unroll 1
-            for (int t = 0; t < 4; ++t) {
-                f32x16 acc;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = lds[SP_B3 + (t * 2 + h) * 16 + r];
-                acc = mcp_tile_split<4>(w3s + (size_t)t * 4 * 3 * 64 + lane, x2, acc);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) m = fmaxf(m, acc[r]);
-            }
-            score[ct] = fmaxf(m, __shfl_xor(m, 32));
         }
+        McpSplit3 xa1[4], xb1[4], xa2[4], xb2[4];
+        f32x16 a2[2], b2t[2], a3[4], b3t[4];
+        float ma = 0.f, mb = 0.f;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) mcp_relu_split4(l1[0][u >> 2], u & 3, xa1[u >> 1]);   // nothing to hide under yet
+        __builtin_amdgcn_sched_barrier(0);
+        // A layer 2 | ReLU + split of B's layer 1
+        split_layer<2, NF_SPLIT, 0>(w2l, lds + SP_B2 + h * 16, xa1, a2, [&](int r) { if (r < 8) mcp_relu_split4(l1[1][r >> 2], r & 3, xb1[r >> 1]); });
+        // B layer 2 | ReLU + split of A's layer 2 (its second tile was finished four k-steps before it is first read)
+        split_layer<2, NF_SPLIT, 0>(w2l, lds + SP_B2 + h * 16, xb1, b2t, [&](int r) { if (r < 8) mcp_relu_split4(a2[r >> 2], r & 3, xa2[r >> 1]); });
+        // A layer 3 | ReLU + split of B's layer 2, then the channel max of A's tiles 0 and 1 (max over ReLU = ReLU of max)
+        split_layer<4, NF_SPLIT, NF_MAX>(w3l, lds + SP_B3 + h * 16, xa2, a3, [&](int r) {
+            if (r < 8) mcp_relu_split4(b2t[r >> 2], r & 3, xb2[r >> 1]);
+            else ma = max4(ma, a3[(r - 8) >> 2], (r - 8) & 3);
+        });
+        // B layer 3 | the channel max of A's tiles 2 and 3, then of B's tiles 0 and 1
+        split_layer<4, NF_MAX, NF_MAX>(w3l, lds + SP_B3 + h * 16, xb2, b3t, [&](int r) {
+            if (r < 8) ma = max4(ma, a3[2 + (r >> 2)], r & 3);
+            else mb = max4(mb, b3t[(r - 8) >> 2], (r - 8) & 3);
+        });
+#pragma unroll
+        for (int u = 0; u < 8; ++u) mb = max4(mb, b3t[2 + (u >> 2)], u & 3);
+        score[0] = fmaxf(ma, __shfl_xor(ma, 32));  // the two lane halves hold the other 64 channels
+        score[1] = fmaxf(mb, __shfl_xor(mb, 32));
         const float mx = wave_max(fmaxf(score[0], score[1]));
         const float e0 = expf(score[0] - mx), e1 = expf(score[1] - mx);
         const float den = wave_sum(e0 + e1);

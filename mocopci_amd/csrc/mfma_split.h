@@ -68,6 +68,48 @@ __device__ __forceinline__ mcp_f32x16 mcp_mfma_split(const uint4 *w, const McpSp
     acc = mcp_mfma_bf16(w1, x.p1, acc);
     return acc;
 }
+// ReLU and split of registers 4q..4q+3 of an accumulator tile (a quarter tile, half a k-step), q = 0..3: the arithmetic of mcp_split8 on
+// max(a, 0), written into the low (q even) or high (q odd) half of the pieces of k-step q >> 1.  26 vector instructions: one batch of
+// filler work for mcp_kstep_fill.
+__device__ __forceinline__ void mcp_relu_split4(const mcp_f32x16 &a, int q, McpSplit3 &o) {
+    float v[4], r1[4], r2[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        v[i] = fmaxf(a[4 * q + i], 0.f);
+        r1[i] = v[i] - __uint_as_float(mcp_top16(v[i]));
+        r2[i] = r1[i] - __uint_as_float(mcp_top16(r1[i]));
+    }
+    const uint32_t a1 = mcp_pack_hi(v[0], v[1]), b1 = mcp_pack_hi(v[2], v[3]);
+    const uint32_t a2 = mcp_pack_hi(r1[0], r1[1]), b2 = mcp_pack_hi(r1[2], r1[3]);
+    const uint32_t a3 = mcp_pack_hi(r2[0], r2[1]), b3 = mcp_pack_hi(r2[2], r2[3]);
+    if (q & 1) { o.p1.z = a1; o.p1.w = b1; o.p2.z = a2; o.p2.w = b2; o.p3.z = a3; o.p3.w = b3; }
+    else       { o.p1.x = a1; o.p1.y = b1; o.p2.x = a2; o.p2.y = b2; o.p3.x = a3; o.p3.y = b3; }
+}
+// One k-step: the six MFMAs of acc += W(s) . X(s), small terms first, closed by a scheduling barrier that nothing crosses (a mask that
+// let VALU/MFMA cross, 0xE, produced WRONG results with this compiler in the fusion test: the vector instructions that then moved up were the
+// readers of the accumulator the MFMAs had just written).  fill() is a batch of vector work that must not depend on acc or on anything an MFMA
+// of the last six wrote; NF is the number of vector instructions it compiles to (at most 30).  They are dealt out evenly behind the six
+// MFMAs, so at most five per gap: up to six single-issue vector instructions hide in such a gap (profiles/mfma_gap_probe.txt).
+template <int NF, class Fill>
+__device__ __forceinline__ mcp_f32x16 mcp_kstep_fill(const uint4 &w1, const uint4 &w2, const uint4 &w3, const McpSplit3 &x, mcp_f32x16 acc, Fill fill) {
+    fill();
+    acc = mcp_mfma_bf16(w3, x.p1, acc);
+    acc = mcp_mfma_bf16(w1, x.p3, acc);
+    acc = mcp_mfma_bf16(w2, x.p2, acc);
+    acc = mcp_mfma_bf16(w2, x.p1, acc);
+    acc = mcp_mfma_bf16(w1, x.p2, acc);
+    acc = mcp_mfma_bf16(w1, x.p1, acc);
+    if constexpr (NF > 0) {
+        static_assert(NF <= 30, "at most five fillers per MFMA gap");
+#define MCP_GAP(i)                                                                        /* one MFMA, then its even share of the batch */ \
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                                                    \
+    if constexpr ((NF + 5 - (i)) / 6 > 0) __builtin_amdgcn_sched_group_barrier(0x002, (NF + 5 - (i)) / 6, 0);
+        MCP_GAP(0) MCP_GAP(1) MCP_GAP(2) MCP_GAP(3) MCP_GAP(4) MCP_GAP(5)
+#undef MCP_GAP
+    }
+    __builtin_amdgcn_sched_barrier(MCP_SPLIT_SCHED_MASK);
+    return acc;
+}
 // One output tile over KSTEPS k-steps: acc += sum_s W(s) . X(s).  ws points at this lane's entry of (k-step 0, piece 1); k-steps
 // are 3 * 64 uint4 apart.  The weight pieces of step s+1 are read while the six MFMAs of step s run, and a scheduling barrier
 // per step keeps the compiler from hoisting every LDS read of the (unrolled) layer to its top, which costs ~100 registers.
@@ -83,13 +125,13 @@ __device__ __forceinline__ mcp_f32x16 mcp_tile_split(const uint4 *ws, const McpS
             n1 = nx[0]; n2 = nx[64]; n3 = nx[128];
         }
 #endif
-        acc = mcp_mfma_bf16(w3, xs[s].p1, acc);
-        acc = mcp_mfma_bf16(w1, xs[s].p3, acc);
+        acc = mcp_mfma_bf16(w3, xs[s].p1, acc);  // the bare k-step, written out: through mcp_kstep_fill<0> the same six MFMAs come out with
+        acc = mcp_mfma_bf16(w1, xs[s].p3, acc);  // their LDS reads and waits in another order in linear / mlp / ptblock / cross
         acc = mcp_mfma_bf16(w2, xs[s].p2, acc);
         acc = mcp_mfma_bf16(w2, xs[s].p1, acc);
         acc = mcp_mfma_bf16(w1, xs[s].p2, acc);
         acc = mcp_mfma_bf16(w1, xs[s].p1, acc);
-        __builtin_amdgcn_sched_barrier(MCP_SPLIT_SCHED_MASK);  // nothing moves across: a mask that let VALU/MFMA cross (0xE) produced WRONG results with this compiler (fusion test) and no speed-up
+        __builtin_amdgcn_sched_barrier(MCP_SPLIT_SCHED_MASK);  // nothing moves across (see mcp_kstep_fill)
         w1 = n1; w2 = n2; w3 = n3;
     }
     return acc;
