@@ -549,6 +549,48 @@ int mcp_group_mlp_grad(int b, int n, int m, int c, int nsample, int use_xyz, int
                        float *grad_new_xyz, float *grad_row_bias, float *const *grad_w, float *const *grad_b, float *out, void *workspace,
                        size_t workspace_bytes, mcp_stream_t stream);
 
+/* mcp_group_mlp's layer with TRAINING-MODE BatchNorm behind every product (csrc/group_mlp_bn.hip).  Inputs, use_xyz, pool and qlen as
+ * mcp_group_mlp (no row_bias).  Over the live pairs R = {(p, j): p a live centre, j < nsample} (count m; every slot counts, the ones
+ * that repeat the ball query's first hit included), k = idx[p,j], for l = 1 .. L:  x = [xyz[k] - new_xyz[p] (use_xyz) | features[k]],
+ * z_l = W_l h_(l-1) + b_l,  mu_l = mean_R z_l,  v_l = mean_R (z_l - mu_l)^2 (biased),  rstd_l = 1 / sqrt(v_l + eps_l),
+ * y_l = gamma_l (z_l - mu_l) rstd_l + beta_l,  h_l = ReLU(y_l),  out[p] = max_j h_(L,j) (pool 0) or (sum_j h_(L,j)) / nsample (pool 1).
+ * mcp_group_mlp_bn_forward writes out (B,M,widths[L-1]; zeros for padded centres), mean[l], var[l], rstd[l] (widths[l] floats each:
+ * host arrays of `layers` device pointers) and the live count m as one device int32.  gamma / beta: host arrays of `layers` device
+ * pointers, a NULL entry is ones / zeros; eps: a host array of `layers` floats, each > 0.  packed: mcp_group_mlp_bn_pack's image
+ * (mcp_group_mlp_bn_packed_floats floats), ONE image for both directions, built from the UNFOLDED (W_l, b_l) (zeros for an absent
+ * bias), W_1 (widths[0], 3 + c) in the module's order with the position columns first; rebuilt whenever a weight changes.
+ * mcp_group_mlp_bn_backward takes the forward's inputs again, mean and rstd as the forward wrote them and grad_out (B,M,widths[L-1]) =
+ * dL/dout, and writes -- with gy_L the pool's gradient through [y_L > 0] (max: grad_out[p,ch] to the LOWEST j with h_(L,j)[ch] ==
+ * out[p,ch], F.max_pool2d's rule, nothing for a pooled value <= 0; mean: grad_out[p] / nsample to every slot), dbeta_l, dgamma_l,
+ * gz_l, gy_(l-1) as mcp_fp_mlp_bn_backward and dx = W_1^T gz_1 per pair -- each only when its pointer is not NULL,
+ *   grad_features (B,N,c) += dx[3:] and grad_xyz (B,N,3) += dx[:3] at row k through (order, seg) as mcp_group_mlp_grad; rows that no
+ *       slot gathers get exact zeros;
+ *   grad_new_xyz (B,M,3) = -sum_j dx[:3] in slot order, zeros for padded centres;
+ *   grad_w[l] (widths[l], cin_l; required); grad_b[l], grad_gamma[l], grad_beta[l] (widths[l]): host arrays of `layers` device
+ *       pointers, a NULL entry of the last three is not written (grad_b is zero in exact arithmetic: the statistics absorb a bias).
+ * It keeps no activation: the forward passes run again with the statistics given, so every ReLU mask and every pool winner is the
+ * forward's.  idx and the lengths get no gradient.  A padded centre has none of its float inputs read (grad_out included), takes
+ * part in no statistic and adds nothing to any sum; its row of idx must be readable.  No atomics: every sum runs in a fixed order, two
+ * calls give identical bits.  The variance is merged from (count, mean, M2) triples.  With m < 2 every division is by max(m, 1).
+ * workspace: mcp_group_mlp_bn_workspace_bytes(b, m, ..., backward) caller-owned bytes (backward = 0: z_l per pair and the partials;
+ * 1: also x, h_l, gy_l, gz_l, dx and mcp_linear_wgrad's sums).  Supported shapes: those of mcp_group_mlp; anything else
+ * MCP_ERR_UNSUPPORTED (sizes: 0), nothing launched.  features, packed, out, grad_out, grad_features, workspace 16-byte aligned.  No
+ * allocation, no environment variable, no host read of a length. */
+int mcp_group_mlp_bn_packed_floats(int c, int use_xyz, int layers, const int *widths);
+int mcp_group_mlp_bn_pack(int c, int use_xyz, int layers, const int *widths, const float *const *w, const float *const *b, float *packed,
+                          mcp_stream_t stream);
+size_t mcp_group_mlp_bn_workspace_bytes(int b, int m, int c, int nsample, int use_xyz, int layers, const int *widths, int backward);
+int mcp_group_mlp_bn_forward(int b, int n, int m, int c, int nsample, int use_xyz, int pool, int layers, const int *widths, const float *xyz,
+                             const float *new_xyz, const float *features, const int *idx, const int *qlen, const float *packed,
+                             const float *const *gamma, const float *const *beta, const float *eps, float *out, float *const *mean,
+                             float *const *var, float *const *rstd, int *count, void *workspace, size_t workspace_bytes, mcp_stream_t stream);
+int mcp_group_mlp_bn_backward(int b, int n, int m, int c, int nsample, int use_xyz, int pool, int layers, const int *widths, const float *xyz,
+                              const float *new_xyz, const float *features, const int *idx, const int *qlen, const float *packed,
+                              const float *const *gamma, const float *const *beta, const float *const *mean, const float *const *rstd,
+                              const float *grad_out, const int *order, const int *seg, float *grad_features, float *grad_xyz,
+                              float *grad_new_xyz, float *const *grad_w, float *const *grad_b, float *const *grad_gamma,
+                              float *const *grad_beta, void *workspace, size_t workspace_bytes, mcp_stream_t stream);
+
 /* Backward of mcp_cross_volume for one cross layer given by its own weights (the reference differentiates pointconv_util.py:765-781
  * with autograd over three materialised (B,D,32,N1) tensors; its hand-written backward pieces are the atomicAdd scatters of
  * group_points_gpu.cu:8-44).  xyz1, xyz2, points1, points2, idx / idx2 as mcp_cross_volume (no batch map); wpos (D,3), bpos (D),

@@ -91,6 +91,11 @@ SIGNATURES = {
     "mcp_fp_mlp_bn_workspace_bytes": [_i, _i, _i, _i, _i, _p, _i],
     "mcp_fp_mlp_bn_forward": [_i] * 7 + [_p] * 17 + [ctypes.c_size_t, _p],
     "mcp_fp_mlp_bn_backward": [_i] * 7 + [_p] * 22 + [ctypes.c_size_t, _p],
+    "mcp_group_mlp_bn_packed_floats": [_i, _i, _i, _p],
+    "mcp_group_mlp_bn_pack": [_i, _i, _i, _p, _p, _p, _p, _p],
+    "mcp_group_mlp_bn_workspace_bytes": [_i, _i, _i, _i, _i, _i, _p, _i],
+    "mcp_group_mlp_bn_forward": [_i] * 8 + [_p] * 16 + [ctypes.c_size_t, _p],
+    "mcp_group_mlp_bn_backward": [_i] * 8 + [_p] * 22 + [ctypes.c_size_t, _p],
     "mcp_cross_grad_floats": [_i],
     "mcp_cross_grad_workspace_bytes": [_i, _i, _i],
     "mcp_cross_grad": [_i] * 5 + [_p] * 17 + [ctypes.c_size_t, _p],
@@ -160,7 +165,7 @@ _RESTYPES = {"mcp_error_string": ctypes.c_char_p, "mcp_fps_workspace_bytes": cty
              "mcp_linear_wgrad_workspace_bytes": ctypes.c_size_t, "mcp_scatter_segments_workspace_bytes": ctypes.c_size_t,
              "mcp_prelu_dropout_grad_workspace_bytes": ctypes.c_size_t, "mcp_emd_levels_floats": ctypes.c_size_t,
              "mcp_fp_mlp_grad_workspace_bytes": ctypes.c_size_t, "mcp_group_mlp_grad_workspace_bytes": ctypes.c_size_t,
-             "mcp_fp_mlp_bn_workspace_bytes": ctypes.c_size_t}
+             "mcp_fp_mlp_bn_workspace_bytes": ctypes.c_size_t, "mcp_group_mlp_bn_workspace_bytes": ctypes.c_size_t}
 
 _lib = None
 

@@ -1,5 +1,6 @@
 // fp_mlp_tile.h -- the device code and the launch code that the three units of the fused feature-propagation layer share: the forward
-// (fp_mlp.hip), its backward (fp_mlp_grad.hip) and the training-mode BatchNorm form (fp_mlp_bn.hip).  fp_mlp_shape.h holds the host's
+// (fp_mlp.hip), its backward (fp_mlp_grad.hip) and the training-mode BatchNorm form (fp_mlp_bn.hip; through fp_mlp_bn_pass.h also the
+// set-abstraction layer's, group_mlp_bn.hip, which brings its own gather).  fp_mlp_shape.h holds the host's
 // shape arithmetic; this header holds what a wave does with one column of the MFMA: its row (FpRow), the layer-1 input k-step
 // (FpGather), the slab sequence with the hazard fence (FpSlabs), the small tile helpers, the dx epilogue, and the launch.  Every unit
 // keeps its argument structs, its pack kernel, its layer control flow and its epilogues.

@@ -1030,6 +1030,97 @@ class _FpMlpBnLayerFn(torch.autograd.Function):
         return (None, None, None, None, None, None, None, d_known, d_skip if ctx.needs_input_grad[8] else None, *pieces)
 
 
+# ---- set-abstraction layer with training-mode BatchNorm (csrc/group_mlp_bn.hip) ----
+def group_mlp_bn_supported(c, widths, nsample=1, use_xyz=True):
+    """The shapes mcp_group_mlp_bn_forward / _backward are built for: every shape of mcp_group_mlp (no row_bias)."""
+    return group_mlp_supported(c, widths, nsample, use_xyz)
+
+
+def group_mlp_bn_packed_floats(c, widths, use_xyz=True):
+    """Floats of mcp_group_mlp_bn_pack's image, one for both directions: per layer 32-channel output tiles x k-steps x 3 pieces x 64
+    lanes x 16 B (layer 1: the k-steps of c + 3 contiguous columns), the biases, then the transposed slabs -- for l = L .. 2 two
+    k-steps per tile of gz_l into the tiles of layer l - 1, then those of gz_1 into the ceil((c + 3) / 32) tiles of dx."""
+    tiles = [w // 32 for w in widths]
+    cin = c + (3 if use_xyz else 0)
+    ks = [(cin + 15) // 16] + [w // 16 for w in widths[:-1]]
+    fwd = sum(t * k for t, k in zip(tiles, ks))
+    bwd = sum(2 * tiles[l] * tiles[l - 1] for l in range(1, len(tiles))) + 2 * tiles[0] * ((cin + 31) // 32)
+    return (fwd + bwd) * 3 * 64 * 4 + sum(widths)
+
+
+# Shape classes (column group 8 | 16 | 32 | 64, feature channels, widths) -> fewest centres B * M at which the module's fused
+# training-mode route (ball query, transposition, mcp_group_mlp_bn_forward, mcp_group_mlp_bn_backward, the running-statistics update)
+# measured faster, forward + backward, than the composition's forward + backward by more than the composition's own spread
+# (tools/group_mlp_bn_times.py -> profiles/group_mlp_bn_times.json).  A class without a row keeps the composition.
+# Measured at B = 8 in train() (ms, forward + backward, composition first / fused / composition again): 16384 -> 1024 / ns 16 / 4 ->
+# 32/32/64 1.224 / 1.326 / 1.299 (spread 0.897), 1024 -> 256 / ns 16 / 64 -> 64/64/128 1.115 / 1.179 / 1.170 (spread 0.261), 256 -> 64 /
+# ns 8 / 128 -> 128/128/256 1.370 / 1.373 / 1.445 (spread 0.319): the fused route is 8 %, 6 % and 0.3 % slower than the composition's
+# first row, inside the composition's own spread everywhere, and no class enters.  What the route does change is the memory the
+# forward keeps for the backward: 4.7 MB against 144.7 MB at the first level.  Largest relative gradient difference between the
+# routes: 3.6e-06.
+# The table ships empty, as its two siblings do: filling it changes what existing callers run and is a change of its own.
+GROUP_MLP_BN_FUSED_CLASSES = {}
+
+
+def group_mlp_bn_routes_fused(c, widths, nsample, centres):
+    """PointnetSAModuleMSG's route predicate under a training-mode BatchNorm: a pure function of the padded shapes."""
+    least = GROUP_MLP_BN_FUSED_CLASSES.get(group_mlp_class(c, widths, nsample))
+    return least is not None and centres >= least
+
+
+def group_mlp_bn_pack_weights(weights, use_xyz=True):
+    """mcp_group_mlp_bn_pack's image from the unfolded [(W (out, in), b (out,)), ...] fp32 device tensors -> (packed, widths)."""
+    widths = [int(w.shape[0]) for w, _ in weights]
+    c = int(weights[0][0].shape[1]) - (3 if use_xyz else 0)
+    lib = _lib.load()
+    wid = (ctypes.c_int * len(widths))(*widths)
+    n = lib.mcp_group_mlp_bn_packed_floats(c, int(bool(use_xyz)), len(widths), wid) if len(widths) <= 3 and c >= 0 else 0
+    if n == 0:
+        raise _lib.Unsupported(f"group_mlp_bn: unsupported shape c={c} widths={widths}")
+    ws = [w.contiguous() for w, _ in weights]
+    bs = [b.contiguous() for _, b in weights]
+    packed = _grad_empty((n,), torch.float32, ws[0].device)
+    _call("mcp_group_mlp_bn_pack", packed, c, int(bool(use_xyz)), len(widths), wid, _ptr_array(ws), _ptr_array(bs), _lib.fptr(packed))
+    return packed, widths
+
+
+class _GroupMlpBnLayerFn(torch.autograd.Function):
+    """mcp_group_mlp_bn_forward with its hand-written backward (mcp_group_mlp_bn_backward).  Kept between the two: the inputs and the
+    per-layer (mean, rstd) -- no activation; the backward runs the forward passes again with the statistics given.  Outputs: out, then
+    per layer (mean, biased variance), then the live count; all but out are marked non-differentiable.  Gradients: xyz, new_xyz,
+    features, every W, b, gamma and beta; idx and the lengths get none."""
+
+    @staticmethod
+    def forward(ctx, be, pool, use_xyz, idx, ql, eps, xyz, new_xyz, features, *params):
+        xyz, new_xyz = xyz.detach().contiguous(), new_xyz.detach().contiguous()
+        features = None if features is None else features.detach().contiguous()
+        params = [None if t is None else t.detach().contiguous() for t in params]
+        layers = list(zip(params[0::4], params[1::4], params[2::4], params[3::4]))
+        out, mean, var, rstd, count = be.group_mlp_bn_forward(xyz, new_xyz, features, idx, layers, eps, pool=pool, use_xyz=use_xyz, new_xyz_lengths=ql)
+        ctx.be, ctx.pool, ctx.use_xyz, ctx.layers = be, pool, use_xyz, len(layers)
+        ctx.save_for_backward(idx, ql, xyz, new_xyz, features, *params, *mean, *rstd)
+        stats = [t for pair in zip(mean, var) for t in pair]
+        ctx.mark_non_differentiable(*stats, count)
+        return (out, *stats, count)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out, *_):
+        idx, ql, xyz, new_xyz, features, *rest = ctx.saved_tensors
+        L = ctx.layers
+        params, mean, rstd = rest[:4 * L], rest[4 * L:5 * L], rest[5 * L:]
+        layers = list(zip(params[0::4], params[1::4], params[2::4], params[3::4]))
+        need = ctx.needs_input_grad
+        d_feat, d_xyz, d_new, d_layers = ctx.be.group_mlp_bn_backward(
+            xyz, new_xyz, features, idx, layers, mean, rstd, grad_out, pool=ctx.pool, use_xyz=ctx.use_xyz, new_xyz_lengths=ql,
+            want_features=need[8] and features is not None, want_xyz=need[6] and ctx.use_xyz, want_new_xyz=need[7] and ctx.use_xyz)
+        zeros = lambda t, wanted: torch.zeros_like(t) if wanted else None   # coordinates that never enter the layer
+        if not ctx.use_xyz:
+            d_xyz, d_new = zeros(xyz, need[6]), zeros(new_xyz, need[7])
+        pieces = [t for quad in d_layers for t in quad]
+        return (None, None, None, None, None, None, d_xyz, d_new, d_feat, *pieces)
+
+
 class _ChamferLengthsFn(torch.autograd.Function):
     """_ChamferFn over the valid prefixes of a padded batch (pytorch3d's x_lengths / y_lengths with its default reductions):
     value_b = sum_{i<xl} dxy_i / max(xl,1) + sum_{j<yl} dyx_j / max(yl,1).  Forward: the length-aware search returns 0 for every
@@ -1899,6 +1990,98 @@ class HipBackend:
         ul = lengths_tensor(unknown_lengths, B, n, known_feats.device)
         flat = [t for layer in layers for t in layer[:4]]
         out, *rest = _FpMlpBnLayerFn.apply(self, rule, idx.contiguous(), dist, w3, ul, tuple(float(layer[4]) for layer in layers), known_feats, skip, *flat)
+        return out, list(zip(rest[0:-1:2], rest[1:-1:2])), rest[-1]
+
+    def _group_mlp_bn_check(self, name, xyz, new_xyz, features, idx, layers, use_xyz):
+        B, N, _ = xyz.shape
+        M, nsample = new_xyz.shape[1], idx.shape[2]
+        C = 0 if features is None else features.shape[2]
+        if tuple(idx.shape[:2]) != (B, M) or (features is not None and tuple(features.shape[:2]) != (B, N)):
+            raise RuntimeError(f"{name}: idx {tuple(idx.shape)} / features do not match B={B}, N={N}, M={M}")
+        widths = [int(l[0].shape[0]) for l in layers]
+        cin = C + (3 if use_xyz else 0)
+        if not group_mlp_bn_supported(C, widths, nsample, use_xyz) or int(layers[0][0].shape[1]) != cin:
+            raise _lib.Unsupported(f"{name}: unsupported shape c={C} widths={widths} nsample={nsample}")
+        for (w, b, gamma, beta), k, o in zip(layers, [cin, *widths[:-1]], widths):
+            if tuple(w.shape) != (o, k) or any(t is not None and tuple(t.shape) != (o,) for t in (b, gamma, beta)):
+                raise RuntimeError(f"{name}: expected W {(o, k)} and b, gamma, beta {(o,)}")
+        if B == 0 or N == 0 or M == 0:
+            raise RuntimeError(f"{name}: empty batch, cloud or centre list")
+        return B, N, M, C, nsample, widths
+
+    def group_mlp_bn_forward(self, xyz, new_xyz, features, idx, layers, eps, pool="max", use_xyz=True, new_xyz_lengths=None):
+        """The set-abstraction layer with batch statistics (mcp_group_mlp_bn_forward): arguments as group_mlp, layers = [(W (out, in),
+        b or None, gamma or None, beta or None), ...] fp32 with W_1's position columns first, eps one float per layer -> (out
+        (B,M,widths[-1]), [mean_l], [biased var_l], [rstd_l], count (1,) int32: the live (centre, slot) pairs, on the device).
+        Padded centres give zeros and enter no statistic."""
+        B, N, M, C, nsample, widths = self._group_mlp_bn_check("group_mlp_bn_forward", xyz, new_xyz, features, idx, layers, use_xyz)
+        if len(eps) != len(layers) or not all(float(e) > 0 for e in eps):
+            raise RuntimeError("group_mlp_bn_forward: one eps > 0 per layer")
+        dev = xyz.device
+        lib = _lib.load()
+        ql = lengths_tensor(new_xyz_lengths, B, M, dev)
+        packed, _ = group_mlp_bn_pack_weights([(w, torch.zeros_like(w[:, 0]) if b is None else b) for w, b, _, _ in layers], use_xyz)
+        wid = (ctypes.c_int * len(widths))(*widths)
+        need = lib.mcp_group_mlp_bn_workspace_bytes(B, M, C, nsample, int(bool(use_xyz)), len(widths), wid, 0)
+        if need == 0:
+            raise _lib.Unsupported(f"group_mlp_bn_forward: unsupported shape c={C} widths={widths} pairs={B * M * nsample}")
+        ws = _grad_empty((need,), torch.uint8, dev)
+        out = _grad_empty((B, M, widths[-1]), torch.float32, dev)
+        mean, var, rstd = ([_grad_empty((o,), torch.float32, dev) for o in widths] for _ in range(3))
+        count = _grad_empty((1,), torch.int32, dev)
+        _call("mcp_group_mlp_bn_forward", xyz, B, N, M, C, nsample, int(bool(use_xyz)), GROUP_MLP_POOLS[pool], len(widths), wid, _lib.fptr(xyz),
+              _lib.fptr(new_xyz), None if features is None else _lib.fptr(features), _lib.iptr(idx), None if ql is None else _lib.iptr(ql),
+              _lib.fptr(packed), _ptr_array([g for _, _, g, _ in layers]), _ptr_array([bt for _, _, _, bt in layers]),
+              (ctypes.c_float * len(eps))(*[float(e) for e in eps]), _lib.fptr(out), _ptr_array(mean), _ptr_array(var), _ptr_array(rstd),
+              _lib.iptr(count), ws.data_ptr(), need)
+        return out, mean, var, rstd, count
+
+    def group_mlp_bn_backward(self, xyz, new_xyz, features, idx, layers, mean, rstd, grad_out, pool="max", use_xyz=True, new_xyz_lengths=None,
+                              want_features=True, want_xyz=True, want_new_xyz=True):
+        """Backward of group_mlp_bn_forward (mcp_group_mlp_bn_backward) from the forward's inputs, its per-layer (mean, rstd) and
+        grad_out (B,M,widths[-1]) -> (grad_features (B,N,C), grad_xyz (B,N,3), grad_new_xyz (B,M,3) -- each None when not wanted or not
+        part of the layer --, [(dW, db or None, dgamma or None, dbeta or None), ...]; a parameter that is None gets None).
+        Bit-reproducible; unsupported shapes raise."""
+        B, N, M, C, nsample, widths = self._group_mlp_bn_check("group_mlp_bn_backward", xyz, new_xyz, features, idx, layers, use_xyz)
+        if tuple(grad_out.shape) != (B, M, widths[-1]):
+            raise RuntimeError(f"group_mlp_bn_backward: grad_out {tuple(grad_out.shape)}, expected {(B, M, widths[-1])}")
+        dev = xyz.device
+        lib = _lib.load()
+        ql = lengths_tensor(new_xyz_lengths, B, M, dev)
+        grad_out = grad_out.contiguous()
+        packed, _ = group_mlp_bn_pack_weights([(w, torch.zeros_like(w[:, 0]) if b is None else b) for w, b, _, _ in layers], use_xyz)
+        wid = (ctypes.c_int * len(widths))(*widths)
+        need = lib.mcp_group_mlp_bn_workspace_bytes(B, M, C, nsample, int(bool(use_xyz)), len(widths), wid, 1)
+        if need == 0:
+            raise _lib.Unsupported(f"group_mlp_bn_backward: unsupported shape c={C} widths={widths} pairs={B * M * nsample}")
+        want_features, want_xyz, want_new_xyz = bool(want_features) and C > 0, bool(want_xyz) and use_xyz, bool(want_new_xyz) and use_xyz
+        ws = _grad_empty((need,), torch.uint8, dev)
+        d_feat = _grad_empty((B, N, C), torch.float32, dev) if want_features else None
+        d_xyz = _grad_empty((B, N, 3), torch.float32, dev) if want_xyz else None
+        d_new = _grad_empty((B, M, 3), torch.float32, dev) if want_new_xyz else None
+        like = lambda t: None if t is None else _grad_empty(tuple(t.shape), torch.float32, dev)
+        d_layers = [tuple(like(t) for t in layer) for layer in layers]
+        order, seg = _scatter_segments(idx.reshape(B, M * nsample), N) if (want_features or want_xyz) else (None, None)
+        opt = lambda t, ptr=_lib.fptr: None if t is None else ptr(t)
+        _call("mcp_group_mlp_bn_backward", xyz, B, N, M, C, nsample, int(bool(use_xyz)), GROUP_MLP_POOLS[pool], len(widths), wid, _lib.fptr(xyz),
+              _lib.fptr(new_xyz), opt(features), _lib.iptr(idx), opt(ql, _lib.iptr), _lib.fptr(packed), _ptr_array([g for _, _, g, _ in layers]),
+              _ptr_array([bt for _, _, _, bt in layers]), _ptr_array(list(mean)), _ptr_array(list(rstd)), _lib.fptr(grad_out),
+              opt(order, _lib.iptr), opt(seg, _lib.iptr), opt(d_feat), opt(d_xyz), opt(d_new),
+              *[_ptr_array([d[i] for d in d_layers]) for i in range(4)], ws.data_ptr(), need)
+        return d_feat, d_xyz, d_new, d_layers
+
+    def group_mlp_bn_layer(self, xyz, new_xyz, features, idx, layers, pool="max", use_xyz=True, new_xyz_lengths=None):
+        """The set-abstraction layer under a training-mode BatchNorm from its own parameters: layers = [(W (out, in), b or None, gamma or
+        None, beta or None, eps), ...]; other arguments as group_mlp -> (out (B,M,widths[-1]), [(mean_l, biased var_l), ...], count
+        (1,) int32 on the device: the live (centre, slot) pairs).  An autograd function -- mcp_group_mlp_bn_forward,
+        mcp_group_mlp_bn_backward -- with gradients for xyz, new_xyz, features and every W, b, gamma, beta; idx, the lengths, the
+        statistics and the count get none.  It runs with or without a wanted gradient (the caller's running statistics need the batch
+        statistics either way)."""
+        B, M = new_xyz.shape[0], new_xyz.shape[1]
+        ql = lengths_tensor(new_xyz_lengths, B, M, xyz.device)
+        flat = [t for layer in layers for t in layer[:4]]
+        out, *rest = _GroupMlpBnLayerFn.apply(self, pool, bool(use_xyz), idx.contiguous(), ql, tuple(float(layer[4]) for layer in layers), xyz, new_xyz,
+                                              features, *flat)
         return out, list(zip(rest[0:-1:2], rest[1:-1:2])), rest[-1]
 
     def ptblock_layer(self, xyz, q, k, v, idx, weights, packed=None):

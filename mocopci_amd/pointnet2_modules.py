@@ -14,6 +14,10 @@ Two routes give the same layer:
     forward, mcp_group_mlp_grad backward: the ball query on detached coordinates, gradients for xyz, new_xyz, the features and the
     stack's parameters through ops.fold_conv_bn_grad), taken in eval() or without BatchNorm for a class of
     ops.GROUP_MLP_GRAD_FUSED_CLASSES (tools/group_mlp_grad_times.py; `grad_route` overrides it).
+    Under train() with BatchNorm a scale has a third route: the layer with batch statistics, ops.HipBackend.group_mlp_bn_layer
+    (mcp_group_mlp_bn_forward / mcp_group_mlp_bn_backward), after which the module updates every BatchNorm2d's running statistics as
+    torch does -- taken with or without a wanted gradient, never with lengths or with npoint=None, for a class of
+    ops.GROUP_MLP_BN_FUSED_CLASSES (tools/group_mlp_bn_times.py; `bn_route` overrides it).
 PointnetFPModule has the same two routes: the composition -- three_nn, the weights in torch, three_interpolate, cat, the shared
 stack -- and one mcp_fp_mlp launch after the three-neighbour search (ops.HipBackend.fp_mlp; ops.FP_MLP_FUSED_CLASSES from
 tools/fp_mlp_times.py).  When a gradient is wanted its fused route is the differentiable layer ops.HipBackend.fp_mlp_layer
@@ -49,6 +53,18 @@ def _conv_unit(cin, cout, bn, instance_norm):
     return unit
 
 
+def _track(bn, mean, var, rows):
+    """nn.BatchNorm2d's update of its running statistics from the batch mean and the biased batch variance over `rows` rows."""
+    if not bn.track_running_stats or bn.running_mean is None:
+        return
+    with torch.no_grad():
+        if bn.num_batches_tracked is not None:
+            bn.num_batches_tracked += 1
+        f = bn.momentum if bn.momentum is not None else 1.0 / bn.num_batches_tracked.to(torch.float32)
+        bn.running_mean.mul_(1.0 - f).add_(f * mean)
+        bn.running_var.mul_(1.0 - f).add_(f * (var * (rows / (rows - 1.0))))
+
+
 def _shared_mlp(spec, bn, instance_norm):
     mlp = nn.Sequential()
     for j in range(len(spec) - 1):
@@ -61,8 +77,10 @@ class PointnetSAModuleMSG(nn.Module):
     nsamples[i] slots, the shared MLP mlps[i] (its first entry counts the feature channels; 3 is added with use_xyz) and the pool.
     npoint=None groups the whole cloud (GroupAll).  route: "measured" (default), "always" or "never" for the fused route when no
     gradient is wanted; grad_route: the same three values, independently, for the fused differentiable route (mcp_group_mlp forward,
-    mcp_group_mlp_grad backward) when one is -- eligible in eval() or with bn=False; a training-mode BatchNorm keeps the
-    composition."""
+    mcp_group_mlp_grad backward) when one is -- eligible in eval() or with bn=False.  bn_route: the same three values,
+    independently, for the route with batch statistics (mcp_group_mlp_bn_forward / mcp_group_mlp_bn_backward) under train() with
+    bn=True, with or without a wanted gradient; a call with lengths keeps the composition there (its batch statistics count the
+    padded rows, the kernel's do not), and so does npoint=None."""
 
     def __init__(self, *, npoint: int, radii: List[float], nsamples: List[int], mlps: List[List[int]], bn: bool = True, use_xyz: bool = True,
                  pool_method="max_pool", instance_norm=False):
@@ -74,6 +92,7 @@ class PointnetSAModuleMSG(nn.Module):
         self.npoint, self.use_xyz, self.pool_method, self.bn, self.instance_norm = npoint, use_xyz, pool_method, bn, instance_norm
         self.route = "measured"
         self.grad_route = "measured"
+        self.bn_route = "measured"
         self.groupers, self.mlps = nn.ModuleList(), nn.ModuleList()
         for radius, nsample, spec in zip(radii, nsamples, mlps):
             self.groupers.append(pu.QueryAndGroup(radius, nsample, use_xyz=use_xyz) if npoint is not None else pu.GroupAll(use_xyz))
@@ -116,6 +135,17 @@ class PointnetSAModuleMSG(nn.Module):
             return False
         return self.grad_route == "always" or ops.group_mlp_grad_routes_fused(channels, widths, g.nsample, centres)
 
+    def fused_scale_bn(self, i, channels, centres, with_lengths=False):
+        """Whether scale i of a call under train() with BatchNorm takes the fused route with batch statistics (a batch of one pair is
+        left to torch, which refuses it)."""
+        if not (self.training and self.bn) or self.npoint is None or with_lengths or self.bn_route == "never":
+            return False
+        g = self.groupers[i]
+        widths = [u.conv.out_channels for u in self.mlps[i].children()]
+        if centres * g.nsample < 2 or not ops.group_mlp_bn_supported(channels, widths, g.nsample, self.use_xyz):
+            return False
+        return self.bn_route == "always" or ops.group_mlp_bn_routes_fused(channels, widths, g.nsample, centres)
+
     def forward(self, xyz: torch.Tensor, features: torch.Tensor = None, new_xyz=None, xyz_lengths=None, new_xyz_lengths=None):
         """xyz (B,N,3), features (B,C,N) or None, new_xyz (B,npoint,3) or None (sampled here) -> new_xyz, (B, sum C_out, npoint).
         xyz_lengths / new_xyz_lengths (forms: ops.lengths_tensor): element b is its first xyz_lengths[b] points with the centres
@@ -140,6 +170,19 @@ class PointnetSAModuleMSG(nn.Module):
         rows_grad = None  # the same, attached to the graph, for the differentiable fused scales
         outs = []
         for i, grouper in enumerate(self.groupers):
+            if self.fused_scale_bn(i, C, B * M, with_lengths):
+                if features is not None and rows_grad is None:
+                    rows_grad = features.transpose(1, 2).contiguous()
+                # the neighbour list is a constant of the layer: no gradient reaches the search
+                idx = be.ball_query(xyz.detach().contiguous(), new_xyz.detach().contiguous(), grouper.radius, grouper.nsample)
+                convs, bns = self._layers(i)
+                layers = [(c.weight.flatten(1), c.bias, b.weight, b.bias, b.eps) for c, b in zip(convs, bns)]
+                pooled, stats, _ = be.group_mlp_bn_layer(xyz.contiguous(), new_xyz.contiguous(), rows_grad, idx, layers, pool=self.pool_method,
+                                                         use_xyz=self.use_xyz)
+                for b, (mean, var) in zip(bns, stats):
+                    _track(b, mean, var, B * M * grouper.nsample)
+                outs.append(pooled.transpose(1, 2))
+                continue
             if not wants_grad and self.fused_scale(i, C, B * M):
                 packed, widths = self._packed_weights(i)
                 x, c = xyz.detach().contiguous(), new_xyz.detach().contiguous()
@@ -246,18 +289,6 @@ class PointnetFPModule(nn.Module):
             return False
         return self.bn_route == "always" or ops.fp_mlp_bn_routes_fused(c2, c1, widths, rows)
 
-    @staticmethod
-    def _track(bn, mean, var, rows):
-        """nn.BatchNorm2d's update of its running statistics from the batch mean and the biased batch variance over `rows` rows."""
-        if not bn.track_running_stats or bn.running_mean is None:
-            return
-        with torch.no_grad():
-            if bn.num_batches_tracked is not None:
-                bn.num_batches_tracked += 1
-            f = bn.momentum if bn.momentum is not None else 1.0 / bn.num_batches_tracked.to(torch.float32)
-            bn.running_mean.mul_(1.0 - f).add_(f * mean)
-            bn.running_var.mul_(1.0 - f).add_(f * (var * (rows / (rows - 1.0))))
-
     def weights(self, dist):
         """(B,n,3) interpolation weights of three_nn's distances under `weighting`; a row without a finite distance gets zeros."""
         if self.weighting == "pointnet2":
@@ -293,7 +324,7 @@ class PointnetFPModule(nn.Module):
             layers = [(c.weight.flatten(1), c.bias, b.weight, b.bias, b.eps) for c, b in zip(convs, bns)]
             out, stats, _ = ops.backend().fp_mlp_bn_layer(rows, skip, idx, dist, layers, rule=self.weighting)
             for b, (mean, var) in zip(bns, stats):
-                self._track(b, mean, var, B * n)
+                _track(b, mean, var, B * n)
             return out.transpose(1, 2)
         if known is not None and not wants_grad and self.fused(C2, C1, B * n):
             packed, widths = self._packed_weights(C2)
