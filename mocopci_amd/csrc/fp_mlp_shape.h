@@ -1,14 +1,14 @@
 // fp_mlp_shape.h -- the shape arithmetic of the fused feature-propagation layer, shared by its forward (fp_mlp.hip), its backward
 // (fp_mlp_grad.hip) and its training-mode BatchNorm form (fp_mlp_bn.hip): which shapes are built, the k-steps and output tiles of
 // every layer, the size of the forward weight image, the register class, and how a caller-owned workspace is laid out.  Host code
-// only; the device code and the launch code the three units share are in fp_mlp_tile.h, which includes this header.
+// only; the device code and the launch code the three units share are in fp_mlp_tile.h, which includes this header.  MAX_LAYERS,
+// TILE_U4, LDS_IMAGE_BYTES and FpTake are also the set-abstraction layer's (group_mlp_shape.h includes this header), so nothing
+// here names a workgroup's size: WAVES and THREADS are fp_mlp_tile.h's.
 #pragma once
 #include "common.h"
 
 namespace {
 
-constexpr int WAVES = 4;
-constexpr int THREADS = 64 * WAVES;
 constexpr int MAX_LAYERS = 3;
 constexpr int TILE_U4 = 3 * 64;               // uint4 of one (output tile, k-step): three pieces of 64 lanes
 constexpr int LDS_IMAGE_BYTES = 64 * 1024;    // largest weight image staged whole

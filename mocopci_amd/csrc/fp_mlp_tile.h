@@ -19,6 +19,8 @@
 
 namespace {
 
+constexpr int WAVES = 4;
+constexpr int THREADS = 64 * WAVES;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 

@@ -39,47 +39,17 @@
 // of at most 64 KB is staged in LDS once per workgroup (two workgroups per CU still fit); a larger one is read through L2 tile by
 // tile, as cross_grad_kernel<128> reads its image.  Register classes: KMAX = 4 (c <= 64 and hidden widths <= 64; two waves per
 // SIMD) and KMAX = 8 (one wave per SIMD).
-#include "common.h"
-#include "mfma_split.h"
-#include "group_mlp_shape.h"
+//
+// The column's centre, the position operand, the head of a layer-1 tile, the butterflies, the pack kernel and the launch are
+// group_mlp_tile.h's, shared with group_mlp_grad.hip and group_mlp_bn.hip.
+#include <type_traits>
+
+#include "group_mlp_tile.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int WAVES = 4;
 constexpr int POOL_ROW = 256;                 // floats of a wave's pooled row (the widest last layer)
-
-// One layer of the image.  Pieces: mcp_split_weights' layout over the columns col0 .. col0 + cvalid - 1 of w (tiles * 32, ld),
-// zero beyond cvalid up to 16 * ks.  pos (layer 1 only): [t][s][lane] = w[32t + (lane&31)][2s + (lane>>5)] for the three coordinate
-// columns, 0 for the fourth.  Bias: [t][h][r].
-__global__ __launch_bounds__(256) void group_mlp_pack_kernel(const float *__restrict__ w, const float *__restrict__ b, int ld, int col0, int cvalid,
-                                                             int ks, int tiles, int use_xyz, uint4 *__restrict__ dstw, float *__restrict__ dstpos,
-                                                             float *__restrict__ dstb) {
-    const int first = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256;
-    for (int e = first; e < tiles * ks * 64; e += stride) {
-        const int lane = e & 63, s = (e >> 6) % ks, t = (e >> 6) / ks;
-        float v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int ch = 32 * (s >> 1) + mcp_chan_of(8 * (s & 1) + i, lane >> 5);
-            v[i] = ch < cvalid ? w[(size_t)(32 * t + (lane & 31)) * ld + col0 + ch] : 0.f;
-        }
-        const McpSplit3 sp = mcp_split8(v);
-        uint4 *o = dstw + (size_t)(t * ks + s) * 3 * 64 + lane;
-        o[0] = sp.p1;
-        o[64] = sp.p2;
-        o[128] = sp.p3;
-    }
-    if (dstpos)
-        for (int e = first; e < tiles * 128; e += stride) {
-            const int lane = e & 63, s = (e >> 6) & 1, t = e >> 7, cc = 2 * s + (lane >> 5);
-            dstpos[e] = (use_xyz && cc < 3) ? w[(size_t)(32 * t + (lane & 31)) * ld + cc] : 0.f;
-        }
-    for (int e = first; e < tiles * 32; e += stride) {
-        const int r = e & 15, h = (e >> 4) & 1, t = e >> 5;
-        dstb[e] = b[32 * t + mcp_chan_of(r, h)];
-    }
-}
 
 struct GmArgs {
     long long total;  // B * M centres
@@ -124,19 +94,8 @@ __global__ __launch_bounds__(64 * WAVES, KMAX == 4 ? 2 : 1) void group_mlp_kerne
     float *prow = prow_all + wave * POOL_ROW;
     const int P = 1 << a.logp, G = 32 >> a.logp, slot = col & (P - 1);
     const int wfirst = a.tiles[0] * 32, wlast = a.tiles[a.layers - 1] * 32;
-    const bool fits32 = mcp_fits32(a.total);
     const float fn = (float)a.nsample;
 
-    auto bias_tile = [&](int l, int t, int hh) {
-        f32x16 acc;
-        const float4 *bq = reinterpret_cast<const float4 *>(small + a.boff[l] + (t * 2 + hh) * 16);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const float4 v = bq[g];
-            acc[4 * g + 0] = v.x; acc[4 * g + 1] = v.y; acc[4 * g + 2] = v.z; acc[4 * g + 3] = v.w;
-        }
-        return acc;
-    };
     auto relu_tile = [&](f32x16 acc) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = fmaxf(acc[r], 0.f);
@@ -146,16 +105,9 @@ __global__ __launch_bounds__(64 * WAVES, KMAX == 4 ? 2 : 1) void group_mlp_kerne
     const long long units = (a.total + G - 1) / G;
     const McpUnits deal = mcp_units_by_xcd(units, WAVES);
     for (long long unit = deal.first + wave; unit < deal.limit; unit += deal.stride) {
-        const long long p = unit * G + (col >> a.logp);  // this column's centre
-        const bool inr = p < a.total;
-        const long long bb = inr ? mcp_div(p, a.m, fits32) : 0;
-        bool live = inr;
-        if (inr && qlen) {
-            const int ql = min(max(qlen[bb], 0), a.m);
-            live = (int)(p - bb * a.m) < ql;
-        }
-        float cx = 0.f, cy = 0.f, cz = 0.f;
-        if (live && a.use_xyz) { cx = new_xyz[p * 3 + 0]; cy = new_xyz[p * 3 + 1]; cz = new_xyz[p * 3 + 2]; }
+        const GmCentre me(unit, col, a.logp, a.total, a.m, qlen);   // this column's centre
+        const long long p = me.p, bb = me.bb;
+        const bool inr = me.inr, live = me.live;
 
         for (int ct = 0; ct < a.ctiles; ++ct) {
             // The lane's offset into the weight image, the position columns and the biases, opaque to the compiler once per tile: every
@@ -166,13 +118,7 @@ __global__ __launch_bounds__(64 * WAVES, KMAX == 4 ? 2 : 1) void group_mlp_kerne
             const bool valid = j < a.nsample;
             const int k = live ? idx[p * a.nsample + (valid ? j : 0)] : 0;
             const long long row = bb * a.n + k;
-            float in0 = 0.f, in1 = 0.f;
-            if (live && a.use_xyz) {
-                const float *q = xyz + row * 3;
-                const float dx = q[0] - cx, dy = q[1] - cy, dz = q[2] - cz;
-                in0 = h ? dy : dx;   // k-step 0: (dx, dy); k-step 1: (dz, 0)
-                in1 = h ? 0.f : dz;
-            }
+            const GmPos pos = gm_position(xyz + row * 3, new_xyz + p * 3, live && a.use_xyz, h);
             McpSplit3 xs0[KMAX];
 #pragma unroll
             for (int s = 0; s < KMAX; ++s) {
@@ -191,27 +137,13 @@ __global__ __launch_bounds__(64 * WAVES, KMAX == 4 ? 2 : 1) void group_mlp_kerne
 
             // output tile t of layer 1, after its ReLU
             auto first_tile = [&](int t) {
-                f32x16 acc = bias_tile(0, t, hl);
-                if (row_bias) {
-                    if (live) {
-                        const float4 *rb = reinterpret_cast<const float4 *>(row_bias + p * wfirst + 32 * t + 4 * h);
-#pragma unroll
-                        for (int g = 0; g < 4; ++g) {
-                            const float4 v = rb[2 * g];
-                            acc[4 * g + 0] += v.x; acc[4 * g + 1] += v.y; acc[4 * g + 2] += v.z; acc[4 * g + 3] += v.w;
-                        }
-                    }
-                }
-                if (a.use_xyz) {
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(small[(t * 2 + 0) * 64 + ll], in0, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(small[(t * 2 + 1) * 64 + ll], in1, acc, 0, 0, 0);
-                }
+                f32x16 acc = gm_layer1_head(small, a.boff[0], t, hl, ll, row_bias, p, wfirst, live, a.use_xyz, pos);
                 if (a.ks[0]) acc = gm_tile_dyn<KMAX>(wimg + a.woff[0] + (size_t)t * a.ks[0] * 3 * 64 + ll, xs0, a.ks[0], acc);
                 return relu_tile(acc);
             };
             // output tile t of layer l >= 1 from the previous layer's split activations
             auto next_tile = [&](int l, int t, const McpSplit3 *xs) {
-                f32x16 acc = bias_tile(l, t, hl);
+                f32x16 acc = gm_bias_tile(small + a.boff[l], t, hl);
                 acc = gm_tile_dyn<KMAX>(wimg + a.woff[l] + (size_t)t * a.ks[l] * 3 * 64 + ll, xs, a.ks[l], acc);
                 return relu_tile(acc);
             };
@@ -219,26 +151,10 @@ __global__ __launch_bounds__(64 * WAVES, KMAX == 4 ? 2 : 1) void group_mlp_kerne
             auto pool_tile = [&](int t, f32x16 acc) {
                 if (a.pool) {
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        float v = valid ? acc[r] : 0.f;
-                        v += __uint_as_float(mcp_dpp<0xB1>(__float_as_uint(v)));    // quad_perm [1,0,3,2]
-                        v += __uint_as_float(mcp_dpp<0x4E>(__float_as_uint(v)));    // quad_perm [2,3,0,1]
-                        v += __uint_as_float(mcp_dpp<0x141>(__float_as_uint(v)));   // row_half_mirror: the other quad of the 8
-                        if (a.logp >= 4) v += __uint_as_float(mcp_dpp<0x140>(__float_as_uint(v)));  // row_mirror: the other 8 of the row
-                        if (a.logp == 5) v += __shfl_xor(v, 16);
-                        acc[r] = v;
-                    }
+                    for (int r = 0; r < 16; ++r) acc[r] = gm_group_sum(valid ? acc[r] : 0.f, a.logp);
                 } else {
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        float v = acc[r];
-                        v = fmaxf(v, __uint_as_float(mcp_dpp<0xB1>(__float_as_uint(v))));
-                        v = fmaxf(v, __uint_as_float(mcp_dpp<0x4E>(__float_as_uint(v))));
-                        v = fmaxf(v, __uint_as_float(mcp_dpp<0x141>(__float_as_uint(v))));
-                        if (a.logp >= 4) v = fmaxf(v, __uint_as_float(mcp_dpp<0x140>(__float_as_uint(v))));
-                        if (a.logp == 5) v = fmaxf(v, __shfl_xor(v, 16));
-                        acc[r] = v;
-                    }
+                    for (int r = 0; r < 16; ++r) acc[r] = gm_group_max(acc[r], a.logp);
                 }
                 if (slot == 0 && inr) {
 #pragma unroll
@@ -293,31 +209,11 @@ __global__ __launch_bounds__(64 * WAVES, KMAX == 4 ? 2 : 1) void group_mlp_kerne
     }
 }
 
-template <int KMAX, bool LDSW>
-int launch_group_mlp(const GmArgs &a, const float *xyz, const float *new_xyz, const float *features, const int *idx, const int *qlen,
-                     const float *row_bias, const float *packed, float *out, hipStream_t s) {
-    auto kern = group_mlp_kernel<KMAX, LDSW>;
-    static McpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_once.done();
-    }
-    const size_t lds = (size_t)(a.small_floats + WAVES * POOL_ROW) * sizeof(float) + (LDSW ? (size_t)a.w_u4 * 16 : 0);
-    const int G = 32 >> a.logp;
-    const long long units = (a.total + G - 1) / G;
-    // persistent grid: the resident slots (256 CUs x 2 or 1 workgroups, see __launch_bounds__)
-    const long long want = (units + WAVES - 1) / WAVES, cap = KMAX == 4 ? 512 : 256;
-    const unsigned grid = (unsigned)max(1LL, min(want, cap));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WAVES), lds, s, a, xyz, new_xyz, features, idx, qlen, row_bias, packed, out);
-    return mcp_launch_status();
-}
-
 }  // namespace
 
 MCP_EXPORT int mcp_group_mlp_packed_floats(int c, int layers, const int *widths) {
     GmShape sh;
-    if (!gm_shape(c, layers, widths, &sh)) return 0;
+    if (!gm_shape(c, 1, layers, widths, &sh)) return 0;   // the image's size does not depend on use_xyz
     return sh.w_u4 * 4 + sh.small_floats;
 }
 
@@ -325,19 +221,15 @@ MCP_EXPORT int mcp_group_mlp_pack(int c, int use_xyz, int layers, const int *wid
                                   mcp_stream_t stream) {
     MCP_CHECK_ARGS(widths && w && b && packed);
     GmShape sh;
-    if (!gm_shape(c, layers, widths, &sh) || (c == 0 && !use_xyz)) return MCP_ERR_UNSUPPORTED;
+    if (!gm_shape(c, use_xyz, layers, widths, &sh)) return MCP_ERR_UNSUPPORTED;
     for (int l = 0; l < layers; ++l) MCP_CHECK_ARGS(w[l] && b[l]);
     if (((uintptr_t)packed) & 15) return MCP_ERR_BAD_ARG;
-    hipStream_t s = (hipStream_t)stream;
     uint4 *pw = reinterpret_cast<uint4 *>(packed);
     float *small = packed + (size_t)sh.w_u4 * 4;
-    for (int l = 0; l < layers; ++l) {
-        const int col0 = (l == 0 && use_xyz) ? 3 : 0;
-        const int cvalid = l == 0 ? c : widths[l - 1], ld = col0 + cvalid;
-        const int work = max(sh.tiles[l] * sh.ks[l] * 64, sh.tiles[l] * 128);
-        hipLaunchKernelGGL(group_mlp_pack_kernel, dim3((work + 255) / 256), dim3(256), 0, s, w[l], b[l], ld, col0, cvalid, sh.ks[l], sh.tiles[l], use_xyz,
-                           pw + sh.woff[l], l == 0 ? small : nullptr, small + sh.boff[l]);
-        const int rc = mcp_launch_status();
+    for (int l = 0; l < layers; ++l) {   // entries [t][s]; layer 1's position columns go to the small part, not behind the features
+        const int col0 = l == 0 ? sh.x.px : 0, cvalid = l == 0 ? c : widths[l - 1];
+        const int rc = gm_pack_fwd((hipStream_t)stream, w[l], b[l], col0 + cvalid, col0, cvalid, 0, sh.ks[l], sh.tiles[l], sh.ks[l], 1, pw + sh.woff[l],
+                                   l == 0 ? small : nullptr, small + sh.boff[l]);
         if (rc != MCP_OK) return rc;
     }
     return MCP_OK;
@@ -349,21 +241,26 @@ MCP_EXPORT int mcp_group_mlp(int b, int n, int m, int c, int nsample, int use_xy
     MCP_CHECK_ARGS(b > 0 && n > 0 && m > 0 && widths && idx && packed && out && (pool == 0 || pool == 1));
     MCP_CHECK_ARGS((!use_xyz || (xyz && new_xyz)) && (c <= 0 || features));
     GmShape sh;
-    if (!gm_shape(c, layers, widths, &sh) || nsample < 1 || nsample > 64 || (c == 0 && !use_xyz)) return MCP_ERR_UNSUPPORTED;
+    if (!gm_shape(c, use_xyz, layers, widths, &sh) || nsample < 1 || nsample > 64) return MCP_ERR_UNSUPPORTED;
     if ((((uintptr_t)features) | ((uintptr_t)row_bias) | ((uintptr_t)out) | ((uintptr_t)packed)) & 15) return MCP_ERR_BAD_ARG;
     GmArgs a;
     a.total = (long long)b * m;
     a.n = n; a.m = m; a.c = c; a.nsample = nsample; a.use_xyz = use_xyz ? 1 : 0; a.pool = pool; a.layers = layers;
-    a.logp = nsample <= 8 ? 3 : nsample <= 16 ? 4 : 5;
-    a.ctiles = nsample > 32 ? 2 : 1;
+    const GmUnits u = gm_units(a.total, nsample);
+    a.logp = u.logp;
+    a.ctiles = u.ctiles;
     for (int l = 0; l < MAX_LAYERS; ++l) { a.ks[l] = sh.ks[l]; a.tiles[l] = sh.tiles[l]; a.woff[l] = sh.woff[l]; a.boff[l] = sh.boff[l]; }
     a.w_u4 = sh.w_u4;
     a.small_floats = sh.small_floats;
-    hipStream_t s = (hipStream_t)stream;
     const bool in_lds = gm_weights_in_lds(sh);
-    if (sh.kmax == 4)
-        return in_lds ? launch_group_mlp<4, true>(a, xyz, new_xyz, features, idx, qlen, row_bias, packed, out, s)
-                      : launch_group_mlp<4, false>(a, xyz, new_xyz, features, idx, qlen, row_bias, packed, out, s);
-    return in_lds ? launch_group_mlp<8, true>(a, xyz, new_xyz, features, idx, qlen, row_bias, packed, out, s)
-                  : launch_group_mlp<8, false>(a, xyz, new_xyz, features, idx, qlen, row_bias, packed, out, s);
+    const size_t lds = (size_t)(a.small_floats + WAVES * POOL_ROW) * sizeof(float) + (in_lds ? (size_t)a.w_u4 * 16 : 0);
+    // persistent grid: the resident slots (256 CUs x 2 or 1 workgroups, see __launch_bounds__)
+    auto go = [&](auto kmax, auto ldsw) {
+        constexpr int K = decltype(kmax)::value;
+        return gm_launch<group_mlp_kernel<K, decltype(ldsw)::value>>(u.units, WAVES, K == 4 ? 512 : 256, lds, (hipStream_t)stream, a, xyz, new_xyz, features,
+                                                                     idx, qlen, row_bias, packed, out);
+    };
+    using std::integral_constant;
+    if (sh.kmax == 4) return in_lds ? go(integral_constant<int, 4>{}, std::true_type{}) : go(integral_constant<int, 4>{}, std::false_type{});
+    return in_lds ? go(integral_constant<int, 8>{}, std::true_type{}) : go(integral_constant<int, 8>{}, std::false_type{});
 }

@@ -4,7 +4,7 @@
 //     h_l = ReLU(y_l),  out[p] = max_j h_(L,j)  or  (sum_j h_(L,j)) / nsample,
 // with mu_l / v_l the mean and the biased variance of z_l over R.  Every slot j < nsample counts, the slots that repeat the ball
 // query's first hit included (the composition counts them too).  The ABI takes W_1 in the module's order, position columns first;
-// inside, a pair's row is [features (c) | position (3)], so that every feature quad is 16-byte aligned (as group_mlp_grad.hip).
+// inside, a pair's row is [features (c) | position (3)], so that every feature quad is 16-byte aligned (GmRow of group_mlp_shape.h).
 //
 // The flat pair list (B, M nsample) is a list of rows like any other: the passes, the statistics, the saved state and the rules are
 // fp_mlp_bn.hip's, through the shared fp_mlp_bn_pass.h -- a wave owns 32 pair rows, four waves per workgroup, one workgroup per 128
@@ -18,8 +18,10 @@
 //                        through the ReLU mask; gy_L per pair and the partials of its sums, a fixed set of centres per workgroup;
 //   gbn_new_xyz_kernel   grad_new_xyz[p] = -sum_j dx[position] in slot order.
 // dx goes per pair to the workspace as (pairs, c) | (pairs, 3); the scatters are mcp_group_rows_grad_sorted over the caller's
-// (order, seg), the weight sums mcp_linear_wgrad (dW_1 in the internal order, then laid into [position | features]), as
-// mcp_group_mlp_grad.
+// (order, seg), the weight sums mcp_linear_wgrad (dW_1 in the internal order, then laid into [position | features]):
+// gm_backward_tail of group_mlp_tile.h, which mcp_group_mlp_grad ends with too.  The same header holds what else the unit shares
+// with group_mlp.hip and group_mlp_grad.hip: the supported shapes (gm_supported), which centres are live (gm_centre_live), the two
+// pack kernels and the backward-only parts of the workspace (gm_back_layout).
 //
 // No atomics, every sum in a fixed order, two calls give identical bits; the variance is Chan-merged; no activation is kept between
 // forward and backward; a padded centre's float inputs, grad_out included, are never read, it takes part in no statistic and writes
@@ -31,6 +33,7 @@
 //
 // Built WITHOUT -fno-honor-nans: a training kernel.
 #include "fp_mlp_bn_pass.h"
+#include "group_mlp_tile.h"
 
 namespace {
 
@@ -86,65 +89,13 @@ struct GbnGather {
     }
 };
 
-// ---- the image.  Internal column j of W_1 is the module's column px + j for j < cfeat (features), j - cfeat for the px position
-// columns behind them; a later layer has cfeat = its input width and px = 0. ----
-__device__ __forceinline__ int gbn_col(int j, int cfeat, int px) { return j < cfeat ? px + j : j < cfeat + px ? j - cfeat : -1; }
-
-// forward slabs of one layer and its bias, in fp_mlp_pack_kernel's layout: slab s holds, for every output tile t, the three pieces of
-// W[32 t + (lane & 31)][col(k)] over the 8 values k of (s, lane >> 5); bias [t][h][r]
-__global__ __launch_bounds__(256) void gbn_pack_fwd_kernel(const float *__restrict__ w, const float *__restrict__ b, int ld, int cfeat, int px, int ks,
-                                                           int tiles, uint4 *__restrict__ dstw, float *__restrict__ dstb) {
-    const int first = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256;
-    for (int e = first; e < tiles * ks * 64; e += stride) {
-        const int lane = e & 63, t = (e >> 6) % tiles, s = (e >> 6) / tiles;
-        float v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int col = gbn_col(32 * (s >> 1) + mcp_chan_of(8 * (s & 1) + i, lane >> 5), cfeat, px);
-            v[i] = col >= 0 ? w[(size_t)(32 * t + (lane & 31)) * ld + col] : 0.f;
-        }
-        const McpSplit3 sp = mcp_split8(v);
-        uint4 *o = dstw + (size_t)(s * tiles + t) * TILE_U4 + lane;
-        o[0] = sp.p1;
-        o[64] = sp.p2;
-        o[128] = sp.p3;
-    }
-    for (int e = first; e < tiles * 32; e += stride) {
-        const int r = e & 15, h = (e >> 4) & 1, t = e >> 5;
-        dstb[e] = b[32 * t + mcp_chan_of(r, h)];
-    }
-}
-// slabs of A = W^T for output tiles tile0 .. tile0 + tiles - 1 over the ks k-steps of W's rows, in fp_mlp_grad_pack_kernel's layout:
-// A[m][k] = w[k * ld + col(m)], zeros where col(m) < 0
-__global__ __launch_bounds__(256) void gbn_pack_bwd_kernel(const float *__restrict__ w, int ld, int cfeat, int px, int tile0, int tiles, int ks,
-                                                           uint4 *__restrict__ dst) {
-    const int first = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256;
-    for (int e = first; e < tiles * ks * 64; e += stride) {
-        const int lane = e & 63, t = (e >> 6) % tiles, s = (e >> 6) / tiles;
-        const int col = gbn_col(32 * (tile0 + t) + (lane & 31), cfeat, px);
-        float v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int k = 32 * (s >> 1) + mcp_chan_of(8 * (s & 1) + i, lane >> 5);
-            v[i] = col >= 0 ? w[(size_t)k * ld + col] : 0.f;
-        }
-        const McpSplit3 sp = mcp_split8(v);
-        uint4 *o = dst + (size_t)(s * tiles + t) * TILE_U4 + lane;
-        o[0] = sp.p1;
-        o[64] = sp.p2;
-        o[128] = sp.p3;
-    }
-}
-
 // ulen[bb] = clamp(qlen[bb], 0, M) nsample: the live pair rows of cloud bb
 __global__ __launch_bounds__(64) void gbn_ulen_kernel(int b, int m, int nsample, const int *__restrict__ qlen, int *__restrict__ ulen) {
     for (int i = threadIdx.x; i < b; i += 64) ulen[i] = min(max(qlen[i], 0), m) * nsample;
 }
 
 __device__ __forceinline__ bool gbn_centre_live(long long pc, long long centres, int m, const int *__restrict__ qlen) {
-    if (!qlen) return true;
-    const long long bb = mcp_div(pc, m, mcp_fits32(centres));
-    return (int)(pc - bb * m) < min(max(qlen[bb], 0), m);
+    return gm_centre_live(pc, qlen ? mcp_div(pc, m, mcp_fits32(centres)) : 0, m, qlen);
 }
 
 // out[p] = pool_j ReLU(a z_L + c) over the centre's nsample rows, in slot order; zeros for a padded centre: one quad per thread
@@ -263,20 +214,11 @@ __global__ __launch_bounds__(256) void gbn_new_xyz_kernel(long long centres, int
 // ---- host side ----
 struct GbnShape {
     FgShape g;          // the shared passes' shape: a layer-1 input of ldx contiguous columns (c2 = ldx, c1 = 0)
-    int c, px, cin, ldx;
+    GmRow x;
 };
 // false: outside mcp_group_mlp's supported set
 inline bool gbn_shape(int c, int use_xyz, int layers, const int *widths, GbnShape *s) {
-    if (layers < 1 || layers > MAX_LAYERS || !widths || c < 0 || c > 128 || (c & 3) || (c == 0 && !use_xyz)) return false;
-    for (int l = 0; l < layers; ++l) {
-        const int w = widths[l];
-        if (!(w == 32 || w == 64 || w == 128 || (l == layers - 1 && w == 256))) return false;
-    }
-    s->c = c;
-    s->px = use_xyz ? 3 : 0;
-    s->cin = c + s->px;
-    s->ldx = (s->cin + 3) & ~3;
-    return fg_shape(s->ldx, 0, layers, widths, &s->g);
+    return gm_supported(c, use_xyz, layers, widths, &s->x) && fg_shape(s->x.ldx, 0, layers, widths, &s->g);
 }
 inline size_t gbn_image_floats(const GbnShape &s) { return ((size_t)s.g.f.w_u4 + s.g.bwd_u4) * 4 + s.g.f.small_floats; }
 
@@ -290,7 +232,8 @@ inline int gbn_cpw(int nsample, int c_last) {
 // The caller-owned workspace: byte offsets of its parts, each 256-byte aligned.
 struct GbnLayout {
     size_t z[MAX_LAYERS], coef[MAX_LAYERS], part, part_cnt, count, ulen;             // forward and backward
-    size_t x, h1, h2, gy[MAX_LAYERS], gz[MAX_LAYERS], dxf, dxp, dw_slice, wgrad, wgrad_bytes;   // backward only
+    size_t gy[MAX_LAYERS];                                                           // backward only: gy_l, then
+    GmBack back;                                                                     // x, h_l, gz_l, dx and the weight sums' parts
     size_t bytes;
 };
 // false: mcp_linear_wgrad does not take one of the layers' products
@@ -306,26 +249,9 @@ inline bool gbn_layout(int b, long long total, const GbnShape &s, const int *wid
     l->part_cnt = take(groups);
     l->count = take(1);
     l->ulen = take((size_t)b);
-    l->wgrad = take.at;
-    l->wgrad_bytes = 0;
     if (backward) {
-        l->x = take(rows * s.ldx);
-        l->h1 = take(layers >= 2 ? rows * widths[0] : 0);
-        l->h2 = take(layers >= 3 ? rows * widths[1] : 0);
         for (int i = 0; i < MAX_LAYERS; ++i) l->gy[i] = take(i < layers ? rows * widths[i] : 0);
-        for (int i = 0; i < MAX_LAYERS; ++i) l->gz[i] = take(i < layers ? rows * widths[i] : 0);
-        l->dxf = take(rows * s.c);
-        l->dxp = take(rows * s.px);
-        l->dw_slice = take(s.px && s.c ? (size_t)widths[0] * s.cin : 0);
-        size_t need = 0;
-        for (int i = 0; i < layers; ++i) {
-            const size_t bytes = mcp_linear_wgrad_workspace_bytes(total, widths[i], i == 0 ? s.cin : widths[i - 1]);
-            if (bytes == 0) return false;
-            if (bytes > need) need = bytes;
-        }
-        l->wgrad_bytes = need;
-        l->wgrad = take.at;
-        take.at += FpTake::up(need);
+        if (!gm_back_layout(take, total, s.x, layers, widths, &l->back)) return false;
     }
     l->bytes = take.at;
     return true;
@@ -346,7 +272,7 @@ int gbn_prepare(BnCall &c, GbnLayout &lay, const GbnShape &sh, int b, int n, int
     c.s = (hipStream_t)stream;
     c.a = BnArgs{};
     c.a.total = c.total;
-    c.a.n = m * nsample; c.a.m = n; c.a.c2 = sh.c; c.a.c1 = sh.px; c.a.rule = nsample;
+    c.a.n = m * nsample; c.a.m = n; c.a.c2 = sh.x.c; c.a.c1 = sh.x.px; c.a.rule = nsample;
     c.a.ksb = sh.g.f.ksb;
     c.q = BnPtrs{};
     c.q.part = c.part(lay.part);
@@ -355,7 +281,7 @@ int gbn_prepare(BnCall &c, GbnLayout &lay, const GbnShape &sh, int b, int n, int
         c.z[l] = c.part(lay.z[l]);
         c.coef[l] = c.part(lay.coef[l]);
         c.gy[l] = backward ? c.part(lay.gy[l]) : nullptr;
-        c.gz[l] = backward ? c.part(lay.gz[l]) : nullptr;
+        c.gz[l] = backward ? c.part(lay.back.gz[l]) : nullptr;
     }
     int *ulen = nullptr;
     if (qlen) {
@@ -389,26 +315,19 @@ MCP_EXPORT int mcp_group_mlp_bn_pack(int c, int use_xyz, int layers, const int *
     uint4 *pw = reinterpret_cast<uint4 *>(packed);
     float *small = packed + (size_t)f.w_u4 * 4;
     int rc;
+    // Slabs: a k-step's entries lie together, [s][t].  Column j of a pair's row is W_1's column px + j for j < c (features), j - c for
+    // the px position columns behind them; a later layer's input is its features alone.
     for (int l = 0; l < layers; ++l) {   // [forward slabs | biases]
-        const int ld = l == 0 ? sh.cin : widths[l - 1];
-        const int work = f.tiles[l] * f.ks[l] * 64;
-        hipLaunchKernelGGL(gbn_pack_fwd_kernel, dim3((work + 255) / 256), dim3(256), 0, s, w[l], b[l], ld, l == 0 ? c : ld, l == 0 ? sh.px : 0, f.ks[l],
-                           f.tiles[l], pw, small + f.boff[l]);
-        if ((rc = mcp_launch_status()) != MCP_OK) return rc;
+        const int ld = l == 0 ? sh.x.cin : widths[l - 1], px = l == 0 ? sh.x.px : 0;
+        if ((rc = gm_pack_fwd(s, w[l], b[l], ld, px, ld - px, px, f.ks[l], f.tiles[l], 1, f.tiles[l], pw, nullptr, small + f.boff[l])) != MCP_OK) return rc;
         pw += (size_t)f.tiles[l] * f.ks[l] * TILE_U4;
     }
     pw = reinterpret_cast<uint4 *>(packed + (size_t)f.w_u4 * 4 + f.small_floats);
-    auto go = [&](const float *wl, int ld, int cfeat, int px, int tile0, int tiles, int ks) {
-        const int work = tiles * ks * 64;
-        hipLaunchKernelGGL(gbn_pack_bwd_kernel, dim3((work + 255) / 256), dim3(256), 0, s, wl, ld, cfeat, px, tile0, tiles, ks, pw);
-        pw += (size_t)tiles * ks * TILE_U4;
-        return mcp_launch_status();
-    };
     for (int l = layers - 1; l >= 1; --l)
-        if ((rc = go(w[l], widths[l - 1], widths[l - 1], 0, 0, f.tiles[l - 1], 2 * f.tiles[l])) != MCP_OK) return rc;
-    for (int c0 = 0; c0 < sh.g.dxt; c0 += f.tmax) {
+        if ((rc = gm_pack_bwd(s, w[l], widths[l - 1], widths[l - 1], 0, 0, f.tiles[l - 1], 2 * f.tiles[l], 1, f.tiles[l - 1], pw)) != MCP_OK) return rc;
+    for (int c0 = 0; c0 < sh.g.dxt; c0 += f.tmax) {   // dx in chunks of tmax output tiles, as BWD_DX takes them
         const int tc = sh.g.dxt - c0 < f.tmax ? sh.g.dxt - c0 : f.tmax;
-        if ((rc = go(w[0], sh.cin, c, sh.px, c0, tc, 2 * f.tiles[0])) != MCP_OK) return rc;
+        if ((rc = gm_pack_bwd(s, w[0], sh.x.cin, c, sh.x.px, c0, tc, 2 * f.tiles[0], 1, tc, pw)) != MCP_OK) return rc;
     }
     return MCP_OK;
 }
@@ -469,8 +388,8 @@ MCP_EXPORT int mcp_group_mlp_bn_backward(int b, int n, int m, int c, int nsample
     int rc = gbn_prepare(call, lay, sh, b, n, m, nsample, widths, true, qlen, nullptr, workspace, workspace_bytes, stream);
     if (rc != MCP_OK) return rc;
     call.q.known_feats = features; call.q.skip = xyz; call.q.dist = new_xyz; call.q.idx = idx; call.q.packed = packed;
-    float *x = call.part(lay.x), *hid[2] = {call.part(lay.h1), call.part(lay.h2)};
-    float *dxf = call.part(lay.dxf), *dxp = call.part(lay.dxp);
+    float *x = call.part(lay.back.x), *hid[2] = {call.part(lay.back.hid[0]), call.part(lay.back.hid[1])};
+    float *dxf = call.part(lay.back.dxf), *dxp = call.part(lay.back.dxp);
     const int *count = reinterpret_cast<const int *>(call.ws + lay.count);
 
     // ---- the forward again, statistics given: x, z_l, h_l ----
@@ -488,34 +407,10 @@ MCP_EXPORT int mcp_group_mlp_bn_backward(int b, int n, int m, int c, int nsample
     if ((rc = mcp_launch_status()) != MCP_OK) return rc;
     if ((rc = backward_passes<GbnGather>(call, widths, groups_last, count, grad_gamma, grad_beta, dxf, dxp)) != MCP_OK) return rc;
 
-    // the scatters: every destination row's addends in ascending position p nsample + j
-    if (grad_features) {
-        rc = mcp_group_rows_grad_sorted(b, n, c, m * nsample, dxf, order, seg, grad_features, stream);
-        if (rc != MCP_OK) return rc;
-    }
-    if (grad_xyz) {
-        rc = mcp_group_rows_grad_sorted(b, n, 3, m * nsample, dxp, order, seg, grad_xyz, stream);
-        if (rc != MCP_OK) return rc;
-    }
     if (grad_new_xyz) {
         hipLaunchKernelGGL(gbn_new_xyz_kernel, dim3((unsigned)((centres * 3 + 255) / 256)), dim3(256), 0, call.s, centres, nsample, dxp, grad_new_xyz);
         if ((rc = mcp_launch_status()) != MCP_OK) return rc;
     }
-    // dW_l = gz_l^T h_(l-1), db_l = column sums of gz_l (zero in exact arithmetic: the statistics absorb a bias)
-    void *wws = call.ws + lay.wgrad;
-    const long long rows = call.total;
-    for (int l = last; l >= 1; --l) {
-        rc = mcp_linear_wgrad(rows, widths[l], widths[l - 1], call.gz[l], widths[l], hid[l - 1], widths[l - 1], grad_w[l], grad_b[l], wws, lay.wgrad_bytes, stream);
-        if (rc != MCP_OK) return rc;
-    }
-    if (!(sh.px && c)) return mcp_linear_wgrad(rows, widths[0], sh.cin, call.gz[0], widths[0], x, sh.ldx, grad_w[0], grad_b[0], wws, lay.wgrad_bytes, stream);
-    // x holds [features | position]: the product goes to a slice and its two column blocks are laid into dW_1 = [position | features]
-    float *slice = call.part(lay.dw_slice);
-    rc = mcp_linear_wgrad(rows, widths[0], sh.cin, call.gz[0], widths[0], x, sh.ldx, slice, grad_b[0], wws, lay.wgrad_bytes, stream);
-    if (rc != MCP_OK) return rc;
-    const size_t pitch = (size_t)sh.cin * sizeof(float);
-    hipError_t e = hipMemcpy2DAsync(grad_w[0] + 3, pitch, slice, pitch, (size_t)c * sizeof(float), (size_t)widths[0], hipMemcpyDeviceToDevice, call.s);
-    if (e != hipSuccess) return (int)e;
-    e = hipMemcpy2DAsync(grad_w[0], pitch, slice + c, pitch, 3 * sizeof(float), (size_t)widths[0], hipMemcpyDeviceToDevice, call.s);
-    return e == hipSuccess ? MCP_OK : (int)e;
+    // the scatters and the weight sums (db_l is zero in exact arithmetic: the statistics absorb a bias)
+    return gm_backward_tail(b, n, m, nsample, sh.x, layers, widths, call.ws, lay.back, order, seg, grad_features, grad_xyz, grad_w, grad_b, stream);
 }

@@ -22,9 +22,10 @@
 //     (B, M nsample) with n = N, the weight sums are mcp_linear_wgrad's fixed-order partial sums.  Two calls give identical bits;
 //   * every output may be NULL and is then not computed (grad_w / grad_b: the arrays are required, as in mcp_fp_mlp_grad);
 //   * the optional `out` is the forward's result again, bit for bit: every output tile of the recompute receives the forward's
-//     sequence of matrix instructions on the forward's own image (bias, row bias, the two K = 4 position products, the k-steps in
-//     ascending order with mcp_mfma_split's six-product order), the pool is the forward's butterfly, and ReLU as a selection has the
-//     bits of fmaxf for every finite value;
+//     sequence of matrix instructions on the forward's own image -- the head of a layer-1 tile (bias, row bias, the two K = 4
+//     position products) is gm_layer1_head of group_mlp_tile.h, the one function both kernels call, then the k-steps in ascending
+//     order with mcp_mfma_split's six-product order --, the pool is gm_group_sum / gm_group_max of the same header, which the
+//     forward calls too, and ReLU as a selection has the bits of fmaxf for every finite value;
 //   * no allocation, no environment variable, no host read of a length; the caller owns the workspace
 //     (mcp_group_mlp_grad_workspace_bytes) and the operand image (mcp_group_mlp_grad_pack, mcp_group_mlp_grad_packed_floats floats).
 //
@@ -39,12 +40,12 @@
 // two per SIMD) and no scratch.
 //   Phase 1 is the forward, tile by tile; x and the h_l go to the workspace, h_L into the slot of gz_L.
 //   Phase 2, per 32-channel tile of the last layer: h_L of the centre's one or two column tiles is read back, pooled with the
-//   forward's butterfly (the optional `out` is written here), and the winner slot of a channel is the minimum, over the group and
+//   butterfly of group_mlp_tile.h (the optional `out` is written here), and the winner slot of a channel is the minimum, over the group and
 //   over both tiles, of "j where h_(L,j) == pooled, else 64" -- so the two tiles of nsample > 32 agree through this FIRST POOLING
 //   PASS over recomputed values, the forward's `out` is not read.  gz_L replaces h_L in place.  Then, layer by layer, the k-steps of
 //   gz_l meet the image of W_l^T, the product is selected by [h_(l-1) > 0] with h_(l-1) read back from the workspace (no mask lives in
 //   a register) and written as gz_(l-1); dx = W_1^T gz_1 is produced tile by tile the same way.  Sums over a group (grad_row_bias,
-//   grad_new_xyz) are the forward's butterfly, the two tiles of nsample > 32 added in order.
+//   grad_new_xyz) are the same butterfly, the two tiles of nsample > 32 added in order.
 // The workspace is the dense per-pair intermediate that the forward avoids: 4 (ldx + 2 sum(widths) - widths[L-1] + c + 3) bytes per
 // (centre, slot) pair.  An in-kernel accumulation of the weight gradients would remove it; that is not done here.
 //
@@ -57,34 +58,26 @@
 //
 // Built WITHOUT -fno-honor-nans: the masks and the ReLU are comparisons and selections, and a training kernel should not be compiled
 // under the assumption that no NaN arrives (a diverged run must show its NaN, not hide it).
-#include "common.h"
-#include "mfma_split.h"
-#include "group_mlp_shape.h"
+//
+// The column's centre, the position operand, the head of a layer-1 tile, the butterflies, the pack kernels, the launch, the
+// workspace's parts and the tail of the entry point are group_mlp_tile.h's, shared with group_mlp.hip and group_mlp_bn.hip.
+#include "group_mlp_tile.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int WAVES = 8;
 constexpr int THREADS = 64 * WAVES;
-constexpr int TILE_U4 = 3 * 64;                       // uint4 of one (output tile, k-step): three pieces of 64 lanes
 constexpr int GRAD_LDS_IMAGE_BYTES = 128 * 1024;      // largest (forward + transposed) image staged in LDS
 constexpr int MAX_GRID = 256;                         // persistent grid: one workgroup per CU
 
 struct GgShape {
     GmShape f;
-    int px;              // 3 with use_xyz, else 0
-    int cin, ldx;        // c + px; floats of a row of x (cin rounded up to whole quads)
-    int dxt;             // 32-channel tiles of dx
     int boff[MAX_LAYERS];// uint4 offset, inside the transposed part, of the pieces that take gz_l (l = 0: into dx, else into layer l - 1)
     int bwd_u4;
 };
 
 inline bool gg_shape(int c, int use_xyz, int layers, const int *widths, GgShape *s) {
-    if (!gm_shape(c, layers, widths, &s->f) || (c == 0 && !use_xyz)) return false;
-    s->px = use_xyz ? 3 : 0;
-    s->cin = c + s->px;
-    s->ldx = (s->cin + 3) & ~3;
-    s->dxt = (s->cin + 31) / 32;
+    if (!gm_shape(c, use_xyz, layers, widths, &s->f)) return false;
     int u4 = 0;
     for (int l = 0; l < MAX_LAYERS; ++l) s->boff[l] = 0;
     for (int l = layers - 1; l >= 1; --l) {
@@ -92,37 +85,13 @@ inline bool gg_shape(int c, int use_xyz, int layers, const int *widths, GgShape 
         u4 += s->f.tiles[l - 1] * 2 * s->f.tiles[l] * TILE_U4;
     }
     s->boff[0] = u4;
-    u4 += s->dxt * 2 * s->f.tiles[0] * TILE_U4;
+    u4 += s->f.x.dxt * 2 * s->f.tiles[0] * TILE_U4;
     s->bwd_u4 = u4;
     return true;
 }
 // the staging predicate, a function of (c, use_xyz, widths) alone (ops.group_mlp_grad_weights_in_lds mirrors it)
 inline bool gg_weights_in_lds(const GgShape &s) { return ((size_t)s.f.w_u4 + s.bwd_u4) * 16 <= (size_t)GRAD_LDS_IMAGE_BYTES; }
 inline size_t gg_image_floats(const GgShape &s) { return ((size_t)s.f.w_u4 + s.bwd_u4) * 4 + s.f.small_floats; }
-
-// Pieces of A = W^T for `tiles` output tiles (32 rows m of A each) over the ks k-steps of W's rows: entry ((t * ks + s) * 3 + piece)
-// * 64 + lane holds the 8 bf16 pieces of A[32 t + (lane & 31)][k] = w[k * ld + col(m)], k = 32 (s >> 1) + chan_of(8 (s & 1) + i,
-// lane >> 5).  col(m) = col0 + m for m < cfeat (the feature columns), m - cfeat for the px position rows that follow; zeros beyond.
-__global__ __launch_bounds__(256) void group_mlp_grad_pack_kernel(const float *__restrict__ w, int ld, int col0, int cfeat, int px, int tiles, int ks,
-                                                                  uint4 *__restrict__ dst) {
-    const int first = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256;
-    for (int e = first; e < tiles * ks * 64; e += stride) {
-        const int lane = e & 63, s = (e >> 6) % ks, t = (e >> 6) / ks;
-        const int m = 32 * t + (lane & 31);
-        const int colm = m < cfeat ? col0 + m : m < cfeat + px ? m - cfeat : -1;
-        float v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int k = 32 * (s >> 1) + mcp_chan_of(8 * (s & 1) + i, lane >> 5);
-            v[i] = colm >= 0 ? w[(size_t)k * ld + colm] : 0.f;
-        }
-        const McpSplit3 sp = mcp_split8(v);
-        uint4 *o = dst + (size_t)(t * ks + s) * TILE_U4 + lane;
-        o[0] = sp.p1;
-        o[64] = sp.p2;
-        o[128] = sp.p3;
-    }
-}
 
 struct GgArgs {
     long long total;  // B * M centres
@@ -140,32 +109,6 @@ struct GgIn {
 struct GgOut {
     float *x, *hid[2], *gz[MAX_LAYERS], *gzl, *dxf, *dxp, *grad_new_xyz, *grad_row_bias, *out;   // gzl = gz[layers - 1]
 };
-
-// sum / max / min over each column group of P = 8, 16, 32 lanes, the result in every lane of the group: the forward's butterfly
-__device__ __forceinline__ float gg_group_sum(float v, int logp) {
-    v += __uint_as_float(mcp_dpp<0xB1>(__float_as_uint(v)));    // quad_perm [1,0,3,2]
-    v += __uint_as_float(mcp_dpp<0x4E>(__float_as_uint(v)));    // quad_perm [2,3,0,1]
-    v += __uint_as_float(mcp_dpp<0x141>(__float_as_uint(v)));   // row_half_mirror: the other quad of the 8
-    if (logp >= 4) v += __uint_as_float(mcp_dpp<0x140>(__float_as_uint(v)));  // row_mirror: the other 8 of the row
-    if (logp == 5) v += __shfl_xor(v, 16);
-    return v;
-}
-__device__ __forceinline__ float gg_group_max(float v, int logp) {
-    v = fmaxf(v, __uint_as_float(mcp_dpp<0xB1>(__float_as_uint(v))));
-    v = fmaxf(v, __uint_as_float(mcp_dpp<0x4E>(__float_as_uint(v))));
-    v = fmaxf(v, __uint_as_float(mcp_dpp<0x141>(__float_as_uint(v))));
-    if (logp >= 4) v = fmaxf(v, __uint_as_float(mcp_dpp<0x140>(__float_as_uint(v))));
-    if (logp == 5) v = fmaxf(v, __shfl_xor(v, 16));
-    return v;
-}
-__device__ __forceinline__ int gg_group_min(int v, int logp) {
-    v = min(v, (int)mcp_dpp<0xB1>((uint32_t)v));
-    v = min(v, (int)mcp_dpp<0x4E>((uint32_t)v));
-    v = min(v, (int)mcp_dpp<0x141>((uint32_t)v));
-    if (logp >= 4) v = min(v, (int)mcp_dpp<0x140>((uint32_t)v));
-    if (logp == 5) v = min(v, __shfl_xor(v, 16));
-    return v;
-}
 
 template <bool LDSW>
 __global__ __launch_bounds__(THREADS, 1) void group_mlp_grad_kernel(const GgArgs a, const GgIn in, const GgOut o) {
@@ -191,7 +134,6 @@ __global__ __launch_bounds__(THREADS, 1) void group_mlp_grad_kernel(const GgArgs
     const int P = 1 << a.logp, G = 32 >> a.logp, slot = col & (P - 1);
     const int L = a.layers;
     const int wfirst = a.tiles[0] * 32, wlast = a.tlast * 32;
-    const bool fits32 = mcp_fits32(a.total);
     const float fn = (float)a.nsample;
 
     // the two quads of k-step s of a row (`row` points at channel 4 h of it); quads at or beyond `lim` channels, and every quad of a
@@ -213,16 +155,6 @@ __global__ __launch_bounds__(THREADS, 1) void group_mlp_grad_kernel(const GgArgs
             const float v[8] = {n0.x, n0.y, n0.z, n0.w, n1.x, n1.y, n1.z, n1.w};
             acc = mcp_mfma_split(w + (size_t)s * TILE_U4, mcp_split8(v), acc);
             n0 = m0; n1 = m1;
-        }
-        return acc;
-    };
-    auto bias_tile = [&](int l, int t) {
-        f32x16 acc;
-        const float4 *bq = reinterpret_cast<const float4 *>(small + a.bias[l] + (t * 2 + h) * 16);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const float4 v = bq[g];
-            acc[4 * g + 0] = v.x; acc[4 * g + 1] = v.y; acc[4 * g + 2] = v.z; acc[4 * g + 3] = v.w;
         }
         return acc;
     };
@@ -251,14 +183,9 @@ __global__ __launch_bounds__(THREADS, 1) void group_mlp_grad_kernel(const GgArgs
     const long long units = (a.total + G - 1) / G;
     const McpUnits deal = mcp_units_by_xcd(units, WAVES);
     for (long long unit = deal.first + wave; unit < deal.limit; unit += deal.stride) {
-        const long long p = unit * G + (col >> a.logp);  // this column's centre
-        const bool inr = p < a.total;
-        const long long bb = inr ? mcp_div(p, a.m, fits32) : 0;
-        bool live = inr;
-        if (inr && in.qlen) {
-            const int ql = min(max(in.qlen[bb], 0), a.m);
-            live = (int)(p - bb * a.m) < ql;
-        }
+        const GmCentre me(unit, col, a.logp, a.total, a.m, in.qlen);   // this column's centre
+        const long long p = me.p, bb = me.bb;
+        const bool inr = me.inr, live = me.live;
         // the pair row of this column in column tile ct; a column at or beyond nsample owns none
         auto pair_row = [&](int ct, bool &valid) {
             const int j = ct * 32 + slot;
@@ -275,17 +202,8 @@ __global__ __launch_bounds__(THREADS, 1) void group_mlp_grad_kernel(const GgArgs
             const int j = ct * 32 + slot;
             const int k = live ? in.idx[p * a.nsample + (j < a.nsample ? j : 0)] : 0;
             const long long src = bb * a.n + k;
-            float in0 = 0.f, in1 = 0.f;
-            if (a.use_xyz) {
-                float dx = 0.f, dy = 0.f, dz = 0.f;
-                if (live) {
-                    const float *q = in.xyz + src * 3, *ctr = in.new_xyz + p * 3;
-                    dx = q[0] - ctr[0]; dy = q[1] - ctr[1]; dz = q[2] - ctr[2];
-                }
-                in0 = h ? dy : dx;   // k-step 0: (dx, dy); k-step 1: (dz, 0)
-                in1 = h ? 0.f : dz;
-                if (valid && h == 0) *reinterpret_cast<float4 *>(o.x + pr * a.ldx + a.c) = make_float4(dx, dy, dz, 0.f);
-            }
+            const GmPos pos = gm_position(in.xyz + src * 3, in.new_xyz + p * 3, live && a.use_xyz, h);
+            if (a.use_xyz && valid && h == 0) *reinterpret_cast<float4 *>(o.x + pr * a.ldx + a.c) = make_float4(pos.dx, pos.dy, pos.dz, 0.f);
             const float *frow = in.features + src * a.c + 4 * h;   // formed, not read, when c = 0 or the centre is padded
             if (valid) {   // the feature part of x
                 float *xr = o.x + pr * a.ldx + 4 * h;
@@ -299,21 +217,7 @@ __global__ __launch_bounds__(THREADS, 1) void group_mlp_grad_kernel(const GgArgs
             float *h1row = (L == 1 ? o.gz[0] : o.hid[0]) + pr * wfirst + 4 * h;
 #pragma unroll 1
             for (int t = 0; t < a.tiles[0]; ++t) {
-                f32x16 acc = bias_tile(0, t);
-                if (in.row_bias) {
-                    if (live) {
-                        const float4 *rb = reinterpret_cast<const float4 *>(in.row_bias + p * wfirst + 32 * t + 4 * h);
-#pragma unroll
-                        for (int g = 0; g < 4; ++g) {
-                            const float4 v = rb[2 * g];
-                            acc[4 * g + 0] += v.x; acc[4 * g + 1] += v.y; acc[4 * g + 2] += v.z; acc[4 * g + 3] += v.w;
-                        }
-                    }
-                }
-                if (a.use_xyz) {
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(small[(t * 2 + 0) * 64 + lane], in0, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(small[(t * 2 + 1) * 64 + lane], in1, acc, 0, 0, 0);
-                }
+                f32x16 acc = gm_layer1_head(small, a.bias[0], t, h, lane, in.row_bias, p, wfirst, live, a.use_xyz, pos);
                 if (a.ks0) {
                     acc = tile_from_row(acc, wfwd + a.woff[0] + (size_t)t * a.ks0 * TILE_U4 + lane, frow, a.ks0, live, a.c);
                 } else {
@@ -336,7 +240,7 @@ __global__ __launch_bounds__(THREADS, 1) void group_mlp_grad_kernel(const GgArgs
                 float *hout = (l == 1 && L > 2 ? o.hid[1] : o.gz[l]) + pr * wout + 4 * h;
 #pragma unroll 1
                 for (int t = 0; t < a.tiles[l]; ++t) {
-                    f32x16 acc = bias_tile(l, t);
+                    f32x16 acc = gm_bias_tile(small + a.bias[l], t, h);
                     acc = tile_from_row(acc, wfwd + a.woff[l] + (size_t)t * (2 * a.tiles[l - 1]) * TILE_U4 + lane, hin, 2 * a.tiles[l - 1], valid, win);
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[r] = acc[r] > 0.f ? acc[r] : 0.f;
@@ -363,8 +267,8 @@ __global__ __launch_bounds__(THREADS, 1) void group_mlp_grad_kernel(const GgArgs
                 if (a.pool) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        float s = gg_group_sum(ha[r], a.logp);   // a column beyond nsample holds 0
-                        if (a.ctiles == 2) s = s + gg_group_sum(hb[r], a.logp);
+                        float s = gm_group_sum(ha[r], a.logp);   // a column beyond nsample holds 0
+                        if (a.ctiles == 2) s = s + gm_group_sum(hb[r], a.logp);
                         pooled[r] = s / fn;
                         const float gy = gv[r] / fn;
                         ga[r] = (valid0 && ha[r] > 0.f) ? gy : 0.f;
@@ -373,11 +277,11 @@ __global__ __launch_bounds__(THREADS, 1) void group_mlp_grad_kernel(const GgArgs
                 } else {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        float mx = gg_group_max(ha[r], a.logp);  // h >= 0: the zeros of the columns beyond nsample change no maximum
-                        if (a.ctiles == 2) mx = fmaxf(mx, gg_group_max(hb[r], a.logp));
+                        float mx = gm_group_max(ha[r], a.logp);  // h >= 0: the zeros of the columns beyond nsample change no maximum
+                        if (a.ctiles == 2) mx = fmaxf(mx, gm_group_max(hb[r], a.logp));
                         pooled[r] = mx;
-                        int win = gg_group_min((valid0 && ha[r] == mx) ? slot : 64, a.logp);
-                        if (a.ctiles == 2) win = min(win, gg_group_min((valid1 && hb[r] == mx) ? 32 + slot : 64, a.logp));
+                        int win = gm_group_min((valid0 && ha[r] == mx) ? slot : 64, a.logp);
+                        if (a.ctiles == 2) win = min(win, gm_group_min((valid1 && hb[r] == mx) ? 32 + slot : 64, a.logp));
                         ga[r] = (valid0 && slot == win && ha[r] > 0.f) ? gv[r] : 0.f;
                         gb[r] = (valid1 && 32 + slot == win && hb[r] > 0.f) ? gv[r] : 0.f;
                     }
@@ -393,8 +297,8 @@ __global__ __launch_bounds__(THREADS, 1) void group_mlp_grad_kernel(const GgArgs
                     f32x16 sum;
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        float s = gg_group_sum(ga[r], a.logp);
-                        if (a.ctiles == 2) s = s + gg_group_sum(gb[r], a.logp);
+                        float s = gm_group_sum(ga[r], a.logp);
+                        if (a.ctiles == 2) s = s + gm_group_sum(gb[r], a.logp);
                         sum[r] = s;
                     }
                     if (head) store_tile(o.grad_row_bias + p * wfirst + 4 * h, t, sum);
@@ -421,7 +325,7 @@ __global__ __launch_bounds__(THREADS, 1) void group_mlp_grad_kernel(const GgArgs
                     if (l == 1 && o.grad_row_bias) {
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
-                            const float s = gg_group_sum(acc[r], a.logp);
+                            const float s = gm_group_sum(acc[r], a.logp);
                             sum[r] = ct ? sum[r] + s : s;
                         }
                     }
@@ -459,7 +363,7 @@ __global__ __launch_bounds__(THREADS, 1) void group_mlp_grad_kernel(const GgArgs
                             d[0] = px; d[1] = py; d[2] = pz;
                         }
                         if (o.grad_new_xyz) {
-                            const float tx = gg_group_sum(px, a.logp), ty = gg_group_sum(py, a.logp), tz = gg_group_sum(pz, a.logp);
+                            const float tx = gm_group_sum(px, a.logp), ty = gm_group_sum(py, a.logp), tz = gm_group_sum(pz, a.logp);
                             sx = ct ? sx + tx : tx; sy = ct ? sy + ty : ty; sz = ct ? sz + tz : tz;
                         }
                     }
@@ -471,54 +375,6 @@ __global__ __launch_bounds__(THREADS, 1) void group_mlp_grad_kernel(const GgArgs
             }
         }
     }
-}
-
-template <bool LDSW>
-int launch_group_mlp_grad(const GgArgs &a, const GgIn &in, const GgOut &o, hipStream_t s) {
-    auto kern = group_mlp_grad_kernel<LDSW>;
-    static McpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_once.done();
-    }
-    const size_t lds = (size_t)a.small_floats * sizeof(float) + (LDSW ? ((size_t)a.w_u4 + a.bwd_u4) * 16 : 0);
-    const int G = 32 >> a.logp;
-    const long long units = (a.total + G - 1) / G;
-    const long long want = (units + WAVES - 1) / WAVES;
-    const unsigned grid = (unsigned)max(1LL, min(want, (long long)MAX_GRID));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), lds, s, a, in, o);
-    return mcp_launch_status();
-}
-
-// The caller-owned workspace: byte offsets of its parts, each 256-byte aligned.
-struct GgLayout {
-    size_t x, hid[2], gz[MAX_LAYERS], dxf, dxp, dw_slice, wgrad, wgrad_bytes, bytes;
-};
-inline size_t gg_up(size_t v) { return (v + 255) & ~(size_t)255; }
-// false: mcp_linear_wgrad does not take one of the layers' products
-inline bool gg_layout(long long rows_ll, const GgShape &s, const int *widths, GgLayout *l) {
-    size_t at = 0;
-    auto take = [&](size_t floats) { const size_t here = at; at += gg_up(floats * sizeof(float)); return here; };
-    const size_t rows = (size_t)rows_ll;
-    const int L = s.f.layers;
-    l->x = take(rows * s.ldx);
-    l->hid[0] = take(L >= 2 ? rows * widths[0] : 0);
-    l->hid[1] = take(L >= 3 ? rows * widths[1] : 0);
-    for (int i = 0; i < MAX_LAYERS; ++i) l->gz[i] = take(i < L ? rows * widths[i] : 0);
-    l->dxf = take(rows * s.f.c);
-    l->dxp = take(rows * s.px);
-    l->dw_slice = take(s.px && s.f.c ? (size_t)widths[0] * s.cin : 0);
-    size_t need = 0;
-    for (int i = 0; i < L; ++i) {
-        const size_t b = mcp_linear_wgrad_workspace_bytes(rows_ll, widths[i], i == 0 ? s.cin : widths[i - 1]);
-        if (b == 0) return false;
-        if (b > need) need = b;
-    }
-    l->wgrad = at;
-    l->wgrad_bytes = need;
-    l->bytes = at + gg_up(need);
-    return true;
 }
 
 }  // namespace
@@ -536,23 +392,20 @@ MCP_EXPORT int mcp_group_mlp_grad_pack(int c, int use_xyz, int layers, const int
     if (!gg_shape(c, use_xyz, layers, widths, &sh)) return MCP_ERR_UNSUPPORTED;
     int rc = mcp_group_mlp_pack(c, use_xyz, layers, widths, w, b, packed, stream);   // [forward pieces | position columns, biases]
     if (rc != MCP_OK) return rc;
+    const GmShape &f = sh.f;
     hipStream_t s = (hipStream_t)stream;
-    uint4 *pw = reinterpret_cast<uint4 *>(packed + (size_t)sh.f.w_u4 * 4 + sh.f.small_floats);
-    auto go = [&](const float *wl, int ld, int col0, int cfeat, int px, int tiles, int ks, int off) {
-        const int work = tiles * ks * 64;
-        hipLaunchKernelGGL(group_mlp_grad_pack_kernel, dim3((work + 255) / 256), dim3(256), 0, s, wl, ld, col0, cfeat, px, tiles, ks, pw + off);
-        return mcp_launch_status();
-    };
+    uint4 *pw = reinterpret_cast<uint4 *>(packed + (size_t)f.w_u4 * 4 + f.small_floats);   // the transposed pieces in the order of boff, entries [t][s]
     for (int l = layers - 1; l >= 1; --l)
-        if ((rc = go(w[l], widths[l - 1], 0, widths[l - 1], 0, sh.f.tiles[l - 1], 2 * sh.f.tiles[l], sh.boff[l])) != MCP_OK) return rc;
-    return go(w[0], sh.cin, sh.px, c, sh.px, sh.dxt, 2 * sh.f.tiles[0], sh.boff[0]);
+        if ((rc = gm_pack_bwd(s, w[l], widths[l - 1], widths[l - 1], 0, 0, f.tiles[l - 1], 2 * f.tiles[l], 2 * f.tiles[l], 1, pw)) != MCP_OK) return rc;
+    return gm_pack_bwd(s, w[0], f.x.cin, c, f.x.px, 0, f.x.dxt, 2 * f.tiles[0], 2 * f.tiles[0], 1, pw);
 }
 
 MCP_EXPORT size_t mcp_group_mlp_grad_workspace_bytes(int b, int m, int c, int nsample, int use_xyz, int layers, const int *widths) {
     GgShape sh;
     if (b <= 0 || m <= 0 || nsample < 1 || nsample > 64 || !gg_shape(c, use_xyz, layers, widths, &sh)) return 0;
-    GgLayout lay;
-    return gg_layout((long long)b * m * nsample, sh, widths, &lay) ? lay.bytes : 0;
+    FpTake take;
+    GmBack lay;
+    return gm_back_layout(take, (long long)b * m * nsample, sh.f.x, layers, widths, &lay) ? take.at : 0;
 }
 
 MCP_EXPORT int mcp_group_mlp_grad(int b, int n, int m, int c, int nsample, int use_xyz, int pool, int layers, const int *widths, const float *xyz,
@@ -569,56 +422,35 @@ MCP_EXPORT int mcp_group_mlp_grad(int b, int n, int m, int c, int nsample, int u
     const uintptr_t quads = (uintptr_t)features | (uintptr_t)row_bias | (uintptr_t)packed | (uintptr_t)grad_out | (uintptr_t)out |
                             (uintptr_t)grad_row_bias | (uintptr_t)grad_features | (uintptr_t)workspace;
     if (quads & 15) return MCP_ERR_BAD_ARG;
-    const long long total = (long long)b * m, rows = total * nsample;
+    const long long total = (long long)b * m;
     if ((long long)m * nsample > 0x7FFFFFFFLL) return MCP_ERR_UNSUPPORTED;
-    GgLayout lay;
-    if (!gg_layout(rows, sh, widths, &lay)) return MCP_ERR_UNSUPPORTED;
-    if (workspace_bytes < lay.bytes) return MCP_ERR_BAD_ARG;
+    const GmShape &f = sh.f;
+    FpTake take;   // the workspace is the backward-only parts and nothing else
+    GmBack lay;
+    if (!gm_back_layout(take, total * nsample, f.x, layers, widths, &lay)) return MCP_ERR_UNSUPPORTED;
+    if (workspace_bytes < take.at) return MCP_ERR_BAD_ARG;
     char *ws = reinterpret_cast<char *>(workspace);
     auto part = [&](size_t off) { return reinterpret_cast<float *>(ws + off); };
-    float *x = part(lay.x), *hid[2] = {part(lay.hid[0]), part(lay.hid[1])}, *gz[MAX_LAYERS] = {part(lay.gz[0]), part(lay.gz[1]), part(lay.gz[2])};
-    float *dxf = part(lay.dxf), *dxp = part(lay.dxp);
 
-    const GmShape &f = sh.f;
+    const GmUnits u = gm_units(total, nsample);
     GgArgs a;
     a.total = total;
     a.n = n; a.m = m; a.c = c; a.nsample = nsample; a.use_xyz = use_xyz ? 1 : 0; a.pool = pool; a.layers = layers;
-    a.logp = nsample <= 8 ? 3 : nsample <= 16 ? 4 : 5;
-    a.ctiles = nsample > 32 ? 2 : 1;
+    a.logp = u.logp;
+    a.ctiles = u.ctiles;
     a.ks0 = f.ks[0];
     for (int l = 0; l < MAX_LAYERS; ++l) { a.tiles[l] = f.tiles[l]; a.woff[l] = f.woff[l]; a.bias[l] = f.boff[l]; a.boff[l] = sh.boff[l]; }
     a.tlast = f.tiles[layers - 1];
-    a.w_u4 = f.w_u4; a.small_floats = f.small_floats; a.bwd_u4 = sh.bwd_u4; a.dxt = sh.dxt; a.ldx = sh.ldx;
+    a.w_u4 = f.w_u4; a.small_floats = f.small_floats; a.bwd_u4 = sh.bwd_u4; a.dxt = f.x.dxt; a.ldx = f.x.ldx;
     a.want_dx = (grad_features || grad_xyz || grad_new_xyz) ? 1 : 0;
     const GgIn in{xyz, new_xyz, features, row_bias, packed, grad_out, idx, qlen};
-    const GgOut o{x, {hid[0], hid[1]}, {gz[0], gz[1], gz[2]}, gz[layers - 1], dxf, dxp, grad_new_xyz, grad_row_bias, out};
+    const GgOut o{part(lay.x), {part(lay.hid[0]), part(lay.hid[1])}, {part(lay.gz[0]), part(lay.gz[1]), part(lay.gz[2])}, part(lay.gz[layers - 1]),
+                  part(lay.dxf), part(lay.dxp), grad_new_xyz, grad_row_bias, out};
+    const bool in_lds = gg_weights_in_lds(sh);
+    const size_t lds = (size_t)a.small_floats * sizeof(float) + (in_lds ? ((size_t)a.w_u4 + a.bwd_u4) * 16 : 0);
     hipStream_t s = (hipStream_t)stream;
-    int rc = gg_weights_in_lds(sh) ? launch_group_mlp_grad<true>(a, in, o, s) : launch_group_mlp_grad<false>(a, in, o, s);
+    const int rc = in_lds ? gm_launch<group_mlp_grad_kernel<true>>(u.units, WAVES, MAX_GRID, lds, s, a, in, o)
+                          : gm_launch<group_mlp_grad_kernel<false>>(u.units, WAVES, MAX_GRID, lds, s, a, in, o);
     if (rc != MCP_OK) return rc;
-
-    // the scatters: every destination row's addends in ascending position p nsample + j
-    if (grad_features) {
-        rc = mcp_group_rows_grad_sorted(b, n, c, m * nsample, dxf, order, seg, grad_features, stream);
-        if (rc != MCP_OK) return rc;
-    }
-    if (grad_xyz) {
-        rc = mcp_group_rows_grad_sorted(b, n, 3, m * nsample, dxp, order, seg, grad_xyz, stream);
-        if (rc != MCP_OK) return rc;
-    }
-    // dW_l = gz_l^T h_(l-1), db_l = column sums of gz_l
-    void *wws = ws + lay.wgrad;
-    for (int l = layers - 1; l >= 1; --l) {
-        rc = mcp_linear_wgrad(rows, widths[l], widths[l - 1], gz[l], widths[l], hid[l - 1], widths[l - 1], grad_w[l], grad_b[l], wws, lay.wgrad_bytes, stream);
-        if (rc != MCP_OK) return rc;
-    }
-    if (!(sh.px && c)) return mcp_linear_wgrad(rows, widths[0], sh.cin, gz[0], widths[0], x, sh.ldx, grad_w[0], grad_b[0], wws, lay.wgrad_bytes, stream);
-    // x holds [features | position]: the product goes to a slice and its two column blocks are laid into dW_1 = [position | features]
-    float *slice = part(lay.dw_slice);
-    rc = mcp_linear_wgrad(rows, widths[0], sh.cin, gz[0], widths[0], x, sh.ldx, slice, grad_b[0], wws, lay.wgrad_bytes, stream);
-    if (rc != MCP_OK) return rc;
-    const size_t pitch = (size_t)sh.cin * sizeof(float);
-    hipError_t e = hipMemcpy2DAsync(grad_w[0] + 3, pitch, slice, pitch, (size_t)c * sizeof(float), (size_t)widths[0], hipMemcpyDeviceToDevice, s);
-    if (e != hipSuccess) return (int)e;
-    e = hipMemcpy2DAsync(grad_w[0], pitch, slice + c, pitch, 3 * sizeof(float), (size_t)widths[0], hipMemcpyDeviceToDevice, s);
-    return e == hipSuccess ? MCP_OK : (int)e;
+    return gm_backward_tail(b, n, m, nsample, f.x, layers, widths, ws, lay, order, seg, grad_features, grad_xyz, grad_w, grad_b, stream);
 }
