@@ -258,6 +258,22 @@ int mcp_knn_pruned_lengths(int b, int q, int n, int k, int dist_form, const floa
 int mcp_knn_cosine(int b, int q, int n, int c, int k, const float *qfeat, const float *rfeat, int *idx, float *dist,
                    float *workspace, mcp_stream_t stream);
 
+/* mcp_knn_cosine on a padded batch of feature sets of different sizes: element bb searches only the first rlen[bb] rows of rfeat
+ * and only its first qlen[bb] query rows are live.  qlen, rlen: (B) int32 DEVICE arrays, read by the kernels (no synchronisation)
+ * and clamped there to [0,Q] / [0,N]; either may be NULL = every row valid, and with both NULL the call IS mcp_knn_cosine (same
+ * launches, same bits).  C in {64,128,256}, 1 <= K <= 16, workspace B*(Q+N)*C floats as there; the rows of the workspace that
+ * belong to padded rows are left unwritten and nothing depends on them.  The search is split from the padded sizes; the result
+ * does not depend on the split.
+ *   live rows (i < qlen[bb]):    the K smallest under (1 - cosine, index) among references 0 .. rlen[bb]-1, ascending -- what
+ *                                mcp_knn_cosine returns for the two valid prefixes on their own; if rlen[bb] < K the tail repeats
+ *                                the last valid entry; if rlen[bb] == 0, index 0 and distance 0;
+ *   padded rows (i >= qlen[bb]): index 0, distance 0.
+ * Rows of qfeat and rfeat beyond a length are never read: their contents influence no output bit.  Errors as mcp_knn_cosine
+ * (nothing is launched): K > 16 or another C is MCP_ERR_UNSUPPORTED; a null qfeat, rfeat, idx or workspace, a non-positive
+ * dimension or a pointer that is not 16-byte aligned is MCP_ERR_BAD_ARG.  Profiled as MCP_KERNEL_KNN_COSINE. */
+int mcp_knn_cosine_lengths(int b, int q, int n, int c, int k, const float *qfeat, const float *rfeat, const int *qlen,
+                           const int *rlen, int *idx, float *dist, float *workspace, mcp_stream_t stream);
+
 /* index_points_group / index_points_gather (mocopci.py:1190-1215) without the permute copies:
  * points (B,N,C) channel-last, idx (B,T) -> out (B,T,C) (T = S*K or S), whole C*4-byte rows. */
 int mcp_group_rows(int b, int n, int c, int t, const float *points, const int *idx, float *out, mcp_stream_t stream);

@@ -50,6 +50,7 @@ SIGNATURES = {
     "mcp_tile_boxes_lengths": [_i, _i, _p, _p, _p, _p],
     "mcp_knn_pruned_lengths": [_i] * 5 + [_p] * 10,
     "mcp_knn_cosine": [_i] * 5 + [_p] * 6,
+    "mcp_knn_cosine_lengths": [_i] * 5 + [_p] * 8,
     "mcp_group_rows": [_i, _i, _i, _i, _p, _p, _p, _p],
     "mcp_interp3": [_i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p],
     "mcp_interp3_weights": [_i, _i, _i, _p, _p, _p, _p, _p],

@@ -40,9 +40,10 @@ def knn_point(nsample, xyz, new_xyz):
     return ops.backend().knn(new_xyz.contiguous(), xyz.contiguous(), nsample).long()
 
 
-def knn_point_cosine(nsample, xyz, new_xyz):
-    """pointconv_util.py:142-153 on (B,N,C) features."""
-    return ops.backend().knn_cosine(new_xyz.contiguous(), xyz.contiguous(), nsample).long()
+def knn_point_cosine(nsample, xyz, new_xyz, lengths=None, new_lengths=None):
+    """pointconv_util.py:142-153 on (B,N,C) features.  lengths (B,) belongs to xyz, the references, and new_lengths (B,) to
+    new_xyz, the queries (forms: ops.lengths_tensor): rows beyond them are padding, see ops.HipBackend.knn_cosine."""
+    return ops.backend().knn_cosine(new_xyz.contiguous(), xyz.contiguous(), nsample, query_lengths=new_lengths, ref_lengths=lengths).long()
 
 
 def index_points_group(points, knn_idx):

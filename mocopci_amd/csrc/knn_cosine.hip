@@ -26,25 +26,65 @@ constexpr int K = 16, QS = 16, CHK = 4, RT = 32, WAVES = 4;
 
 __device__ __forceinline__ int chan_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
+// Per-cloud lengths of a padded batch (mcp_knn_cosine_lengths), the compile-time switch of the two shipped kernels: each is stated once
+// with a trailing parameter pack L that is either empty -- the plain kernel, with the parameter list and the code it always had -- or
+// one Lengths.  qlen / rlen are (B) int32 device arrays (either may be null: every row of that set is valid); q / n are the padded
+// sizes, which the normalisation needs to find a tile's batch element (the search has them among its own parameters).
+struct Lengths {
+    const int *qlen, *rlen;
+    int q, n;
+};
+__device__ __forceinline__ Lengths lengths_of() { return Lengths{nullptr, nullptr, 0, 0}; }
+__device__ __forceinline__ Lengths lengths_of(const Lengths &l) { return l; }
+// what a padded query row gets: index 0, distance 0 (od may be null)
+__device__ __forceinline__ void store_zeros(int kout, int *oi, float *od) {
+    for (int j = 0; j < kout; ++j) {
+        oi[j] = 0;
+        if (od) od[j] = 0.f;
+    }
+}
+
 // x / sqrt(sum(x^2) + 1e-8): sequential sum of rounded squares (oracle canon).  A wave stages RW consecutive rows
 // through LDS with coalesced float4 traffic (rows are contiguous in memory), lane r < RW sums row r in channel order
 // from a padded (conflict-free) tile, and the scaled rows go back out coalesced.
-template <int C>
+//
+// Without lengths the tiles cover the flat row ranges (rows_a = B*Q, rows_b = B*N).  With lengths a tile lies inside ONE batch element
+// -- ceil(Q / RW) (ceil(N / RW)) tiles for each of the B elements, from the padded size, since the host does not know the lengths -- and
+// is cut at the element's length, read here and clamped; a tile at or beyond the length is skipped.  Rows at or beyond a length are
+// neither loaded nor written (their part of the workspace keeps whatever it held); the arithmetic of a live row is the same.
+template <int C, class... L>
 __global__ __launch_bounds__(256) void normalize_rows_kernel(long long rows_a, const float *__restrict__ xa, float *__restrict__ ya,
-                                                             long long rows_b, const float *__restrict__ xb, float *__restrict__ yb) {
+                                                             long long rows_b, const float *__restrict__ xb, float *__restrict__ yb,
+                                                             L... lens) {
+    constexpr bool LEN = sizeof...(L) != 0;
     constexpr int RW = C <= 64 ? 64 : (C == 128 ? 32 : 16), S = C + 1, V = RW * C / 4;  // float4s per tile
     __shared__ float tile[4][RW * S];
     __shared__ float den[4][RW];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const Lengths len = lengths_of(lens...);
+    // with lengths the tile number decides an element and a length: made wave-uniform for the compiler (scalar loads and branches)
+    const int lane = threadIdx.x & 63, wave = LEN ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
     float *t = tile[wave];
     // both feature sets of a search in ONE launch: tiles [0, ta) belong to (xa, ya), the rest to (xb, yb)
-    const long long ta = (rows_a + RW - 1) / RW, tb = (rows_b + RW - 1) / RW;
+    const int tpa = LEN ? (len.q + RW - 1) / RW : 0, tpb = LEN ? (len.n + RW - 1) / RW : 0;   // with lengths: tiles per element
+    const long long ta = LEN ? rows_a / len.q * tpa : (rows_a + RW - 1) / RW, tb = LEN ? rows_b / len.n * tpb : (rows_b + RW - 1) / RW;
     for (long long g = (long long)blockIdx.x * 4 + wave; g < ta + tb; g += (long long)gridDim.x * 4) {
         const bool second = g >= ta;
         const float *x = second ? xb : xa;
         float *y = second ? yb : ya;
-        const long long rows = second ? rows_b : rows_a, r0 = (second ? g - ta : g) * RW;
-        const int live = (int)min((long long)RW, rows - r0);
+        long long r0;
+        int live;
+        if (LEN) {
+            const int per = second ? len.n : len.q, tpe = second ? tpb : tpa;
+            const long long gg = second ? g - ta : g;
+            const int bb = (int)(gg / tpe), first = (int)(gg % tpe) * RW;
+            live = min(RW, mcp_clamped_len(second ? len.rlen : len.qlen, bb, per) - first);
+            if (live <= 0) continue;   // wave-uniform: the whole tile is padding
+            r0 = (long long)bb * per + first;
+        } else {
+            const long long rows = second ? rows_b : rows_a;
+            r0 = (second ? g - ta : g) * RW;
+            live = (int)min((long long)RW, rows - r0);
+        }
         const float4 *src = reinterpret_cast<const float4 *>(x + r0 * C);
         __builtin_amdgcn_wave_barrier();
         for (int e = lane; e < V; e += 64) {
@@ -75,11 +115,27 @@ __global__ __launch_bounds__(256) void normalize_rows_kernel(long long rows_a, c
     }
 }
 
-template <int C>
-void launch_normalize(long long rows_a, const float *xa, float *ya, long long rows_b, const float *xb, float *yb, hipStream_t s) {
+// everything a search is given; qlen / rlen only where LEN
+struct Args {
+    int b, q, n, k;
+    const int *qlen, *rlen;
+    int *idx;
+    float *dist;
+    hipStream_t s;
+};
+
+template <int C, bool LEN>
+void launch_normalize(const Args &a, const float *xa, float *ya, const float *xb, float *yb) {
     constexpr int RW = C <= 64 ? 64 : (C == 128 ? 32 : 16);
-    const long long tiles = (rows_a + RW - 1) / RW + (rows_b + RW - 1) / RW, blocks = (tiles + 3) / 4;
-    hipLaunchKernelGGL(normalize_rows_kernel<C>, dim3((unsigned)min(blocks, 4096LL)), dim3(256), 0, s, rows_a, xa, ya, rows_b, xb, yb);
+    const long long rows_a = (long long)a.b * a.q, rows_b = (long long)a.b * a.n;
+    if constexpr (LEN) {
+        const long long tiles = (long long)a.b * (mcp_divup(a.q, RW) + mcp_divup(a.n, RW)), blocks = (tiles + 3) / 4;
+        hipLaunchKernelGGL((normalize_rows_kernel<C, Lengths>), dim3((unsigned)min(blocks, 4096LL)), dim3(256), 0, a.s, rows_a, xa, ya, rows_b,
+                           xb, yb, Lengths{a.qlen, a.rlen, a.q, a.n});
+    } else {
+        const long long tiles = (rows_a + RW - 1) / RW + (rows_b + RW - 1) / RW, blocks = (tiles + 3) / 4;
+        hipLaunchKernelGGL(normalize_rows_kernel<C>, dim3((unsigned)min(blocks, 4096LL)), dim3(256), 0, a.s, rows_a, xa, ya, rows_b, xb, yb);
+    }
 }
 
 template <int C>
@@ -181,10 +237,24 @@ __global__ __launch_bounds__(64 * WAVES) void knn_cosine_kernel(int q, int n, in
 // same lines, the next 32 channels are in flight while the 16 MFMAs of these run) -- no LDS tile, no workgroup barrier in the loop;
 // the RS partial lists meet in LDS at the end.  The k-ordered fp32 fma chain per (query, reference) and the (distance, index) order
 // are unchanged, so the indices are the same bits.
-template <int C, int RS>
-__global__ __launch_bounds__(64 * RS) void knn_cosine_split_kernel(int q, int n, int kout, const float *__restrict__ nq,
+//
+// Stated once (see Lengths).  Without lengths it is the plain search.  With them it is the search of a padded batch
+// (mcp_knn_cosine_lengths): element b searches only the first rlen[b] rows of nr and only its first qlen[b] query rows are live.
+// Against the plain search:
+//   * both lengths are one scalar load each (blockIdx.y indexes them), clamped to [0, Q] / [0, N];
+//   * the tile count, and with it what a wave owns, comes from rlen[b]; the clamp of the last tile's row and the "ri < n" filter use it
+//     too.  A wave may own no tile -- with rlen[b] == 0 none does and no row address is formed -- and still meets the others at the two
+//     barriers of the final merge with an all-empty list, which stores as index 0 / distance 0;
+//   * a workgroup whose 32 queries are all padding writes its zeros and leaves, all of it and before the first barrier and the first
+//     load; in one that stays a padded query lane reads row 0 of its element (live: qlen[b] > 32 * blockIdx.x >= 0) and stores zeros;
+//   * so no row beyond a length is read, in particular none of the workspace rows the normalisation left unwritten.
+// The per-pair fma chain and the selection do not depend on which wave owns a tile: live rows are the plain search of the two prefixes,
+// whatever RS the host picked from the padded sizes.
+template <int C, int RS, class... L>
+__global__ __launch_bounds__(64 * RS) void knn_cosine_split_kernel(int q, int n_padded, int kout, const float *__restrict__ nq,
                                                                    const float *__restrict__ nr, int *__restrict__ idx,
-                                                                   float *__restrict__ dist) {
+                                                                   float *__restrict__ dist, L... lens) {
+    constexpr bool LEN = sizeof...(L) != 0;
     constexpr int CH = C / 32;                   // chunks of 32 channels (16 k-steps) per tile
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, col = lane & 31;
@@ -192,7 +262,14 @@ __global__ __launch_bounds__(64 * RS) void knn_cosine_split_kernel(int q, int n,
 
     const int b = blockIdx.y;
     const int qi = blockIdx.x * 32 + col;
-    const bool live = qi < q;
+    // valid rows of this element: queries (row stride stays q) and references (row stride stays n_padded)
+    const Lengths len = lengths_of(lens...);
+    const int qv = LEN ? mcp_clamped_len(len.qlen, b, q) : q, n = LEN ? mcp_clamped_len(len.rlen, b, n_padded) : n_padded;
+    if (LEN && (int)blockIdx.x * 32 >= qv) {   // workgroup-uniform: nothing but padding here
+        if (wave == 0 && h == 0 && qi < q) store_zeros(kout, idx + ((size_t)b * q + qi) * kout, dist ? dist + ((size_t)b * q + qi) * kout : nullptr);
+        return;
+    }
+    const bool live = qi < qv;
     const float *qrow = nq + ((size_t)b * q + (live ? qi : 0)) * C;
     // channel parity h of the query's row (the B operand of k-step i is channel 2i + h).  C <= 128: in registers (whole 16-byte loads,
     // two of the four floats kept).  C = 256 would be 128 registers per lane -- with the staging sets and the selection lists that
@@ -212,7 +289,7 @@ __global__ __launch_bounds__(64 * RS) void knn_cosine_split_kernel(int q, int n,
             bq[QL ? 0 : 2 * j + 1] = h ? v.w : v.z;
         }
     }
-    nr += (size_t)b * n * C;
+    nr += (size_t)b * n_padded * C;
 
     u64 a[K];
 #pragma unroll
@@ -300,34 +377,40 @@ __global__ __launch_bounds__(64 * RS) void knn_cosine_split_kernel(int q, int n,
         }
         mcp_merge_sorted<K, K>(a, o);
     }
-    if (!live) return;
+    if (LEN ? qi >= q : !live) return;
     int *oi = idx + ((size_t)b * q + qi) * kout;
     float *od = dist ? dist + ((size_t)b * q + qi) * kout : nullptr;
-    mcp_store_list<K>(a, kout, oi, od);
+    if (LEN && !live) store_zeros(kout, oi, od);   // a padded query of a workgroup that had live ones
+    else mcp_store_list<K>(a, kout, oi, od);
 }
 
-template <int C, int RS>
-int launch_cosine_split(int b, int q, int n, int k, const float *nq, const float *nr, int *idx, float *dist, hipStream_t s) {
+template <int C, int RS, bool LEN>
+int launch_cosine_split(const Args &a, const float *nq, const float *nr) {
     static_assert(K == QS && (C / 32) % 2 == 0, "the partial lists reuse the queues; chunks are consumed in pairs");
     const size_t lds = (size_t)RS * QS * 64 * sizeof(uint2) + (C > 128 ? (size_t)(C / 2) * 64 * sizeof(float) : 0);
-    auto kern = knn_cosine_split_kernel<C, RS>;
-    static McpPerDeviceOnce attr_once;
+    constexpr auto plain = knn_cosine_split_kernel<C, RS>;
+    constexpr auto len = knn_cosine_split_kernel<C, RS, Lengths>;
+    static McpPerDeviceOnce attr_once;   // one per instantiation, that is per kernel symbol
     if (attr_once.need()) {
-        { const hipError_t attr_e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); if (attr_e_ != hipSuccess) return (int)attr_e_; }
+        const void *kern = LEN ? reinterpret_cast<const void *>(len) : reinterpret_cast<const void *>(plain);
+        { const hipError_t attr_e_ = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); if (attr_e_ != hipSuccess) return (int)attr_e_; }
         attr_once.done();
     }
-    hipLaunchKernelGGL(kern, dim3(mcp_divup(q, 32), b), dim3(64 * RS), lds, s, q, n, k, nq, nr, idx, dist);
+    const dim3 grid(mcp_divup(a.q, 32), a.b), block(64 * RS);
+    if constexpr (LEN) hipLaunchKernelGGL(len, grid, block, lds, a.s, a.q, a.n, a.k, nq, nr, a.idx, a.dist, Lengths{a.qlen, a.rlen, a.q, a.n});
+    else hipLaunchKernelGGL(plain, grid, block, lds, a.s, a.q, a.n, a.k, nq, nr, a.idx, a.dist);
     return mcp_launch_status();
 }
 
-// reference parts per workgroup: enough waves to cover the chip's 1024 SIMDs twice where the problem allows it
-template <int C>
-int launch_cosine_auto(int b, int q, int n, int k, const float *nq, const float *nr, int *idx, float *dist, hipStream_t s) {
-    const long long groups = (long long)b * ((q + 31) / 32);
-    const int tiles = (n + RT - 1) / RT;
-    if (groups * 2 >= 2048 || tiles < 4) return launch_cosine_split<C, 2>(b, q, n, k, nq, nr, idx, dist, s);
-    if (groups * 4 >= 2048 || tiles < 8) return launch_cosine_split<C, 4>(b, q, n, k, nq, nr, idx, dist, s);
-    return launch_cosine_split<C, 8>(b, q, n, k, nq, nr, idx, dist, s);
+// reference parts per workgroup: enough waves to cover the chip's 1024 SIMDs twice where the problem allows it.  From the PADDED sizes,
+// with lengths too: the host does not know them (reading them would be a synchronisation), and the result does not depend on RS.
+template <int C, bool LEN>
+int launch_cosine_auto(const Args &a, const float *nq, const float *nr) {
+    const long long groups = (long long)a.b * ((a.q + 31) / 32);
+    const int tiles = (a.n + RT - 1) / RT;
+    if (groups * 2 >= 2048 || tiles < 4) return launch_cosine_split<C, 2, LEN>(a, nq, nr);
+    if (groups * 4 >= 2048 || tiles < 8) return launch_cosine_split<C, 4, LEN>(a, nq, nr);
+    return launch_cosine_split<C, 8, LEN>(a, nq, nr);
 }
 
 template <int C>
@@ -343,38 +426,49 @@ int launch_cosine(int b, int q, int n, int k, const float *nq, const float *nr, 
     return mcp_launch_status();
 }
 
+#ifdef MCP_AB
+int g_cosine_use_old = 0;   // A/B builds only: 1 = round 3's shared-tile kernel
+#endif
+
+// normalise both sets, then search: the two launches of either entry point
+template <int C, bool LEN>
+int search_c(const Args &a, const float *qfeat, const float *rfeat, float *nq, float *nr) {
+    launch_normalize<C, LEN>(a, qfeat, nq, rfeat, nr);
+    const int rc = mcp_launch_status();
+    if (rc != MCP_OK) return rc;
+#ifdef MCP_AB
+    if (!LEN && g_cosine_use_old) return launch_cosine<C>(a.b, a.q, a.n, a.k, nq, nr, a.idx, a.dist, a.s);
+#endif
+    return launch_cosine_auto<C, LEN>(a, nq, nr);
+}
+
+template <bool LEN>
+int search(int c, const Args &a, const float *qfeat, const float *rfeat, float *workspace) {
+    MCP_CHECK_ARGS(a.b > 0 && a.q > 0 && a.n > 0 && c > 0 && a.k > 0 && qfeat && rfeat && a.idx && workspace);
+    if (a.k > K || (c != 64 && c != 128 && c != 256)) return MCP_ERR_UNSUPPORTED;
+    if ((((uintptr_t)qfeat) | ((uintptr_t)rfeat) | ((uintptr_t)workspace)) & 15) return MCP_ERR_BAD_ARG;  // float4 row traffic
+    float *nq = workspace, *nr = workspace + (size_t)a.b * a.q * c;
+    mcp_prof_begin(MCP_KERNEL_KNN_COSINE, a.s);
+    const int rc = c == 64    ? search_c<64, LEN>(a, qfeat, rfeat, nq, nr)
+                   : c == 128 ? search_c<128, LEN>(a, qfeat, rfeat, nq, nr)
+                              : search_c<256, LEN>(a, qfeat, rfeat, nq, nr);
+    mcp_prof_end(MCP_KERNEL_KNN_COSINE, a.s);
+    return rc;
+}
+
 }  // namespace
 
 #ifdef MCP_AB
-static int g_cosine_use_old = 0;   // A/B builds only: 1 = round 3's shared-tile kernel
 extern "C" __attribute__((visibility("default"))) void mcp_knn_cosine_use_old(int on) { g_cosine_use_old = on; }
 #endif
 
 MCP_EXPORT int mcp_knn_cosine(int b, int q, int n, int c, int k, const float *qfeat, const float *rfeat, int *idx, float *dist,
                               float *workspace, mcp_stream_t stream) {
-    MCP_CHECK_ARGS(b > 0 && q > 0 && n > 0 && c > 0 && k > 0 && qfeat && rfeat && idx && workspace);
-    if (k > K || (c != 64 && c != 128 && c != 256)) return MCP_ERR_UNSUPPORTED;
-    if ((((uintptr_t)qfeat) | ((uintptr_t)rfeat) | ((uintptr_t)workspace)) & 15) return MCP_ERR_BAD_ARG;  // float4 row traffic
-    hipStream_t s = (hipStream_t)stream;
-    float *nq = workspace, *nr = workspace + (size_t)b * q * c;
-    mcp_prof_begin(MCP_KERNEL_KNN_COSINE, s);
-    const long long rq = (long long)b * q, rr = (long long)b * n;
-    if (c == 64) launch_normalize<64>(rq, qfeat, nq, rr, rfeat, nr, s);
-    else if (c == 128) launch_normalize<128>(rq, qfeat, nq, rr, rfeat, nr, s);
-    else launch_normalize<256>(rq, qfeat, nq, rr, rfeat, nr, s);
-    int rc = mcp_launch_status();
-    if (rc == MCP_OK) {
-#ifdef MCP_AB
-        if (g_cosine_use_old)
-            rc = c == 64    ? launch_cosine<64>(b, q, n, k, nq, nr, idx, dist, s)
-                 : c == 128 ? launch_cosine<128>(b, q, n, k, nq, nr, idx, dist, s)
-                            : launch_cosine<256>(b, q, n, k, nq, nr, idx, dist, s);
-        else
-#endif
-        rc = c == 64    ? launch_cosine_auto<64>(b, q, n, k, nq, nr, idx, dist, s)
-             : c == 128 ? launch_cosine_auto<128>(b, q, n, k, nq, nr, idx, dist, s)
-                        : launch_cosine_auto<256>(b, q, n, k, nq, nr, idx, dist, s);
-    }
-    mcp_prof_end(MCP_KERNEL_KNN_COSINE, s);
-    return rc;
+    return search<false>(c, Args{b, q, n, k, nullptr, nullptr, idx, dist, (hipStream_t)stream}, qfeat, rfeat, workspace);
+}
+
+MCP_EXPORT int mcp_knn_cosine_lengths(int b, int q, int n, int c, int k, const float *qfeat, const float *rfeat, const int *qlen,
+                                      const int *rlen, int *idx, float *dist, float *workspace, mcp_stream_t stream) {
+    if (!qlen && !rlen) return mcp_knn_cosine(b, q, n, c, k, qfeat, rfeat, idx, dist, workspace, stream);  // the same launches, the same bits
+    return search<true>(c, Args{b, q, n, k, qlen, rlen, idx, dist, (hipStream_t)stream}, qfeat, rfeat, workspace);
 }

@@ -1544,15 +1544,24 @@ class HipBackend:
               _lib.fptr(dist) if return_dist else None)
         return (idx, dist) if return_dist else idx
 
-    def knn_cosine(self, qfeat, rfeat, k, return_dist=False):
+    def knn_cosine(self, qfeat, rfeat, k, return_dist=False, query_lengths=None, ref_lengths=None):
         """knn_point_cosine(k, rfeat, qfeat) (pointconv_util.py:111-153) on channel-last features:
-        (B,Q,C),(B,N,C) -> (B,Q,k) int32, ascending by (1 - cosine, index).  MFMA kernel, C in {64,128,256}."""
+        (B,Q,C),(B,N,C) -> (B,Q,k) int32, ascending by (1 - cosine, index).  MFMA kernel, C in {64,128,256}.
+        query_lengths / ref_lengths (forms: lengths_tensor): element b searches only rfeat[b, :ref_lengths[b]] and only
+        qfeat[b, :query_lengths[b]] is live.  Live rows get what the search of the two prefixes on their own returns (fewer than k
+        references: the tail repeats the last valid entry; none: index 0, distance 0); padded query rows get index 0 and distance 0;
+        padded rows of either set are never read.  Without lengths nothing changes."""
         qfeat, rfeat = qfeat.detach().contiguous(), rfeat.detach().contiguous()
         B, Q, C = qfeat.shape
         N = rfeat.shape[1]
         idx = torch.empty((B, Q, k), dtype=torch.int32, device=qfeat.device)
         dist = torch.empty((B, Q, k), dtype=torch.float32, device=qfeat.device) if return_dist else None
         ws = torch.empty((B * (Q + N) * C,), dtype=torch.float32, device=qfeat.device)
+        if query_lengths is not None or ref_lengths is not None:
+            ql, rl = lengths_tensor(query_lengths, B, Q, qfeat.device), lengths_tensor(ref_lengths, B, N, qfeat.device)
+            _call("mcp_knn_cosine_lengths", qfeat, B, Q, N, C, k, _lib.fptr(qfeat), _lib.fptr(rfeat), None if ql is None else _lib.iptr(ql),
+                  None if rl is None else _lib.iptr(rl), _lib.iptr(idx), _lib.fptr(dist) if return_dist else None, _lib.fptr(ws))
+            return (idx, dist) if return_dist else idx
         _call("mcp_knn_cosine", qfeat, B, Q, N, C, k, _lib.fptr(qfeat), _lib.fptr(rfeat), _lib.iptr(idx),
               _lib.fptr(dist) if return_dist else None, _lib.fptr(ws))
         return (idx, dist) if return_dist else idx
