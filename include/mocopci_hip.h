@@ -751,6 +751,46 @@ int mcp_attention_wide_grad_lse(int bf, int nq, int nk, int heads, int hd, const
                                 int v_stride, float scale, float drop_p, unsigned seed, const float *out, const float *grad_out, const float *lse,
                                 float *grad_q, float *grad_kv, void *workspace, size_t workspace_bytes, mcp_stream_t stream);
 
+/* ---- attention over a padded batch whose elements have their own lengths ----
+ * qlen, klen: (BF) int32 device arrays; either may be NULL (that side is full).  The kernels read them and clamp to [0, nq] / [0, nk]
+ * themselves; the host never reads them back, so a call causes no synchronisation.  klen is indexed by the key / value tensor's own
+ * batch element: with a rotation, the queries of element b use klen[(b + kv_batch_shift) mod BF].  nq and nk stay the padded sizes:
+ * they give the batch strides and, under dropout, the rows and columns of the hash (a length changes which entries exist, not their
+ * mask).  With ql, kl the clamped lengths of an element:
+ *     query rows i <  ql   softmax_{j < kl}(q_i . k_j scale) v_j; lse that row's log-sum-exp (log2 domain);
+ *     query rows i >= ql   out = 0, lse = 0 (the rows are written: the caller need not clear out);
+ *     kl = 0               every row of out and lse is 0; nothing is NaN or inf.
+ * Backward: grad_q is 0 in rows >= ql and everywhere in an element with kl = 0; grad_kv (both halves) is 0 in rows >= kl and everywhere
+ * in an element with ql = 0; live rows hold the gradients of the function above.  No value of q, k, v, out or grad_out at or beyond a
+ * length reaches an output (padding may hold NaN or inf); the backward's D = dO . O pass covers the padded tensor, but its values at
+ * rows >= ql are never read.  Key loops end at kl and a workgroup whose rows all lie beyond the length writes its zeros and returns:
+ * the cost follows the live part.  A live row is computed by the same instruction sequence as the plain call on the element's sliced
+ * prefixes (head widths 8 - 64: bit for bit; width 256: the key-split dispatch is decided from the PADDED sizes, and the key stages
+ * are then shared out over the waves from the element's own kl).  Both arrays NULL: the plain call, forwarded.  Status codes as the
+ * plain calls; qlen / klen need 4-byte alignment.
+ *
+ * mcp_attention_lengths: mcp_attention (hd in {8, 16, 32, 64, 256}, rotation, row strides) with lengths. */
+int mcp_attention_lengths(int bf, int nq, int nk, int heads, int hd, const float *q, int q_stride, const float *k, int k_stride,
+                          const float *v, int v_stride, int kv_batch_shift, float scale, const int *qlen, const int *klen, float *out,
+                          int out_stride, mcp_stream_t stream);
+/* The training forwards mcp_attention_small_lse (hd 8 / 16) and mcp_attention_wide_lse (hd 32 / 64 / 256) with lengths; lse may be NULL. */
+int mcp_attention_small_lse_lengths(int bf, int nq, int nk, int heads, int hd, const float *q, int q_stride, const float *k, int k_stride,
+                                    const float *v, int v_stride, float scale, float drop_p, unsigned seed, float *out, float *lse,
+                                    const int *qlen, const int *klen, mcp_stream_t stream);
+int mcp_attention_wide_lse_lengths(int bf, int nq, int nk, int heads, int hd, const float *q, int q_stride, const float *k, int k_stride,
+                                   const float *v, int v_stride, float scale, float drop_p, unsigned seed, float *out, float *lse,
+                                   const int *qlen, const int *klen, mcp_stream_t stream);
+/* The backwards mcp_attention_small_grad_lse and mcp_attention_wide_grad_lse with lengths (out, lse: the length forward's); workspace as
+ * the plain calls (mcp_attention_small_grad_workspace_bytes / mcp_attention_wide_grad_workspace_bytes). */
+int mcp_attention_small_grad_lse_lengths(int bf, int nq, int nk, int heads, int hd, const float *q, int q_stride, const float *k, int k_stride,
+                                         const float *v, int v_stride, float scale, float drop_p, unsigned seed, const float *out,
+                                         const float *grad_out, const float *lse, float *grad_q, float *grad_kv, void *workspace,
+                                         size_t workspace_bytes, const int *qlen, const int *klen, mcp_stream_t stream);
+int mcp_attention_wide_grad_lse_lengths(int bf, int nq, int nk, int heads, int hd, const float *q, int q_stride, const float *k, int k_stride,
+                                        const float *v, int v_stride, float scale, float drop_p, unsigned seed, const float *out,
+                                        const float *grad_out, const float *lse, float *grad_q, float *grad_kv, void *workspace,
+                                        size_t workspace_bytes, const int *qlen, const int *klen, mcp_stream_t stream);
+
 /* Row normalisation with the additions in front of it (nn.LayerNorm semantics: biased variance, eps inside the root):
  *     z = x[r] (+ y[r]) (+ bias);   out[r] = (z - mean z) * rsqrt(var z + eps) (* gamma + beta)
  * x, y, out (rows, c) with row strides in floats; y, bias, gamma, beta may be NULL; c <= 1024.  Replaces the LayerNorm launches

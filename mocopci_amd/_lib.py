@@ -119,6 +119,11 @@ SIGNATURES = {
     "mcp_attention_wide_lse": [_i] * 5 + [_p, _i, _p, _i, _p, _i, _f, _f, ctypes.c_uint, _p, _p, _p],
     "mcp_attention_wide_grad_workspace_bytes": [_i] * 5,
     "mcp_attention_wide_grad_lse": [_i] * 5 + [_p, _i, _p, _i, _p, _i, _f, _f, ctypes.c_uint, _p, _p, _p, _p, _p, _p, ctypes.c_size_t, _p],
+    "mcp_attention_lengths": [_i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _i, _i, _f, _p, _p, _p, _i, _p],
+    "mcp_attention_small_lse_lengths": [_i] * 5 + [_p, _i, _p, _i, _p, _i, _f, _f, ctypes.c_uint, _p, _p, _p, _p, _p],
+    "mcp_attention_wide_lse_lengths": [_i] * 5 + [_p, _i, _p, _i, _p, _i, _f, _f, ctypes.c_uint, _p, _p, _p, _p, _p],
+    "mcp_attention_small_grad_lse_lengths": [_i] * 5 + [_p, _i, _p, _i, _p, _i, _f, _f, ctypes.c_uint, _p, _p, _p, _p, _p, _p, ctypes.c_size_t, _p, _p, _p],
+    "mcp_attention_wide_grad_lse_lengths": [_i] * 5 + [_p, _i, _p, _i, _p, _i, _f, _f, ctypes.c_uint, _p, _p, _p, _p, _p, _p, ctypes.c_size_t, _p, _p, _p],
     "mcp_chamfer_nn": [_i, _i, _i, _p, _p, _p, _p, _p],
     "mcp_chamfer_nn_lengths": [_i, _i, _i, _p, _p, _p, _p, _p, _p, _p],
     "mcp_ptblock_packed_floats": [],

@@ -11,6 +11,7 @@
 // Every sum has a fixed order (lane-local chains, two lane halves added once): results repeat bit for bit.
 #include "common.h"
 #include "attention_dropout.h"
+#include "attention_lengths.h"
 
 namespace {
 
@@ -41,18 +42,33 @@ struct Stage {
 // that normalise the softmax are taken before the mask, as softmax -> dropout -> matmul does) ----
 // lse != NULL: the row's log-sum-exp (log2 domain, the statistic attention_stats_kernel recomputes) is written for the backward --
 // a training forward keeps it (mcp_attention_small_lse) and the backward skips the statistics pass.  DROP = false: no mask.
-template <int HD, bool DROP>
+// L: empty, or one AttnLengths -- the length form (attention_lengths.h): the key loop ends at the element's kl, rows at or beyond ql
+// are zeros (out and lse), an element without keys is zeros.
+template <int HD, bool DROP, class... L>
 __global__ __launch_bounds__(64 * WAVES) void attention_small_drop_kernel(int nq, int nk, int heads, const float *__restrict__ q, int qs,
                                                                           const float *__restrict__ k, int ks, const float *__restrict__ v, int vs,
                                                                           float scale_log2e, uint32_t seed, uint32_t threshold, float inv_keep,
-                                                                          float *__restrict__ out, float *__restrict__ lse) {
+                                                                          float *__restrict__ out, float *__restrict__ lse, L... lens) {
+    constexpr bool LEN = sizeof...(L) != 0;
     constexpr int KS = HD + 1;
     __shared__ float kt[2][KT * KS];
     __shared__ __attribute__((aligned(16))) float vt[2][KT * HD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, col = lane & 31;
     const int head = blockIdx.y, bf = blockIdx.z;
     const int qi = blockIdx.x * (32 * WAVES) + wave * 32 + col;
-    const bool live = qi < nq;
+    const AttnSpan sp = attn_span(nq, nk, bf, bf, lens...);
+    const int ql = sp.ql, kl = sp.kl;
+    if constexpr (LEN) {
+        // a query block wholly beyond the length, or an element without keys: zeros, before a key is loaded
+        if ((int)blockIdx.x * (32 * WAVES) >= ql || kl == 0) {
+            if (qi < nq) {
+                attn_zero_row<HD / 2>(out + ((size_t)bf * nq + qi) * (size_t)(heads * HD) + head * HD + h * (HD / 2));
+                if (lse && h == 0) lse[((size_t)bf * heads + head) * nq + qi] = 0.f;
+            }
+            return;
+        }
+    }
+    const bool live = qi < ql;
     const size_t qrow = (size_t)bf * nq + (live ? qi : 0);
     const uint32_t row = (uint32_t)(((size_t)bf * heads + head) * nq + qi);
     q += qrow * qs + head * HD;
@@ -73,7 +89,7 @@ __global__ __launch_bounds__(64 * WAVES) void attention_small_drop_kernel(int nq
             const bool isv = e >= F4;
             const int f = isv ? e - F4 : e, r_ = f / (HD / 4), c4 = f % (HD / 4), key = t * KT + r_;
             pre[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (e < 2 * F4 && key < nk) pre[u] = *reinterpret_cast<const float4 *>((isv ? v + (size_t)key * vs : k + (size_t)key * ks) + c4 * 4);
+            if (e < 2 * F4 && key < kl) pre[u] = *reinterpret_cast<const float4 *>((isv ? v + (size_t)key * vs : k + (size_t)key * ks) + c4 * 4);
         }
     };
     auto stash = [&](int buf) {
@@ -91,7 +107,7 @@ __global__ __launch_bounds__(64 * WAVES) void attention_small_drop_kernel(int nq
             }
         }
     };
-    const int stages = (nk + KT - 1) / KT;
+    const int stages = (kl + KT - 1) / KT;
     fetch(0);
     stash(0);
     for (int t = 0; t < stages; ++t) {
@@ -107,10 +123,10 @@ __global__ __launch_bounds__(64 * WAVES) void attention_small_drop_kernel(int nq
 #pragma unroll
             for (int s = 0; s < HD / 2; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[2 * s], qf[s], acc, 0, 0, 0);
             const int kbase = t * KT + sub * 32;
-            if (kbase + 32 > nk) {
+            if (kbase + 32 > kl) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    if (kbase + chan_of(r, h) >= nk) acc[r] = -INFINITY;
+                    if (kbase + chan_of(r, h) >= kl) acc[r] = -INFINITY;
             }
             float mt = acc[0];
 #pragma unroll
@@ -156,6 +172,12 @@ __global__ __launch_bounds__(64 * WAVES) void attention_small_drop_kernel(int nq
 #pragma unroll
         for (int d = 0; d < HD; d += 4) *reinterpret_cast<float4 *>(dst + d) = make_float4(res[d], res[d + 1], res[d + 2], res[d + 3]);
         if (lse) lse[((size_t)bf * heads + head) * nq + qi] = mm + __builtin_amdgcn_logf(lsum);  // v_log_f32 is log2: as attention_stats_kernel
+    }
+    if constexpr (LEN) {
+        if (!live && qi < nq && h == 0) {
+            attn_zero_row<HD>(out + ((size_t)bf * nq + qi) * (size_t)(heads * HD) + head * HD);
+            if (lse) lse[((size_t)bf * heads + head) * nq + qi] = 0.f;
+        }
     }
 }
 
@@ -266,12 +288,15 @@ __global__ __launch_bounds__(64 * WAVES) void attention_stats_kernel(int nq, int
 }
 
 // ---- dq: query-stationary ----
-template <int HD, bool DROP>
+// L: empty, or one AttnLengths: the key loop ends at the element's kl, rows at or beyond ql are zeros.  L and D of a row at or beyond
+// ql (the dsum pass covers the padded tensor, so D may be anything there) are never read: lanes past ql take row 0 of the element.
+template <int HD, bool DROP, class... LN>
 __global__ __launch_bounds__(64 * WAVES, 2) void attention_dq_kernel(int nq, int nk, int heads, const float *__restrict__ q, int qs, const float *__restrict__ k,
                                                                   int ks, const float *__restrict__ v, int vs, float scale_log2e, float scale,
                                                                   uint32_t seed, uint32_t threshold, float inv_keep,
                                                                   const float *__restrict__ gout, const float *__restrict__ lse,
-                                                                  const float *__restrict__ dsum, float *__restrict__ dq) {
+                                                                  const float *__restrict__ dsum, float *__restrict__ dq, LN... lens) {
+    constexpr bool LEN = sizeof...(LN) != 0;   // (L is the row's log-sum-exp below)
     constexpr int KS = HD + 1;
     __shared__ float kt[2][KT * KS];                                  // K, padded: A operand of S
     __shared__ float vt[2][KT * KS];                                  // V, padded: A operand of dP
@@ -279,7 +304,15 @@ __global__ __launch_bounds__(64 * WAVES, 2) void attention_dq_kernel(int nq, int
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, col = lane & 31;
     const int head = blockIdx.y, bf = blockIdx.z;
     const int qi = blockIdx.x * (32 * WAVES) + wave * 32 + col;
-    const bool live = qi < nq;
+    const AttnSpan sp = attn_span(nq, nk, bf, bf, lens...);
+    const int kl = sp.kl;
+    const bool live = qi < sp.ql;
+    if constexpr (LEN) {
+        if ((int)blockIdx.x * (32 * WAVES) >= sp.ql) {   // the query block lies beyond the length: zeros
+            if (qi < nq) attn_zero_row<HD / 2>(dq + ((size_t)bf * nq + qi) * (size_t)(heads * HD) + head * HD + h * (HD / 2));
+            return;
+        }
+    }
     const size_t qrow = (size_t)bf * nq + (live ? qi : 0);
     q += qrow * qs + head * HD;
     k += (size_t)bf * nk * ks + head * HD;
@@ -306,7 +339,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void attention_dq_kernel(int nq, int
             const bool isv = e >= F4;
             const int f = isv ? e - F4 : e, row = f / (HD / 4), c4 = f % (HD / 4), key = t * KT + row;
             pre[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (e < 2 * F4 && key < nk) pre[u] = *reinterpret_cast<const float4 *>((isv ? v + (size_t)key * vs : k + (size_t)key * ks) + c4 * 4);
+            if (e < 2 * F4 && key < kl) pre[u] = *reinterpret_cast<const float4 *>((isv ? v + (size_t)key * vs : k + (size_t)key * ks) + c4 * 4);
         }
     };
     auto stash = [&](int buf) {
@@ -321,7 +354,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void attention_dq_kernel(int nq, int
             if (!isv) *reinterpret_cast<float4 *>(&kp[buf][row * HD + c4 * 4]) = pre[u];
         }
     };
-    const int stages = (nk + KT - 1) / KT;
+    const int stages = (kl + KT - 1) / KT;
     fetch(0);
     stash(0);
     for (int t = 0; t < stages; ++t) {
@@ -344,7 +377,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void attention_dq_kernel(int nq, int
             for (int r = 0; r < 16; ++r) {
                 const int key = sub * 32 + chan_of(r, h);
                 float p = __builtin_amdgcn_exp2f(acc[r] - L);
-                if (kbase + chan_of(r, h) >= nk) p = 0.f;
+                if (kbase + chan_of(r, h) >= kl) p = 0.f;
                 const float mk = DROP ? drop_scale(seed, drow, (uint32_t)(kbase + chan_of(r, h)), threshold, inv_keep) : 1.0f;
                 float ds = p * (mk * accp[r] - D);
                 int off = key * HD;
@@ -371,15 +404,21 @@ __global__ __launch_bounds__(64 * WAVES, 2) void attention_dq_kernel(int nq, int
 #pragma unroll
         for (int d = 0; d < HD; d += 4) *reinterpret_cast<float4 *>(dst + d) = make_float4(res[d], res[d + 1], res[d + 2], res[d + 3]);
     }
+    if constexpr (LEN) {
+        if (!live && qi < nq && h == 0) attn_zero_row<HD>(dq + ((size_t)bf * nq + qi) * (size_t)(heads * HD) + head * HD);
+    }
 }
 
 // ---- dkv: key-stationary; writes dK | dV into a (BF, Nk, 2 heads HD) tensor laid out like the forward's kv ----
-template <int HD, bool DROP>
+// L: empty, or one AttnLengths: the query loop ends at the element's ql (no L, D, Q or dO row beyond it is loaded), rows at or beyond kl
+// are zeros in both halves.
+template <int HD, bool DROP, class... L>
 __global__ __launch_bounds__(64 * WAVES, 2) void attention_dkv_kernel(int nq, int nk, int heads, const float *__restrict__ q, int qs, const float *__restrict__ k,
                                                                    int ks, const float *__restrict__ v, int vs, float scale_log2e, float scale,
                                                                    uint32_t seed, uint32_t threshold, float inv_keep,
                                                                    const float *__restrict__ gout, const float *__restrict__ lse,
-                                                                   const float *__restrict__ dsum, float *__restrict__ dkv) {
+                                                                   const float *__restrict__ dsum, float *__restrict__ dkv, L... lens) {
+    constexpr bool LEN = sizeof...(L) != 0;
     constexpr int KS = HD + 1;
     __shared__ float qt[2][KT * KS];                                  // Q, padded: A operand of S
     __shared__ float gt[2][KT * KS];                                  // dO, padded: A operand of dP
@@ -389,7 +428,19 @@ __global__ __launch_bounds__(64 * WAVES, 2) void attention_dkv_kernel(int nq, in
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, col = lane & 31;
     const int head = blockIdx.y, bf = blockIdx.z;
     const int ki = blockIdx.x * (32 * WAVES) + wave * 32 + col;
-    const bool live = ki < nk;
+    const AttnSpan sp = attn_span(nq, nk, bf, bf, lens...);
+    const int ql = sp.ql;
+    const bool live = ki < sp.kl;
+    if constexpr (LEN) {
+        if ((int)blockIdx.x * (32 * WAVES) >= sp.kl) {   // the key block lies beyond the length: zeros in dK and dV
+            if (ki < nk) {
+                float *z = dkv + ((size_t)bf * nk + ki) * (size_t)(2 * heads * HD) + head * HD + h * (HD / 2);
+                attn_zero_row<HD / 2>(z);
+                attn_zero_row<HD / 2>(z + heads * HD);
+            }
+            return;
+        }
+    }
     const size_t krow = (size_t)bf * nk + (live ? ki : 0);
     const float *kr_ = k + krow * ks + head * HD, *vr_ = v + krow * vs + head * HD;
     q += (size_t)bf * nq * qs + head * HD;
@@ -416,12 +467,12 @@ __global__ __launch_bounds__(64 * WAVES, 2) void attention_dkv_kernel(int nq, in
             const bool isg = e >= F4;
             const int f = isg ? e - F4 : e, row = f / (HD / 4), c4 = f % (HD / 4), qq = t * KT + row;
             pre[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (e < 2 * F4 && qq < nq) pre[u] = *reinterpret_cast<const float4 *>((isg ? gout + (size_t)qq * (heads * HD) : q + (size_t)qq * qs) + c4 * 4);
+            if (e < 2 * F4 && qq < ql) pre[u] = *reinterpret_cast<const float4 *>((isg ? gout + (size_t)qq * (heads * HD) : q + (size_t)qq * qs) + c4 * 4);
         }
         if (tid < KT) {
             const int qq = t * KT + tid;
-            pl = qq < nq ? lse[qq] : INFINITY;  // a query beyond nq contributes p = exp2(s - inf) = 0
-            pd = qq < nq ? dsum[qq] : 0.f;
+            pl = qq < ql ? lse[qq] : INFINITY;  // a query beyond ql contributes p = exp2(s - inf) = 0
+            pd = qq < ql ? dsum[qq] : 0.f;
         }
     };
     auto stash = [&](int buf) {
@@ -440,7 +491,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void attention_dkv_kernel(int nq, in
             dt[buf][tid] = pd;
         }
     };
-    const int stages = (nq + KT - 1) / KT;
+    const int stages = (ql + KT - 1) / KT;
     fetch(0);
     stash(0);
     for (int t = 0; t < stages; ++t) {
@@ -500,13 +551,20 @@ __global__ __launch_bounds__(64 * WAVES, 2) void attention_dkv_kernel(int nq, in
             *reinterpret_cast<float4 *>(dst + heads * HD + d) = make_float4(rv[d], rv[d + 1], rv[d + 2], rv[d + 3]);
         }
     }
+    if constexpr (LEN) {
+        if (!live && ki < nk && h == 0) {
+            float *z = dkv + ((size_t)bf * nk + ki) * (size_t)(2 * heads * HD) + head * HD;
+            attn_zero_row<HD>(z);
+            attn_zero_row<HD>(z + heads * HD);
+        }
+    }
 }
 
 // saved_lse != NULL: the forward's log-sum-exp (mcp_attention_small_lse): only D = dO . O is computed here; else the statistics pass
-template <int HD, bool DROP>
+template <int HD, bool DROP, class... L>
 int launch_all(int bf, int nq, int nk, int heads, const float *q, int qs, const float *k, int ks, const float *v, int vs, float scale, uint32_t seed,
                uint32_t threshold, float inv_keep, const float *out, const float *gout, float *dq, float *dkv, float *lse, float *dsum,
-               const float *saved_lse, hipStream_t s) {
+               const float *saved_lse, hipStream_t s, L... lens) {
     const float sl2 = scale * 1.44269504088896340736f;
     const dim3 gq(mcp_divup(nq, 32 * WAVES), heads, bf), gk(mcp_divup(nk, 32 * WAVES), heads, bf);
     if (saved_lse) {
@@ -516,10 +574,10 @@ int launch_all(int bf, int nq, int nk, int heads, const float *q, int qs, const 
     } else {
         hipLaunchKernelGGL(attention_stats_kernel<HD>, gq, dim3(64 * WAVES), 0, s, nq, nk, heads, q, qs, k, ks, sl2, out, gout, lse, dsum);
     }
-    hipLaunchKernelGGL((attention_dq_kernel<HD, DROP>), gq, dim3(64 * WAVES), 0, s, nq, nk, heads, q, qs, k, ks, v, vs, sl2, scale, seed, threshold, inv_keep,
-                       gout, lse, dsum, dq);
-    hipLaunchKernelGGL((attention_dkv_kernel<HD, DROP>), gk, dim3(64 * WAVES), 0, s, nq, nk, heads, q, qs, k, ks, v, vs, sl2, scale, seed, threshold, inv_keep,
-                       gout, lse, dsum, dkv);
+    hipLaunchKernelGGL((attention_dq_kernel<HD, DROP, L...>), gq, dim3(64 * WAVES), 0, s, nq, nk, heads, q, qs, k, ks, v, vs, sl2, scale, seed, threshold, inv_keep,
+                       gout, lse, dsum, dq, lens...);
+    hipLaunchKernelGGL((attention_dkv_kernel<HD, DROP, L...>), gk, dim3(64 * WAVES), 0, s, nq, nk, heads, q, qs, k, ks, v, vs, sl2, scale, seed, threshold, inv_keep,
+                       gout, lse, dsum, dkv, lens...);
     return mcp_launch_status();
 }
 
@@ -531,8 +589,9 @@ MCP_EXPORT size_t mcp_attention_small_grad_workspace_bytes(int bf, int nq, int h
 }
 
 namespace {
+template <class... L>
 int forward_with(int bf, int nq, int nk, int heads, int hd, const float *q, int q_stride, const float *k, int k_stride, const float *v, int v_stride,
-                 float scale, float drop_p, unsigned seed, float *out, float *lse, mcp_stream_t stream);
+                 float scale, float drop_p, unsigned seed, float *out, float *lse, mcp_stream_t stream, L... lens);
 }
 
 MCP_EXPORT int mcp_attention_small_dropout(int bf, int nq, int nk, int heads, int hd, const float *q, int q_stride, const float *k, int k_stride,
@@ -547,9 +606,19 @@ MCP_EXPORT int mcp_attention_small_lse(int bf, int nq, int nk, int heads, int hd
     return forward_with(bf, nq, nk, heads, hd, q, q_stride, k, k_stride, v, v_stride, scale, drop_p, seed, out, lse, stream);
 }
 
+// ---- per-element lengths (attention_lengths.h); both arrays NULL: the plain call above ----
+MCP_EXPORT int mcp_attention_small_lse_lengths(int bf, int nq, int nk, int heads, int hd, const float *q, int q_stride, const float *k, int k_stride,
+                                               const float *v, int v_stride, float scale, float drop_p, unsigned seed, float *out, float *lse,
+                                               const int *qlen, const int *klen, mcp_stream_t stream) {
+    if (((uintptr_t)lse | (uintptr_t)qlen | (uintptr_t)klen) & 3) return MCP_ERR_BAD_ARG;   // scalar accesses only
+    if (!qlen && !klen) return forward_with(bf, nq, nk, heads, hd, q, q_stride, k, k_stride, v, v_stride, scale, drop_p, seed, out, lse, stream);
+    return forward_with(bf, nq, nk, heads, hd, q, q_stride, k, k_stride, v, v_stride, scale, drop_p, seed, out, lse, stream, AttnLengths{qlen, klen});
+}
+
 namespace {
+template <class... L>
 int forward_with(int bf, int nq, int nk, int heads, int hd, const float *q, int q_stride, const float *k, int k_stride, const float *v, int v_stride,
-                 float scale, float drop_p, unsigned seed, float *out, float *lse, mcp_stream_t stream) {
+                 float scale, float drop_p, unsigned seed, float *out, float *lse, mcp_stream_t stream, L... lens) {
     MCP_CHECK_ARGS(bf > 0 && nq > 0 && nk > 0 && heads > 0 && q && k && v && out);
     if (hd != 8 && hd != 16) return MCP_ERR_UNSUPPORTED;
     if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15) return MCP_ERR_BAD_ARG;
@@ -562,8 +631,8 @@ int forward_with(int bf, int nq, int nk, int heads, int hd, const float *q, int 
     const dim3 grid(mcp_divup(nq, 32 * WAVES), heads, bf);
     mcp_prof_begin(MCP_KERNEL_ATTENTION, s);
 #define MCP_ATT_FWD(HD_, DROP_)                                                                                                                     \
-    hipLaunchKernelGGL((attention_small_drop_kernel<HD_, DROP_>), grid, dim3(64 * WAVES), 0, s, nq, nk, heads, q, q_stride, k, k_stride, v, v_stride, sl2, \
-                       seed, threshold, inv_keep, out, lse)
+    hipLaunchKernelGGL((attention_small_drop_kernel<HD_, DROP_, L...>), grid, dim3(64 * WAVES), 0, s, nq, nk, heads, q, q_stride, k, k_stride, v, v_stride, \
+                       sl2, seed, threshold, inv_keep, out, lse, lens...)
     if (drop_p > 0.f) {
         if (hd == 8) MCP_ATT_FWD(8, true); else MCP_ATT_FWD(16, true);
     } else {
@@ -576,9 +645,10 @@ int forward_with(int bf, int nq, int nk, int heads, int hd, const float *q, int 
 }  // namespace
 
 namespace {
+template <class... L>
 int grad_with(int bf, int nq, int nk, int heads, int hd, const float *q, int q_stride, const float *k, int k_stride, const float *v, int v_stride, float scale,
               float drop_p, unsigned seed, const float *out, const float *grad_out, const float *saved_lse, float *grad_q, float *grad_kv, void *workspace,
-              size_t workspace_bytes, mcp_stream_t stream);
+              size_t workspace_bytes, mcp_stream_t stream, L... lens);
 }
 
 MCP_EXPORT int mcp_attention_small_grad(int bf, int nq, int nk, int heads, int hd, const float *q, int q_stride, const float *k, int k_stride, const float *v,
@@ -596,10 +666,24 @@ MCP_EXPORT int mcp_attention_small_grad_lse(int bf, int nq, int nk, int heads, i
                      workspace_bytes, stream);
 }
 
+MCP_EXPORT int mcp_attention_small_grad_lse_lengths(int bf, int nq, int nk, int heads, int hd, const float *q, int q_stride, const float *k, int k_stride,
+                                                    const float *v, int v_stride, float scale, float drop_p, unsigned seed, const float *out,
+                                                    const float *grad_out, const float *lse, float *grad_q, float *grad_kv, void *workspace,
+                                                    size_t workspace_bytes, const int *qlen, const int *klen, mcp_stream_t stream) {
+    MCP_CHECK_ARGS(lse);
+    if (((uintptr_t)qlen | (uintptr_t)klen) & 3) return MCP_ERR_BAD_ARG;
+    if (!qlen && !klen)
+        return grad_with(bf, nq, nk, heads, hd, q, q_stride, k, k_stride, v, v_stride, scale, drop_p, seed, out, grad_out, lse, grad_q, grad_kv, workspace,
+                         workspace_bytes, stream);
+    return grad_with(bf, nq, nk, heads, hd, q, q_stride, k, k_stride, v, v_stride, scale, drop_p, seed, out, grad_out, lse, grad_q, grad_kv, workspace,
+                     workspace_bytes, stream, AttnLengths{qlen, klen});
+}
+
 namespace {
+template <class... L>
 int grad_with(int bf, int nq, int nk, int heads, int hd, const float *q, int q_stride, const float *k, int k_stride, const float *v, int v_stride, float scale,
               float drop_p, unsigned seed, const float *out, const float *grad_out, const float *saved_lse, float *grad_q, float *grad_kv, void *workspace,
-              size_t workspace_bytes, mcp_stream_t stream) {
+              size_t workspace_bytes, mcp_stream_t stream, L... lens) {
     MCP_CHECK_ARGS(bf > 0 && nq > 0 && nk > 0 && heads > 0 && q && k && v && out && grad_out && grad_q && grad_kv && workspace);
     if (hd != 8 && hd != 16) return MCP_ERR_UNSUPPORTED;
     if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out | (uintptr_t)grad_out | (uintptr_t)grad_q | (uintptr_t)grad_kv) & 15) return MCP_ERR_BAD_ARG;
@@ -612,7 +696,7 @@ int grad_with(int bf, int nq, int nk, int heads, int hd, const float *q, int q_s
     float *lse = static_cast<float *>(workspace), *dsum = lse + (size_t)bf * heads * nq;
     mcp_prof_begin(MCP_KERNEL_ATTENTION, s);
     int rc;
-#define MCP_ATT_ARGS bf, nq, nk, heads, q, q_stride, k, k_stride, v, v_stride, scale, seed, threshold, inv_keep, out, grad_out, grad_q, grad_kv, lse, dsum, saved_lse, s
+#define MCP_ATT_ARGS bf, nq, nk, heads, q, q_stride, k, k_stride, v, v_stride, scale, seed, threshold, inv_keep, out, grad_out, grad_q, grad_kv, lse, dsum, saved_lse, s, lens...
     if (drop_p > 0.f) rc = hd == 8 ? launch_all<8, true>(MCP_ATT_ARGS) : launch_all<16, true>(MCP_ATT_ARGS);
     else rc = hd == 8 ? launch_all<8, false>(MCP_ATT_ARGS) : launch_all<16, false>(MCP_ATT_ARGS);
 #undef MCP_ATT_ARGS

@@ -4,9 +4,12 @@
 // The training forward adds two things to the inference one: with `lse` the row's log-sum-exp (log2 domain) is stored, and with DROP
 // the hash mask of attention_dropout.h multiplies P in P.V only (row sums are taken before the mask).  Same instruction sequence per
 // (query, key) and the same dispatch rule (wide_keys_split), so at drop_p = 0 the training output is the inference output bit for bit.
+// Each body ends in a parameter pack that is empty for these kernels and one AttnLengths for their length forms (attention_lengths.h;
+// attention_lengths.hip and the AttnLengths instantiations of attention_wide_grad.hip): per-element query / key counts of a padded batch.
 #pragma once
 #include "common.h"
 #include "attention_dropout.h"
+#include "attention_lengths.h"
 
 namespace {
 
@@ -31,13 +34,24 @@ struct WideCfg {
     static constexpr size_t LDS_BYTES = 2 * (size_t)KT * (KS + HD) * sizeof(float);
 };
 
+// what a length form (attention_lengths.h) writes for a query row at or beyond its element's length, or of an element without keys:
+// zeros, each lane half its half of the head's channels, and a zero log-sum-exp
+template <int HD>
+__device__ __forceinline__ void wide_zero_rows(bool inside, int h, float *dst, float *lse) {
+    if (!inside) return;
+    attn_zero_row<HD / 2>(dst + h * (HD / 2));
+    if (lse && h == 0) *lse = 0.f;
+}
+
 // bkv: the batch element whose keys / values the queries of batch element blockIdx.z attend to; os: row stride of out (floats);
-// heads, seed, threshold, inv_keep are read only with lse or DROP (row = the query's index over (batch, head, query))
-template <int HD, bool DROP>
+// heads, seed, threshold, inv_keep are read only with lse or DROP (row = the query's index over (batch, head, query));
+// lens: empty, or one AttnLengths (the key loop then ends at the element's own length kl, rows at or beyond ql are zeros)
+template <int HD, bool DROP, class... L>
 __device__ __forceinline__ void attention_wide_body(float *lds_w, int nq, int nk, int heads, const float *__restrict__ q, int qs,
                                                     const float *__restrict__ k, int ks, const float *__restrict__ v, int vs, int bkv,
                                                     float scale_log2e, uint32_t seed, uint32_t threshold, float inv_keep,
-                                                    float *__restrict__ out, int os, float *__restrict__ lse) {
+                                                    float *__restrict__ out, int os, float *__restrict__ lse, L... lens) {
+    constexpr bool LEN = sizeof...(L) != 0;
     using C = WideCfg<HD>;
     constexpr int KT = C::KT, KS = C::KS, TD = C::TD;
     float *kt = lds_w;                   // [2][KT][KS]
@@ -45,7 +59,16 @@ __device__ __forceinline__ void attention_wide_body(float *lds_w, int nq, int nk
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, col = lane & 31;
     const int head = blockIdx.y, bf = blockIdx.z;
     const int qi = blockIdx.x * (32 * WAVES) + wave * 32 + col;
-    const bool live = qi < nq;
+    const AttnSpan sp = attn_span(nq, nk, bf, bkv, lens...);   // the element's own lengths (nq, nk without)
+    const int kl = sp.kl;
+    const bool live = qi < sp.ql;
+    if constexpr (LEN) {
+        // a query block wholly beyond the length, or an element without keys: zeros, before a key is loaded
+        if ((int)blockIdx.x * (32 * WAVES) >= sp.ql || kl == 0) {
+            wide_zero_rows<HD>(qi < nq, h, out + ((size_t)bf * nq + qi) * os + head * HD, lse ? lse + ((size_t)bf * heads + head) * nq + qi : nullptr);
+            return;
+        }
+    }
     const uint32_t row = (uint32_t)(((size_t)bf * heads + head) * nq + qi);
     q += ((size_t)bf * nq + (live ? qi : 0)) * qs + head * HD;
     k += (size_t)bkv * nk * ks + head * HD;
@@ -75,8 +98,8 @@ __device__ __forceinline__ void attention_wide_body(float *lds_w, int nq, int nk
         for (int u = 0; u < LOADS; ++u) {
             const int e = tid + u * 64 * WAVES;
             const int row = e / F4_ROW, c4 = e % F4_ROW, key = t * KT + row;
-            pre[u] = make_float4(0.f, 0.f, 0.f, 0.f);  // keys past nk: zero rows (their scores are masked, 0 * 0 stays 0)
-            if (e < F4_TILE && key < nk) pre[u] = *reinterpret_cast<const float4 *>(src + (size_t)key * stride + c4 * 4);
+            pre[u] = make_float4(0.f, 0.f, 0.f, 0.f);  // keys past kl: zero rows (their scores are masked, 0 * 0 stays 0)
+            if (e < F4_TILE && key < kl) pre[u] = *reinterpret_cast<const float4 *>(src + (size_t)key * stride + c4 * 4);
         }
     };
     auto stash_k = [&](int buf) {
@@ -96,7 +119,7 @@ __device__ __forceinline__ void attention_wide_body(float *lds_w, int nq, int nk
         }
     };
 
-    const int stages = (nk + KT - 1) / KT;
+    const int stages = (kl + KT - 1) / KT;
     fetch(0, k, ks);
     stash_k(0);
     fetch(0, v, vs);
@@ -127,10 +150,10 @@ __device__ __forceinline__ void attention_wide_body(float *lds_w, int nq, int nk
             asm volatile("s_nop 15\n\ts_nop 1" ::: "memory");
         }
         const int kbase = t * KT;
-        if (kbase + KT > nk) {
+        if (kbase + KT > kl) {
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                if (kbase + chan_of(r, h) >= nk) acc[r] = -INFINITY;
+                if (kbase + chan_of(r, h) >= kl) acc[r] = -INFINITY;
         }
         float mt = acc[0];
 #pragma unroll
@@ -173,6 +196,8 @@ __device__ __forceinline__ void attention_wide_body(float *lds_w, int nq, int nk
                 *reinterpret_cast<float4 *>(dst + 32 * d + 8 * g + 4 * h) =
                     make_float4(o[d][4 * g] * inv, o[d][4 * g + 1] * inv, o[d][4 * g + 2] * inv, o[d][4 * g + 3] * inv);
         if (lse && h == 0) lse[((size_t)bf * heads + head) * nq + qi] = m + __builtin_amdgcn_logf(lsum);  // v_log_f32 is log2
+    } else if constexpr (LEN) {
+        wide_zero_rows<HD>(qi < nq, h, out + ((size_t)bf * nq + qi) * os + head * HD, lse ? lse + ((size_t)bf * heads + head) * nq + qi : nullptr);
     }
 }
 
@@ -195,11 +220,12 @@ struct WideSplitCfg {
     static_assert(TD % WAVES == 0, "output tiles shared out evenly");
 };
 
-template <int HD, bool DROP>
+template <int HD, bool DROP, class... L>
 __device__ __forceinline__ void attention_wide_ksplit_body(float *lds_ws, int nq, int nk, int heads, const float *__restrict__ q, int qs,
                                                            const float *__restrict__ k, int ks, const float *__restrict__ v, int vs, int bkv,
                                                            float scale_log2e, uint32_t seed, uint32_t threshold, float inv_keep,
-                                                           float *__restrict__ out, int os, float *__restrict__ lse) {
+                                                           float *__restrict__ out, int os, float *__restrict__ lse, L... lens) {
+    constexpr bool LEN = sizeof...(L) != 0;
     using C = WideSplitCfg<HD>;
     constexpr int KT = C::KT, KS = C::KS, TD = C::TD, BUF = C::BUF;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, col = lane & 31;
@@ -207,7 +233,17 @@ __device__ __forceinline__ void attention_wide_ksplit_body(float *lds_ws, int nq
     float *ml = lds_ws + WAVES * BUF;                       // [WAVES][2][64]: running maximum, row sum
     const int head = blockIdx.y, bf = blockIdx.z;
     const int qi = blockIdx.x * 32 + col;
-    const bool live = qi < nq;
+    // With lengths the key stages are shared out from the element's own kl: a short element leaves waves without a stage (they enter
+    // the merge with m = -inf, l = 0 and weigh nothing); one without keys, or a query block beyond ql, is zeros before a key is loaded
+    const AttnSpan sp = attn_span(nq, nk, bf, bkv, lens...);
+    const int kl = sp.kl;
+    const bool live = qi < sp.ql;
+    if constexpr (LEN) {
+        if ((int)blockIdx.x * 32 >= sp.ql || kl == 0) {
+            if (wave == 0) wide_zero_rows<HD>(qi < nq, h, out + ((size_t)bf * nq + qi) * os + head * HD, lse ? lse + ((size_t)bf * heads + head) * nq + qi : nullptr);
+            return;
+        }
+    }
     const uint32_t row = (uint32_t)(((size_t)bf * heads + head) * nq + qi);
     q += ((size_t)bf * nq + (live ? qi : 0)) * qs + head * HD;
     k += (size_t)bkv * nk * ks + head * HD;
@@ -237,7 +273,7 @@ __device__ __forceinline__ void attention_wide_ksplit_body(float *lds_ws, int nq
         for (int u = 0; u < PER_LANE; ++u) {
             const int e = u * 64 + lane;
             const int row = e / F4_ROW, c4 = e % F4_ROW, key = t * KT + row;
-            pre[u] = key < nk ? *reinterpret_cast<const float4 *>(src + (size_t)key * stride + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+            pre[u] = key < kl ? *reinterpret_cast<const float4 *>(src + (size_t)key * stride + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     };
     auto commit = [&](bool padded) {
@@ -255,7 +291,7 @@ __device__ __forceinline__ void attention_wide_ksplit_body(float *lds_ws, int nq
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
     };
-    const int stages = (nk + KT - 1) / KT;
+    const int stages = (kl + KT - 1) / KT;
     if (wave < stages) issue(wave, k, ks);
     for (int t = wave; t < stages; t += WAVES) {
         commit(true);                      // this stage's K tile
@@ -273,10 +309,10 @@ __device__ __forceinline__ void attention_wide_ksplit_body(float *lds_ws, int nq
         commit(false);
         if (t + WAVES < stages) issue(t + WAVES, k, ks);   // the next stage's K tile: in flight under the softmax and the P.V MFMAs
         const int kbase = t * KT;
-        if (kbase + KT > nk) {
+        if (kbase + KT > kl) {
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                if (kbase + chan_of(r, h) >= nk) acc[r] = -INFINITY;
+                if (kbase + chan_of(r, h) >= kl) acc[r] = -INFINITY;
         }
         float mt = acc[0];
 #pragma unroll
@@ -347,6 +383,8 @@ __device__ __forceinline__ void attention_wide_ksplit_body(float *lds_ws, int nq
                 *reinterpret_cast<float4 *>(dst + 32 * d + 8 * g + 4 * h) = make_float4(res[4 * g], res[4 * g + 1], res[4 * g + 2], res[4 * g + 3]);
         }
         if (lse && wave == 0 && h == 0) lse[((size_t)bf * heads + head) * nq + qi] = mm + __builtin_amdgcn_logf(lsum);
+    } else if constexpr (LEN) {
+        if (wave == 0) wide_zero_rows<HD>(qi < nq, h, out + ((size_t)bf * nq + qi) * os + head * HD, lse ? lse + ((size_t)bf * heads + head) * nq + qi : nullptr);
     }
 }
 

@@ -29,25 +29,26 @@ namespace {
 // forward
 // =====================================================================================================================================
 // out is dense (row stride heads * HD), keys / values are the batch element's own
-template <int HD, bool DROP>
+// L: empty, or one AttnLengths (attention_lengths.h) -- the length forms of mcp_attention_wide_lse_lengths
+template <int HD, bool DROP, class... L>
 __global__ __launch_bounds__(64 * WAVES, 1) void attention_wide_lse_kernel(int nq, int nk, int heads, const float *__restrict__ q, int qs,
                                                                            const float *__restrict__ k, int ks, const float *__restrict__ v, int vs,
                                                                            float scale_log2e, uint32_t seed, uint32_t threshold, float inv_keep,
-                                                                           float *__restrict__ out, float *__restrict__ lse) {
+                                                                           float *__restrict__ out, float *__restrict__ lse, L... lens) {
     extern __shared__ __attribute__((aligned(16))) float lds_w[];
     attention_wide_body<HD, DROP>(lds_w, nq, nk, heads, q, qs, k, ks, v, vs, (int)blockIdx.z, scale_log2e, seed, threshold, inv_keep, out, heads * HD,
-                                  lse);
+                                  lse, lens...);
 }
 
 // the keys split over the waves of a workgroup
-template <int HD, bool DROP>
+template <int HD, bool DROP, class... L>
 __global__ __launch_bounds__(64 * WAVES, 1) void attention_wide_ksplit_lse_kernel(int nq, int nk, int heads, const float *__restrict__ q, int qs,
                                                                                   const float *__restrict__ k, int ks, const float *__restrict__ v, int vs,
                                                                                   float scale_log2e, uint32_t seed, uint32_t threshold, float inv_keep,
-                                                                                  float *__restrict__ out, float *__restrict__ lse) {
+                                                                                  float *__restrict__ out, float *__restrict__ lse, L... lens) {
     extern __shared__ __attribute__((aligned(16))) float lds_ws[];
     attention_wide_ksplit_body<HD, DROP>(lds_ws, nq, nk, heads, q, qs, k, ks, v, vs, (int)blockIdx.z, scale_log2e, seed, threshold, inv_keep, out,
-                                         heads * HD, lse);
+                                         heads * HD, lse, lens...);
 }
 
 // dynamic LDS above the 64 KB default: the attribute is set once per device and kernel instantiation
@@ -62,22 +63,23 @@ int allow_lds() {
     return MCP_OK;
 }
 
-template <int HD, bool DROP>
+// lens: empty, or one AttnLengths; the key-split dispatch is decided from the padded sizes either way (the host never reads a length)
+template <int HD, bool DROP, class... L>
 int launch_forward(int bf, int nq, int nk, int heads, const float *q, int qs, const float *k, int ks, const float *v, int vs, float sl2, uint32_t seed,
-                   uint32_t threshold, float inv_keep, float *out, float *lse, hipStream_t s) {
+                   uint32_t threshold, float inv_keep, float *out, float *lse, hipStream_t s, L... lens) {
     if constexpr (HD == 256) {
         if (wide_keys_split(bf, nq, nk, heads)) {
-            constexpr auto kern = attention_wide_ksplit_lse_kernel<HD, DROP>;
+            constexpr auto kern = attention_wide_ksplit_lse_kernel<HD, DROP, L...>;
             if (const int rc = allow_lds<kern>()) return rc;
             hipLaunchKernelGGL(kern, dim3(mcp_divup(nq, 32), heads, bf), dim3(64 * WAVES), WideSplitCfg<HD>::LDS_BYTES, s, nq, nk, heads, q, qs, k, ks, v, vs,
-                               sl2, seed, threshold, inv_keep, out, lse);
+                               sl2, seed, threshold, inv_keep, out, lse, lens...);
             return mcp_launch_status();
         }
     }
-    constexpr auto kern = attention_wide_lse_kernel<HD, DROP>;
+    constexpr auto kern = attention_wide_lse_kernel<HD, DROP, L...>;
     if (const int rc = allow_lds<kern>()) return rc;
     hipLaunchKernelGGL(kern, dim3(mcp_divup(nq, 32 * WAVES), heads, bf), dim3(64 * WAVES), WideCfg<HD>::LDS_BYTES, s, nq, nk, heads, q, qs, k, ks, v, vs, sl2,
-                       seed, threshold, inv_keep, out, lse);
+                       seed, threshold, inv_keep, out, lse, lens...);
     return mcp_launch_status();
 }
 
@@ -169,12 +171,15 @@ __device__ __forceinline__ void merge_partials(float *xch, int wave, int lane, f
 }
 
 // ---- dq: query-stationary ----
-template <int HD, bool DROP>
+// L: empty, or one AttnLengths: the key loop ends at the element's kl, rows at or beyond ql are zeros.  L and D of a row at or beyond
+// ql (the dsum pass covers the padded tensor, so D may be anything there) are never read: lanes past ql take row 0 of the element.
+template <int HD, bool DROP, class... LN>
 __global__ __launch_bounds__(64 * WAVES, 1) void attention_wide_dq_kernel(int nq, int nk, int heads, const float *__restrict__ q, int qs,
                                                                           const float *__restrict__ k, int ks, const float *__restrict__ v, int vs,
                                                                           float scale_log2e, float scale, uint32_t seed, uint32_t threshold, float inv_keep,
                                                                           const float *__restrict__ gout, const float *__restrict__ lse,
-                                                                          const float *__restrict__ dsum, float *__restrict__ dq) {
+                                                                          const float *__restrict__ dsum, float *__restrict__ dq, LN... lens) {
+    constexpr bool LEN = sizeof...(LN) != 0;   // (L is the row's log-sum-exp below)
     using C = GradCfg<HD>;
     constexpr int SPLIT = C::SPLIT, CW = C::CW, TD = C::TD, RS = C::RS, PER = C::PER;
     extern __shared__ __attribute__((aligned(16))) float lds_g[];
@@ -185,9 +190,17 @@ __global__ __launch_bounds__(64 * WAVES, 1) void attention_wide_dq_kernel(int nq
     float *xch = lds_g + WAVES * C::WAVE_FLOATS;
     const int head = blockIdx.y, bf = blockIdx.z;
     const int qi = rb * 32 + col;
-    const bool live = qi < nq;
+    const AttnSpan sp = attn_span(nq, nk, bf, bf, lens...);
+    const int kl = sp.kl;
+    const bool live = qi < sp.ql;
     const size_t qrow = (size_t)bf * nq + (live ? qi : 0);
     const int c0 = head * HD + part * CW;
+    if constexpr (LEN) {
+        if (rb * 32 >= sp.ql) {   // the row block (one per wave, or one per workgroup with the channel split) lies beyond the length: zeros
+            if (qi < nq) attn_zero_row<CW / 2>(dq + ((size_t)bf * nq + qi) * (size_t)(heads * HD) + c0 + h * (CW / 2));
+            return;
+        }
+    }
     const float *qp = q + qrow * qs + c0, *gp = gout + qrow * (size_t)(heads * HD) + c0;
     k += (size_t)bf * nk * ks + c0;
     v += (size_t)bf * nk * vs + c0;
@@ -211,13 +224,13 @@ __global__ __launch_bounds__(64 * WAVES, 1) void attention_wide_dq_kernel(int nq
         for (int r = 0; r < 16; ++r) acc_q[d][r] = 0.f;
 
     float4 pk[PER], pv[PER];
-    const int stages = (nk + 31) / 32;
-    tile_issue<CW, PER>(pk, pv, lane, 0, nk, k, (size_t)ks, v, (size_t)vs);
+    const int stages = (kl + 31) / 32;
+    tile_issue<CW, PER>(pk, pv, lane, 0, kl, k, (size_t)ks, v, (size_t)vs);
     for (int t = 0; t < stages; ++t) {
         tile_commit<CW, PER>(pk, pv, lane, kt, vt);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        if (t + 1 < stages) tile_issue<CW, PER>(pk, pv, lane, t + 1, nk, k, (size_t)ks, v, (size_t)vs);
+        if (t + 1 < stages) tile_issue<CW, PER>(pk, pv, lane, t + 1, kl, k, (size_t)ks, v, (size_t)vs);
         const float *ka = &kt[col * RS + h], *va = &vt[col * RS + h];
         f32x16 acc, accp;
 #pragma unroll
@@ -234,7 +247,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void attention_wide_dq_kernel(int nq
         for (int r = 0; r < 16; ++r) {
             const int key = kbase + chan_of(r, h);
             float p = __builtin_amdgcn_exp2f(acc[r] - L);
-            if (key >= nk) p = 0.f;
+            if (key >= kl) p = 0.f;
             const float mk = DROP ? drop_scale(seed, drow, (uint32_t)key, threshold, inv_keep) : 1.0f;
             ds[r] = p * ((DROP ? mk * accp[r] : accp[r]) - D);
         }
@@ -245,6 +258,12 @@ __global__ __launch_bounds__(64 * WAVES, 1) void attention_wide_dq_kernel(int nq
                 acc_q[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(kt[chan_of(r, h) * RS + 32 * d + col], ds[r], acc_q[d], 0, 0, 0);
         __builtin_amdgcn_wave_barrier();   // this tile's LDS reads are issued before the next tile is written (a wave's LDS accesses are served in order)
     }
+    if constexpr (LEN) {
+        // The length form's exit from the tile loop runs into the scaled stores of acc_q without the wait states a 16-pass MFMA result
+        // needs before a vector read (tools/isa_lint.py found 13 of 18 on that path; the same gap of this compiler's hazard recogniser as
+        // in attention_wide_body, attention_wide_fwd.h) -- spelled out here, once per launch and wave.  The plain kernel's layout has them.
+        asm volatile("s_nop 15\n\ts_nop 1" ::: "memory");
+    }
     if (live) {
         float *dst = dq + qrow * (size_t)(heads * HD) + c0;
 #pragma unroll
@@ -253,16 +272,21 @@ __global__ __launch_bounds__(64 * WAVES, 1) void attention_wide_dq_kernel(int nq
             for (int g = 0; g < 4; ++g)  // registers 4g..4g+3 = channels 32d + 8g + 4h .. +3
                 *reinterpret_cast<float4 *>(dst + 32 * d + 8 * g + 4 * h) =
                     make_float4(acc_q[d][4 * g] * scale, acc_q[d][4 * g + 1] * scale, acc_q[d][4 * g + 2] * scale, acc_q[d][4 * g + 3] * scale);
+    } else if constexpr (LEN) {
+        if (qi < nq) attn_zero_row<CW / 2>(dq + ((size_t)bf * nq + qi) * (size_t)(heads * HD) + c0 + h * (CW / 2));
     }
 }
 
 // ---- dkv: key-stationary; writes dK | dV into a (BF, Nk, 2 heads HD) tensor laid out like the forward's kv ----
-template <int HD, bool DROP>
+// L: empty, or one AttnLengths: the query loop ends at the element's ql (no L, D, Q or dO row beyond it is loaded), rows at or beyond kl
+// are zeros in both halves.
+template <int HD, bool DROP, class... L>
 __global__ __launch_bounds__(64 * WAVES, 1) void attention_wide_dkv_kernel(int nq, int nk, int heads, const float *__restrict__ q, int qs,
                                                                            const float *__restrict__ k, int ks, const float *__restrict__ v, int vs,
                                                                            float scale_log2e, float k_scale, uint32_t seed, uint32_t threshold, float inv_keep,
                                                                            const float *__restrict__ gout, const float *__restrict__ lse,
-                                                                           const float *__restrict__ dsum, float *__restrict__ dkv) {
+                                                                           const float *__restrict__ dsum, float *__restrict__ dkv, L... lens) {
+    constexpr bool LEN = sizeof...(L) != 0;
     using C = GradCfg<HD>;
     constexpr int SPLIT = C::SPLIT, CW = C::CW, TD = C::TD, RS = C::RS, PER = C::PER;
     extern __shared__ __attribute__((aligned(16))) float lds_g[];
@@ -273,9 +297,20 @@ __global__ __launch_bounds__(64 * WAVES, 1) void attention_wide_dkv_kernel(int n
     float *xch = lds_g + WAVES * C::WAVE_FLOATS;
     const int head = blockIdx.y, bf = blockIdx.z;
     const int ki = rb * 32 + col;
-    const bool live = ki < nk;
+    const bool live = ki < attn_klen(nk, bf, lens...);
     const size_t krow = (size_t)bf * nk + (live ? ki : 0);
     const int c0 = head * HD + part * CW;
+    const int ql = attn_qlen(nq, bf, lens...);
+    if constexpr (LEN) {
+        if (rb * 32 >= attn_klen(nk, bf, lens...)) {   // the key block lies beyond the length: zeros in dK and dV
+            if (ki < nk) {
+                float *z = dkv + ((size_t)bf * nk + ki) * (size_t)(2 * heads * HD) + c0 + h * (CW / 2);
+                attn_zero_row<CW / 2>(z);
+                attn_zero_row<CW / 2>(z + heads * HD);
+            }
+            return;
+        }
+    }
     const float *kp = k + krow * ks + c0, *vp = v + krow * vs + c0;
     q += (size_t)bf * nq * qs + c0;
     gout += (size_t)bf * nq * (size_t)(heads * HD) + c0;
@@ -303,12 +338,12 @@ __global__ __launch_bounds__(64 * WAVES, 1) void attention_wide_dkv_kernel(int n
 
     float4 pq[PER], pg[PER];
     float pstat = 0.f;
-    auto issue_stat = [&](int t) {   // lanes 0..31: the queries' log-sum-exp, lanes 32..63: their D; a query past nq contributes p = exp2(s - inf) = 0
+    auto issue_stat = [&](int t) {   // lanes 0..31: the queries' log-sum-exp, lanes 32..63: their D; a query past ql contributes p = exp2(s - inf) = 0
         const int qq = t * 32 + col;
-        pstat = qq < nq ? (h ? dsum[qq] : lse[qq]) : (h ? 0.f : INFINITY);
+        pstat = qq < ql ? (h ? dsum[qq] : lse[qq]) : (h ? 0.f : INFINITY);
     };
-    const int stages = (nq + 31) / 32;
-    tile_issue<CW, PER>(pq, pg, lane, 0, nq, q, (size_t)qs, gout, (size_t)(heads * HD));
+    const int stages = (ql + 31) / 32;
+    tile_issue<CW, PER>(pq, pg, lane, 0, ql, q, (size_t)qs, gout, (size_t)(heads * HD));
     issue_stat(0);
     for (int t = 0; t < stages; ++t) {
         tile_commit<CW, PER>(pq, pg, lane, qt, gt, scale_log2e);
@@ -316,7 +351,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void attention_wide_dkv_kernel(int n
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         if (t + 1 < stages) {
-            tile_issue<CW, PER>(pq, pg, lane, t + 1, nq, q, (size_t)qs, gout, (size_t)(heads * HD));
+            tile_issue<CW, PER>(pq, pg, lane, t + 1, ql, q, (size_t)qs, gout, (size_t)(heads * HD));
             issue_stat(t + 1);
         }
         const float *qa = &qt[col * RS + h], *ga = &gt[col * RS + h];
@@ -358,30 +393,37 @@ __global__ __launch_bounds__(64 * WAVES, 1) void attention_wide_dkv_kernel(int n
                 *reinterpret_cast<float4 *>(dst + heads * HD + 32 * d + 8 * g + 4 * h) =
                     make_float4(acc_v[d][4 * g], acc_v[d][4 * g + 1], acc_v[d][4 * g + 2], acc_v[d][4 * g + 3]);
             }
+    } else if constexpr (LEN) {
+        if (ki < nk) {
+            float *z = dkv + ((size_t)bf * nk + ki) * (size_t)(2 * heads * HD) + c0 + h * (CW / 2);
+            attn_zero_row<CW / 2>(z);
+            attn_zero_row<CW / 2>(z + heads * HD);
+        }
     }
 }
 
-template <int HD, bool DROP>
+template <int HD, bool DROP, class... L>
 int launch_backward(int bf, int nq, int nk, int heads, const float *q, int qs, const float *k, int ks, const float *v, int vs, float scale, uint32_t seed,
                     uint32_t threshold, float inv_keep, const float *out, const float *gout, const float *lse, float *dq, float *dkv, float *dsum,
-                    hipStream_t s) {
+                    hipStream_t s, L... lens) {
     using C = GradCfg<HD>;
     const float sl2 = scale * 1.44269504088896340736f;
-    constexpr auto kq = attention_wide_dq_kernel<HD, DROP>;
-    constexpr auto kk = attention_wide_dkv_kernel<HD, DROP>;
+    constexpr auto kq = attention_wide_dq_kernel<HD, DROP, L...>;
+    constexpr auto kk = attention_wide_dkv_kernel<HD, DROP, L...>;
     if (const int rc = allow_lds<kq>()) return rc;
     if (const int rc = allow_lds<kk>()) return rc;
     const long long rows = (long long)bf * nq * heads;
     hipLaunchKernelGGL(attention_wide_dsum_kernel<HD>, dim3((unsigned)((rows * (HD / 4) + 255) / 256)), dim3(256), 0, s, rows, heads, out, gout, nq, dsum);
     hipLaunchKernelGGL(kq, dim3(mcp_divup(nq, 32 * C::RPW), heads, bf), dim3(64 * WAVES), C::LDS_BYTES, s, nq, nk, heads, q, qs, k, ks, v, vs, sl2, scale, seed,
-                       threshold, inv_keep, gout, lse, dsum, dq);
+                       threshold, inv_keep, gout, lse, dsum, dq, lens...);
     hipLaunchKernelGGL(kk, dim3(mcp_divup(nk, 32 * C::RPW), heads, bf), dim3(64 * WAVES), C::LDS_BYTES, s, nq, nk, heads, q, qs, k, ks, v, vs, sl2, 0.69314718055994530942f /* scale / sl2 */,
-                       seed, threshold, inv_keep, gout, lse, dsum, dkv);
+                       seed, threshold, inv_keep, gout, lse, dsum, dkv, lens...);
     return mcp_launch_status();
 }
 
+template <class... L>
 int forward_with(int bf, int nq, int nk, int heads, int hd, const float *q, int q_stride, const float *k, int k_stride, const float *v, int v_stride,
-                 float scale, float drop_p, unsigned seed, float *out, float *lse, mcp_stream_t stream) {
+                 float scale, float drop_p, unsigned seed, float *out, float *lse, mcp_stream_t stream, L... lens) {
     MCP_CHECK_ARGS(bf > 0 && nq > 0 && nk > 0 && heads > 0 && q && k && v && out);
     if (hd != 32 && hd != 64 && hd != 256) return MCP_ERR_UNSUPPORTED;
     if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15) return MCP_ERR_BAD_ARG;
@@ -393,9 +435,34 @@ int forward_with(int bf, int nq, int nk, int heads, int hd, const float *q, int 
     const float sl2 = scale * 1.44269504088896340736f;
     int rc;
     mcp_prof_begin(MCP_KERNEL_ATTENTION, s);
-#define MCP_ATT_ARGS bf, nq, nk, heads, q, q_stride, k, k_stride, v, v_stride, sl2, seed, threshold, inv_keep, out, lse, s
+#define MCP_ATT_ARGS bf, nq, nk, heads, q, q_stride, k, k_stride, v, v_stride, sl2, seed, threshold, inv_keep, out, lse, s, lens...
     if (drop_p > 0.f) rc = hd == 32 ? launch_forward<32, true>(MCP_ATT_ARGS) : hd == 64 ? launch_forward<64, true>(MCP_ATT_ARGS) : launch_forward<256, true>(MCP_ATT_ARGS);
     else rc = hd == 32 ? launch_forward<32, false>(MCP_ATT_ARGS) : hd == 64 ? launch_forward<64, false>(MCP_ATT_ARGS) : launch_forward<256, false>(MCP_ATT_ARGS);
+#undef MCP_ATT_ARGS
+    mcp_prof_end(MCP_KERNEL_ATTENTION, s);
+    return rc;
+}
+
+template <class... L>
+int backward_with(int bf, int nq, int nk, int heads, int hd, const float *q, int q_stride, const float *k, int k_stride, const float *v, int v_stride,
+                  float scale, float drop_p, unsigned seed, const float *out, const float *grad_out, const float *lse, float *grad_q, float *grad_kv,
+                  void *workspace, size_t workspace_bytes, mcp_stream_t stream, L... lens) {
+    MCP_CHECK_ARGS(bf > 0 && nq > 0 && nk > 0 && heads > 0 && q && k && v && out && grad_out && lse && grad_q && grad_kv && workspace);
+    if (hd != 32 && hd != 64 && hd != 256) return MCP_ERR_UNSUPPORTED;
+    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out | (uintptr_t)grad_out | (uintptr_t)grad_q | (uintptr_t)grad_kv) & 15) return MCP_ERR_BAD_ARG;
+    if (((uintptr_t)lse | (uintptr_t)workspace) & 3) return MCP_ERR_BAD_ARG;   // scalar float accesses only
+    if ((q_stride | k_stride | v_stride) & 3) return MCP_ERR_BAD_ARG;
+    if (workspace_bytes < mcp_attention_wide_grad_workspace_bytes(bf, nq, nk, heads, hd)) return MCP_ERR_BAD_ARG;
+    uint32_t threshold;
+    float inv_keep;
+    if (!drop_params(drop_p, &threshold, &inv_keep)) return MCP_ERR_BAD_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    float *dsum = static_cast<float *>(workspace);
+    mcp_prof_begin(MCP_KERNEL_ATTENTION, s);
+    int rc;
+#define MCP_ATT_ARGS bf, nq, nk, heads, q, q_stride, k, k_stride, v, v_stride, scale, seed, threshold, inv_keep, out, grad_out, lse, grad_q, grad_kv, dsum, s, lens...
+    if (drop_p > 0.f) rc = hd == 32 ? launch_backward<32, true>(MCP_ATT_ARGS) : hd == 64 ? launch_backward<64, true>(MCP_ATT_ARGS) : launch_backward<256, true>(MCP_ATT_ARGS);
+    else rc = hd == 32 ? launch_backward<32, false>(MCP_ATT_ARGS) : hd == 64 ? launch_backward<64, false>(MCP_ATT_ARGS) : launch_backward<256, false>(MCP_ATT_ARGS);
 #undef MCP_ATT_ARGS
     mcp_prof_end(MCP_KERNEL_ATTENTION, s);
     return rc;
@@ -423,23 +490,27 @@ MCP_EXPORT size_t mcp_attention_wide_grad_workspace_bytes(int bf, int nq, int nk
 MCP_EXPORT int mcp_attention_wide_grad_lse(int bf, int nq, int nk, int heads, int hd, const float *q, int q_stride, const float *k, int k_stride,
                                            const float *v, int v_stride, float scale, float drop_p, unsigned seed, const float *out, const float *grad_out,
                                            const float *lse, float *grad_q, float *grad_kv, void *workspace, size_t workspace_bytes, mcp_stream_t stream) {
-    MCP_CHECK_ARGS(bf > 0 && nq > 0 && nk > 0 && heads > 0 && q && k && v && out && grad_out && lse && grad_q && grad_kv && workspace);
-    if (hd != 32 && hd != 64 && hd != 256) return MCP_ERR_UNSUPPORTED;
-    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out | (uintptr_t)grad_out | (uintptr_t)grad_q | (uintptr_t)grad_kv) & 15) return MCP_ERR_BAD_ARG;
-    if (((uintptr_t)lse | (uintptr_t)workspace) & 3) return MCP_ERR_BAD_ARG;   // scalar float accesses only
-    if ((q_stride | k_stride | v_stride) & 3) return MCP_ERR_BAD_ARG;
-    if (workspace_bytes < mcp_attention_wide_grad_workspace_bytes(bf, nq, nk, heads, hd)) return MCP_ERR_BAD_ARG;
-    uint32_t threshold;
-    float inv_keep;
-    if (!drop_params(drop_p, &threshold, &inv_keep)) return MCP_ERR_BAD_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    float *dsum = static_cast<float *>(workspace);
-    mcp_prof_begin(MCP_KERNEL_ATTENTION, s);
-    int rc;
-#define MCP_ATT_ARGS bf, nq, nk, heads, q, q_stride, k, k_stride, v, v_stride, scale, seed, threshold, inv_keep, out, grad_out, lse, grad_q, grad_kv, dsum, s
-    if (drop_p > 0.f) rc = hd == 32 ? launch_backward<32, true>(MCP_ATT_ARGS) : hd == 64 ? launch_backward<64, true>(MCP_ATT_ARGS) : launch_backward<256, true>(MCP_ATT_ARGS);
-    else rc = hd == 32 ? launch_backward<32, false>(MCP_ATT_ARGS) : hd == 64 ? launch_backward<64, false>(MCP_ATT_ARGS) : launch_backward<256, false>(MCP_ATT_ARGS);
-#undef MCP_ATT_ARGS
-    mcp_prof_end(MCP_KERNEL_ATTENTION, s);
-    return rc;
+    return backward_with(bf, nq, nk, heads, hd, q, q_stride, k, k_stride, v, v_stride, scale, drop_p, seed, out, grad_out, lse, grad_q, grad_kv, workspace,
+                         workspace_bytes, stream);
+}
+
+// ---- per-element lengths (attention_lengths.h); both arrays NULL: the plain calls above ----
+MCP_EXPORT int mcp_attention_wide_lse_lengths(int bf, int nq, int nk, int heads, int hd, const float *q, int q_stride, const float *k, int k_stride,
+                                              const float *v, int v_stride, float scale, float drop_p, unsigned seed, float *out, float *lse,
+                                              const int *qlen, const int *klen, mcp_stream_t stream) {
+    if (((uintptr_t)lse | (uintptr_t)qlen | (uintptr_t)klen) & 3) return MCP_ERR_BAD_ARG;   // scalar accesses only
+    if (!qlen && !klen) return forward_with(bf, nq, nk, heads, hd, q, q_stride, k, k_stride, v, v_stride, scale, drop_p, seed, out, lse, stream);
+    return forward_with(bf, nq, nk, heads, hd, q, q_stride, k, k_stride, v, v_stride, scale, drop_p, seed, out, lse, stream, AttnLengths{qlen, klen});
+}
+
+MCP_EXPORT int mcp_attention_wide_grad_lse_lengths(int bf, int nq, int nk, int heads, int hd, const float *q, int q_stride, const float *k, int k_stride,
+                                                   const float *v, int v_stride, float scale, float drop_p, unsigned seed, const float *out,
+                                                   const float *grad_out, const float *lse, float *grad_q, float *grad_kv, void *workspace,
+                                                   size_t workspace_bytes, const int *qlen, const int *klen, mcp_stream_t stream) {
+    if (((uintptr_t)qlen | (uintptr_t)klen) & 3) return MCP_ERR_BAD_ARG;
+    if (!qlen && !klen)
+        return backward_with(bf, nq, nk, heads, hd, q, q_stride, k, k_stride, v, v_stride, scale, drop_p, seed, out, grad_out, lse, grad_q, grad_kv,
+                             workspace, workspace_bytes, stream);
+    return backward_with(bf, nq, nk, heads, hd, q, q_stride, k, k_stride, v, v_stride, scale, drop_p, seed, out, grad_out, lse, grad_q, grad_kv, workspace,
+                         workspace_bytes, stream, AttnLengths{qlen, klen});
 }

@@ -126,6 +126,29 @@ def attention_twin(q, kv, heads, scale):
     return o.permute(0, 2, 1, 3).reshape(BF, Nq, C)
 
 
+def attention_lengths_twin(q, kv, heads, scale, qlen, klen):
+    """attention_twin over a padded batch with per-element lengths (qlen, klen: (BF,) integer device tensors or None = full), as the
+    dense masked formulation: rows i < ql attend to keys j < kl, rows >= ql and elements with kl = 0 are zeros.  Padding is replaced
+    by zeros before any product, so NaN or inf there reaches neither the output nor a gradient."""
+    BF, Nq, C = q.shape
+    Nk, hd = kv.shape[1], C // heads
+    dev = q.device
+    ql = torch.full((BF,), Nq, device=dev) if qlen is None else qlen.clamp(0, Nq)
+    kl = torch.full((BF,), Nk, device=dev) if klen is None else klen.clamp(0, Nk)
+    qm = torch.arange(Nq, device=dev).view(1, Nq) < ql.view(BF, 1)
+    km = torch.arange(Nk, device=dev).view(1, Nk) < kl.view(BF, 1)
+    q = torch.where(qm.unsqueeze(-1), q, q.new_zeros(()))
+    kv = torch.where(km.unsqueeze(-1), kv, kv.new_zeros(()))
+    qh = q.reshape(BF, Nq, heads, hd).permute(0, 2, 1, 3)
+    kvh = kv.reshape(BF, Nk, 2, heads, hd).permute(2, 0, 3, 1, 4)
+    some = (kl > 0).view(BF, 1, 1, 1)
+    s = torch.matmul(qh, kvh[0].transpose(-1, -2)) * scale
+    s = s.masked_fill(~km.view(BF, 1, 1, Nk) & some, float("-inf"))   # an element without keys keeps finite scores; its P is dropped below
+    p = torch.where(km.view(BF, 1, 1, Nk), torch.softmax(s, dim=-1), s.new_zeros(()))
+    o = torch.where(qm.view(BF, 1, Nq, 1), torch.matmul(p, kvh[1]), s.new_zeros(()))   # (where, not a product: a NaN gradient stays out)
+    return o.permute(0, 2, 1, 3).reshape(BF, Nq, C)
+
+
 def linear_twin(xs, w, b, slope, res):
     """Linear over the concatenation of the pieces + one-slope activation + residual (Conv1d wrapper, mocopci.py:1111-1127)."""
     x = torch.cat(list(xs), dim=-1) if isinstance(xs, (tuple, list)) else xs

@@ -282,25 +282,35 @@ class _CrossFn(torch.autograd.Function):
         return (None, None, None, d_xyz1, d_xyz2, d_points1, d_points2, *pieces)
 
 
+def _len_ptr(lens):
+    """Device pointer of a lengths array as lengths_tensor returns it; None stays None (that side is full)."""
+    return None if lens is None else _lib.iptr(lens)
+
+
 class _AttentionSmallFn(torch.autograd.Function):
-    """mcp_attention_small (head dims 8 / 16) with its hand-written backward (mcp_attention_small_grad: row statistics, dQ, dK/dV)."""
+    """mcp_attention_small (head dims 8 / 16) with its hand-written backward (mcp_attention_small_grad: row statistics, dQ, dK/dV).
+    qlen / klen: (BF,) int32 device tensors or None -- per-element lengths (the *_lengths entries), carried to the backward."""
 
     @staticmethod
-    def forward(ctx, be, q, kv, heads, scale, drop_p, seed):
+    def forward(ctx, be, q, kv, heads, scale, drop_p, seed, qlen=None, klen=None):
         q, kv = q.detach().contiguous(), kv.detach().contiguous()
         BF, Nq, C = q.shape
         Nk = kv.shape[1]
         out = torch.empty((BF, Nq, C), dtype=torch.float32, device=q.device)
         lse = torch.empty((BF, heads, Nq), dtype=torch.float32, device=q.device)   # kept for the backward: no statistics pass there
-        _call("mcp_attention_small_lse", q, BF, Nq, Nk, heads, C // heads, _lib.fptr(q), C, _lib.fptr(kv), 2 * C, kv.data_ptr() + 4 * C, 2 * C,
-              float(scale), float(drop_p), int(seed), out.data_ptr(), lse.data_ptr())
+        if qlen is None and klen is None:
+            _call("mcp_attention_small_lse", q, BF, Nq, Nk, heads, C // heads, _lib.fptr(q), C, _lib.fptr(kv), 2 * C, kv.data_ptr() + 4 * C, 2 * C,
+                  float(scale), float(drop_p), int(seed), out.data_ptr(), lse.data_ptr())
+        else:
+            _call("mcp_attention_small_lse_lengths", q, BF, Nq, Nk, heads, C // heads, _lib.fptr(q), C, _lib.fptr(kv), 2 * C, kv.data_ptr() + 4 * C, 2 * C,
+                  float(scale), float(drop_p), int(seed), out.data_ptr(), lse.data_ptr(), _len_ptr(qlen), _len_ptr(klen))
         ctx.heads, ctx.scale, ctx.drop_p, ctx.seed = heads, scale, drop_p, seed
-        ctx.save_for_backward(q, kv, out, lse)
+        ctx.save_for_backward(q, kv, out, lse, qlen, klen)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        q, kv, out, lse = ctx.saved_tensors
+        q, kv, out, lse, qlen, klen = ctx.saved_tensors
         BF, Nq, C = q.shape
         Nk, heads = kv.shape[1], ctx.heads
         lib = _lib.load()
@@ -308,32 +318,42 @@ class _AttentionSmallFn(torch.autograd.Function):
         dq, dkv = torch.empty_like(q), torch.empty_like(kv)
         need = lib.mcp_attention_small_grad_workspace_bytes(BF, Nq, heads)
         ws = torch.empty((need,), dtype=torch.uint8, device=q.device)
-        _call("mcp_attention_small_grad_lse", q, BF, Nq, Nk, heads, C // heads, q.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 4 * C, 2 * C,
-              float(ctx.scale), float(ctx.drop_p), int(ctx.seed), _lib.fptr(out), _lib.fptr(grad_out), _lib.fptr(lse), _lib.fptr(dq), _lib.fptr(dkv),
-              ws.data_ptr(), need)
-        return None, dq, dkv, None, None, None, None
+        if qlen is None and klen is None:
+            _call("mcp_attention_small_grad_lse", q, BF, Nq, Nk, heads, C // heads, q.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 4 * C, 2 * C,
+                  float(ctx.scale), float(ctx.drop_p), int(ctx.seed), _lib.fptr(out), _lib.fptr(grad_out), _lib.fptr(lse), _lib.fptr(dq), _lib.fptr(dkv),
+                  ws.data_ptr(), need)
+        else:
+            _call("mcp_attention_small_grad_lse_lengths", q, BF, Nq, Nk, heads, C // heads, q.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 4 * C,
+                  2 * C, float(ctx.scale), float(ctx.drop_p), int(ctx.seed), _lib.fptr(out), _lib.fptr(grad_out), _lib.fptr(lse), _lib.fptr(dq),
+                  _lib.fptr(dkv), ws.data_ptr(), need, _len_ptr(qlen), _len_ptr(klen))
+        return None, dq, dkv, None, None, None, None, None, None
 
 
 class _AttentionWideFn(torch.autograd.Function):
     """mcp_attention_wide (head widths 32 / 64 / 256) with its hand-written backward (mcp_attention_wide_grad_lse: D = dO . O, dQ, dK/dV
-    on fp32 MFMA); the forward keeps the rows' log-sum-exp, dropout is the in-kernel hash mask of the narrow heads."""
+    on fp32 MFMA); the forward keeps the rows' log-sum-exp, dropout is the in-kernel hash mask of the narrow heads.
+    qlen / klen: (BF,) int32 device tensors or None -- per-element lengths (the *_lengths entries), carried to the backward."""
 
     @staticmethod
-    def forward(ctx, be, q, kv, heads, scale, drop_p, seed):
+    def forward(ctx, be, q, kv, heads, scale, drop_p, seed, qlen=None, klen=None):
         q, kv = q.detach().contiguous(), kv.detach().contiguous()
         BF, Nq, C = q.shape
         Nk = kv.shape[1]
         out = torch.empty((BF, Nq, C), dtype=torch.float32, device=q.device)
         lse = torch.empty((BF, heads, Nq), dtype=torch.float32, device=q.device)   # kept for the backward: no second forward there
-        _call("mcp_attention_wide_lse", q, BF, Nq, Nk, heads, C // heads, _lib.fptr(q), C, _lib.fptr(kv), 2 * C, kv.data_ptr() + 4 * C, 2 * C,
-              float(scale), float(drop_p), int(seed), out.data_ptr(), lse.data_ptr())
+        if qlen is None and klen is None:
+            _call("mcp_attention_wide_lse", q, BF, Nq, Nk, heads, C // heads, _lib.fptr(q), C, _lib.fptr(kv), 2 * C, kv.data_ptr() + 4 * C, 2 * C,
+                  float(scale), float(drop_p), int(seed), out.data_ptr(), lse.data_ptr())
+        else:
+            _call("mcp_attention_wide_lse_lengths", q, BF, Nq, Nk, heads, C // heads, _lib.fptr(q), C, _lib.fptr(kv), 2 * C, kv.data_ptr() + 4 * C, 2 * C,
+                  float(scale), float(drop_p), int(seed), out.data_ptr(), lse.data_ptr(), _len_ptr(qlen), _len_ptr(klen))
         ctx.heads, ctx.scale, ctx.drop_p, ctx.seed = heads, scale, drop_p, seed
-        ctx.save_for_backward(q, kv, out, lse)
+        ctx.save_for_backward(q, kv, out, lse, qlen, klen)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        q, kv, out, lse = ctx.saved_tensors
+        q, kv, out, lse, qlen, klen = ctx.saved_tensors
         BF, Nq, C = q.shape
         Nk, heads = kv.shape[1], ctx.heads
         lib = _lib.load()
@@ -341,10 +361,15 @@ class _AttentionWideFn(torch.autograd.Function):
         dq, dkv = torch.empty_like(q), torch.empty_like(kv)
         need = lib.mcp_attention_wide_grad_workspace_bytes(BF, Nq, Nk, heads, C // heads)
         ws = torch.empty((need,), dtype=torch.uint8, device=q.device)
-        _call("mcp_attention_wide_grad_lse", q, BF, Nq, Nk, heads, C // heads, q.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 4 * C, 2 * C,
-              float(ctx.scale), float(ctx.drop_p), int(ctx.seed), _lib.fptr(out), _lib.fptr(grad_out), _lib.fptr(lse), _lib.fptr(dq), _lib.fptr(dkv),
-              ws.data_ptr(), need)
-        return None, dq, dkv, None, None, None, None
+        if qlen is None and klen is None:
+            _call("mcp_attention_wide_grad_lse", q, BF, Nq, Nk, heads, C // heads, q.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 4 * C, 2 * C,
+                  float(ctx.scale), float(ctx.drop_p), int(ctx.seed), _lib.fptr(out), _lib.fptr(grad_out), _lib.fptr(lse), _lib.fptr(dq), _lib.fptr(dkv),
+                  ws.data_ptr(), need)
+        else:
+            _call("mcp_attention_wide_grad_lse_lengths", q, BF, Nq, Nk, heads, C // heads, q.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 4 * C,
+                  2 * C, float(ctx.scale), float(ctx.drop_p), int(ctx.seed), _lib.fptr(out), _lib.fptr(grad_out), _lib.fptr(lse), _lib.fptr(dq),
+                  _lib.fptr(dkv), ws.data_ptr(), need, _len_ptr(qlen), _len_ptr(klen))
+        return None, dq, dkv, None, None, None, None, None, None
 
 
 def _prelu_drop_fwd(z, slope, drop_p=0.0, seed=0):
@@ -2167,17 +2192,31 @@ class HipBackend:
               float(slope), _lib.fptr(out))
         return out
 
-    def attention(self, q, kv, heads, scale=None, dropout_p=0.0):
+    def attention(self, q, kv, heads, scale=None, dropout_p=0.0, query_lengths=None, key_lengths=None):
         """softmax(q k^T * scale) v per head, reading the projection outputs in place: q (BF,Nq,C), kv (BF,Nk,2C)
         laid out [k | v] as the reference's kv Linear produces (mocopci.py:74-75, :653-654) -> (BF,Nq,C).  dropout_p > 0: attention
         dropout on the softmax matrix inside the kernel (head dims 8 / 16 / 32 / 64 / 256), the mask a counter-based hash seeded from
-        torch's CPU generator (reproducible under torch.manual_seed; see mcp_attention_small_dropout, mcp_attention_wide_dropout)."""
+        torch's CPU generator (reproducible under torch.manual_seed; see mcp_attention_small_dropout, mcp_attention_wide_dropout).
+        query_lengths / key_lengths: per-element lengths of a padded batch (see lengths_tensor; None = full): rows below the query
+        length attend to the keys below the key length; rows at or beyond it, and every row of an element without keys, are zeros, as
+        are the gradients of padded rows.  Padding may hold anything (NaN, inf).  No synchronisation."""
         BF, Nq, C = q.shape
         Nk = kv.shape[1]
         hd = C // heads
         if scale is None:
             scale = hd ** -0.5
         fn = _AttentionSmallFn if hd in (8, 16) else _AttentionWideFn
+        if query_lengths is not None or key_lengths is not None:
+            qlen = lengths_tensor(query_lengths, BF, Nq, q.device)
+            klen = lengths_tensor(key_lengths, BF, Nk, q.device)
+            if hd not in (8, 16, 32, 64, 256):
+                if dropout_p > 0.0:
+                    raise RuntimeError("attention dropout inside the kernel: head dims 8 / 16 / 32 / 64 / 256")
+                return grad.attention_lengths_twin(q, kv, heads, float(scale), qlen, klen)   # the dense masked formulation
+            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if dropout_p > 0.0 else 0  # CPU generator: no device synchronisation
+            if grad.wants_grad(q, kv):
+                return fn.apply(self, q, kv, heads, float(scale), float(dropout_p), seed, qlen, klen)
+            return self._attention_lengths(q, kv, heads, float(scale), float(dropout_p), seed, qlen, klen)
         if dropout_p > 0.0:
             if hd not in (8, 16, 32, 64, 256):
                 raise RuntimeError("attention dropout inside the kernel: head dims 8 / 16 / 32 / 64 / 256")
@@ -2207,6 +2246,21 @@ class HipBackend:
               float(scale), out.data_ptr(), C)
         return out
 
+    def _attention_lengths(self, q, kv, heads, scale, drop_p, seed, qlen, klen):
+        """_attention over a padded batch: qlen / klen (BF,) int32 device tensors or None."""
+        q, kv = q.contiguous(), kv.contiguous()
+        BF, Nq, C = q.shape
+        Nk, hd = kv.shape[1], C // heads
+        out = torch.empty((BF, Nq, C), dtype=torch.float32, device=q.device)
+        if drop_p > 0.0:   # the training forward without its log-sum-exp
+            name = "mcp_attention_small_lse_lengths" if hd in (8, 16) else "mcp_attention_wide_lse_lengths"
+            _call(name, q, BF, Nq, Nk, heads, hd, q.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 4 * C, 2 * C,
+                  float(scale), float(drop_p), int(seed), out.data_ptr(), None, _len_ptr(qlen), _len_ptr(klen))
+            return out
+        _call("mcp_attention_lengths", q, BF, Nq, Nk, heads, hd, q.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 4 * C, 2 * C, 0,
+              float(scale), _len_ptr(qlen), _len_ptr(klen), out.data_ptr(), C)
+        return out
+
     def prelu_dropout(self, z, slope, drop_p):
         """dropout(prelu(z, slope), drop_p) of a training forward (Mlp_T's act + drop, mocopci.py:1561-1562) as one pass, with a
         one-pass backward; slope: the layer's 1-element parameter.  The mask is a counter-based hash seeded from torch's CPU
@@ -2216,15 +2270,22 @@ class HipBackend:
             raise RuntimeError("prelu_dropout: one slope for all channels (nn.PReLU())")
         return _PreluDropFn.apply(z, slope, float(drop_p), seed)
 
-    def attention_rot(self, q, k, v, heads, kv_shift, scale=None):
+    def attention_rot(self, q, k, v, heads, kv_shift, scale=None, query_lengths=None, key_lengths=None):
         """Attention over one stacked batch whose keys / values come from batch element (b + kv_shift) mod BF: q, k, v are
-        (BF,N,C) views with unit channel stride (e.g. column slices of one packed projection, read in place).  Inference only."""
+        (BF,N,C) views with unit channel stride (e.g. column slices of one packed projection, read in place).  Inference only.
+        query_lengths / key_lengths: as attention(); key_lengths is indexed by the k / v tensors' own batch element, so the queries
+        of element b see key_lengths[(b + kv_shift) mod BF]."""
         BF, Nq, C = q.shape
         Nk, hd = k.shape[1], C // heads
         for t, n in ((q, Nq), (k, Nk), (v, Nk)):
             if not (t.is_cuda and t.dtype == torch.float32 and t.stride(2) == 1 and t.stride(0) == n * t.stride(1)):
                 raise RuntimeError("attention_rot: (BF,N,C) float32 CUDA views with unit channel stride and dense batches")
         out = torch.empty((BF, Nq, C), dtype=torch.float32, device=q.device)
+        if query_lengths is not None or key_lengths is not None:
+            qlen, klen = lengths_tensor(query_lengths, BF, Nq, q.device), lengths_tensor(key_lengths, BF, Nk, q.device)
+            _call("mcp_attention_lengths", q, BF, Nq, Nk, heads, hd, q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), v.data_ptr(),
+                  v.stride(1), int(kv_shift), float(hd ** -0.5 if scale is None else scale), _len_ptr(qlen), _len_ptr(klen), out.data_ptr(), C)
+            return out
         _call("mcp_attention", q, BF, Nq, Nk, heads, hd, q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), v.data_ptr(), v.stride(1),
               int(kv_shift), float(hd ** -0.5 if scale is None else scale), out.data_ptr(), C)
         return out
