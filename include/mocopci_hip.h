@@ -402,6 +402,34 @@ int mcp_fusion_bn_backward_saved(int b, int n, int nb, const float *p1, const fl
                                  float *grad_p1, float *grad_nb, float *grad_weights, float *grad_affine, void *workspace, size_t workspace_bytes,
                                  mcp_stream_t stream);
 
+/* mcp_fusion_bn_forward / mcp_fusion_bn_backward on a padded batch of clouds of different sizes (csrc/fusion_bn_lengths.hip).
+ *   len     (B) device int32, clamped to [0, n] inside the kernels: point p of element bb is live iff p < len[bb].  NULL: the call is
+ *           the dense entry point, bit for bit (count then receives b * n).
+ *   count   (forward; may be NULL) one device int32 that receives the LIVE POINTS of the call, sum of the clamped lengths (saturated
+ *           at 2^31 - 1).  The statistics run over m = 64 * count rows; the caller's running-variance update scales by m / (m - 1).
+ * Statistics: the live rows are R = {(bb, p, j): p live, j < 64}; every mean and variance of the three layers, every mean term of the
+ * backward and every entry of grad_weights / grad_affine runs over R only.  The variance is formed as in the dense call (sums of
+ * z - s and (z - s)^2, merged in double); the shift s is the conv output at the first row of the first LIVE point.  m < 2 (no live
+ * point): every division is by max(m, 1), there is no shift, nothing is NaN or Inf and the statistics mean nothing.
+ * A padded point, forward: its row of out is zero; none of its rows of p1, idx, idx2 is read.  Backward: its row of grad_out is not
+ * read, its row of grad_p1 and its 64 rows of grad_nb are exact zeros, its rows of row_c / row_dy / row_a / dy2 / dy1 are
+ * UNSPECIFIED (not written, and no pass reads them), it adds nothing to grad_weights, grad_affine or any partial sum, and its row
+ * of idx is not read by these kernels (the caller's mcp_scatter_segments still walks it and leaves out-of-range values out).
+ * The indices of live points are trusted; the caller makes them point at live rows of p2.
+ * No length is read on the host, nothing is allocated, no atomics: every sum runs in a fixed order and two calls give identical
+ * bits.  The grids are those of b * n points and live points are dealt in padded order, so with every len[bb] == n every output is
+ * bit-identical to the dense entry point.  Workspaces: mcp_fusion_bn_workspace_bytes / mcp_fusion_bn_grad_workspace_bytes (b, n), as
+ * dense.  The pair that keeps the forward's scores (mcp_fusion_bn_forward_save / mcp_fusion_bn_backward_saved) has no length form:
+ * the backward here re-evaluates the layer. */
+int mcp_fusion_bn_forward_lengths(int b, int n, int nb, const float *p1, const float *p2, const int *idx, const int *idx2, const int *len,
+                                  const float *w1, const float *b1, const float *w2, const float *b2, const float *w3, const float *b3, float eps,
+                                  float *bn, float *var, float *out, int *count, void *workspace, size_t workspace_bytes, mcp_stream_t stream);
+int mcp_fusion_bn_backward_lengths(int b, int n, int nb, const float *p1, const float *p2, const int *idx, const int *idx2, const int *len,
+                                   const float *w1, const float *b1, const float *w2, const float *b2, const float *w3, const float *b3, const float *bn,
+                                   const float *grad_out, int *row_c, float *row_dy, float *row_a, float *dy2, float *dy1, float *grad_p1,
+                                   float *grad_nb, float *grad_weights, float *grad_affine, void *workspace, size_t workspace_bytes,
+                                   mcp_stream_t stream);
+
 /* Cost-volume cross() after its neighbour searches (pointconv_util.py:750-781, :894-922, :1126-1161):
  * xyz1 (B,N1,3), xyz2 (B,N2,3), points1 (B,N1,D), points2 (B,N2,D) channel-last (16-byte aligned),
  * idx (B,N1,32) int32 into set 2 (16 feature-cosine + 16 xyz neighbours) -> out (B,N1,D) = max over the 32

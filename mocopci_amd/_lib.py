@@ -72,6 +72,8 @@ SIGNATURES = {
     "mcp_fusion_bn_backward": [_i, _i, _i] + [_p] * 22 + [ctypes.c_size_t, _p],
     "mcp_fusion_bn_forward_save": [_i, _i, _i] + [_p] * 10 + [_f] + [_p] * 7 + [ctypes.c_size_t, _p],
     "mcp_fusion_bn_backward_saved": [_i, _i, _i] + [_p] * 25 + [ctypes.c_size_t, _p],
+    "mcp_fusion_bn_forward_lengths": [_i, _i, _i] + [_p] * 11 + [_f] + [_p] * 5 + [ctypes.c_size_t, _p],
+    "mcp_fusion_bn_backward_lengths": [_i, _i, _i] + [_p] * 23 + [ctypes.c_size_t, _p],
     "mcp_cross_packed_floats": [_i],
     "mcp_cross_pack": [_i, _p, _p, _p, _p, _p, _p],
     "mcp_cross_volume": [_i] * 5 + [_p] * 7 + [_i, _p, _p, _p],

@@ -107,6 +107,54 @@ def fusion_twin(G, p1, p2, idx, w1, b1, w2, b2, w3, b3):
     return torch.sum(wgt.unsqueeze(-1) * nb, dim=2)
 
 
+def live_points(lengths, batch, n, device):
+    """(B, N) bool: point p of element b is live iff p < lengths[b] (clamped to [0, n]); lengths: a (B,) integer tensor on `device`."""
+    return torch.arange(n, device=device).view(1, n) < lengths.reshape(batch, 1).clamp(0, n)
+
+
+def _masked_fusion_inputs(G, p1, p2, idx, live):
+    """Padding replaced by zeros / index 0 before anything is gathered, so NaN or an out-of-range index there reaches nothing."""
+    idx = whole(idx)
+    zero = p1.new_zeros(())
+    p1 = torch.where(live.unsqueeze(-1), p1, zero)
+    p2 = torch.where(live.unsqueeze(-1), p2, zero)
+    idx = torch.where(live.unsqueeze(-1), idx, torch.zeros((), dtype=idx.dtype, device=idx.device))
+    if G is None:
+        nb = p2[torch.arange(p2.shape[0], device=p2.device).view(-1, 1, 1), idx.long()]
+    else:
+        nb = G(p2, idx)
+    return p1, nb
+
+
+def fusion_bn_lengths_twin(G, p1, p2, idx, conv, affine, eps, lengths):
+    """The fusion layer of one reference call on BATCH statistics (net.train()) over a padded batch, as plain differentiable torch:
+    every mean and biased variance runs over the m = 64 * sum(lengths) rows of live points only (divided by max(m, 1)), out is zero
+    on padded points.  conv = (w1, b1, w2, b2, w3, b3), affine = (gamma1, beta1, ...); G: the row gather (None: torch indexing).
+    -> (out (B,N,3), bn (1024: per layer mean | rstd | gamma | beta), var (256), count = the live points, int32 on the device):
+    what ops.HipBackend.fusion_bn(lengths=) returns from csrc/fusion_bn_lengths.hip."""
+    B, N, _ = p1.shape
+    live = live_points(lengths, B, N, p1.device)
+    count = live.sum()
+    rows = (64 * count).clamp(min=1).to(p1.dtype)
+    p1, nb = _masked_fusion_inputs(G, p1, p2, idx, live)
+    resi = nb - p1.unsqueeze(2)
+    x = torch.cat([resi, torch.linalg.vector_norm(resi, dim=-1, keepdim=True)], dim=-1)
+    w = live.view(B, N, 1, 1)
+    zero = p1.new_zeros(())
+    bn, var = [], []
+    for i in range(3):
+        z = F.linear(x, conv[2 * i], conv[2 * i + 1])
+        mean = torch.where(w, z, zero).sum(dim=(0, 1, 2)) / rows
+        v = torch.where(w, (z - mean).square(), zero).sum(dim=(0, 1, 2)) / rows
+        rstd = torch.rsqrt(v + eps)
+        x = torch.relu((z - mean) * (affine[2 * i] * rstd) + affine[2 * i + 1])
+        bn += [mean.detach(), rstd.detach(), affine[2 * i].detach(), affine[2 * i + 1].detach()]
+        var.append(v.detach())
+    wgt = torch.softmax(x.amax(dim=-1), dim=-1)
+    out = torch.where(live.unsqueeze(-1), torch.sum(wgt.unsqueeze(-1) * nb, dim=2), zero)
+    return out, torch.cat(bn), torch.cat(var), count.to(torch.int32)
+
+
 def ptblock_twin(G, xyz, q, k, v, idx, wd1, bd1, wd2, bd2, wg1, bg1, wg2, bg2):
     """TransformerBlock.forward after knn and the projections, pointT_layer2.py:64-75."""
     kk, vv = G(k, idx), G(v, idx)

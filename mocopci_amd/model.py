@@ -986,19 +986,36 @@ class MoCoPCI(nn.Module):
             return (self.W(conv) * scale[:, None]).contiguous(), ((self.Bv(conv) - P[bn + ".running_mean"]) * scale + P[bn + ".bias"]).contiguous()
         return self.derived(("fold", conv, bn), fold)
 
-    def fusion(self, p1, p2, k=32, idx_self=None, calls=1):
-        """MultiFrameEstimatier.knn_group + fusion (mocopci.py:798-819).  p1, p2 (B,N,3)."""
+    def fusion(self, p1, p2, k=32, idx_self=None, calls=1, lengths=None):
+        """MultiFrameEstimatier.knn_group + fusion (mocopci.py:798-819).  p1, p2 (B,N,3).
+        lengths (forms: ops.lengths_tensor; one entry per batch element, for p1 and p2 alike): rows at or beyond a length are
+        padding -- the searches see live rows only, the output is zero on padded rows and, under train(), the batch statistics run
+        over live points' rows (fusion_batch_stats).  Every cloud must hold at least k live points, so that a live point's
+        neighbours are live."""
         be = ops.backend()
         m = "multi_frame_inference.conv."
+        if lengths is not None and not hasattr(be, "fusion_bn"):
+            raise NotImplementedError("fusion(lengths=): the neighbour searches with lengths need the HIP backend; fusion_batch_stats takes the lists")
+        lens = None if lengths is None else ops.lengths_tensor(lengths, p1.shape[0], p1.shape[1], p1.device)
+        kw = {} if lens is None else dict(query_lengths=lens, ref_lengths=lens)
         if idx_self is None:
-            idx_self = be.knn(p1, p1, k)
-        idx = (idx_self, be.knn(p1, p2, k))                                        # 2 x (B,N,k), both index p2
+            idx_self = be.knn(p1, p1, k, **kw)
+        idx = (idx_self, be.knn(p1, p2, k, **kw))                                  # 2 x (B,N,k), both index p2
         if self._mode is not None:
-            return self.fusion_batch_stats(p1, p2.contiguous(), idx, calls)
+            return self.fusion_batch_stats(p1, p2.contiguous(), idx, calls, lengths=lens)
         wb = [t for ci, bi in ((0, 1), (3, 4), (6, 7)) for t in self.folded_conv_bn(m + str(ci), m + str(bi), 1e-3)]
+        if lens is not None:
+            return be.fusion_mlp(p1, p2.contiguous(), idx, *wb, lengths=lens)
         return be.fusion_mlp(p1, p2.contiguous(), idx, *wb)
 
-    def fusion_batch_stats(self, p1, p2, idx, calls):
+    @staticmethod
+    def unbias_factor(count):
+        """m / (m - 1) for m = 64 * count rows (count: the live points of a call, an integer tensor), on count's device; 1 where
+        m < 2 (nothing to unbias: the statistics of a call without a live point mean nothing)."""
+        rows = 64.0 * count.to(torch.float32)
+        return torch.where(rows > 1, rows / (rows - 1).clamp(min=1), torch.ones_like(rows))
+
+    def fusion_batch_stats(self, p1, p2, idx, calls, lengths=None):
         """fusion (mocopci.py:810-819) in a net.train() forward: the three Conv2d + BatchNorm2d(eps 1e-3) + ReLU layers with BATCH
         statistics, so nothing can be folded and the layers run unfused on the gathered (B,N,64,.) tensor.  The batch holds
         `calls` consecutive reference calls (the three interpolated frames, mocopci.py:1046-1051), each normalised with its own
@@ -1016,11 +1033,16 @@ class MoCoPCI(nn.Module):
             aff = [t for _, bi in layers for t in (P[m + f"{bi}.weight"], P[m + f"{bi}.bias"])]
             per = p1.shape[0] // calls
             rows = per * p1.shape[1] * 64
-            outs, stats = [], []
+            lens = None if lengths is None else ops.lengths_tensor(lengths, p1.shape[0], p1.shape[1], p1.device)
+            outs, stats, counts = [], [], []
             for c in range(calls):
                 sl = slice(c * per, (c + 1) * per)
                 idx_c = tuple(i[sl] for i in idx) if isinstance(idx, (tuple, list)) else idx[sl]
-                out, bn, var = be.fusion_bn(p1[sl], p2[sl], idx_c, conv, aff, 1e-3)
+                if lens is None:
+                    out, bn, var = be.fusion_bn(p1[sl], p2[sl], idx_c, conv, aff, 1e-3)
+                else:   # the statistics over the live points' rows only; the call's live points stay on the device
+                    out, bn, var, count = be.fusion_bn(p1[sl], p2[sl], idx_c, conv, aff, 1e-3, lengths=lens[sl])
+                    counts.append(count)
                 outs.append(out)
                 stats.append((bn, var))
             with torch.no_grad():
@@ -1028,13 +1050,39 @@ class MoCoPCI(nn.Module):
                 mom = self.BN_MOMENTUM
                 coef, keep = self.ema_coefficients(calls, mom, p1.device)
                 bns, vrs = torch.stack([b for b, _ in stats]), torch.stack([v for _, v in stats])     # (calls, 1024), (calls, 256)
+                unbias = rows / (rows - 1)
+                if lens is not None:   # m / (m - 1) per call, m = 64 live points, formed on the device (no host read of a count)
+                    vrs, unbias = vrs * self.unbias_factor(torch.stack(counts)).unsqueeze(1), 1.0
                 at_bn = at_var = 0
                 for (_, bi), ch in zip(layers, (64, 64, 128)):
                     P[m + f"{bi}.running_mean"].mul_(keep).add_(coef @ bns[:, at_bn:at_bn + ch])
-                    P[m + f"{bi}.running_var"].mul_(keep).add_(coef @ vrs[:, at_var:at_var + ch], alpha=rows / (rows - 1))
+                    P[m + f"{bi}.running_var"].mul_(keep).add_(coef @ vrs[:, at_var:at_var + ch], alpha=unbias)
                     P[m + f"{bi}.num_batches_tracked"].add_(calls)
                     at_bn += 4 * ch
                     at_var += ch
+            return torch.cat(outs, dim=0)
+        if lengths is not None:
+            # a backend without the kernels (the CPU oracle): the plain torch formulation with masked statistics, call by call
+            P = self._params()
+            conv = [t for ci, _ in layers for t in (self.W(m + str(ci)), self.Bv(m + str(ci)))]
+            aff = [t for _, bi in layers for t in (P[m + f"{bi}.weight"], P[m + f"{bi}.bias"])]
+            lens = lengths if torch.is_tensor(lengths) else torch.as_tensor(lengths)
+            lens = lens.to(p1.device)
+            per = p1.shape[0] // calls
+            outs = []
+            for c in range(calls):
+                sl = slice(c * per, (c + 1) * per)
+                out, bn, var, count = grad.fusion_bn_lengths_twin(be.group_rows, p1[sl], p2[sl], grad.whole(idx)[sl], conv, aff, 1e-3, lens[sl])
+                outs.append(out)
+                with torch.no_grad():
+                    at_bn = at_var = 0
+                    for (_, bi), ch in zip(layers, (64, 64, 128)):
+                        mom = self.BN_MOMENTUM
+                        P[m + f"{bi}.running_mean"].mul_(1.0 - mom).add_(bn[at_bn:at_bn + ch], alpha=mom)
+                        P[m + f"{bi}.running_var"].mul_(1.0 - mom).add_(var[at_var:at_var + ch] * self.unbias_factor(count), alpha=mom)
+                        P[m + f"{bi}.num_batches_tracked"].add_(1)
+                        at_bn += 4 * ch
+                        at_var += ch
             return torch.cat(outs, dim=0)
         idx = grad.whole(idx)
         if p1.shape[0] * p1.shape[1] * idx.shape[-1] * 128 * 4 <= self.CHECKPOINT_BYTES or not torch.is_grad_enabled():

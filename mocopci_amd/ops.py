@@ -1230,9 +1230,16 @@ class _FusionBNFn(torch.autograd.Function):
     non-differentiable by-products for the caller's running-estimate update)."""
 
     @staticmethod
-    def forward(ctx, be, eps, ia, ib, p1, p2, w1, b1, w2, b2, w3, b3, g1, e1, g2, e2, g3, e3):
+    def forward(ctx, be, eps, ia, ib, lens, p1, p2, w1, b1, w2, b2, w3, b3, g1, e1, g2, e2, g3, e3):
         conv = [t.detach().contiguous() for t in (w1, b1, w2, b2, w3, b3)]
         p1, p2 = p1.detach().contiguous(), p2.detach().contiguous()
+        ctx.has_lengths = lens is not None
+        if lens is not None:
+            # per-cloud lengths (csrc/fusion_bn_lengths.hip): the forward keeps no scores, the backward re-evaluates the layer
+            out, bn, var, count = be.fusion_bn_forward(p1, p2, ia if ib is None else (ia, ib), conv, (g1, e1, g2, e2, g3, e3), eps, lengths=lens)
+            ctx.save_for_backward(ia, ib, p1, p2, *conv, bn, lens)
+            ctx.mark_non_differentiable(bn, var, count)
+            return out, bn, var, count
         rows = p1.shape[0] * p1.shape[1] * 64
         # kept for the backward: every neighbour's score, its layer-3 channel and zhat3 there (12 bytes per row) -- the backward's first
         # pass then has no layer to re-evaluate
@@ -1244,8 +1251,11 @@ class _FusionBNFn(torch.autograd.Function):
         return out, bn, var
 
     @staticmethod
-    def backward(ctx, grad_out, _gbn, _gvar):
-        ia, ib, p1, p2, w1, b1, w2, b2, w3, b3, bn, save_c, save_z, save_s = ctx.saved_tensors
+    def backward(ctx, grad_out, _gbn, _gvar, _gcount=None):
+        if ctx.has_lengths:
+            ia, ib, p1, p2, w1, b1, w2, b2, w3, b3, bn, lens = ctx.saved_tensors
+        else:
+            ia, ib, p1, p2, w1, b1, w2, b2, w3, b3, bn, save_c, save_z, save_s = ctx.saved_tensors
         B, N, _ = p1.shape
         rows = B * N * 64
         lib, dev = _lib.load(), p1.device
@@ -1259,19 +1269,24 @@ class _FusionBNFn(torch.autograd.Function):
         d_aff = torch.empty((512,), dtype=torch.float32, device=dev)
         need = lib.mcp_fusion_bn_grad_workspace_bytes(B, N)
         ws = torch.empty((need,), dtype=torch.uint8, device=dev)
-        _call("mcp_fusion_bn_backward_saved", p1, B, N, 64, _lib.fptr(p1), _lib.fptr(p2), _lib.iptr(ia), None if ib is None else _lib.iptr(ib),
-              *[_lib.fptr(t) for t in (w1, b1, w2, b2, w3, b3, bn, grad_out)], _lib.iptr(save_c), _lib.fptr(save_z), _lib.fptr(save_s),
-              _lib.iptr(row_c), _lib.fptr(row_dy), _lib.fptr(row_a), _lib.fptr(dy2),
-              _lib.fptr(dy1), _lib.fptr(d_p1), _lib.fptr(d_nb), _lib.fptr(d_w), _lib.fptr(d_aff), ws.data_ptr(), need)
+        scratch = (_lib.iptr(row_c), _lib.fptr(row_dy), _lib.fptr(row_a), _lib.fptr(dy2), _lib.fptr(dy1), _lib.fptr(d_p1), _lib.fptr(d_nb), _lib.fptr(d_w),
+                   _lib.fptr(d_aff), ws.data_ptr(), need)
+        if ctx.has_lengths:
+            _call("mcp_fusion_bn_backward_lengths", p1, B, N, 64, _lib.fptr(p1), _lib.fptr(p2), _lib.iptr(ia), None if ib is None else _lib.iptr(ib),
+                  _lib.iptr(lens), *[_lib.fptr(t) for t in (w1, b1, w2, b2, w3, b3, bn, grad_out)], *scratch)
+        else:
+            _call("mcp_fusion_bn_backward_saved", p1, B, N, 64, _lib.fptr(p1), _lib.fptr(p2), _lib.iptr(ia), None if ib is None else _lib.iptr(ib),
+                  *[_lib.fptr(t) for t in (w1, b1, w2, b2, w3, b3, bn, grad_out)], _lib.iptr(save_c), _lib.fptr(save_z), _lib.fptr(save_s), *scratch)
         d_p2 = None
-        if ctx.needs_input_grad[5]:
+        if ctx.needs_input_grad[6]:
+            # (a padded point's rows of d_nb are zeros and its list may hold anything: the segmented scatter leaves out-of-range entries out)
             d_p2 = _group_rows_grad(d_nb, ia if ib is None else torch.cat((ia, ib), dim=-1), p2.shape[1])
         pieces, at = [], 0
         for t in (w1, b1, w2, b2, w3, b3):
             pieces.append(d_w[at:at + t.numel()].view(t.shape))
             at += t.numel()
         aff = [d_aff[0:64], d_aff[64:128], d_aff[128:192], d_aff[192:256], d_aff[256:384], d_aff[384:512]]
-        return (None, None, None, None, d_p1, d_p2, *pieces, *aff)
+        return (None, None, None, None, None, d_p1, d_p2, *pieces, *aff)
 
 
 class _FusionFn(torch.autograd.Function):
@@ -1649,8 +1664,20 @@ class HipBackend:
               _lib.iptr(idx3), _lib.fptr(w3))
         return out
 
-    def fusion_mlp(self, p1, p2, idx, w1, b1, w2, b2, w3, b3):
-        """fusion after the neighbour searches (mocopci.py:803-819), BN folded into (w,b): -> (B,N,3).  Differentiable."""
+    def fusion_mlp(self, p1, p2, idx, w1, b1, w2, b2, w3, b3, lengths=None):
+        """fusion after the neighbour searches (mocopci.py:803-819), BN folded into (w,b): -> (B,N,3).  Differentiable.
+        lengths (forms: lengths_tensor): rows of p1 / p2 at or beyond lengths[b] are padding.  This is the DENSE kernel plus
+        masking, no kernel of its own (every sum of this layer is per point, so lengths only save work): padded rows of p1 and p2
+        are replaced by zeros and padded rows of idx by 0 before the call, out is zero on padded rows, live rows have the dense
+        call's bits, and gradients reach live rows only."""
+        if lengths is not None:
+            B, N, _ = p1.shape
+            live = grad.live_points(lengths_tensor(lengths, B, N, p1.device), B, N, p1.device).unsqueeze(-1)
+            zero = p1.new_zeros(())
+            halves = idx if isinstance(idx, (tuple, list)) else (idx,)
+            halves = tuple(torch.where(live, h, torch.zeros((), dtype=h.dtype, device=h.device)) for h in halves)
+            out = self.fusion_mlp(torch.where(live, p1, zero), torch.where(live, p2, zero), halves if len(halves) > 1 else halves[0], w1, b1, w2, b2, w3, b3)
+            return torch.where(live, out, zero)
         if not grad.wants_grad(p1, p2, w1, b1, w2, b2, w3, b3):
             return self._fusion_mlp(p1, p2, idx, w1, b1, w2, b2, w3, b3)
         ia, ib = idx if isinstance(idx, (tuple, list)) else (idx, None)
@@ -1658,21 +1685,30 @@ class HipBackend:
             return grad.fusion_twin(self.group_rows, p1, p2, idx, w1, b1, w2, b2, w3, b3)
         return _FusionFn.apply(self, ia.contiguous(), None if ib is None else ib.contiguous(), p1, p2, w1, b1, w2, b2, w3, b3)
 
-    def fusion_bn(self, p1, p2, idx, conv, affine, eps):
+    def fusion_bn(self, p1, p2, idx, conv, affine, eps, lengths=None):
         """The fusion layer of ONE reference call on batch statistics, differentiable w.r.t. p1, p2, the conv weights and the
-        BatchNorm weight / bias: -> (out (B,N,3), bn, var) -- see _FusionBNFn."""
+        BatchNorm weight / bias: -> (out (B,N,3), bn, var) -- see _FusionBNFn.
+        lengths (forms: lengths_tensor): the rows of p1 and p2 at or beyond lengths[b] are padding (mcp_fusion_bn_forward_lengths /
+        mcp_fusion_bn_backward_lengths): every statistic and every gradient runs over the live points' rows only, out and the
+        gradients of p1 are zero on padded rows, whose values and index rows are never read.  -> (out, bn, var, count) with count the
+        live points (one int32 on the device; the statistics' rows are 64 * count).  The indices of live points must point at live
+        rows of p2."""
         ia, ib = idx if isinstance(idx, (tuple, list)) else (idx, None)
         if ia.shape[-1] + (0 if ib is None else ib.shape[-1]) != 64:
             raise ValueError("fusion_bn: the batch-statistics kernels take 64 neighbours per point (2 x 32 or one list of 64)")
-        return _FusionBNFn.apply(self, float(eps), ia.contiguous(), None if ib is None else ib.contiguous(), p1, p2, *conv, *affine)
+        lens = lengths_tensor(lengths, p1.shape[0], p1.shape[1], p1.device)
+        return _FusionBNFn.apply(self, float(eps), ia.contiguous(), None if ib is None else ib.contiguous(), lens, p1, p2, *conv, *affine)
 
-    def fusion_bn_forward(self, p1, p2, idx, conv, affine, eps, saved=None):
+    def fusion_bn_forward(self, p1, p2, idx, conv, affine, eps, saved=None, lengths=None):
         """The fusion layer of ONE reference call on batch statistics (net.train(); mocopci.py:810-819 with nn.BatchNorm2d in training
         mode): conv = (w1, b1, w2, b2, w3, b3) raw conv weights, affine = (gamma1, beta1, gamma2, beta2, gamma3, beta3).
         -> out (B,N,3), bn (1024: per layer mean | rstd | gamma | beta), var (256: biased batch variances 64 | 64 | 128).  No autograd.
         saved: (int32, float32, float32) tensors of B*N*64 elements that receive every neighbour's arg-max channel, zhat3 there and score
-        (mcp_fusion_bn_forward_save; what mcp_fusion_bn_backward_saved reads)."""
+        (mcp_fusion_bn_forward_save; what mcp_fusion_bn_backward_saved reads).
+        lengths: per-cloud lengths (see fusion_bn; not together with saved) -> (out, bn, var, count)."""
         lib = _lib.load()
+        if lengths is not None and saved is not None:
+            raise ValueError("fusion_bn_forward: the forward that keeps its scores has no length form")
         p1, p2 = p1.contiguous(), p2.contiguous()
         conv = [t.detach().contiguous() for t in conv]
         B, N, _ = p1.shape
@@ -1687,6 +1723,13 @@ class HipBackend:
         out = torch.empty((B, N, 3), dtype=torch.float32, device=p1.device)
         need = lib.mcp_fusion_bn_workspace_bytes(B, N)
         ws = torch.empty((need,), dtype=torch.uint8, device=p1.device)
+        if lengths is not None:
+            lens = lengths_tensor(lengths, B, N, p1.device)
+            count = torch.empty((1,), dtype=torch.int32, device=p1.device)
+            _call("mcp_fusion_bn_forward_lengths", p1, B, N, 64, _lib.fptr(p1), _lib.fptr(p2), _lib.iptr(ia), None if ib is None else _lib.iptr(ib),
+                  _lib.iptr(lens), *[_lib.fptr(t) for t in conv], float(eps), _lib.fptr(bn), _lib.fptr(var), _lib.fptr(out), _lib.iptr(count), ws.data_ptr(),
+                  need)
+            return out, bn, var, count.view(())
         if saved is None:
             _call("mcp_fusion_bn_forward", p1, B, N, 64, _lib.fptr(p1), _lib.fptr(p2), _lib.iptr(ia), None if ib is None else _lib.iptr(ib),
                   *[_lib.fptr(t) for t in conv], float(eps), _lib.fptr(bn), _lib.fptr(var), _lib.fptr(out), ws.data_ptr(), need)
