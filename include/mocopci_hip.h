@@ -80,15 +80,38 @@ int mcp_furthest_point_sampling_fresh(int b, int n, int m, const float *xyz, int
  *   rows at or beyond l are never read: their contents reach no output bit.
  * The tie rule needs no per-element block size: the reference's order for a cloud of ANY length is the one of its 1024-thread block,
  * (bitrev_10(k mod 1024), k div 1024) (csrc/fps_lengths.hip).
- * n <= 16384: one workgroup per element, points and running distances in registers, register slices and waves wholly beyond l
- * skipped; no workspace (the query returns 0).  n > 16384: a streaming kernel bounded by l that keeps its running distances in the
- * workspace: mcp_fps_lengths_workspace_bytes returns b*n*4, and the call returns MCP_ERR_UNSUPPORTED when workspace is NULL or
- * smaller.  The buffer is only used during the call (stream-ordered) and needs no initialisation.
+ * Four kernel forms give those same bits; which one runs is a pure function of the PADDED shape and the workspace size
+ * (mcp_fps_lengths_form; no length is read by the host):
+ *   n < 1024, or m <= 1 (n <= 16384)    resident: one workgroup per element, points and running distances in registers, register
+ *                                       slices and waves wholly beyond l skipped; no workspace
+ *   1024 <= n <= 16384, m > 1           spatial: the Morton-sorted, box-pruned kernel of the length-free call over the l live
+ *                                       points; no workspace
+ *   16384 < n <= 65536                  tiled (the length-free call's tiled kernel over ceil(l / 64) live tiles) when workspace_bytes
+ *                                       >= mcp_fps_lengths_pruned_workspace_bytes (20 bytes per point of the cloud padded to 64, the
+ *                                       figure of mcp_fps_workspace_bytes); else streaming (bounded by l, running distances in the
+ *                                       workspace) when workspace_bytes >= mcp_fps_lengths_workspace_bytes = b*n*4; else
+ *                                       MCP_ERR_UNSUPPORTED, as with a NULL workspace: nothing is launched
+ *   n > 65536                           streaming, workspace b*n*4 as above
+ * mcp_fps_lengths_workspace_bytes is the least a call needs (0 for n <= 16384), mcp_fps_lengths_pruned_workspace_bytes what the
+ * fastest form uses (the same value outside 16384 < n <= 65536).  The buffer is only used during the call (stream-ordered) and needs
+ * no initialisation.
+ * mcp_fps_lengths_form: host only, launches nothing; the form (MCP_FPS_LENGTHS_*) a call of mcp_furthest_point_sampling_lengths with a
+ * non-NULL len and a non-NULL workspace of that size takes, or MCP_ERR_UNSUPPORTED.  The call dispatches through this function.
+ * mcp_furthest_point_sampling_lengths_unpruned: the same arguments and results from the resident (n <= 16384) and streaming forms
+ * alone -- the cross-check of the pruned forms and their timing baseline (tools/fps_lengths_times.py).
  * Error codes as for the length-free calls (MCP_ERR_BAD_ARG: b <= 0, n <= 0, NULL xyz or idx; nothing is launched); m <= 0
  * returns MCP_OK. */
+#define MCP_FPS_LENGTHS_RESIDENT 0
+#define MCP_FPS_LENGTHS_SPATIAL 1
+#define MCP_FPS_LENGTHS_TILED 2
+#define MCP_FPS_LENGTHS_STREAMING 3
 size_t mcp_fps_lengths_workspace_bytes(int b, int n, int m);
+size_t mcp_fps_lengths_pruned_workspace_bytes(int b, int n, int m);
+int mcp_fps_lengths_form(int b, int n, int m, size_t workspace_bytes);
 int mcp_furthest_point_sampling_lengths(int b, int n, int m, const float *xyz, const int *len, int *idx, float *sampled_xyz,
                                         void *workspace, size_t workspace_bytes, mcp_stream_t stream);
+int mcp_furthest_point_sampling_lengths_unpruned(int b, int n, int m, const float *xyz, const int *len, int *idx, float *sampled_xyz,
+                                                 void *workspace, size_t workspace_bytes, mcp_stream_t stream);
 
 /* gather_points_wrapper(b,c,n,npoints,points,idx,out)     sampling.cpp:11-22, sampling_gpu.cu:8-44
  * points (B,C,N), idx (B,npoints) -> out (B,C,npoints). */

@@ -24,6 +24,9 @@ SIGNATURES = {
     "mcp_furthest_point_sampling_fresh": [_i, _i, _i, _p, _p, _p, _p, ctypes.c_size_t, _p],
     "mcp_fps_lengths_workspace_bytes": [_i, _i, _i],
     "mcp_furthest_point_sampling_lengths": [_i, _i, _i, _p, _p, _p, _p, _p, ctypes.c_size_t, _p],
+    "mcp_fps_lengths_pruned_workspace_bytes": [_i, _i, _i],
+    "mcp_fps_lengths_form": [_i, _i, _i, ctypes.c_size_t],
+    "mcp_furthest_point_sampling_lengths_unpruned": [_i, _i, _i, _p, _p, _p, _p, _p, ctypes.c_size_t, _p],
     "mcp_gather_points": [_i, _i, _i, _i, _p, _p, _p, _p],
     "mcp_gather_points_grad": [_i, _i, _i, _i, _p, _p, _p, _p],
     "mcp_group_points": [_i, _i, _i, _i, _i, _p, _p, _p, _p],
@@ -164,7 +167,8 @@ SIGNATURES = {
     "mcp_prof_enable": [_i],
     "mcp_prof_collect": [_i, _p, _p],
 }
-_RESTYPES = {"mcp_error_string": ctypes.c_char_p, "mcp_fps_workspace_bytes": ctypes.c_size_t, "mcp_fps_lengths_workspace_bytes": ctypes.c_size_t, "mcp_fusion_grad_workspace_bytes": ctypes.c_size_t,
+_RESTYPES = {"mcp_error_string": ctypes.c_char_p, "mcp_fps_workspace_bytes": ctypes.c_size_t, "mcp_fps_lengths_workspace_bytes": ctypes.c_size_t,
+             "mcp_fps_lengths_pruned_workspace_bytes": ctypes.c_size_t, "mcp_fusion_grad_workspace_bytes": ctypes.c_size_t,
              "mcp_cross_grad_workspace_bytes": ctypes.c_size_t, "mcp_cross256_grad_workspace_bytes": ctypes.c_size_t,
              "mcp_pointconv_agg_grad_workspace_bytes": ctypes.c_size_t,
              "mcp_fusion_bn_workspace_bytes": ctypes.c_size_t, "mcp_fusion_bn_grad_workspace_bytes": ctypes.c_size_t,

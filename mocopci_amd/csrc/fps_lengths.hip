@@ -9,12 +9,16 @@
 // them exactly as bitrev_10(k) does; and for n >= 1024, L is 10.  So the L = 10 key, (bitrev_10(k mod 1024), k div 1024), is the
 // reference's order for every length, and a length only decides which points take part.
 //
-// n <= 16384: one 1024-thread workgroup per element; thread t keeps points t, t + 1024, ... and their running distances in
-// registers for the whole call (register slice p = points [1024 p, 1024 p + 1024)), as fps_resident_kernel does.  A thread is one
-// reference thread of the 1024-thread block, so inside a thread ties go to the lowest p.  Points at k >= len start at -INFINITY
-// (never selected); slices that lie wholly beyond the length are skipped by a scalar test, and so are the waves of slice 0 that
-// hold no point, so a short element does less vector work.  n > 16384: a streaming kernel bounded by the length, its running
-// distances in the caller's workspace.
+// Four forms, chosen from the PADDED shape and the workspace size alone (mcp_fps_lengths_form; the host never reads a length):
+//   resident  (n < 1024, or m <= 1 up to n = 16384; everything up to 16384 in the unpruned entry point): one 1024-thread workgroup
+//             per element; thread t keeps points t, t + 1024, ... and their running distances in registers for the whole call
+//             (register slice p = points [1024 p, 1024 p + 1024)), as fps_resident_kernel does.  A thread is one reference thread of
+//             the 1024-thread block, so inside a thread ties go to the lowest p.  Points at k >= len start at -INFINITY (never
+//             selected); slices that lie wholly beyond the length are skipped by a scalar test, and so are the waves of slice 0 that
+//             hold no point, so a short element does less vector work.
+//   spatial   (1024 <= n <= 16384, m > 1) and
+//   tiled     (16384 < n <= 65536 with the tiled workspace): the Morton-sorted, box-pruned kernels of fps_pruned.h under FPS_LEN 1.
+//   streaming (n > 16384 otherwise): a streaming kernel bounded by the length, its running distances in the caller's workspace.
 #include <math.h>
 
 #include "common.h"
@@ -39,7 +43,15 @@ __device__ __forceinline__ void len_emit_empty(int *__restrict__ idxs, float *__
         for (int i = tid; i < m * 3; i += LT) pts[i] = 0.0f;
 }
 
-// optional last step: the coordinates of the selected points (fps_emit_points of fps.hip); every index is below the length
+}  // namespace
+
+// the pruned kernels in their length forms (fps_len_spatial_kernel, fps_len_tiled_kernel); they use the three names above
+#define FPS_LEN 1
+#include "fps_pruned.h"
+
+namespace {
+
+// optional last step: the coordinates of the selected points (fps_emit_points of fps_pruned.h); every index is below the length
 __device__ __forceinline__ void len_emit_points(const float *__restrict__ xyz, const int *idxs, float *__restrict__ pts, int m, int tid) {
     if (!pts) return;
     __syncthreads();
@@ -214,19 +226,41 @@ int launch_resident(int b, int n, int m, const float *xyz, const int *len, int *
 
 size_t stream_workspace_bytes(int b, int n) { return (size_t)b * (size_t)n * sizeof(float); }
 
-int dispatch(int b, int n, int m, const float *xyz, const int *len, int *idx, float *pts, void *ws, size_t ws_bytes, hipStream_t s) {
-    if (n > LEN_RESIDENT_MAX && (!ws || ws_bytes < stream_workspace_bytes(b, n))) return MCP_ERR_UNSUPPORTED;
+// the spatial kernel's points per thread by the padded n (a 1024-thread workgroup sorts 1024 P >= n keys, P >= 2)
+int launch_spatial_len(int b, int n, int m, const float *xyz, const int *len, int *idx, float *pts, hipStream_t s) {
+    if (n <= 2 * LT) return launch_spatial<LT, 2>(b, n, m, 10, xyz, len, idx, pts, s);
+    if (n <= 4 * LT) return launch_spatial<LT, 4>(b, n, m, 10, xyz, len, idx, pts, s);
+    if (n <= 8 * LT) return launch_spatial<LT, 8>(b, n, m, 10, xyz, len, idx, pts, s);
+    return launch_spatial<LT, 16>(b, n, m, 10, xyz, len, idx, pts, s);
+}
+
+// the form the unpruned dispatch takes (resident / streaming), and the one the pruned dispatch takes: pure functions of the padded
+// shape and the workspace size
+int unpruned_form(int b, int n, size_t ws_bytes) {
+    if (n <= LEN_RESIDENT_MAX) return MCP_FPS_LENGTHS_RESIDENT;
+    return ws_bytes >= stream_workspace_bytes(b, n) ? MCP_FPS_LENGTHS_STREAMING : MCP_ERR_UNSUPPORTED;
+}
+
+int pruned_form(int b, int n, int m, size_t ws_bytes) {
+    if (n <= LEN_RESIDENT_MAX) return n >= LT && m > 1 ? MCP_FPS_LENGTHS_SPATIAL : MCP_FPS_LENGTHS_RESIDENT;
+    if (tiled_range(n) && ws_bytes >= tiled_workspace_bytes(b, n)) return MCP_FPS_LENGTHS_TILED;
+    return unpruned_form(b, n, ws_bytes);
+}
+
+int dispatch(int form, int b, int n, int m, const float *xyz, const int *len, int *idx, float *pts, void *ws, hipStream_t s) {
+    if (form < 0 || form > MCP_FPS_LENGTHS_STREAMING) return form;  // MCP_ERR_UNSUPPORTED: nothing is launched
     int rc;
     mcp_prof_begin(MCP_KERNEL_FPS, s);
-    if (n <= LT) rc = launch_resident<1>(b, n, m, xyz, len, idx, pts, s);
+    if (form == MCP_FPS_LENGTHS_SPATIAL) rc = launch_spatial_len(b, n, m, xyz, len, idx, pts, s);
+    else if (form == MCP_FPS_LENGTHS_TILED) rc = launch_tiled(b, n, m, xyz, len, idx, pts, static_cast<char *>(ws), s);
+    else if (form == MCP_FPS_LENGTHS_STREAMING) {
+        hipLaunchKernelGGL(fps_lengths_stream_kernel, dim3(b), dim3(LT), 0, s, n, m, xyz, len, static_cast<float *>(ws), idx, pts);
+        rc = mcp_launch_status();
+    } else if (n <= LT) rc = launch_resident<1>(b, n, m, xyz, len, idx, pts, s);
     else if (n <= 2 * LT) rc = launch_resident<2>(b, n, m, xyz, len, idx, pts, s);
     else if (n <= 4 * LT) rc = launch_resident<4>(b, n, m, xyz, len, idx, pts, s);
     else if (n <= 8 * LT) rc = launch_resident<8>(b, n, m, xyz, len, idx, pts, s);
-    else if (n <= LEN_RESIDENT_MAX) rc = launch_resident<16>(b, n, m, xyz, len, idx, pts, s);
-    else {
-        hipLaunchKernelGGL(fps_lengths_stream_kernel, dim3(b), dim3(LT), 0, s, n, m, xyz, len, static_cast<float *>(ws), idx, pts);
-        rc = mcp_launch_status();
-    }
+    else rc = launch_resident<16>(b, n, m, xyz, len, idx, pts, s);
     mcp_prof_end(MCP_KERNEL_FPS, s);
     return rc;
 }
@@ -238,10 +272,28 @@ MCP_EXPORT size_t mcp_fps_lengths_workspace_bytes(int b, int n, int m) {
     return (b > 0 && n > LEN_RESIDENT_MAX) ? stream_workspace_bytes(b, n) : 0;
 }
 
+MCP_EXPORT size_t mcp_fps_lengths_pruned_workspace_bytes(int b, int n, int m) {
+    return (b > 0 && tiled_range(n)) ? tiled_workspace_bytes(b, n) : mcp_fps_lengths_workspace_bytes(b, n, m);
+}
+
+MCP_EXPORT int mcp_fps_lengths_form(int b, int n, int m, size_t workspace_bytes) {
+    MCP_CHECK_ARGS(b > 0 && n > 0);
+    return pruned_form(b, n, m, workspace_bytes);
+}
+
 MCP_EXPORT int mcp_furthest_point_sampling_lengths(int b, int n, int m, const float *xyz, const int *len, int *idx, float *sampled_xyz,
                                                    void *workspace, size_t workspace_bytes, mcp_stream_t stream) {
     MCP_CHECK_ARGS(b > 0 && n > 0 && xyz && idx);
     if (m <= 0) return MCP_OK;
     if (!len) return mcp_furthest_point_sampling_fresh(b, n, m, xyz, idx, sampled_xyz, workspace, workspace_bytes, stream);
-    return dispatch(b, n, m, xyz, len, idx, sampled_xyz, workspace, workspace_bytes, (hipStream_t)stream);
+    return dispatch(mcp_fps_lengths_form(b, n, m, workspace ? workspace_bytes : 0), b, n, m, xyz, len, idx, sampled_xyz, workspace,
+                    (hipStream_t)stream);
+}
+
+MCP_EXPORT int mcp_furthest_point_sampling_lengths_unpruned(int b, int n, int m, const float *xyz, const int *len, int *idx,
+                                                            float *sampled_xyz, void *workspace, size_t workspace_bytes, mcp_stream_t stream) {
+    MCP_CHECK_ARGS(b > 0 && n > 0 && xyz && idx);
+    if (m <= 0) return MCP_OK;
+    if (!len) return mcp_furthest_point_sampling_fresh(b, n, m, xyz, idx, sampled_xyz, workspace, workspace_bytes, stream);
+    return dispatch(unpruned_form(b, n, workspace ? workspace_bytes : 0), b, n, m, xyz, len, idx, sampled_xyz, workspace, (hipStream_t)stream);
 }

@@ -1339,7 +1339,9 @@ class HipBackend:
             lens = lengths_tensor(lengths, B, N, xyz.device)
             out = torch.empty((B, npoint), dtype=torch.int32, device=xyz.device)
             pts = torch.empty((B, npoint, 3), dtype=torch.float32, device=xyz.device) if with_points else None
-            need = _lib.load().mcp_fps_lengths_workspace_bytes(B, N, npoint)  # the streaming form's running distances (N > 16384), else 0
+            # what the fastest form for this padded shape uses: the tiled kernel's sorted cloud (16384 < N <= 65536), the streaming
+            # form's running distances beyond, 0 up to 16384 (mcp_fps_lengths_form names the form the call then takes)
+            need = _lib.load().mcp_fps_lengths_pruned_workspace_bytes(B, N, npoint)
             ws = torch.empty((need,), dtype=torch.uint8, device=xyz.device) if need else None
             _call("mcp_furthest_point_sampling_lengths", xyz, B, N, npoint, _lib.fptr(xyz), _lib.iptr(lens), _lib.iptr(out),
                   None if pts is None else _lib.fptr(pts), ws.data_ptr() if need else None, need)

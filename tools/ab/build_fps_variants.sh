@@ -45,7 +45,8 @@ mkdir -p $W/new/csrc $W/include2 && cp mocopci_amd/csrc/*.h $W/new/csrc/ && mkdi
 mkdir -p $W/n/m/csrc $W/n/include && cp mocopci_amd/csrc/*.h $W/n/m/csrc/ && cp include/mocopci_hip.h $W/n/include/
 sed -e 's|^typedef mcp_f2 f2;.*|typedef float f2 __attribute__((ext_vector_type(2)));|' \
     -e 's|^__device__ __forceinline__ f2 f2_fma(f2 a, f2 b, f2 c) { return mcp_f2_fma(a, b, c); }|__device__ __forceinline__ f2 f2_fma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }|' \
-    mocopci_amd/csrc/fps.hip > $W/n/m/csrc/fps.hip
+    mocopci_amd/csrc/fps_pruned.h > $W/n/m/csrc/fps_pruned.h   # (the pair type is stated in the header fps.hip shares with fps_lengths.hip)
+cp mocopci_amd/csrc/fps.hip $W/n/m/csrc/fps.hip
 (cd $W/n/m/csrc && /opt/rocm/bin/hipcc $OLDFLAGS -c fps.hip -o fps_new_packed.o 2>/dev/null)
 link libfps_new_packed.so $W/n/m/csrc/fps_new_packed.o
 # D: old source, scalar pairs (today's common.h supplies mcp_f2)
