@@ -2484,12 +2484,16 @@ class HipBackend:
         return grad.run(fused, twin, x, w, b, in_slope)
 
     def mlp2_pack(self, w1, b1, w2, b2):
-        """Operand image of one two-layer MLP for mlp2 (split once; do this once per block)."""
+        """Operand image of one two-layer MLP for mlp2 (split once; do this once per block).  A bias given as None is packed as zeros."""
         hidden, cin = w1.shape
         cout = w2.shape[0]
         n = _lib.load().mcp_mlp2_packed_floats(cin, hidden, cout)
         if n == 0:
             raise RuntimeError(f"mlp2 does not support cin={cin}, hidden={hidden}, cout={cout}")
+        if b1 is None:
+            b1 = torch.zeros((hidden,), dtype=torch.float32, device=w1.device)
+        if b2 is None:
+            b2 = torch.zeros((cout,), dtype=torch.float32, device=w1.device)
         packed = torch.empty((n,), dtype=torch.float32, device=w1.device)
         _call("mcp_mlp2_pack", w1, cin, hidden, cout, _lib.fptr(w1.contiguous()), _lib.fptr(b1.contiguous()), _lib.fptr(w2.contiguous()),
               _lib.fptr(b2.contiguous()), _lib.fptr(packed))

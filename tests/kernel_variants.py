@@ -11,7 +11,12 @@ expected_grad_kernels() names the set of kernels one backward call launches and 
 its points (or point pairs) to workgroups; GRAD_CASES parametrises test_fused_grad_variants_gpu.py, and test_kernel_variants_cpu.py
 checks that they reach every kernel the backward units emit and every edge of their persistent loops.  BN_CASES,
 expected_bn_kernels() and bn_launch_grid() do the same for the train-mode fusion layer (fusion_bn.hip, forward and backward in one
-unit, two grid caps in one call) and parametrise test_fusion_bn_variants_gpu.py.  A plain module, imported by the tests."""
+unit, two grid caps in one call) and parametrise test_fusion_bn_variants_gpu.py.
+
+wgrad_launch() restates the host dispatch of the weight-gradient kernel (linear_grad.hip: tiles-per-wave variant, stages per
+workgroup, idle workgroups, how each operand is staged); WGRAD_CASES parametrises test_linear_grad_edges_gpu.py.
+attention_small_grad_launch() does the same for the three narrow-head attention backward kernels (attention_grad.hip) and
+ATTN_GRAD_COUNTS is the grid of query / key counts test_attention_grad_edges_gpu.py crosses.  A plain module, imported by the tests."""
 
 def _cdiv(a, b):
     return (a + b - 1) // b
@@ -553,3 +558,118 @@ def case_id(c):
     """A readable pytest id: the variant and the shape (the fused cases: their tag first)."""
     shape = ",".join(v if k == "tag" else f"{k}={v}" for k, v in c.items() if k != "op" and v not in (None, False))
     return f"{expected_kernel(**c)}[{shape}]".replace(" ", "")
+
+
+# ---- the weight gradient of a tall per-point Linear (linear_grad.hip): dW = gz^T x, db = column sums of gz.  A workgroup stages
+# 32 rows of both operands, its four waves share the 32 x 32 output tiles, the workgroups' partial results are added by a second kernel ----
+WGRAD_ROWS, WGRAD_WAVES, WGRAD_MAX_WGS = 32, 4, 256       # WG_ROWS, WAVES, MAX_WGS, linear_grad.hip:21
+WGRAD_MAX_N, WGRAD_MAX_TPW = 256, 16                      # supported(), linear_grad.hip:124; the widest instantiation, :166
+WGRAD_LDS_BYTES = 160 * 1024                              # supported(), linear_grad.hip:124; the opt-in, :156
+WGRAD_LDS_DEFAULT = 64 * 1024                             # dynamic LDS a kernel may use without the opt-in of :156
+
+
+def _pad32(v):
+    return (v + 31) & ~31                                            # np, kp: linear_grad.hip:33, :123, :147
+
+
+def wgrad_lds_bytes(n, k):
+    return WGRAD_ROWS * (_pad32(n) + _pad32(k) + 8) * 4              # linear_grad.hip:149 (the same expression in supported(), :124)
+
+
+def wgrad_supported(rows, n, k):
+    """supported(), linear_grad.hip:122-125: what mcp_linear_wgrad_workspace_bytes answers with a non-zero size."""
+    return (rows > 0 and n > 0 and k > 0 and n <= WGRAD_MAX_N and (_pad32(n) // 32) * (_pad32(k) // 32) <= WGRAD_MAX_TPW * WGRAD_WAVES
+            and wgrad_lds_bytes(n, k) <= WGRAD_LDS_BYTES)
+
+
+def wgrad_max_k(n):
+    """The largest k the kernel takes at this n."""
+    return max(k for k in range(1, 4096) if wgrad_supported(1, n, k))
+
+
+def _wgrad_staging(width, stride, offset_floats):
+    """(staged as float4, the reasons it is not): linear_grad.hip:45 -- the width a multiple of 32, the row stride a multiple of 4, the
+    base on a 16-byte boundary (offset_floats: the view's first element, in floats from its 16-byte-aligned storage)."""
+    why = [name for name, bad in (("width", width & 31), ("stride", stride & 3), ("base", (4 * offset_floats) & 15)) if bad]
+    return not why, tuple(why)
+
+
+def wgrad_launch(rows, n, k, gz_stride=None, x_stride=None, gz_offset_floats=0, x_offset_floats=0):
+    """The launch mcp_linear_wgrad makes: tiles-per-wave variant, workgroups, stages per workgroup, workgroups left without a stage,
+    and how each operand is staged.  Strides default to the widths (contiguous operands)."""
+    gs, xs = n if gz_stride is None else gz_stride, k if x_stride is None else x_stride
+    if not wgrad_supported(rows, n, k):                              # linear_grad.hip:141
+        raise ValueError(f"wgrad: rows={rows}, n={n}, k={k} is not built")
+    if gs < n or xs < k:                                             # linear_grad.hip:143
+        raise ValueError("wgrad: a row stride below the width")
+    stages = _cdiv(rows, WGRAD_ROWS)                                 # linear_grad.hip:146
+    wgs = min(stages, WGRAD_MAX_WGS)                                 # wgs_of, linear_grad.hip:126-129
+    per = _cdiv(stages, wgs)                                         # linear_grad.hip:146
+    tiles = (_pad32(n) // 32) * (_pad32(k) // 32)                    # linear_grad.hip:148
+    tpw = _cdiv(tiles, WGRAD_WAVES)
+    variant = next(v for v in (1, 2, 4, 8, 16) if tpw <= v)          # linear_grad.hip:162-166
+    gz_vec, gz_why = _wgrad_staging(n, gs, gz_offset_floats)
+    x_vec, x_why = _wgrad_staging(k, xs, x_offset_floats)
+    return dict(variant=variant, kernel=f"linear_wgrad_kernel<{variant}>", workgroups=wgs, stages=stages, stages_per_wg=per,
+                idle=wgs - _cdiv(stages, per),                       # workgroup b takes stages b per .. (b + 1) per, linear_grad.hip:44
+                tail_rows=rows - (stages - 1) * WGRAD_ROWS,          # live rows of the last stage (the rest are zero-filled, :52, :59)
+                tiles=tiles, tiles_per_wave=[len(range(w, tiles, WGRAD_WAVES)) for w in range(WGRAD_WAVES)],   # wave w: tiles w, w + 4, ..., :70
+                lds_bytes=wgrad_lds_bytes(n, k), gz_vec=gz_vec, gz_why=gz_why, x_vec=x_vec, x_why=x_why)
+
+
+def _wg(tag, rows, n, k, gz=None, x=None, block=None):
+    """gz / x: None (contiguous), or (W, c0): the operand is columns c0 : c0 + width of a (rows, W) tensor whose other columns hold NaN.
+    k = None: the largest k the kernel takes at this n (found by the test through mcp_linear_wgrad_workspace_bytes).
+    block = (N, c0): dW / db are rows c0 : c0 + n of an (N, k) / (N,) pair pre-filled with a sentinel (ops._wgrad's column blocks)."""
+    return dict(op="wgrad", tag=tag, rows=rows, n=n, k=k, gz=gz, x=x, block=block)
+
+
+WGRAD_CASES = [
+    _wg("one-row", 1, 32, 32),                               # one row, one stage, one partial in the reduce
+    _wg("two-stages", 33, 32, 32),                           # two stages, 31 zero-filled rows
+    _wg("256-full-stages", 8192, 64, 32),                    # 256 full stages, no tail
+    _wg("idle-workgroups", 8193, 3, 32),                     # 257 stages: 2 per workgroup, 127 workgroups idle; n < 32
+    _wg("k<32", 2049, 32, 3),                                # element-wise x
+    _wg("padded-tiles", 4099, 40, 67),                       # padded tiles both ways: 2 x 3 tiles, variant 2
+    _wg("variant-2-whole", 4099, 128, 64),                   # 8 tiles
+    _wg("variant-4", 2049, 256, 64),                         # 16 tiles; every thread owns a bias column
+    _wg("variant-8-column-block", 2049, 256, 128, gz=(512, 256), block=(512, 256)),   # 32 tiles; ops._wgrad's second column block
+    _wg("variant-16-uneven", 4099, 64, 536),                 # 34 tiles: waves 0-1 own nine, waves 2-3 eight (the PointConv projection)
+    _wg("variant-16-full", 2049, 256, 256),                  # 64 tiles
+    _wg("gz-base", 2049, 64, 64, gz=(68, 1)),                # gz 4 bytes off a 16-byte boundary at a vector width
+    _wg("x-stride", 2049, 64, 64, x=(66, 0)),                # x with a row stride that is no multiple of 4
+    _wg("gz-stride", 2049, 64, 64, gz=(66, 0)),              # the same two reasons on the other operand
+    _wg("x-base", 2049, 64, 64, x=(68, 1)),
+    _wg("lds-limit", 2049, 32, None),                        # LDS just under the 160 KB opt-in
+]
+
+
+def wgrad_shape(c):
+    """(rows, n, k, gz_stride, x_stride, gz_offset_floats, x_offset_floats) of a case, k = None resolved through the mirror."""
+    k = wgrad_max_k(c["n"]) if c["k"] is None else c["k"]
+    gs, go = (c["n"], 0) if c["gz"] is None else c["gz"]
+    xs, xo = (k, 0) if c["x"] is None else c["x"]
+    return c["rows"], c["n"], k, gs, xs, go, xo
+
+
+def wgrad_case_id(c):
+    return f"{wgrad_launch(*wgrad_shape(c))['kernel']}[{c['tag']},rows={c['rows']},n={c['n']},k={c['k'] or 'max'}]"
+
+
+# ---- the narrow-head attention backward (attention_grad.hip): a wave owns 32 rows of the stationary side (queries in stats and dq,
+# keys in dkv), a workgroup 128, the other side streams through double-buffered LDS stages of 64 rows ----
+ATTN_GRAD_TILE, ATTN_GRAD_WAVES, ATTN_GRAD_KT = 32, 4, 64     # the MFMA tile; WAVES, KT: attention_grad.hip:19
+ATTN_GRAD_BLOCK = ATTN_GRAD_TILE * ATTN_GRAD_WAVES           # rows per workgroup: attention_grad.hip:214, :306, :430, :569
+# one row; a wave's tile -1 / 0 / +1; one stage -1 / 0 / +1 (a second stage that holds one row); two stages -1 / 0 / +1 (the third
+# stage reuses buffer 0; 128 is also a workgroup block -1 / 0 / +1: a second workgroup that holds one row); 193: the fourth stage reuses buffer 1
+ATTN_GRAD_COUNTS = (1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 193)
+
+
+def attention_small_grad_launch(nq, nk):
+    """{kernel: dict(workgroups, last_tile, stages, last_stage)} of one backward call without lengths: `workgroups` along the stationary
+    side (launch_all, attention_grad.hip:569), last_tile the live rows of the last wave tile, `stages` of the streamed side
+    (:242, :357, :494), last_stage the live rows of the last one."""
+    def role(stationary, streamed):
+        return dict(workgroups=_cdiv(stationary, ATTN_GRAD_BLOCK), last_tile=(stationary - 1) % ATTN_GRAD_TILE + 1,
+                    stages=_cdiv(streamed, ATTN_GRAD_KT), last_stage=(streamed - 1) % ATTN_GRAD_KT + 1)
+    return {"attention_stats_kernel": role(nq, nk), "attention_dq_kernel": role(nq, nk), "attention_dkv_kernel": role(nk, nq)}

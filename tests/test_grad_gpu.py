@@ -418,11 +418,13 @@ def test_attention_dropout_kernels_match_the_dense_formulation_under_the_same_ma
     assert torch.equal(o1, o2) and not torch.equal(o1, o3)
 
 
-@pytest.mark.parametrize("shape", [(3, 1000, 256), (7, 33), (4099,)])
+@pytest.mark.parametrize("shape", [(3, 1000, 256), (7, 33), (4099,), (8388608 + 4096,), (8388608 + 4099,)])
 def test_prelu_dropout_kernels_match_torch_under_the_same_mask(shape):
     """mcp_prelu_dropout and its backward (Mlp_T's act + drop under net.train(), mocopci.py:1561-1562): the mask is a counter-based hash
     of (seed, element index), rebuilt here with the same integer arithmetic; output is exact, dz exact, the slope gradient within fp32
-    summation error of float64 and the same bits on every call; kept fraction = 1 - p."""
+    summation error of float64 and the same bits on every call; kept fraction = 1 - p.  The two counts above 2048 * 256 * 16 run the
+    workgroup cap (prelu_dropout.hip: MAX_WGS): a grid-stride loop of more than one round and a reduce over 2048 partials, on the
+    float4 path and, with the odd count, on the scalar one."""
     be = ops.backend()
     p, seed, M = 0.25, 987654321, 0xFFFFFFFF
     z, g = rnd(410, *shape).to(DEV), rnd(411, *shape).to(DEV)

@@ -13,8 +13,14 @@ The train-mode fusion layer (fusion_bn: forward and backward passes in one unit)
 kernel_variants.expected_bn_kernels of at least one entry of BN_CASES (the cases of test_fusion_bn_variants_gpu.py, which hold the unit
 to float64 at its loop edges) or in BN_NOT_LAUNCHED, and BN_EDGES states the edges of its two grid caps on kernel_variants.bn_launch_grid.
 
-Still outside: attention_grad.hip, attention_wide_grad.hip, linear_grad.hip, the MLP backward, emd_grad.hip and
-interp3_grad.hip have no parity cases of this form; tests/test_grad_gpu.py and its neighbours compare them at workload-like shapes."""
+The weight-gradient kernel of the per-point Linear (linear_grad) too: every linear_wgrad_kernel instantiation must be what
+kernel_variants.wgrad_launch names for an entry of WGRAD_CASES (the cases of test_linear_grad_edges_gpu.py), and WGRAD_EDGES states the
+staging forms, stage counts and tile splits the cases must reach.  The narrow-head attention backward (attention_grad) has no variants
+to pick from -- one kernel per head width -- so ATTN_GRAD_EDGES only states which query / key counts
+kernel_variants.ATTN_GRAD_COUNTS must hold, as predicates on kernel_variants.attention_small_grad_launch.
+
+Still outside: attention_wide_grad.hip, emd_grad.hip and interp3_grad.hip have no parity cases of this form; tests/test_grad_gpu.py and
+its neighbours compare them at workload-like shapes."""
 import os
 import re
 import shutil
@@ -469,3 +475,112 @@ def test_every_kernel_of_the_batch_statistics_fusion_layer_has_a_parity_case():
     assert not missing, f"fusion_bn kernels without a parity case in tests/kernel_variants.py BN_CASES: {missing}"
     stale = sorted(covered - wanted)
     assert not stale, f"cases name kernels the library does not build: {stale}"
+
+
+# ---- the weight gradient of the per-point Linear: variants, staging forms, stage counts -----------------------------------------------
+WGRAD_UNITS = ("linear_grad",)
+WGRAD_NOT_LAUNCHED = {}   # every linear_wgrad_kernel instantiation is picked by some tile count; the reduce kernel runs in every call
+
+
+def test_the_wgrad_mirror_follows_the_c_conditions():
+    # supported(), linear_grad.hip:122-125; wgs_of :126-129; the dispatch :145-149, :162-166; the staging forms :45
+    L, ok = kv.wgrad_launch, kv.wgrad_supported
+    assert [L(4096, n, k)["variant"] for n, k in ((32, 32), (64, 64), (64, 65), (128, 64), (128, 65), (256, 128), (256, 129), (256, 256))] == [1, 1, 2, 2, 4, 8, 16, 16]
+    assert L(1, 32, 32)["workgroups"] == 1 and L(8192, 32, 32)["workgroups"] == 256 and L(8193, 32, 32)["stages_per_wg"] == 2
+    assert L(8193, 32, 32)["idle"] == 127 and L(16384, 32, 32)["idle"] == 0 and L(16385, 32, 32)["idle"] == 85     # 513 stages, 3 each: 171 busy
+    assert L(196608, 64, 536)["stages_per_wg"] == 24 and L(196608, 64, 536)["tiles_per_wave"] == [9, 9, 8, 8]
+    assert L(33, 32, 32)["tail_rows"] == 1 and L(64, 32, 32)["tail_rows"] == 32
+    assert not ok(100, 257, 32) and ok(100, 256, 256) and not ok(100, 256, 257) and not ok(0, 32, 32)
+    assert ok(100, 32, 1216) and not ok(100, 32, 1217) and kv.wgrad_max_k(32) == 1216     # the LDS limit: 32 (np + kp + 8) 4 <= 160 KB
+    assert kv.wgrad_max_k(64) == 1024 and kv.wgrad_max_k(256) == 256            # the tile limit: 2 x 32 and 8 x 8 tiles on four waves of 16
+    st = lambda **kw: (lambda r: (r["gz_vec"], r["gz_why"], r["x_vec"], r["x_why"]))(L(4096, 64, 64, **kw))
+    assert st() == (True, (), True, ())
+    assert st(gz_stride=68) == (True, (), True, ()) and st(gz_stride=66) == (False, ("stride",), True, ())
+    assert st(x_offset_floats=4) == (True, (), True, ()) and st(x_stride=68, x_offset_floats=1) == (True, (), False, ("base",))
+    assert L(4096, 3, 32)["gz_why"] == ("width", "stride") and L(4096, 3, 32, gz_stride=4)["gz_why"] == ("width",)
+    for bad in ((100, 512, 32), (100, 32, 1248)):
+        with pytest.raises(ValueError):
+            L(*bad)
+    with pytest.raises(ValueError):
+        L(100, 64, 64, gz_stride=60)
+
+
+WGRAD_EDGES = {
+    **{f"tiles-per-wave variant {v}": (lambda v: lambda c, g: g["variant"] == v)(v) for v in (1, 2, 4, 8, 16)},
+    **{f"{op} staged as float4": (lambda op: lambda c, g: g[f"{op}_vec"])(op) for op in ("gz", "x")},
+    **{f"{op} staged element-wise because of its {why} alone": (lambda op, why: lambda c, g: g[f"{op}_why"] == (why,))(op, why)
+       for op in ("gz", "x") for why in ("width", "stride", "base")},
+    "a single row": lambda c, g: c["rows"] == 1,
+    "a single-stage launch": lambda c, g: g["stages"] == 1,
+    "two stages, the second with one live row": lambda c, g: g["stages"] == 2 and g["tail_rows"] == 1,
+    "exactly 256 full stages": lambda c, g: g["stages"] == kv.WGRAD_MAX_WGS and g["tail_rows"] == kv.WGRAD_ROWS and g["stages_per_wg"] == 1,
+    "two stages per workgroup with idle workgroups": lambda c, g: g["stages_per_wg"] == 2 and g["idle"] > 0,
+    "n below one tile": lambda c, g: c["n"] < 32,
+    "k below one tile": lambda c, g: c["k"] is not None and c["k"] < 32,
+    "padded tiles on both axes": lambda c, g: c["n"] % 32 and c["k"] is not None and c["k"] % 32 and g["tiles"] > 1,
+    "every thread owns a bias column": lambda c, g: c["n"] == 64 * kv.WGRAD_WAVES,
+    "the 16-variant full (64 tiles)": lambda c, g: g["variant"] == 16 and g["tiles"] == 64 and g["tiles_per_wave"] == [16] * 4,
+    "the 16-variant uneven (34 tiles: 9 / 9 / 8 / 8)": lambda c, g: g["variant"] == 16 and g["tiles_per_wave"] == [9, 9, 8, 8],
+    "a column block of a wider gz written into a block of a larger dW / db": lambda c, g: c["block"] is not None and c["gz"] is not None and c["gz"][1] == c["block"][1] > 0,
+    "LDS above the 64 KB default": lambda c, g: g["lds_bytes"] > kv.WGRAD_LDS_DEFAULT,
+    "the largest k at its n: LDS just under the 160 KB opt-in": lambda c, g: c["k"] is None and g["lds_bytes"] + 32 * 32 * 4 > kv.WGRAD_LDS_BYTES >= g["lds_bytes"],
+}
+
+
+def wgrad_cases_reaching(edge):
+    return [kv.wgrad_case_id(c) for c in kv.WGRAD_CASES if WGRAD_EDGES[edge](c, kv.wgrad_launch(*kv.wgrad_shape(c)))]
+
+
+def test_the_wgrad_cases_reach_every_variant_staging_form_and_stage_count():
+    missing = [edge for edge in WGRAD_EDGES if not wgrad_cases_reaching(edge)]
+    assert not missing, missing
+    ids = [kv.wgrad_case_id(c) for c in kv.WGRAD_CASES]
+    assert len(set(ids)) == len(ids)
+    assert all(c["rows"] * (c["n"] + (c["k"] or kv.wgrad_max_k(c["n"]))) <= 4 << 20 for c in kv.WGRAD_CASES)   # small: seconds on the device
+
+
+def test_every_wgrad_kernel_instantiation_has_a_parity_case():
+    emitted = emitted_kernels(WGRAD_UNITS)
+    assert "linear_wgrad_reduce_kernel" in emitted and "linear_wgrad_kernel<16>" in emitted, sorted(emitted)   # the demangling worked
+    wanted = emitted - set(WGRAD_NOT_LAUNCHED) - {"linear_wgrad_reduce_kernel"}
+    covered = {kv.wgrad_launch(*kv.wgrad_shape(c))["kernel"] for c in kv.WGRAD_CASES}
+    missing = sorted(wanted - covered)
+    assert not missing, f"linear_wgrad_kernel instantiations without a case in tests/kernel_variants.py WGRAD_CASES: {missing}"
+    stale = sorted(covered - wanted)
+    assert not stale, f"cases name kernels the library does not build: {stale}"
+
+
+# ---- the narrow-head attention backward: the counts that sit on the kernels' own boundaries ------------------------------------------
+def _attn_edges(role, side):
+    """Edges of one kernel: its stationary side in wave tiles of 32 and workgroup blocks of 128, its streamed side in stages of 64."""
+    T, B = kv.ATTN_GRAD_TILE, kv.ATTN_GRAD_BLOCK
+    R = lambda g: g[role]
+    return {
+        f"{role}: one {side} row": lambda nq, nk, g: R(g)["workgroups"] == 1 and R(g)["last_tile"] == 1 and (nq if side == "query" else nk) == 1,
+        f"{role}: a last wave tile with {T - 1} live rows": lambda nq, nk, g: R(g)["last_tile"] == T - 1,
+        f"{role}: a full single tile": lambda nq, nk, g: R(g)["workgroups"] == 1 and R(g)["last_tile"] == T and (nq if side == "query" else nk) == T,
+        f"{role}: a second wave with one live row": lambda nq, nk, g: (nq if side == "query" else nk) == T + 1,
+        f"{role}: a last workgroup block one row short": lambda nq, nk, g: (nq if side == "query" else nk) == B - 1,
+        f"{role}: one full workgroup block": lambda nq, nk, g: (nq if side == "query" else nk) == B,
+        f"{role}: a second workgroup that holds one row": lambda nq, nk, g: R(g)["workgroups"] == 2 and (nq if side == "query" else nk) == B + 1,
+        f"{role}: one streamed row": lambda nq, nk, g: R(g)["stages"] == 1 and R(g)["last_stage"] == 1,
+        **{f"{role}: one stage with {n} rows": (lambda n: lambda nq, nk, g: R(g)["stages"] == 1 and R(g)["last_stage"] == n)(n) for n in (T - 1, T, T + 1, 2 * T - 1)},
+        **{f"{role}: {s} stages, the last with {n} rows": (lambda s, n: lambda nq, nk, g: R(g)["stages"] == s and R(g)["last_stage"] == n)(s, n)
+           for s, n in ((1, 64), (2, 1), (2, 63), (2, 64), (3, 1), (4, 1))},     # 3 stages: buffer 0 a second time; 4: buffer 1 a second time
+    }
+
+
+ATTN_GRAD_EDGES = {**_attn_edges("attention_stats_kernel", "query"), **_attn_edges("attention_dq_kernel", "query"), **_attn_edges("attention_dkv_kernel", "key")}
+
+
+def test_the_attention_backward_grid_holds_every_boundary_class():
+    """ATTN_GRAD_COUNTS, crossed with itself, puts a count on and on both sides of every boundary of the three kernels."""
+    assert kv.attention_small_grad_launch(129, 193) == {
+        "attention_stats_kernel": dict(workgroups=2, last_tile=1, stages=4, last_stage=1), "attention_dq_kernel": dict(workgroups=2, last_tile=1, stages=4, last_stage=1),
+        "attention_dkv_kernel": dict(workgroups=2, last_tile=1, stages=3, last_stage=1)}
+    assert kv.attention_small_grad_launch(128, 64)["attention_dkv_kernel"] == dict(workgroups=1, last_tile=32, stages=2, last_stage=64)
+    grid = [(nq, nk, kv.attention_small_grad_launch(nq, nk)) for nq in kv.ATTN_GRAD_COUNTS for nk in kv.ATTN_GRAD_COUNTS]
+    missing = [edge for edge, pred in ATTN_GRAD_EDGES.items() if not any(pred(*p) for p in grid)]
+    assert not missing, missing
+    # the counts the issue behind these tests lists, on both sides (the key-stationary kernel streams the queries)
+    assert set(kv.ATTN_GRAD_COUNTS) >= {1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 193}

@@ -20,58 +20,12 @@ import torch
 
 from mocopci_amd import ops
 from tests import kernel_variants as kv
+from tests.dense_reference import BLOCK, C_LINEAR, SELF_ROWS, U, act, linear_ratio, positive_mean_data, two_term  # shared with the backward products
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-U = 2.0 ** -24
-C_LINEAR = 2.0   # linear_kernel, linear_splitk_kernel, linear_narrow_kernel
 C_MLP2 = 2.0     # mlp2_kernel (both layers)
 C_ATTN = 8.0     # attention_small / wide / wide_ksplit
-BLOCK = 32768    # rows per float64 block of the CPU references
-SELF_ROWS = 8192  # rows of the two-term self-check
-
-
-def _trunc16(t):
-    return (t.contiguous().view(torch.int32) & -65536).view(torch.float32)
-
-
-def two_term(t):
-    """fp32 values cut to the first two bf16 pieces of mfma_split.h's exact split (x1 = top 16 bits, x2 = top 16 bits of the rest):
-    what a kernel that dropped the third piece would multiply."""
-    t = t.float()
-    a1 = _trunc16(t)
-    return a1 + _trunc16(t - a1)
-
-
-def act(z, slope):
-    return torch.where(z > 0, z, z * slope)
-
-
-def positive_mean_data(g, rows, k, n):
-    """x ~ N(0.5, 1), W ~ (N(0, 1) + 1) / K, b ~ N(-0.5, 0.1): the output straddles zero, products mostly share a sign."""
-    x = torch.randn(rows, k, generator=g) + 0.5
-    w = (torch.randn(n, k, generator=g) + 1.0) / k
-    b = torch.randn(n, generator=g) * 0.1 - 0.5
-    return x, w, b
-
-
-def linear_ratio(got, x, w, b, slope, res, c=C_LINEAR, operand=lambda t: t):
-    """max over elements of |got - exact| / bound, with exact = act(W x + b) + res in float64 (operands through `operand` first:
-    two_term for the self-check), computed in row blocks."""
-    K = x.shape[1]
-    w64, b64 = operand(w).double(), b.double()
-    wa, ba = w.double().abs(), b.double().abs()
-    worst = 0.0
-    for r0 in range(0, x.shape[0], BLOCK):
-        xb = x[r0:r0 + BLOCK]
-        z = operand(xb).double() @ w64.T + b64
-        y = act(z, slope)
-        bound = math.sqrt(K) * (xb.double().abs() @ wa.T + ba)
-        if res is not None:
-            y = y + res[r0:r0 + BLOCK].double()
-            bound = bound + res[r0:r0 + BLOCK].double().abs()
-        worst = max(worst, ((got[r0:r0 + BLOCK].double() - y).abs() / (c * U * bound)).max().item())
-    return worst
 
 
 # ---- linear_kernel / linear_splitk_kernel ----------------------------------------------------------------------------------
