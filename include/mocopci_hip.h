@@ -453,6 +453,33 @@ int mcp_fusion_bn_backward_lengths(int b, int n, int nb, const float *p1, const 
                                    float *grad_nb, float *grad_weights, float *grad_affine, void *workspace, size_t workspace_bytes,
                                    mcp_stream_t stream);
 
+/* BatchNorm on BATCH statistics of a channels-last tensor, forward and backward, with per-group lengths (csrc/bn_batch.hip): what
+ * nn.BatchNorm1d / 2d in training mode computes when the reference's blocks call it once per sample (mocopci.py:503-506, :554-561).
+ *   x       (G, F, N, C) float32, contiguous, 16-byte aligned: G groups normalised separately, F frames that share a group's length.
+ *   len     (G) device int32, clamped to [0, n] inside the kernels: row (f, i) of group gg is live iff i < len[gg], so the group has
+ *           m = F * len[gg] live rows.  NULL: every row is live.
+ *   gamma, beta (C); mean, var (G, C): the batch mean and the BIASED batch variance; count (G) int32 receives m.
+ *   y       (G, F, N, C) = (x - mean) * (gamma * rstd) + beta on live rows, rstd = 1 / sqrt(var + eps); exact zeros on padded rows.
+ * Backward: grad_x = gamma * rstd * (grad_y - sum(grad_y) / m - xhat * sum(grad_y * xhat) / m) on live rows, xhat = (x - mean) * rstd
+ * formed again from x, mean and var (nothing of size rows x C is kept besides x); exact zeros on padded rows.  grad_gamma, grad_beta
+ * (C): the groups' sums of grad_y * xhat and of grad_y, added in group order.
+ * Statistics: a group's F * N padded rows are cut into mcp_bn_batch_parts(g, f, n, c) chunks -- a pure function of its arguments, never
+ * of the device or of a length -- one workgroup each; the variance comes from the sums of x - s and (x - s)^2 with the shift
+ * s = x[gg,0,0,:] (live whenever any row is), the chunks merged in chunk order in double.  m == 0: mean 0, var 0, y all zero; m == 1:
+ * var 0; every division is by max(m, 1), nothing is NaN or Inf.  Padded rows of x and of grad_y are never read.
+ * No length is read on the host, nothing is allocated, no atomics: every sum runs in a fixed order and two calls give identical bits;
+ * with every len[gg] == n every output is bit-identical to len == NULL.
+ * c in {32, 64, 128, 256}: anything else MCP_ERR_UNSUPPORTED (workspace size 0).  A non-positive dimension, g > 65535, f * n > 2^30, a
+ * NULL pointer (len excepted), a short workspace or a pointer that is not 16-byte aligned (workspace: 8): MCP_ERR_BAD_ARG.  Nothing is
+ * launched on an error.  workspace: mcp_bn_batch_workspace_bytes(g, f, n, c) caller-owned bytes, for either direction. */
+int mcp_bn_batch_parts(int g, int f, int n, int c);
+size_t mcp_bn_batch_workspace_bytes(int g, int f, int n, int c);
+int mcp_bn_batch_forward(int g, int f, int n, int c, const float *x, const int *len, const float *gamma, const float *beta, float eps, float *mean,
+                         float *var, int *count, float *y, void *workspace, size_t workspace_bytes, mcp_stream_t stream);
+int mcp_bn_batch_backward(int g, int f, int n, int c, const float *x, const int *len, const float *gamma, const float *mean, const float *var, float eps,
+                          const float *grad_y, float *grad_x, float *grad_gamma, float *grad_beta, void *workspace, size_t workspace_bytes,
+                          mcp_stream_t stream);
+
 /* Cost-volume cross() after its neighbour searches (pointconv_util.py:750-781, :894-922, :1126-1161):
  * xyz1 (B,N1,3), xyz2 (B,N2,3), points1 (B,N1,D), points2 (B,N2,D) channel-last (16-byte aligned),
  * idx (B,N1,32) int32 into set 2 (16 feature-cosine + 16 xyz neighbours) -> out (B,N1,D) = max over the 32

@@ -77,6 +77,10 @@ SIGNATURES = {
     "mcp_fusion_bn_backward_saved": [_i, _i, _i] + [_p] * 25 + [ctypes.c_size_t, _p],
     "mcp_fusion_bn_forward_lengths": [_i, _i, _i] + [_p] * 11 + [_f] + [_p] * 5 + [ctypes.c_size_t, _p],
     "mcp_fusion_bn_backward_lengths": [_i, _i, _i] + [_p] * 23 + [ctypes.c_size_t, _p],
+    "mcp_bn_batch_parts": [_i, _i, _i, _i],
+    "mcp_bn_batch_workspace_bytes": [_i, _i, _i, _i],
+    "mcp_bn_batch_forward": [_i] * 4 + [_p] * 4 + [_f] + [_p] * 5 + [ctypes.c_size_t, _p],
+    "mcp_bn_batch_backward": [_i] * 4 + [_p] * 5 + [_f] + [_p] * 5 + [ctypes.c_size_t, _p],
     "mcp_cross_packed_floats": [_i],
     "mcp_cross_pack": [_i, _p, _p, _p, _p, _p, _p],
     "mcp_cross_volume": [_i] * 5 + [_p] * 7 + [_i, _p, _p, _p],
@@ -172,6 +176,7 @@ _RESTYPES = {"mcp_error_string": ctypes.c_char_p, "mcp_fps_workspace_bytes": cty
              "mcp_cross_grad_workspace_bytes": ctypes.c_size_t, "mcp_cross256_grad_workspace_bytes": ctypes.c_size_t,
              "mcp_pointconv_agg_grad_workspace_bytes": ctypes.c_size_t,
              "mcp_fusion_bn_workspace_bytes": ctypes.c_size_t, "mcp_fusion_bn_grad_workspace_bytes": ctypes.c_size_t,
+             "mcp_bn_batch_workspace_bytes": ctypes.c_size_t,
              "mcp_ptblock_grad_workspace_bytes": ctypes.c_size_t, "mcp_attention_small_grad_workspace_bytes": ctypes.c_size_t,
              "mcp_attention_wide_grad_workspace_bytes": ctypes.c_size_t,
              "mcp_linear_wgrad_workspace_bytes": ctypes.c_size_t, "mcp_scatter_segments_workspace_bytes": ctypes.c_size_t,

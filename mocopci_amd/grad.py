@@ -155,6 +155,30 @@ def fusion_bn_lengths_twin(G, p1, p2, idx, conv, affine, eps, lengths):
     return out, torch.cat(bn), torch.cat(var), count.to(torch.int32)
 
 
+def bn_batch_lengths_twin(x, weight, bias, eps, lengths):
+    """BatchNorm on batch statistics of x (G,F,N,C) or (G,N,C), each group normalised alone, over a padded batch, as plain
+    differentiable torch: row (f, i) of group g is live iff i < lengths[g] (None: every row), mean and biased variance run over the
+    m = F * lengths[g] live rows (divided by max(m, 1)), y is zero on padded rows.  Padding is replaced by zeros before any sum, so
+    NaN there reaches neither an output nor a gradient.  -> (y, mean (G,C), var (G,C), count (G) int32 = m): what
+    ops.HipBackend.bn_batch returns from csrc/bn_batch.hip."""
+    G, N, C = x.shape[0], x.shape[-2], x.shape[-1]
+    x4 = x.reshape(G, -1, N, C)
+    Fr = x4.shape[1]
+    if lengths is None:
+        live = torch.ones((G, N), dtype=torch.bool, device=x.device)
+    else:
+        live = live_points(lengths.to(x.device), G, N, x.device)
+    w = live.view(G, 1, N, 1)
+    count = Fr * live.sum(dim=1)
+    m = count.clamp(min=1).to(x.dtype).view(G, 1, 1, 1)
+    zero = x.new_zeros(())
+    x4 = torch.where(w, x4, zero)
+    mean = x4.sum(dim=(1, 2), keepdim=True) / m
+    var = torch.where(w, (x4 - mean).square(), zero).sum(dim=(1, 2), keepdim=True) / m
+    y = torch.where(w, (x4 - mean) * (weight * torch.rsqrt(var + eps)) + bias, zero)
+    return y.reshape(x.shape), mean.reshape(G, C), var.reshape(G, C), count.to(torch.int32)
+
+
 def ptblock_twin(G, xyz, q, k, v, idx, wd1, bd1, wd2, bd2, wg1, bg1, wg2, bg2):
     """TransformerBlock.forward after knn and the projections, pointT_layer2.py:64-75."""
     kk, vv = G(k, idx), G(v, idx)

@@ -228,11 +228,19 @@ class MoCoPCI(nn.Module):
         scale, shift = self.derived(("bn", name, eps), fold)
         return torch.addcmul(shift, x, scale)
 
-    def bn_batch(self, x, name, eps):
+    def bn_batch(self, x, name, eps, lengths=None):
         """BatchNorm in TRAINING mode applied x.shape[0] times in sequence: call g normalises x[g] (any shape, channels last) with
         the statistics of x[g] alone and then updates the running statistics, exactly what the reference's per-sample loops
         (`for i, x in enumerate(xs): self.norm1(x)`, mocopci.py:503-506, :554-561) and its three fusion calls do with
-        nn.BatchNorm1d / 2d: biased variance for the normalisation, unbiased for the running estimate, momentum 0.1."""
+        nn.BatchNorm1d / 2d: biased variance for the normalisation, unbiased for the running estimate, momentum 0.1.
+        lengths (forms: ops.lengths_tensor; one entry per group; x is (G,F,N,C) or (G,N,C)): row (f, i) of group g is live iff
+        i < lengths[g].  Group g's statistics run over its m = F * lengths[g] live rows -- what the call on x[g, ..., :lengths[g], :]
+        computes -- on the backend's kernel (ops.HipBackend.bn_batch) or, on a backend without one, the masked torch formulation of
+        the same definition; the result is zero on padded rows.  The running variance moves by each group's own m / (m - 1), formed
+        on the device (1 where m < 2), num_batches_tracked by G.  A group without a live row updates the running estimates like any
+        other, and its statistics (mean 0, var 0) mean nothing: fusion_batch_stats' rule."""
+        if lengths is not None:
+            return self._bn_batch_lengths(x, name, eps, lengths)
         P = self._params()
         G, C = x.shape[0], x.shape[-1]
         flat = x.reshape(G, -1, C)
@@ -250,6 +258,26 @@ class MoCoPCI(nn.Module):
         shape = (G,) + (1,) * (x.dim() - 2) + (C,)
         scale = P[name + ".weight"] * torch.rsqrt(var + eps)
         return (x - mean.reshape(shape)) * scale.reshape(shape) + P[name + ".bias"]
+
+    def _bn_batch_lengths(self, x, name, eps, lengths):
+        """bn_batch over a padded batch (see there)."""
+        P = self._params()
+        be = ops.backend()
+        G = x.shape[0]
+        if x.dim() not in (3, 4):
+            raise ValueError(f"bn_batch(lengths=): x must be (G,F,N,C) or (G,N,C), got {tuple(x.shape)}")
+        if hasattr(be, "bn_batch"):
+            y, mean, var, count = be.bn_batch(x, P[name + ".weight"], P[name + ".bias"], eps, lengths=lengths)
+        else:   # a backend without the kernels (the CPU oracle): the masked torch formulation
+            lens = ops.lengths_tensor(lengths, G, x.shape[-2], x.device)
+            y, mean, var, count = grad.bn_batch_lengths_twin(x, P[name + ".weight"], P[name + ".bias"], eps, lens)
+        with torch.no_grad():
+            rm, rv, m = P[name + ".running_mean"], P[name + ".running_var"], self.BN_MOMENTUM
+            coef, keep = self.ema_coefficients(G, m, x.device)
+            rm.mul_(keep).add_(coef @ mean.detach())
+            rv.mul_(keep).add_(coef @ (var.detach() * self.unbias_factor(count, rows=1).unsqueeze(1)))
+            P[name + ".num_batches_tracked"].add_(G)
+        return y
 
     @staticmethod
     def halves(t):
@@ -269,10 +297,13 @@ class MoCoPCI(nn.Module):
             cache[key] = torch.tensor([m * (1.0 - m) ** (G - 1 - g) for g in range(G)], dtype=torch.float32, device=device)
         return cache[key], (1.0 - m) ** G
 
-    def norm(self, x, name, eps):
+    def norm(self, x, name, eps, lengths=None):
         """The block's BatchNorm on (samples, ..., C): batch statistics per sample in a net.train() training forward, the running
-        statistics otherwise."""
-        return self.bn_batch(x, name, eps) if self._mode is not None else self.bn_eval(x, name, eps)
+        statistics otherwise.  lengths: per-sample lengths of a padded batch for the batch statistics (bn_batch); the eval form is
+        per point and has no use for them."""
+        if self._mode is None:
+            return self.bn_eval(x, name, eps)
+        return self.bn_batch(x, name, eps) if lengths is None else self.bn_batch(x, name, eps, lengths=lengths)
 
     def dropout(self, x, p):
         return F.dropout(x, p, training=True) if self._mode is not None and p > 0.0 else x
@@ -292,21 +323,29 @@ class MoCoPCI(nn.Module):
     SDPA_DROPOUT = True         # net.train() on the GPU: attention dropout drawn inside the attention kernel (this repo's for head widths 8 / 16 / 32 / 64 / 256, the library's fused attention for any other)
     CHECKPOINT_BYTES = 1 << 30  # net.train() forwards: unfused blocks whose intermediates exceed this are recomputed in the backward, in chunks of about this size
 
-    def attend(self, q, kv, heads, scale=None):
+    def attend(self, q, kv, heads, scale=None, query_lengths=None, key_lengths=None):
         """softmax(q k^T scale) v per head; with attention dropout (net.train()) the probabilities are materialised -- 10.7 GB per
         tensor at level 1 of the B = 8, N = 8192 step, so large calls run in chunks of batch elements under
         torch.utils.checkpoint: nothing of size heads x Nq x Nk outlives a chunk, the backward rebuilds one chunk at a time (the
-        dropout masks come back through the generator state the checkpoint restores)."""
+        dropout masks come back through the generator state the checkpoint restores).
+        query_lengths / key_lengths: per-element lengths of a padded batch, handed to the attention kernels (ops.HipBackend.attention)
+        on the two kernel routes -- no dropout, or dropout drawn inside the kernel; the library's fused attention and the explicit
+        dropout form have no length form and raise RuntimeError."""
         p = self._mode[1] if self._mode is not None else 0.0
+        ragged = query_lengths is not None or key_lengths is not None
+        kw = dict(query_lengths=query_lengths, key_lengths=key_lengths) if ragged else {}
         if p <= 0.0:
-            return ops.backend().attention(q, kv, heads, scale=scale)
+            return ops.backend().attention(q, kv, heads, scale=scale, **kw)
         BF, Nq, C = q.shape
         Nk, hd = kv.shape[1], C // heads
         sc = hd ** -0.5 if scale is None else scale
         if q.is_cuda and self.SDPA_DROPOUT and hd in (8, 16, 32, 64, 256):
             # this repo's attention kernels with the mask generated inside (forward and backward regenerate it from one seed drawn
             # from torch's generator); nothing of size heads x Nq x Nk exists
-            return ops.backend().attention(q, kv, heads, scale=sc, dropout_p=p)
+            return ops.backend().attention(q, kv, heads, scale=sc, dropout_p=p, **kw)
+        if ragged:
+            raise RuntimeError("attend: per-element lengths need the attention kernels (no dropout, or head widths 8 / 16 / 32 / 64 / 256 on the "
+                               "GPU); the library's fused attention and the explicit dropout form have no length form")
         if q.is_cuda and self.SDPA_DROPOUT:
             # head widths no kernel is built for: the library's fused attention draws the dropout mask inside the kernel (forward and
             # backward from one counter-based stream seeded by torch's generator): same distribution as softmax -> F.dropout ->
@@ -623,14 +662,22 @@ class MoCoPCI(nn.Module):
             return (wm @ self.W(fc2)).contiguous(), (wm @ self.Bv(fc2) + bm).contiguous()
         return self.derived(("tail", fc2, mapping), fold)
 
-    def cross_frame_att(self, prefix, x, feats=True):
+    def cross_frame_att(self, prefix, x, feats=True, lengths=None):
         """Cross_Frame_Att.forward (mocopci.py:499-522) batched over samples.  x (B,2,N,C) holds the two
         frames' features; the block's attention runs 4 heads of width C and sums over the two frames,
-        so its 4 head slots come out as 4 'frames' (mocopci.py:619-621); the first is dropped."""
+        so its 4 head slots come out as 4 'frames' (mocopci.py:619-621); the first is dropped.
+        lengths (forms: ops.lengths_tensor; one entry per sample, for both frames): points at or beyond a sample's length are
+        padding.  The batch statistics of norm1 (bn_batch) and the attention (queries and keys alike: the flipped partner frame
+        belongs to the same sample) see live points only; everything else in the block is per point.  Padded rows of x must be
+        finite; padded rows of the outputs are unspecified; no live output and, given a zero upstream gradient on padded rows, no
+        parameter gradient depends on a padded value.  On live rows the block gives what it gives for each sample alone, cut to its
+        length."""
         B, Fr, N, C = x.shape
         P = self._params()
         drop = self._mode[0] if self._mode is not None else 0.0
-        xn = self.norm(x, prefix + ".norm1", 1e-5)                                # per sample over its two frames (mocopci.py:505)
+        lens = None if lengths is None else ops.lengths_tensor(lengths, B, N, x.device)
+        akw = {} if lens is None else dict(query_lengths=lens.repeat_interleave(Fr), key_lengths=lens.repeat_interleave(Fr))
+        xn = self.norm(x, prefix + ".norm1", 1e-5, lengths=lens)                  # per sample over its two frames (mocopci.py:505)
         xr = torch.flip(xn, dims=[1])
         a = prefix + ".attn_feats"
         # head slot 0 is the dropped one and nothing after the attention mixes slots: project only heads 1..3
@@ -640,7 +687,7 @@ class MoCoPCI(nn.Module):
             return wq[C:].contiguous(), None if bq is None else bq[C:].contiguous(), sl(wkv), sl(bkv)
         wq, bq, wkv, bkv = self.derived(("cfa_heads", prefix), heads)
         o = self.attend(F.linear(xn, wq, bq).reshape(B * Fr, N, 3 * C), F.linear(xr, wkv, bkv).reshape(B * Fr, N, 6 * C), 3,
-                        scale=C ** -0.5)                                          # (B*2,N,3C): 3 head slots, each C wide
+                        scale=C ** -0.5, **akw)                                   # (B*2,N,3C): 3 head slots, each C wide
         o = self.dropout(self.lin(o.reshape(B, Fr, N, 3, C).sum(dim=1).transpose(1, 2), a + ".proj"), drop)   # (B,3,N,C)
         t = prefix + ".trans_block_2"
         if not feats and drop <= 0.0:  # only the flows are read (MultiFrameEstimatier.forward never uses cross_block3's features)
@@ -764,19 +811,28 @@ class MoCoPCI(nn.Module):
         frames = self.lin(xf, prefix + ".mapping_xyz")                            # (B,3,N,3)
         return xf, frames
 
-    def multi_frame_att_full(self, prefix, x, heads=8):
+    def multi_frame_att_full(self, prefix, x, heads=8, lengths=None):
         """Multi_Frame_Att.forward (mocopci.py:551-575) on all five frames, for a net.train() training forward: BatchNorm with
         each sample's own statistics over its five frames (so the outer two cannot be skipped), attention / projection /
-        MLP dropout and stochastic depth.  x (B,5,N,C) -> (feature frames, flow frames) of the inner three."""
+        MLP dropout and stochastic depth.  x (B,5,N,C) -> (feature frames, flow frames) of the inner three.
+        lengths (forms: ops.lengths_tensor; one entry per sample, for all five frames): points at or beyond a sample's length are
+        padding.  The batch statistics of norm1 and norm2 (bn_batch) and the attention (queries and keys alike: the flipped
+        partner frame belongs to the same sample) see live points only; everything else in the block is per point.  Padded rows of
+        x must be finite; padded rows of the outputs are unspecified; no live output and, given a zero upstream gradient on padded
+        rows, no parameter gradient depends on a padded value.  On live rows the block gives what it gives for each sample alone,
+        cut to its length."""
         B, Fr, N, C = x.shape
         drop = self._mode[0]
-        xn = self.bn_batch(x, prefix + ".norm1", 1e-5)
+        lens = None if lengths is None else ops.lengths_tensor(lengths, B, N, x.device)
+        bkw = {} if lens is None else dict(lengths=lens)
+        akw = {} if lens is None else dict(query_lengths=lens.repeat_interleave(Fr), key_lengths=lens.repeat_interleave(Fr))
+        xn = self.bn_batch(x, prefix + ".norm1", 1e-5, **bkw)
         xr = torch.flip(xn, dims=[1])
         a = prefix + ".attn_feats"
-        o = self.attend(self.lin(xn, a + ".q").reshape(B * Fr, N, C), self.lin(xr, a + ".kv").reshape(B * Fr, N, 2 * C), heads)
+        o = self.attend(self.lin(xn, a + ".q").reshape(B * Fr, N, C), self.lin(xr, a + ".kv").reshape(B * Fr, N, 2 * C), heads, **akw)
         o = self.dropout(self.lin(o.reshape(B, Fr, N, C), a + ".proj"), drop)
         xn = xn + self.drop_path(o)                                               # mocopci.py:559
-        xb = self.bn_batch(xn, prefix + ".norm2", 1e-5)
+        xb = self.bn_batch(xn, prefix + ".norm2", 1e-5, **bkw)
         x = x + self.drop_path(self.mlp_t(prefix + ".mlp", xb, drop=drop))        # mocopci.py:561-563
         xf = self.mlp_t(prefix + ".trans_block", x, drop=drop)
         frames = self.lin(xf, prefix + ".mapping_xyz")
@@ -1009,10 +1065,11 @@ class MoCoPCI(nn.Module):
         return be.fusion_mlp(p1, p2.contiguous(), idx, *wb)
 
     @staticmethod
-    def unbias_factor(count):
-        """m / (m - 1) for m = 64 * count rows (count: the live points of a call, an integer tensor), on count's device; 1 where
-        m < 2 (nothing to unbias: the statistics of a call without a live point mean nothing)."""
-        rows = 64.0 * count.to(torch.float32)
+    def unbias_factor(count, rows=64):
+        """m / (m - 1) for m = rows * count (count: an integer tensor -- the live points of a fusion call, 64 rows each, or with
+        rows=1 the live rows themselves), on count's device; 1 where m < 2 (nothing to unbias: the statistics of a call without a
+        live point mean nothing)."""
+        rows = float(rows) * count.to(torch.float32)
         return torch.where(rows > 1, rows / (rows - 1).clamp(min=1), torch.ones_like(rows))
 
     def fusion_batch_stats(self, p1, p2, idx, calls, lengths=None):

@@ -609,6 +609,8 @@ def lengths_tensor(lengths, batch, limit, device):
         raise RuntimeError(f"lengths: expected one entry per batch element ({batch}), got {host.numel()}")
     if batch and (int(host.min()) < 0 or int(host.max()) > limit):
         raise RuntimeError(f"lengths: every entry must lie in [0, {limit}], got {host.tolist()}")
+    if torch.device(device).type != "cuda":   # the CPU oracle backend's masked formulations: nothing to upload
+        return host.to(torch.int32)
     return host.to(torch.int32).pin_memory().to(device, non_blocking=True)
 
 
@@ -1289,6 +1291,46 @@ class _FusionBNFn(torch.autograd.Function):
         return (None, None, None, None, None, d_p1, d_p2, *pieces, *aff)
 
 
+class _BNBatchFn(torch.autograd.Function):
+    """BatchNorm on batch statistics of x (G,F,N,C), each group alone, with per-group lengths (csrc/bn_batch.hip), forward and
+    backward.  Returns (y, mean, var, count); the last three are non-differentiable by-products for the caller's running-estimate
+    update.  Kept for the backward: x, mean, var and the lengths -- xhat is formed again."""
+
+    @staticmethod
+    def forward(ctx, eps, lens, x, weight, bias):
+        lib = _lib.load()
+        x, weight, bias = x.detach().contiguous(), weight.detach().contiguous(), bias.detach().contiguous()
+        G, Fr, N, C = x.shape
+        dev = x.device
+        mean, var = torch.empty((G, C), dtype=torch.float32, device=dev), torch.empty((G, C), dtype=torch.float32, device=dev)
+        count = torch.empty((G,), dtype=torch.int32, device=dev)
+        y = torch.empty_like(x)
+        need = lib.mcp_bn_batch_workspace_bytes(G, Fr, N, C)
+        ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+        _call("mcp_bn_batch_forward", x, G, Fr, N, C, _lib.fptr(x), None if lens is None else _lib.iptr(lens), _lib.fptr(weight), _lib.fptr(bias), float(eps),
+              _lib.fptr(mean), _lib.fptr(var), _lib.iptr(count), _lib.fptr(y), ws.data_ptr(), need)
+        ctx.eps, ctx.has_lengths = float(eps), lens is not None
+        ctx.save_for_backward(x, weight, mean, var, *(() if lens is None else (lens,)))
+        ctx.mark_non_differentiable(mean, var, count)
+        return y, mean, var, count
+
+    @staticmethod
+    def backward(ctx, grad_y, _gmean, _gvar, _gcount):
+        x, weight, mean, var = ctx.saved_tensors[:4]
+        lens = ctx.saved_tensors[4] if ctx.has_lengths else None
+        lib = _lib.load()
+        G, Fr, N, C = x.shape
+        dev = x.device
+        grad_y = grad_y.contiguous()
+        d_x = torch.empty_like(x)
+        d_gamma, d_beta = torch.empty((C,), dtype=torch.float32, device=dev), torch.empty((C,), dtype=torch.float32, device=dev)
+        need = lib.mcp_bn_batch_workspace_bytes(G, Fr, N, C)
+        ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+        _call("mcp_bn_batch_backward", x, G, Fr, N, C, _lib.fptr(x), None if lens is None else _lib.iptr(lens), _lib.fptr(weight), _lib.fptr(mean),
+              _lib.fptr(var), ctx.eps, _lib.fptr(grad_y), _lib.fptr(d_x), _lib.fptr(d_gamma), _lib.fptr(d_beta), ws.data_ptr(), need)
+        return None, None, d_x, d_gamma, d_beta
+
+
 class _FusionFn(torch.autograd.Function):
     """mcp_fusion with its hand-written backward (mcp_fusion_grad): the layer is re-evaluated inside the backward kernel, the
     neighbour gradients go through the deterministic segmented scatter, weight gradients are fixed-order sums."""
@@ -1740,6 +1782,25 @@ class HipBackend:
                   *[_lib.fptr(t) for t in conv], float(eps), _lib.fptr(bn), _lib.fptr(var), _lib.fptr(out), _lib.iptr(saved[0]), _lib.fptr(saved[1]),
                   _lib.fptr(saved[2]), ws.data_ptr(), need)
         return out, bn, var
+
+    BN_BATCH_CHANNELS = (32, 64, 128, 256)
+
+    def bn_batch(self, x, weight, bias, eps, lengths=None):
+        """BatchNorm on BATCH statistics (net.train()) of x (G,F,N,C) or (G,N,C), channels last: each of the G groups is normalised
+        with its own mean and biased variance (the reference's per-sample loops, mocopci.py:503-506, :554-561), differentiable
+        w.r.t. x, weight and bias (mcp_bn_batch_forward / mcp_bn_batch_backward).  -> (y, mean (G,C), var (G,C), count (G) int32).
+        lengths (forms: lengths_tensor; one entry per group, at most N): row (f, i) of group g is live iff i < lengths[g]; the
+        statistics and the backward's mean terms run over the count[g] = F * lengths[g] live rows, y and the gradient of x are zero
+        on padded rows, whose values are never read.  A group without a live row: mean 0, var 0.  No synchronisation.
+        C outside 32 / 64 / 128 / 256: the masked torch formulation (grad.bn_batch_lengths_twin), same definition."""
+        if x.dim() not in (3, 4):
+            raise ValueError(f"bn_batch: x must be (G,F,N,C) or (G,N,C), got {tuple(x.shape)}")
+        G, N, C = x.shape[0], x.shape[-2], x.shape[-1]
+        lens = lengths_tensor(lengths, G, N, x.device)
+        if C not in self.BN_BATCH_CHANNELS or x.dtype != torch.float32 or x.numel() == 0:
+            return grad.bn_batch_lengths_twin(x, weight, bias, eps, lens)
+        y, mean, var, count = _BNBatchFn.apply(float(eps), lens, x.reshape(G, -1, N, C), weight, bias)
+        return y.reshape(x.shape), mean, var, count
 
     def _fusion_mlp(self, p1, p2, idx, w1, b1, w2, b2, w3, b3):
         p1, p2, w1, b1, w2, b2, w3, b3 = (t.contiguous() for t in (p1, p2, w1, b1, w2, b2, w3, b3))
