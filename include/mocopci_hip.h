@@ -756,6 +756,32 @@ int mcp_pointconv_linear(int b, int n, int s, int d, int k, const float *s_xyz, 
                          const int *idx, const float *w0, const float *b0, const float *w1, const float *b1, const float *w2,
                          const float *b2, const float *packed, int c_out, float slope, float *out, mcp_stream_t stream);
 
+/* PointConv on a padded batch whose elements have their own number of centres: mcp_pointconv_agg, mcp_pointconv_linear and
+ * mcp_pointconv_agg_grad with per-element centre lengths.  Arguments as the dense entry points, plus qlen behind idx: a (B,) int32
+ * DEVICE array that the kernels clamp to [0, s]; the host never reads it (no synchronisation).  qlen == NULL is the dense entry
+ * point: same dispatch, same launch, same bits.
+ *   - Centre i of element bb is live iff i < qlen[bb].
+ *   - Live centres get the dense call's bits; the kernel form is a function of the padded shape alone, as in the dense dispatch.
+ *   - A padded centre has none of its inputs read -- its idx row, new_xyz, the gathered rows, grad_out --, so padding may hold
+ *     anything (NaN, inf, out-of-range indices).  Its output rows are exact zeros: the aggregate; the fused Linear's output row
+ *     (zero, NOT leaky(bias)); grad_new_xyz, grad_gxyz and grad_rows.
+ *   - A padded centre adds nothing to the 176 WeightNet weight gradients: its lanes work on zeros in place of their loads (never on
+ *     padding times a zero gradient), and every sum keeps its fixed order, so full lengths give the dense call's bits.
+ *   - A workgroup (forward) or wave (backward) whose centres are all padded writes its zeros and skips the loads.
+ * The source points (s_xyz, s_points) have no length here: a live centre's idx row names the rows it gathers, and the search that
+ * made it (mcp_knn_lengths, ...) keeps those below the element's reference length. */
+int mcp_pointconv_agg_lengths(int b, int n, int s, int d, int k, const float *s_xyz, const float *new_xyz, const float *s_points,
+                              const int *idx, const int *qlen, const float *w0, const float *b0, const float *w1, const float *b1,
+                              const float *w2, const float *b2, float *out, mcp_stream_t stream);
+int mcp_pointconv_linear_lengths(int b, int n, int s, int d, int k, const float *s_xyz, const float *new_xyz, const float *s_points,
+                                 const int *idx, const int *qlen, const float *w0, const float *b0, const float *w1, const float *b1,
+                                 const float *w2, const float *b2, const float *packed, int c_out, float slope, float *out,
+                                 mcp_stream_t stream);
+int mcp_pointconv_agg_grad_lengths(int b, int n, int s, int d, int k, const float *s_xyz, const float *new_xyz, const float *s_points,
+                                   const int *idx, const int *qlen, const float *w0, const float *b0, const float *w1, const float *b1,
+                                   const float *w2, const float *b2, const float *grad_out, float *grad_new_xyz, float *grad_gxyz,
+                                   float *grad_rows, float *grad_weights, void *workspace, size_t workspace_bytes, mcp_stream_t stream);
+
 /* Multi-head attention with a tiny head dim (8 or 16) in exact fp32, flash style (no (N,N) score tensor):
  * the attention core of InterFrameAttentionInterpretation (mocopci.py:650-667) and CrossAttention (:72-86).
  * q (BF,Nq,*), k/v (BF,Nk,*) are read in place from the projection outputs: element [bf, token, head*hd + d]

@@ -117,6 +117,9 @@ SIGNATURES = {
     "mcp_pointconv_agg_grad_workspace_bytes": [_i, _i],
     "mcp_pointconv_agg_grad": [_i] * 5 + [_p] * 16 + [ctypes.c_size_t, _p],
     "mcp_pointconv_linear": [_i] * 5 + [_p] * 11 + [_i, _f, _p, _p],
+    "mcp_pointconv_agg_lengths": [_i] * 5 + [_p] * 13,
+    "mcp_pointconv_linear_lengths": [_i] * 5 + [_p] * 12 + [_i, _f, _p, _p],
+    "mcp_pointconv_agg_grad_lengths": [_i] * 5 + [_p] * 17 + [ctypes.c_size_t, _p],
     "mcp_attention_small": [_i] * 5 + [_p, _i, _p, _i, _p, _i, _f, _p, _i, _p],
     "mcp_attention_wide": [_i] * 5 + [_p, _i, _p, _i, _p, _i, _f, _p, _i, _p],
     "mcp_attention_small_grad_workspace_bytes": [_i, _i, _i],

@@ -87,6 +87,24 @@ def pointconv_agg_twin(G, s_xyz, new_xyz, s_points, idx, w0, b0, w1, b1, w2, b2)
     return torch.matmul(new_points.transpose(2, 3), w).reshape(B, S, -1)
 
 
+def pointconv_agg_lengths_twin(G, s_xyz, new_xyz, s_points, idx, w0, b0, w1, b1, w2, b2, lengths):
+    """pointconv_agg_twin over a padded batch of centres: centre i of element b is live iff i < lengths[b].  A padded centre's idx row
+    and new_xyz are replaced by 0 before anything is gathered and what was gathered for it by zeros, so NaN or an out-of-range index
+    there reaches neither an output nor a gradient; its row of the aggregate is zero.  What ops.HipBackend.pointconv_agg(
+    centre_lengths=) computes with csrc/pointconv_lengths.hip."""
+    B, S, _ = new_xyz.shape
+    live = live_points(lengths, B, S, new_xyz.device).view(B, S, 1, 1)
+    zero = new_xyz.new_zeros(())
+    idx = torch.where(live.view(B, S, 1), idx, torch.zeros((), dtype=idx.dtype, device=idx.device))
+    centre = torch.where(live.view(B, S, 1), new_xyz, zero)
+    g_xyz = torch.where(live, G(s_xyz, idx) - centre.unsqueeze(2), zero)
+    new_points = torch.cat([g_xyz, torch.where(live, G(s_points, idx), zero)], dim=-1)
+    w = g_xyz
+    for ww, bb in ((w0, b0), (w1, b1), (w2, b2)):
+        w = torch.relu(F.linear(w, ww, bb))
+    return torch.where(live.view(B, S, 1), torch.matmul(new_points.transpose(2, 3), w).reshape(B, S, -1), zero)
+
+
 def cross_twin(G, xyz1, xyz2, points1, points2, idx, wpos, bpos, wmlp, bmlp):
     """cross() after its neighbour searches, pointconv_util.py:765-781 (one mlp layer).  idx: (B,N1,32) or its two halves."""
     idx = whole(idx)
@@ -110,6 +128,15 @@ def fusion_twin(G, p1, p2, idx, w1, b1, w2, b2, w3, b3):
 def live_points(lengths, batch, n, device):
     """(B, N) bool: point p of element b is live iff p < lengths[b] (clamped to [0, n]); lengths: a (B,) integer tensor on `device`."""
     return torch.arange(n, device=device).view(1, n) < lengths.reshape(batch, 1).clamp(0, n)
+
+
+def spread_padded_rows(idx, live, n):
+    """A gather list (B,S,K) whose rows of padded centres (live (B,S) false) may hold anything -> the list a scatter of per-centre
+    gradients may sort: padded centre i names row i mod n in every slot.  Its gradient rows are zeros, so where they land changes no
+    sum; spreading them keeps every destination's segment short (one row for all of them is one serial chain)."""
+    S = idx.shape[1]
+    own = (torch.arange(S, device=idx.device, dtype=idx.dtype) % n).view(1, S, 1)
+    return torch.where(live.unsqueeze(-1), idx, own)
 
 
 def _masked_fusion_inputs(G, p1, p2, idx, live):

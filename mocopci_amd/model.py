@@ -369,33 +369,81 @@ class MoCoPCI(nn.Module):
         return torch.cat([checkpoint(dense, q[i:i + step], kv[i:i + step], use_reentrant=False) for i in range(0, BF, step)], dim=0)
 
     # ---- point-set layers ---------------------------------------------------------------
-    def pointconv(self, prefix, s_xyz, new_xyz, s_points, nsample=32, idx=None, like_rows=None):
+    def pointconv(self, prefix, s_xyz, new_xyz, s_points, nsample=32, idx=None, like_rows=None, centre_lengths=None):
         """PointConv / PointConvD body after sampling (mocopci.py:1315-1346, :1362-1396; group /
         group_query :1218-1266; WeightNet :1289-1300).  idx: the (B,S,nsample) neighbour lists when the caller
         already has them (see sampled_neighbours).  like_rows: the centres are a subset of that many candidate centres which
-        another form of the same forward evaluates all of (see lin): same kernels, same bits."""
+        another form of the same forward evaluates all of (see lin): same kernels, same bits.
+        centre_lengths: (B,) live centres per element of a padded batch (ops.lengths_tensor's forms); the rows of padded centres are
+        zeros in either form, and nothing of them is read (idx must be given: the caller's search knows the reference lengths)."""
         be = ops.backend()
         B, S, _ = new_xyz.shape
         if idx is None:
+            if centre_lengths is not None:
+                raise ValueError("pointconv(centre_lengths=) needs the neighbour lists of the caller's length-aware search")
             idx = be.knn(new_xyz, s_xyz, nsample)
+        kw = {} if centre_lengths is None else dict(centre_lengths=centre_lengths)
         wn = [t for i in range(3) for t in (self.W(f"{prefix}.weightnet.mlp_convs.{i}"), self.Bv(f"{prefix}.weightnet.mlp_convs.{i}"))]
         w, b = self.W(prefix + ".linear"), self.Bv(prefix + ".linear")
         if self.FUSE_POINTCONV and self._live is None and be.pointconv_linear_supported(s_points.shape[-1], w.shape[0], idx.shape[-1],
                                                                                         rows=B * S if like_rows is None else like_rows):
             # levels 0 / 1 and the refinement stage: the (B,S,(3+D)*8) aggregate never leaves the compute unit
             packed = self.derived(("lin_pack", be.name, prefix + ".linear", (w.shape[1],)), lambda: be.pointconv_linear_pack(w, b))
-            return be.pointconv_linear(s_xyz, new_xyz, s_points.contiguous(), idx, *wn, w, b, LEAKY, packed=packed)
-        agg = be.pointconv_agg(s_xyz, new_xyz, s_points.contiguous(), idx, *wn)      # (B,S,(3+D)*8)
-        return self.lin(agg, prefix + ".linear", slope=LEAKY, like_rows=like_rows)
+            return be.pointconv_linear(s_xyz, new_xyz, s_points.contiguous(), idx, *wn, w, b, LEAKY, packed=packed, **kw)
+        agg = be.pointconv_agg(s_xyz, new_xyz, s_points.contiguous(), idx, *wn, **kw)      # (B,S,(3+D)*8)
+        out = self.lin(agg, prefix + ".linear", slope=LEAKY, like_rows=like_rows)
+        if centre_lengths is not None:   # the Linear made leaky(bias) of a padded centre's zero aggregate: zeros, as the one-launch form writes
+            out = torch.where(self.live_rows(centre_lengths, B, S, out.device), out, out.new_zeros(()))
+        return out
 
-    def fps_gather(self, xyz, npoint, return_idx=False):
-        """furthest_point_sample + index_points_gather (mocopci.py:1378-1379)."""
+    @staticmethod
+    def live_rows(lengths, batch, n, device):
+        """(B,n,1) bool: row i of element b is live iff i < lengths[b] (ops.lengths_tensor's forms)."""
+        return grad.live_points(ops.lengths_tensor(lengths, batch, n, device).to(device), batch, n, device).unsqueeze(-1)
+
+    @staticmethod
+    def ragged_lengths(xyz1, lengths1, lengths2):
+        """The per-cloud lengths of a padded pair of frames (B,3,N) as device arrays: (stacked (2B,) = [l1 | l2] for the encoder's
+        stacked frames, (3B,) = [l1 | l1 | l2] for the three warped clouds, l1, l2), or None without lengths.  One length given
+        makes the other full.  Sequences and CPU tensors are validated (one entry per sample, 0 <= len <= N: RuntimeError)."""
+        if lengths1 is None and lengths2 is None:
+            return None
+        B, N, dev = xyz1.shape[0], xyz1.shape[2], xyz1.device
+        full = lambda: torch.full((B,), N, dtype=torch.int32, device=dev)
+        l1 = full() if lengths1 is None else ops.lengths_tensor(lengths1, B, N, dev).to(dev)
+        l2 = full() if lengths2 is None else ops.lengths_tensor(lengths2, B, N, dev).to(dev)
+        return torch.cat([l1, l2]), torch.cat([l1, l1, l2]), l1, l2
+
+    @staticmethod
+    def lengths_key(*lengths):
+        """What a prefetch handle remembers of the lengths it was made under: the values of a sequence / CPU tensor, the identity and
+        version of a device tensor (reading it back would be a synchronisation)."""
+        def one(l):
+            if l is None:
+                return None
+            if torch.is_tensor(l) and l.is_cuda:
+                return ("device", l.data_ptr(), l._version, tuple(l.shape))
+            return tuple(int(v) for v in torch.as_tensor(l).reshape(-1).tolist())
+        return tuple(one(l) for l in lengths)
+
+    def layout(self, xyz1, xyz2, lens=None):
+        """The stacked channel-last layout (2B,N,3) of a pair of frames; with lengths the padded rows are replaced by zeros (one
+        torch.where), so that whatever the padding holds -- NaN -- reaches no per-point layer and no weight gradient."""
+        xyz = torch.cat([xyz1, xyz2], dim=0).transpose(1, 2).contiguous()
+        if lens is None:
+            return xyz
+        return torch.where(self.live_rows(lens[0], xyz.shape[0], xyz.shape[1], xyz.device), xyz, xyz.new_zeros(()))
+
+    def fps_gather(self, xyz, npoint, return_idx=False, lengths=None):
+        """furthest_point_sample + index_points_gather (mocopci.py:1378-1379).  lengths: per-cloud lengths of a padded batch: element
+        b is sampled from xyz[b, :lengths[b]] alone and the sample is full (the sampling keeps selecting when npoint > length)."""
         be = ops.backend()
+        kw = {} if lengths is None else dict(lengths=lengths)
         if xyz.requires_grad and torch.is_grad_enabled():  # training: the gather carries the gradient to the (warped) coordinates
-            sel = be.fps(xyz, npoint)
+            sel = be.fps(xyz, npoint, **kw)
             pts = be.group_rows(xyz, sel)
         else:
-            sel, pts = be.fps(xyz, npoint, with_points=True)          # one launch: the sample and its coordinates
+            sel, pts = be.fps(xyz, npoint, with_points=True, **kw)          # one launch: the sample and its coordinates
         return (pts, sel) if return_idx else pts
 
     @staticmethod
@@ -425,17 +473,19 @@ class MoCoPCI(nn.Module):
             sides[key] = torch.cuda.Stream(device=device)
         return sides[key]
 
-    def issue_inputs_only(self, sched, xyz_fn, after=None):
+    def issue_inputs_only(self, sched, xyz_fn, after=None, lens=None):
         """Everything of a forward that depends on nothing but the inputs, as schedule nodes: the channel-last layout ("xyz"), the four
         FPS levels (mocopci.py:445-463; ("pc", level)), the sampled clouds in the decoder's "other frame" arrangement ("swap_pc") and
         the level-0 self search.  after: see Schedule.run (prefetch() issues these behind the inputs' event, a plain forward behind
-        the caller's stream)."""
+        the caller's stream).  lens: ragged_lengths() of a padded batch: the stacked lengths go to level 1's sampling and to the level-0
+        self search (as query and reference lengths); the sampled levels are full."""
         sched.run("xyz", xyz_fn, after=after)
+        stacked = None if lens is None else lens[0]
         chained = None if after is None else ()   # behind the layout: stream order on the same lane / inline
 
         def level(lvl, npoint):
             src = sched.peek("xyz") if lvl == 1 else sched.peek(("pc", lvl - 1))[0]
-            return self.fps_gather(src, npoint, return_idx=True)        # (points, indices)
+            return self.fps_gather(src, npoint, return_idx=True, lengths=stacked if lvl == 1 else None)        # (points, indices)
         for lvl, npoint in enumerate((2048, 512, 256, 64), start=1):
             sched.run(("pc", lvl), lambda lvl=lvl, npoint=npoint: level(lvl, npoint), after=chained)
 
@@ -445,33 +495,41 @@ class MoCoPCI(nn.Module):
         sched.run("swap_pc", swapped, after=chained)
         # the level-0 self search (0.6 ms with its sorted cloud) on a lane of its own: it neither delays the sampling chain nor waits for it
         xyz = sched.peek("xyz")
-        sched.run("self_search", lambda: ops.backend().knn(xyz, xyz, 32), reads=(xyz,), after=None if after is None else (sched.event("xyz"),))
+        skw = {} if stacked is None else dict(query_lengths=stacked, ref_lengths=stacked)
+        sched.run("self_search", lambda: ops.backend().knn(xyz, xyz, 32, **skw), reads=(xyz,), after=None if after is None else (sched.event("xyz"),))
 
-    def run_encoder(self, xyz, sched=None, speculate=None):
+    def run_encoder(self, xyz, sched=None, speculate=None, lengths=None):
         """PointConvEncoder.forward (mocopci.py:438-468), color == xyz.  The sampling pyramid and the level-0 self search depend only
         on the coordinates: they are schedule nodes, issued here unless the caller already did (prefetch(): they then ran under the
-        PREVIOUS call's tail, and level 1 is not speculated).  A level's cloud is fetched where it is first read."""
+        PREVIOUS call's tail, and level 1 is not speculated).  A level's cloud is fetched where it is first read.
+        lengths: the (2B,) lengths of the stacked padded clouds (rows at or beyond a length must hold zeros: layout()), or what
+        ragged_lengths() returned.  Level 0 is ragged -- its search, its PointConv, level 1's sampling and the all-candidates form of
+        level 1 take the lengths --; every sampled level is full and exactly the pyramid of the cloud alone."""
         p = "encoder."
+        lens = None
+        if lengths is not None:
+            lens = lengths if (isinstance(lengths, tuple) and len(lengths) == 4 and torch.is_tensor(lengths[0])) else (ops.lengths_tensor(lengths, xyz.shape[0], xyz.shape[1], xyz.device).to(xyz.device),)
+        stacked = None if lens is None else lens[0]
         standalone = sched is None   # the encoder alone (tests compare its pyramid / features): none of the decoder's early nodes
         if standalone:
             sched = Schedule(self, xyz.device)
         if speculate is None:
             speculate = self._live is None and not sched.has("xyz") and sched.lane(("pc", 1)) is not None   # inference only
         if not sched.has("xyz"):
-            self.issue_inputs_only(sched, lambda: xyz)
+            self.issue_inputs_only(sched, lambda: xyz, lens=lens)
         pc = lambda lvl: sched.get(("pc", lvl))[0]
 
         self._mark("enc start")
         f0 = self.conv1d_block(xyz, p + "level0_lift")
         idx0 = sched.get("self_search")
-        f0 = self.pointconv(p + "level0", xyz, xyz, f0, idx=idx0)
+        f0 = self.pointconv(p + "level0", xyz, xyz, f0, idx=idx0, centre_lengths=stacked)
         f0_1 = self.conv1d_block(f0, p + "level0_1")
         if speculate:
             # The main stream would now wait ~0.6 ms for the level-1 sampling.  Level 1 is a PointConvD whose centres are
             # SAMPLED points of xyz and whose neighbours are rows of the level-0 self search (sampled_neighbours), so its
             # output for every candidate centre can be computed before the sample is known -- 4x the work, on an otherwise
             # idle chip -- and the sampled rows gathered afterwards (same per-row arithmetic, same kernels: lin(like_rows=)).
-            f1_all = self.conv1d_block(self.pointconv(p + "level1", xyz, xyz, f0_1, idx=idx0), p + "level1_0")
+            f1_all = self.conv1d_block(self.pointconv(p + "level1", xyz, xyz, f0_1, idx=idx0, centre_lengths=stacked), p + "level1_0")
             pc1, sel1 = sched.get(("pc", 1))
             f1 = ops.backend().group_rows(f1_all, sel1)
         else:
@@ -1186,24 +1244,29 @@ class MoCoPCI(nn.Module):
         return torch.cat(outs, dim=0)
 
     # ---- decoder ------------------------------------------------------------------------
-    def run_decoder(self, pcs, feats, B, train=False):
+    def run_decoder(self, pcs, feats, B, train=False, lens=None):
         """_decoder run to completion (no deferred tail)."""
-        gen = self._decoder(pcs, feats, B, train=train)
+        gen = self._decoder(pcs, feats, B, train=train, lens=lens)
         try:
             next(gen)
         except StopIteration as stop:
             return stop.value
         raise RuntimeError("decoder yielded without defer")
 
-    def _decoder(self, pcs, feats, B, train=False, defer=False):
+    def _decoder(self, pcs, feats, B, train=False, defer=False, lens=None):
         """MultiFrameEstimatier.forward (mocopci.py:821-1059) as a generator: with defer=True it yields ONCE, right after the
         refinement stage's furthest point sampling has been launched on its side stream -- the caller may enqueue other work on
         this stream there (begin() / finish(): the next batch's encoder and decoder) -- and finishes when resumed; without defer it
         never yields.  The result is the generator's return value.  pcs/feats hold both frames stacked on
         the batch axis (frame 1 = [:B], frame 2 = [B:]).  Returns out_lst: 3 x (B,N,3); with train=True
         (flows_lst_f, flows_lst_b, out_lst) as the reference does (mocopci.py:1056-1059), every (direction, frame) flow of every
-        level being computed then (the training loss reads them all)."""
+        level being computed then (the training loss reads them all).
+        lens: ragged_lengths() of a padded batch.  Only level 0 is ragged: the warped clouds have the lengths [l1 | l1 | l2], which go
+        to the refinement stage's sampling, the warped self search, the all-candidates PointConvD and fusion(lengths=); the output
+        frames are zero on padded rows, and with train=True so are the level-0 flows (the two mixed entries below min(l1, l2))."""
         m = "multi_frame_inference."
+        lens3 = None if lens is None else lens[1]
+        kw3 = {} if lens3 is None else dict(query_lengths=lens3, ref_lengths=lens3)
         dev = pcs[0].device
         sw = lambda t: torch.roll(t, B, 0) if t.requires_grad else torch.cat([t[B:], t[:B]], dim=0)   # swap the two frames (training graph: a roll, see run_encoder)
         sched = self._sched
@@ -1365,10 +1428,10 @@ class MoCoPCI(nn.Module):
         sched.run("wf", lambda: self.conv1d_block(f0 + up_flow @ self.area_matrix(3, f0.shape[-1], dev), m + "rlevel0"), reads=(f0,))
         # the refinement stage's sampling: a 1.2-1.4 ms latency chain on 24 CUs
         if train:   # the index chain alone goes to the lane (no gradient); the gather that carries the gradient to `warped` stays here
-            sched.run("refine_fps", lambda: ops.backend().fps(warped.detach(), 2048))
+            sched.run("refine_fps", lambda: ops.backend().fps(warped.detach(), 2048, **({} if lens3 is None else dict(lengths=lens3))))
         else:
-            sched.run("refine_fps", lambda: self.fps_gather(warped, 2048, return_idx=True))
-        idx_self = ops.backend().knn(warped, warped, 32)      # fusion's self search: independent of the refine branch
+            sched.run("refine_fps", lambda: self.fps_gather(warped, 2048, return_idx=True, lengths=lens3))
+        idx_self = ops.backend().knn(warped, warped, 32, **kw3)      # fusion's self search: independent of the refine branch
         be = ops.backend()
         like = warped.shape[0] * warped.shape[1]   # kernels as for every candidate centre (what the speculative form computes): same bits
         if defer and sched.lane("refine_fps") is not None:
@@ -1388,7 +1451,7 @@ class MoCoPCI(nn.Module):
             # same speculation as in the encoder: PointConvD of EVERY candidate centre and the Point-Transformer's four
             # per-point projections are computed while the sampling runs, the sampled rows are gathered afterwards
             t = m + "shape1"
-            dfeat_all = self.pointconv(m + "level1", warped, warped, sched.get("wf"), idx=idx_self)
+            dfeat_all = self.pointconv(m + "level1", warped, warped, sched.get("wf"), idx=idx_self, centre_lengths=lens3)
             qkv_all = self.qkv_projection(t, dfeat_all)                           # (3B,N,192)
             self._mark("refine speculation done (before FPS wait)")
             down, sel = sched.get("refine_fps")
@@ -1410,7 +1473,7 @@ class MoCoPCI(nn.Module):
         self._mark("ptblock + interp done")
         refine = self.pred_head(upf, m + "pred")                                   # (3B,N,3): Linear, ReLU, Linear
         self._mark("refine coords done")
-        final = self.fusion(warped, refine, idx_self=idx_self, calls=3)
+        final = self.fusion(warped, refine, idx_self=idx_self, calls=3, lengths=lens3)
         self._mark("fusion done")
         out_lst = list(final.split(B))
         if not train:
@@ -1421,12 +1484,20 @@ class MoCoPCI(nn.Module):
         lv = {1: lv1, 2: per(frame2s), 3: per(frame3s)}                            # direction 0 forward, 1 backward
         flows_f = [[p1[0] + up_f[i] for i in range(3)], [p1[0] + up_b[2 - i] for i in range(3)]]
         flows_b = [[p2[0] + up_b[i] for i in range(3)], [p2[0] + up_f[2 - i] for i in range(3)]]
+        if lens is not None:
+            # level 0 is ragged: a flow is live where its frame is; the mixed entries (mocopci.py:1014-1015: one frame's rows added to
+            # flows sampled at the other frame's points) are reproduced as they are and are live below min(l1, l2)
+            N0, zero = p1[0].shape[1], p1[0].new_zeros(())
+            live = lambda l: self.live_rows(l, B, N0, dev)
+            both = torch.minimum(lens[2], lens[3])
+            flows_f = [[torch.where(live(lens[2]), f, zero) for f in flows_f[0]], [torch.where(live(both), f, zero) for f in flows_f[1]]]
+            flows_b = [[torch.where(live(lens[3]), f, zero) for f in flows_b[0]], [torch.where(live(both), f, zero) for f in flows_b[1]]]
         for l in (1, 2, 3):
             flows_f.append([p1[l] + lv[l][0][i] for i in range(3)])
             flows_b.append([p2[l] + lv[l][1][2 - i] for i in range(3)])
         return flows_f, flows_b, out_lst
 
-    def prefetch(self, xyz1, xyz2, inputs_ready=None):
+    def prefetch(self, xyz1, xyz2, inputs_ready=None, lengths1=None, lengths2=None):
         """Issue NOW everything of an inference forward on (xyz1, xyz2) that depends on nothing but the inputs -- the channel-last
         layout, the encoder's furthest-point-sampling pyramid (a ~2.5 ms chain of latency-bound kernels on 16 CUs) and the level-0
         self search -- on side lanes (issue_inputs_only), and return a handle for forward(..., prefetched=handle).  A serving loop
@@ -1435,8 +1506,10 @@ class MoCoPCI(nn.Module):
         event after which the inputs are complete (a loader's copy-stream event); without it the work is ordered behind the current
         stream.  The inputs must stay unmodified until the consuming forward has run: an in-place refill of the same buffers (copy_, any
         in-place op) is detected through the tensors' version counters and the handle is then refused; writes through raw pointers
-        are not seen.  Returns None on backends without streams."""
+        are not seen.  lengths1 / lengths2: as in forward(); the handle records them, and a forward under other lengths refuses it.
+        Returns None on backends without streams."""
         dev = xyz1.device
+        lens = self.ragged_lengths(xyz1, lengths1, lengths2)
         sched = Schedule(self, dev)
         if sched.lane("xyz") is None:
             return None
@@ -1446,11 +1519,11 @@ class MoCoPCI(nn.Module):
             inputs_ready.record(main)
         scope = {}
         with torch.no_grad(), ops.backend().cloud_scope(scope):
-            self.issue_inputs_only(sched, lambda: torch.cat([xyz1, xyz2], dim=0).transpose(1, 2).contiguous(), after=(inputs_ready,))
-        return {"inputs": (xyz1.data_ptr(), xyz2.data_ptr(), tuple(xyz1.shape)), "versions": (xyz1._version, xyz2._version),
+            self.issue_inputs_only(sched, lambda: self.layout(xyz1, xyz2, lens), after=(inputs_ready,), lens=lens)
+        return {"lengths": self.lengths_key(lengths1, lengths2), "lens": lens, "inputs": (xyz1.data_ptr(), xyz2.data_ptr(), tuple(xyz1.shape)), "versions": (xyz1._version, xyz2._version),
                 "stream": main.stream_id, "sched": sched, "scope": scope}
 
-    def begin(self, xyz1, xyz2, prefetched=None, then_prefetch=None, inputs_ready=None):
+    def begin(self, xyz1, xyz2, prefetched=None, then_prefetch=None, inputs_ready=None, lengths1=None, lengths2=None):
         """First part of an inference forward, for a loop that keeps two batches in flight (software pipelining of consecutive
         batches on ONE stream): everything up to and including the launch of the refinement stage's furthest point sampling
         (encoder, decoder levels 3..1, warped clouds, their self search).  Returns a handle; finish(handle) enqueues the rest
@@ -1465,15 +1538,15 @@ class MoCoPCI(nn.Module):
         be = ops.backend()
         h = prefetched
         if h is None and inputs_ready is not None:
-            h = self.prefetch(xyz1, xyz2, inputs_ready)
+            h = self.prefetch(xyz1, xyz2, inputs_ready, lengths1=lengths1, lengths2=lengths2)
         scope = {} if h is None else h["scope"]
         with torch.no_grad(), be.cloud_scope(scope):
-            xyz, sched = self._consume_prefetched(h, xyz1, xyz2)
+            xyz, sched, lens = self._consume_prefetched(h, xyz1, xyz2, lengths1, lengths2)
             self._sched = sched
-            pcs, feats = self.run_encoder(xyz, sched)
+            pcs, feats = self.run_encoder(xyz, sched, lengths=lens)
             if then_prefetch is not None:
-                self._next = self.prefetch(*then_prefetch)
-            gen = self._decoder(pcs, feats, B, defer=True)
+                self._next = self._prefetch_next(then_prefetch)
+            gen = self._decoder(pcs, feats, B, defer=True, lens=lens)
             try:
                 reads = next(gen)
                 out = None
@@ -1517,10 +1590,17 @@ class MoCoPCI(nn.Module):
                 t.record_stream(cur)
         return out
 
-    def _consume_prefetched(self, h, xyz1, xyz2):
-        """(xyz, schedule) of a forward: from the prefetch handle (the stream waits for its layout), or laid out here."""
+    def _prefetch_next(self, then_prefetch):
+        """prefetch() of forward(then_prefetch=...): (xyz1, xyz2[, ready event]) or a dict of prefetch()'s arguments (for lengths)."""
+        return self.prefetch(**then_prefetch) if isinstance(then_prefetch, dict) else self.prefetch(*then_prefetch)
+
+    def _consume_prefetched(self, h, xyz1, xyz2, lengths1=None, lengths2=None):
+        """(xyz, schedule, ragged_lengths) of a forward: from the prefetch handle (the stream waits for its layout), or laid out here."""
         if h is None:
-            return torch.cat([xyz1, xyz2], dim=0).transpose(1, 2).contiguous(), Schedule(self, xyz1.device)
+            lens = self.ragged_lengths(xyz1, lengths1, lengths2)
+            return self.layout(xyz1, xyz2, lens), Schedule(self, xyz1.device), lens
+        if h["lengths"] != self.lengths_key(lengths1, lengths2):
+            raise RuntimeError("prefetched handle was made under other lengths")
         main = torch.cuda.current_stream(xyz1.device)
         if h["inputs"] != (xyz1.data_ptr(), xyz2.data_ptr(), tuple(xyz1.shape)) or h["stream"] != main.stream_id:
             raise RuntimeError("prefetched handle belongs to other inputs or another stream")
@@ -1528,14 +1608,15 @@ class MoCoPCI(nn.Module):
             # a loader refilled the buffers in place (copy_ / in-place ops) after prefetch() laid them out: the handle holds the OLD
             # contents.  (Writes through raw pointers are invisible to the version counters and remain the caller's responsibility.)
             raise RuntimeError("the inputs were modified in place after prefetch(): prefetch them again")
-        return h["sched"].get("xyz"), h["sched"]
+        return h["sched"].get("xyz"), h["sched"], h["lens"]
 
     def take_prefetched(self):
         """The handle forward(then_prefetch=...) produced (None if it did not); hands it over once."""
         h, self._next = self.__dict__.get("_next"), None
         return h
 
-    def forward(self, xyz1, xyz2, gt=None, t=None, train=False, inputs_ready=None, prefetched=None, then_prefetch=None):
+    def forward(self, xyz1, xyz2, gt=None, t=None, train=False, inputs_ready=None, prefetched=None, then_prefetch=None, lengths1=None,
+                lengths2=None, gt_lengths=None):
         """MoCoPCI.forward (mocopci.py:1069-1097): xyz1, xyz2 (B,3,N) -> out_lst, 3 x (B,N,3).
         train=True: (frames_lst_f, frames_lst_b, gt_frame, out_lst) as the reference returns, computed with autograd enabled so
         that train.py:135-160's loss can be back-propagated: gradients reach every parameter through the fused kernels
@@ -1551,20 +1632,29 @@ class MoCoPCI(nn.Module):
         THAT event instead of behind the caller's whole stream, so in a loop of forwards it overlaps the previous call's tail.
         prefetched: the handle of an earlier prefetch(xyz1, xyz2) -- that work is then not issued again.
         then_prefetch: (next_xyz1, next_xyz2[, ready event]) -- once this call's encoder is enqueued, prefetch() the NEXT batch, so
-        its sampling chains run under this call's decoder; the handle is collected with take_prefetched()."""
+        its sampling chains run under this call's decoder; the handle is collected with take_prefetched().
+        lengths1 / lengths2 (forms: ops.lengths_tensor; one given makes the other full): the batch is padded, sample b of frame f is
+        the cloud xyz_f[b, :, :lengths_f[b]] alone and the rest of its columns may hold anything (NaN).  Rows < l1[b] of out_lst[0]
+        and out_lst[1] and rows < l2[b] of out_lst[2] are the sample's frames, padded rows are exact zeros, and in eval mode no bit
+        of sample b depends on another sample's content or length.  Only level 0 is ragged (run_encoder, _decoder); with train=True
+        the level-0 flows are masked the same way, and gt_lengths -- three (B,) lengths -- reaches the ground truth's sampling.
+        Below 32 live points a cloud's neighbour lists repeat its last live entry (mcp_knn_lengths) -- equality with the cloud alone
+        is claimed from 32 points up --, and an empty cloud gives zero rows and disturbs no other sample.  Without lengths: the
+        launches and bits of before."""
         B = xyz1.shape[0]
         self._check_cache()
         if not train:
             h = prefetched
             if h is None and inputs_ready is not None:
-                h = self.prefetch(xyz1, xyz2, inputs_ready)
+                h = self.prefetch(xyz1, xyz2, inputs_ready, lengths1=lengths1, lengths2=lengths2)
             with torch.no_grad(), ops.backend().cloud_scope(None if h is None else h["scope"]):
-                xyz, self._sched = self._consume_prefetched(h, xyz1, xyz2)
-                pcs, feats = self.run_encoder(xyz, self._sched)
+                xyz, self._sched, lens = self._consume_prefetched(h, xyz1, xyz2, lengths1, lengths2)
+                pcs, feats = self.run_encoder(xyz, self._sched, lengths=lens)
                 if then_prefetch is not None:
-                    self._next = self.prefetch(*then_prefetch)
-                return self.run_decoder(pcs, feats, B)
-        xyz = torch.cat([xyz1, xyz2], dim=0).transpose(1, 2).contiguous()
+                    self._next = self._prefetch_next(then_prefetch)
+                return self.run_decoder(pcs, feats, B, lens=lens)
+        lens = self.ragged_lengths(xyz1, lengths1, lengths2)
+        xyz = self.layout(xyz1, xyz2, lens)
         self._live = {**dict(self.named_parameters()), **dict(self.named_buffers())}
         self._mode = (float(self.drop_rate), float(self.attn_drop_rate), float(self.drop_path_rate)) if self.training else None
         self._train_lane0 = self.TRAIN_PYRAMID_LANE and not (xyz1.requires_grad or xyz2.requires_grad)
@@ -1578,12 +1668,18 @@ class MoCoPCI(nn.Module):
                     # of the N/4 sample (bit for bit), and the frames are independent clouds: one launch instead of nine.  It reads the
                     # ground truth only and carries no gradient: a schedule node on a lane of its own (a 1.2 ms latency chain on 24 CUs
                     # that used to run after the decoder, on the critical path), fetched where the lists are assembled below
+                    gl = None
+                    if gt_lengths is not None:
+                        if len(gt_lengths) != len(gt):
+                            raise RuntimeError(f"gt_lengths: expected {len(gt)} (B,) lengths, got {len(gt_lengths)}")
+                        gl = torch.cat([ops.lengths_tensor(l, g.shape[0], g.shape[2], xyz.device).to(xyz.device) for l, g in zip(gt_lengths, gt)])
+
                     def gt_down():
                         with torch.no_grad():
-                            return self.fps_gather(torch.cat([g.transpose(1, 2) for g in gt], dim=0).contiguous(), N // 4)
+                            return self.fps_gather(torch.cat([g.transpose(1, 2) for g in gt], dim=0).contiguous(), N // 4, lengths=gl)
                     self._sched.run("gt_down", gt_down)
-                pcs, feats = self.run_encoder(xyz, self._sched)
-                flows_f, flows_b, out_lst = self.run_decoder(pcs, feats, B, train=True)
+                pcs, feats = self.run_encoder(xyz, self._sched, lengths=lens)
+                flows_f, flows_b, out_lst = self.run_decoder(pcs, feats, B, train=True, lens=lens)
                 pts = self._sched.get("gt_down") if gt is not None else None
         finally:
             self._live = None

@@ -197,17 +197,18 @@ def _group_rows_grad(grad_out, idx, n, segments=None):
 
 class _PointConvAggFn(torch.autograd.Function):
     """mcp_pointconv_agg with its hand-written backward (mcp_pointconv_agg_grad): WeightNet recomputed per (centre, neighbour) pair in
-    the backward kernel, per-neighbour gradients through the deterministic segmented scatter, weight gradients fixed-order sums."""
+    the backward kernel, per-neighbour gradients through the deterministic segmented scatter, weight gradients fixed-order sums.
+    qlen: (B,) int32 device tensor or None -- per-element centre lengths (the *_lengths entries), carried to the backward."""
 
     @staticmethod
-    def forward(ctx, be, idx, s_xyz, new_xyz, s_points, w0, b0, w1, b1, w2, b2):
+    def forward(ctx, be, idx, s_xyz, new_xyz, s_points, w0, b0, w1, b1, w2, b2, qlen):
         args = [t.detach().contiguous() for t in (s_xyz, new_xyz, s_points, w0, b0, w1, b1, w2, b2)]
-        ctx.save_for_backward(idx, *args)
-        return be._pointconv_agg(*args[:3], idx, *args[3:])
+        ctx.save_for_backward(idx, *args, qlen)
+        return be._pointconv_agg(*args[:3], idx, *args[3:], qlen=qlen)
 
     @staticmethod
     def backward(ctx, grad_out):
-        idx, s_xyz, new_xyz, s_points, w0, b0, w1, b1, w2, b2 = ctx.saved_tensors
+        idx, s_xyz, new_xyz, s_points, w0, b0, w1, b1, w2, b2, qlen = ctx.saved_tensors
         B, N, D = s_points.shape
         S = new_xyz.shape[1]
         lib, dev = _lib.load(), s_points.device
@@ -218,11 +219,18 @@ class _PointConvAggFn(torch.autograd.Function):
         d_w = torch.empty((lib.mcp_pointconv_agg_grad_floats(),), dtype=torch.float32, device=dev)
         need = lib.mcp_pointconv_agg_grad_workspace_bytes(B, S)
         ws = torch.empty((need,), dtype=torch.uint8, device=dev)
-        _call("mcp_pointconv_agg_grad", s_points, B, N, S, D, 32, _lib.fptr(s_xyz), _lib.fptr(new_xyz), _lib.fptr(s_points), _lib.iptr(idx),
+        entry, lens = ("mcp_pointconv_agg_grad", ()) if qlen is None else ("mcp_pointconv_agg_grad_lengths", (_lib.iptr(qlen),))
+        _call(entry, s_points, B, N, S, D, 32, _lib.fptr(s_xyz), _lib.fptr(new_xyz), _lib.fptr(s_points), _lib.iptr(idx), *lens,
               _lib.fptr(w0), _lib.fptr(b0), _lib.fptr(w1), _lib.fptr(b1), _lib.fptr(w2), _lib.fptr(b2), _lib.fptr(grad_out), _lib.fptr(d_new),
               _lib.fptr(d_gxyz), _lib.fptr(d_rows), _lib.fptr(d_w), ws.data_ptr(), need)
         d_sxyz = d_spoints = None
         if ctx.needs_input_grad[2] or ctx.needs_input_grad[4]:
+            if qlen is not None:
+                # The rows of padded centres came back as zeros; their idx rows -- which may hold anything -- are replaced before the
+                # scatter sorts them: padded centre i names source row i mod N in every slot (grad.spread_padded_rows).  (All of them
+                # on row 0 -- what grad._masked_fusion_inputs does -- leaves ONE thread of the segmented reduction with every padded
+                # entry: the backward of a half-padded 16 x 8192 batch took 111 times the dense call's time.)
+                idx = grad.spread_padded_rows(idx, grad.live_points(qlen, B, S, dev), N)
             segments = _scatter_segments(idx, N)
             if ctx.needs_input_grad[2]:
                 d_sxyz = _group_rows_grad(d_gxyz, idx, N, segments)
@@ -232,7 +240,7 @@ class _PointConvAggFn(torch.autograd.Function):
         for t in (w0, b0, w1, b1, w2, b2):
             pieces.append(d_w[at:at + t.numel()].view(t.shape))
             at += t.numel()
-        return (None, None, d_sxyz, d_new, d_spoints, *pieces)
+        return (None, None, d_sxyz, d_new, d_spoints, *pieces, None)   # (no gradient for the lengths)
 
 
 class _CrossFn(torch.autograd.Function):
@@ -2253,21 +2261,39 @@ class HipBackend:
               _lib.fptr(packed), _lib.fptr(out))
         return out
 
-    def pointconv_agg(self, s_xyz, new_xyz, s_points, idx, w0, b0, w1, b1, w2, b2):
-        """PointConv grouping + WeightNet + aggregation (mocopci.py:1330-1335): -> (B,S,(3+D)*8).  Differentiable."""
+    def pointconv_agg(self, s_xyz, new_xyz, s_points, idx, w0, b0, w1, b1, w2, b2, centre_lengths=None):
+        """PointConv grouping + WeightNet + aggregation (mocopci.py:1330-1335): -> (B,S,(3+D)*8).  Differentiable.
+        centre_lengths: per-element number of live centres of a padded batch (see lengths_tensor; None = all S): centre i of element
+        b is live iff i < centre_lengths[b].  Live centres get the dense call's bits; a padded centre has none of its inputs read
+        (its idx row, new_xyz, the gathered rows, the upstream gradient: they may hold NaN or out-of-range indices), its row is
+        exact zeros, as are its gradient rows, and it adds nothing to the WeightNet's weight gradients.  No synchronisation."""
         D = s_points.shape[-1]
+        if centre_lengths is not None:
+            qlen = lengths_tensor(centre_lengths, new_xyz.shape[0], new_xyz.shape[1], s_points.device)
+            if not grad.wants_grad(s_xyz, new_xyz, s_points, w0, b0, w1, b1, w2, b2):
+                return self._pointconv_agg(s_xyz, new_xyz, s_points, idx, w0, b0, w1, b1, w2, b2, qlen=qlen)
+            if idx.shape[-1] != 32 or D % 4 or D > 256 or tuple(w2.shape) != (8, 8):   # no backward kernel: the masked torch formulation
+                return grad.run(lambda *a: self._pointconv_agg(*a, qlen=qlen),
+                                lambda *a: grad.pointconv_agg_lengths_twin(self.group_rows, *a, qlen), s_xyz, new_xyz, s_points, idx,
+                                w0, b0, w1, b1, w2, b2)
+            return _PointConvAggFn.apply(self, idx.contiguous(), s_xyz, new_xyz, s_points, w0, b0, w1, b1, w2, b2, qlen)
         if not grad.wants_grad(s_xyz, new_xyz, s_points, w0, b0, w1, b1, w2, b2):
             return self._pointconv_agg(s_xyz, new_xyz, s_points, idx, w0, b0, w1, b1, w2, b2)
         if idx.shape[-1] != 32 or D % 4 or D > 256 or tuple(w2.shape) != (8, 8):   # shapes the backward kernel is not built for
             return grad.run(self._pointconv_agg, lambda *a: grad.pointconv_agg_twin(self.group_rows, *a), s_xyz, new_xyz, s_points, idx,
                             w0, b0, w1, b1, w2, b2)
-        return _PointConvAggFn.apply(self, idx.contiguous(), s_xyz, new_xyz, s_points, w0, b0, w1, b1, w2, b2)
+        return _PointConvAggFn.apply(self, idx.contiguous(), s_xyz, new_xyz, s_points, w0, b0, w1, b1, w2, b2, None)
 
-    def _pointconv_agg(self, s_xyz, new_xyz, s_points, idx, w0, b0, w1, b1, w2, b2):
+    def _pointconv_agg(self, s_xyz, new_xyz, s_points, idx, w0, b0, w1, b1, w2, b2, qlen=None):
         s_xyz, new_xyz, s_points, w0, b0, w1, b1, w2, b2 = (t.contiguous() for t in (s_xyz, new_xyz, s_points, w0, b0, w1, b1, w2, b2))
         B, N, D = s_points.shape
         S = new_xyz.shape[1]
         out = torch.empty((B, S, (D + 3) * 8), dtype=torch.float32, device=s_points.device)
+        if qlen is not None:
+            _call("mcp_pointconv_agg_lengths", s_points, B, N, S, D, idx.shape[-1], _lib.fptr(s_xyz), _lib.fptr(new_xyz), _lib.fptr(s_points),
+                  _lib.iptr(idx), _lib.iptr(qlen), _lib.fptr(w0), _lib.fptr(b0), _lib.fptr(w1), _lib.fptr(b1), _lib.fptr(w2), _lib.fptr(b2),
+                  _lib.fptr(out))
+            return out
         _call("mcp_pointconv_agg", s_points, B, N, S, D, idx.shape[-1], _lib.fptr(s_xyz), _lib.fptr(new_xyz), _lib.fptr(s_points),
               _lib.iptr(idx), _lib.fptr(w0), _lib.fptr(b0), _lib.fptr(w1), _lib.fptr(b1), _lib.fptr(w2), _lib.fptr(b2), _lib.fptr(out))
         return out
@@ -2284,15 +2310,22 @@ class HipBackend:
         """Operand image of PointConv's Linear: the same image linear() uses for the (B,S,(3+D)*8) aggregate."""
         return self.linear_pack(w, b, [w.shape[1]])
 
-    def pointconv_linear(self, s_xyz, new_xyz, s_points, idx, w0, b0, w1, b1, w2, b2, w, b, slope, packed=None):
+    def pointconv_linear(self, s_xyz, new_xyz, s_points, idx, w0, b0, w1, b1, w2, b2, w, b, slope, packed=None, centre_lengths=None):
         """PointConv after the sampling in one launch (mocopci.py:1330-1342): grouping, WeightNet, aggregation, Linear, LeakyReLU ->
         (B,S,C_out).  Inference only (a training forward uses pointconv_agg + linear, which carry gradients).
-        packed: pointconv_linear_pack(w, b) if kept."""
+        packed: pointconv_linear_pack(w, b) if kept.  centre_lengths: as in pointconv_agg; a padded centre's row is zero, not
+        leaky(bias)."""
         s_xyz, new_xyz, s_points, w0, b0, w1, b1, w2, b2 = (t.contiguous() for t in (s_xyz, new_xyz, s_points, w0, b0, w1, b1, w2, b2))
         B, N, D = s_points.shape
         S, n = new_xyz.shape[1], w.shape[0]
         pk = packed if packed is not None else self.pointconv_linear_pack(w, b)
         out = torch.empty((B, S, n), dtype=torch.float32, device=s_points.device)
+        if centre_lengths is not None:
+            qlen = lengths_tensor(centre_lengths, B, S, s_points.device)
+            _call("mcp_pointconv_linear_lengths", s_points, B, N, S, D, idx.shape[-1], _lib.fptr(s_xyz), _lib.fptr(new_xyz),
+                  _lib.fptr(s_points), _lib.iptr(idx), _lib.iptr(qlen), _lib.fptr(w0), _lib.fptr(b0), _lib.fptr(w1), _lib.fptr(b1),
+                  _lib.fptr(w2), _lib.fptr(b2), _lib.fptr(pk), n, float(slope), _lib.fptr(out))
+            return out
         _call("mcp_pointconv_linear", s_points, B, N, S, D, idx.shape[-1], _lib.fptr(s_xyz), _lib.fptr(new_xyz), _lib.fptr(s_points),
               _lib.iptr(idx), _lib.fptr(w0), _lib.fptr(b0), _lib.fptr(w1), _lib.fptr(b1), _lib.fptr(w2), _lib.fptr(b2), _lib.fptr(pk), n,
               float(slope), _lib.fptr(out))
