@@ -1,6 +1,6 @@
 // attention_small_fwd.h -- the inference forward of the narrow-head attention (head dims 8 / 16), stated once for mcp_attention /
 // mcp_attention_small (attention.hip) and mcp_attention_lengths (attention_lengths.hip: the same kernel with one AttnLengths behind its
-// parameters).  The arrangement is described at the head of attention.hip.
+// parameters); both launch it through attention_forward_run (attention_forward.h).  The arrangement is described at the head of attention.hip.
 #pragma once
 #include "attention_wide_fwd.h"  // f32x16, WAVES, chan_of; attention_lengths.h
 

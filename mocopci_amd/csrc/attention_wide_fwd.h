@@ -1,11 +1,11 @@
 // attention_wide_fwd.h -- the forward of the wide-head attention (head widths 32 / 64 / 256), stated once for the inference kernels
-// (attention.hip: attention_wide_kernel, attention_wide_ksplit_kernel) and the training kernels (attention_wide_grad.hip:
+// (attention_forward.h: attention_wide_kernel, attention_wide_ksplit_kernel and their length forms) and the training kernels (attention_wide_grad.hip:
 // attention_wide_lse_kernel, attention_wide_ksplit_lse_kernel).  A kernel is its dynamic LDS declaration and one call of a body.
 // The training forward adds two things to the inference one: with `lse` the row's log-sum-exp (log2 domain) is stored, and with DROP
 // the hash mask of attention_dropout.h multiplies P in P.V only (row sums are taken before the mask).  Same instruction sequence per
 // (query, key) and the same dispatch rule (wide_keys_split), so at drop_p = 0 the training output is the inference output bit for bit.
 // Each body ends in a parameter pack that is empty for these kernels and one AttnLengths for their length forms (attention_lengths.h;
-// attention_lengths.hip and the AttnLengths instantiations of attention_wide_grad.hip): per-element query / key counts of a padded batch.
+// the length wrappers of attention_forward.h and the AttnLengths instantiations of attention_wide_grad.hip): per-element query / key counts of a padded batch.
 #pragma once
 #include "common.h"
 #include "attention_dropout.h"

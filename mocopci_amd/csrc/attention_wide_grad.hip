@@ -51,18 +51,6 @@ __global__ __launch_bounds__(64 * WAVES, 1) void attention_wide_ksplit_lse_kerne
                                          heads * HD, lse, lens...);
 }
 
-// dynamic LDS above the 64 KB default: the attribute is set once per device and kernel instantiation
-template <auto KERN>
-int allow_lds() {
-    static McpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_once.done();
-    }
-    return MCP_OK;
-}
-
 // lens: empty, or one AttnLengths; the key-split dispatch is decided from the padded sizes either way (the host never reads a length)
 template <int HD, bool DROP, class... L>
 int launch_forward(int bf, int nq, int nk, int heads, const float *q, int qs, const float *k, int ks, const float *v, int vs, float sl2, uint32_t seed,
@@ -70,14 +58,14 @@ int launch_forward(int bf, int nq, int nk, int heads, const float *q, int qs, co
     if constexpr (HD == 256) {
         if (wide_keys_split(bf, nq, nk, heads)) {
             constexpr auto kern = attention_wide_ksplit_lse_kernel<HD, DROP, L...>;
-            if (const int rc = allow_lds<kern>()) return rc;
+            if (const int rc = mcp_allow_lds<kern>()) return rc;
             hipLaunchKernelGGL(kern, dim3(mcp_divup(nq, 32), heads, bf), dim3(64 * WAVES), WideSplitCfg<HD>::LDS_BYTES, s, nq, nk, heads, q, qs, k, ks, v, vs,
                                sl2, seed, threshold, inv_keep, out, lse, lens...);
             return mcp_launch_status();
         }
     }
     constexpr auto kern = attention_wide_lse_kernel<HD, DROP, L...>;
-    if (const int rc = allow_lds<kern>()) return rc;
+    if (const int rc = mcp_allow_lds<kern>()) return rc;
     hipLaunchKernelGGL(kern, dim3(mcp_divup(nq, 32 * WAVES), heads, bf), dim3(64 * WAVES), WideCfg<HD>::LDS_BYTES, s, nq, nk, heads, q, qs, k, ks, v, vs, sl2,
                        seed, threshold, inv_keep, out, lse, lens...);
     return mcp_launch_status();
@@ -410,8 +398,8 @@ int launch_backward(int bf, int nq, int nk, int heads, const float *q, int qs, c
     const float sl2 = scale * 1.44269504088896340736f;
     constexpr auto kq = attention_wide_dq_kernel<HD, DROP, L...>;
     constexpr auto kk = attention_wide_dkv_kernel<HD, DROP, L...>;
-    if (const int rc = allow_lds<kq>()) return rc;
-    if (const int rc = allow_lds<kk>()) return rc;
+    if (const int rc = mcp_allow_lds<kq>()) return rc;
+    if (const int rc = mcp_allow_lds<kk>()) return rc;
     const long long rows = (long long)bf * nq * heads;
     hipLaunchKernelGGL(attention_wide_dsum_kernel<HD>, dim3((unsigned)((rows * (HD / 4) + 255) / 256)), dim3(256), 0, s, rows, heads, out, gout, nq, dsum);
     hipLaunchKernelGGL(kq, dim3(mcp_divup(nq, 32 * C::RPW), heads, bf), dim3(64 * WAVES), C::LDS_BYTES, s, nq, nk, heads, q, qs, k, ks, v, vs, sl2, scale, seed,

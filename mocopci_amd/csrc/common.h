@@ -90,6 +90,18 @@ struct McpPerDeviceOnce {
     bool need() const { return !(__atomic_load_n(&bits, __ATOMIC_ACQUIRE) & device_bit()); }
     void done() { __atomic_fetch_or(&bits, device_bit(), __ATOMIC_RELEASE); }
 };
+// Dynamic LDS above the 64 KB default for kernel KERN on the current device: the attribute is set once per device and kernel
+// (one flag per instantiation, that is per kernel symbol).  Returns the HIP error, or MCP_OK.
+template <auto KERN>
+int mcp_allow_lds() {
+    static McpPerDeviceOnce attr_once;
+    if (attr_once.need()) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return (int)e;
+        attr_once.done();
+    }
+    return MCP_OK;
+}
 
 static inline int mcp_launch_status() {
     hipError_t e = hipGetLastError();

@@ -429,12 +429,7 @@ int launch_cross256(long long total, int n1, int n2, const float *xyz1, const fl
                     const int *idx2, const int *bmap, int shared, const float *packed, float *out, hipStream_t s) {
     using L = CrossLds<256>;
     const size_t lds = (size_t)2 * X256_TILE_U4 * 16 + (size_t)(L::POS_FLOATS + L::B_FLOATS + X256_WAVES * 256 + (bmap ? MAX_MAPPED_BATCH : 0)) * sizeof(float);
-    static McpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(cross256_stream_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_once.done();
-    }
+    if (const int rc = mcp_allow_lds<cross256_stream_kernel>()) return rc;
     const long long want = (total + X256_WAVES - 1) / X256_WAVES;
     const unsigned grid = (unsigned)max(1LL, min(want, 256LL));  // one resident workgroup per CU
     hipLaunchKernelGGL(cross256_stream_kernel, dim3(grid), dim3(64 * X256_WAVES), lds, s, total, n1, n2, xyz1, xyz2, points1, points2, idx, idx2, bmap, shared,
@@ -449,12 +444,8 @@ int launch_cross(long long total, int n1, int n2, const float *xyz1, const float
     constexpr int WAVES = CrossShape<D>::NW;
     // weights | pos + bias | one points1 row per wave | the batch map (only when one is passed)
     const size_t lds = (L::W_FLOATS / SPLIT + L::POS_FLOATS + L::B_FLOATS + WAVES * D + (bmap ? MAX_MAPPED_BATCH : 0)) * sizeof(float);
-    auto kern = cross_kernel<D, SPLIT>;
-    static McpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        { const hipError_t attr_e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); if (attr_e_ != hipSuccess) return (int)attr_e_; }
-        attr_once.done();
-    }
+    constexpr auto kern = cross_kernel<D, SPLIT>;
+    if (const int rc = mcp_allow_lds<kern>()) return rc;
     // at least 8 points per wave so the weight staging is amortised
     const long long want = (total + WAVES * 8 - 1) / (WAVES * 8);
     // persistent-style grid = exactly the resident slots (256 CUs x 3 or 2 workgroups, see __launch_bounds__): a larger

@@ -411,12 +411,7 @@ MCP_EXPORT int mcp_cross256_grad(int b, int n1, int n2, int k, const float *xyz1
     const Plan pl = plan(total);
     if (workspace_bytes < pl.bytes) return MCP_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
-    static McpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(cross256_grad_z_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_once.done();
-    }
+    if (const int rc = mcp_allow_lds<cross256_grad_z_kernel>()) return rc;
     char *ws = static_cast<char *>(workspace);
     float *packed = reinterpret_cast<float *>(ws);
     int *jstar = reinterpret_cast<int *>(ws + pl.off_j);

@@ -477,13 +477,8 @@ int launch_cross_grad(long long total, int n1, int n2, const float *xyz1, const 
                       const int *idx2, const float *wpos, const float *bpos, const float *wmlp, const float *bmlp, const float *gout, float *d_xyz1,
                       float *d_dir, float *d_points1, float *d_rows, float *d_weights, void *workspace, hipStream_t s) {
     using S = GradShape<D>;
-    auto kern = cross_grad_kernel<D>;
-    static McpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_once.done();
-    }
+    constexpr auto kern = cross_grad_kernel<D>;
+    if (const int rc = mcp_allow_lds<kern>()) return rc;
     unsigned g0, g1;
     grad_grid<D>(total, &g0, &g1);
     uint4 *wt = S::WT_LDS ? nullptr : static_cast<uint4 *>(workspace);  // 16-byte aligned: the workspace is, and the image comes first

@@ -345,12 +345,7 @@ __device__ __forceinline__ void fp_store_dx(const f32x16 (&bank)[TMAX], int c0, 
 // 32 * WAVES rows, front_floats of the unit's own LDS in front of the slabs; the LDS attribute is set once per device and instantiation. ----
 template <auto KERN, int TMAX, bool STREAM, class... Args>
 int fp_launch(long long total, int front_floats, int whole_u4, hipStream_t s, const Args &...args) {
-    static McpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_once.done();
-    }
+    if (const int rc = mcp_allow_lds<KERN>()) return rc;
     const size_t lds = (size_t)front_floats * sizeof(float) + FpSlabs<TMAX, STREAM>::lds_bytes(whole_u4);
     const long long grid = (total + 32 * WAVES - 1) / (32 * WAVES);
     if (grid > 0x7FFFFFFFLL) return MCP_ERR_UNSUPPORTED;

@@ -243,21 +243,13 @@ int launch_resident(int b, int n, int m, int L, const float *xyz, float *temp, i
     const size_t xyz_bytes = (size_t)n * 3 * sizeof(float);
     const size_t idx_bytes = (size_t)(m > 0 ? m : 1) * sizeof(int);  // the selected indices are buffered in LDS (m <= n)
     if (xyz_bytes + slot_bytes + idx_bytes <= 150 * 1024) {
-        auto kern = fps_resident_kernel<T, P, J, GENERIC, true>;
-        static McpPerDeviceOnce attr_once;
-        if (attr_once.need()) {
-            { const hipError_t attr_e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); if (attr_e_ != hipSuccess) return (int)attr_e_; }
-            attr_once.done();
-        }
+        constexpr auto kern = fps_resident_kernel<T, P, J, GENERIC, true>;
+        if (const int rc = mcp_allow_lds<kern>()) return rc;
         hipLaunchKernelGGL(kern, dim3(b), dim3(T), slot_bytes + xyz_bytes + idx_bytes, s, n, m, L, xyz, temp, idx, pts);
     } else {
         if (slot_bytes + idx_bytes > 150 * 1024) return MCP_ERR_UNSUPPORTED;
-        auto kern = fps_resident_kernel<T, P, J, GENERIC, false>;
-        static McpPerDeviceOnce attr_once2;
-        if (attr_once2.need()) {
-            { const hipError_t attr_e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); if (attr_e_ != hipSuccess) return (int)attr_e_; }
-            attr_once2.done();
-        }
+        constexpr auto kern = fps_resident_kernel<T, P, J, GENERIC, false>;
+        if (const int rc = mcp_allow_lds<kern>()) return rc;
         hipLaunchKernelGGL(kern, dim3(b), dim3(T), slot_bytes + idx_bytes, s, n, m, L, xyz, temp, idx, pts);
     }
     return mcp_launch_status();

@@ -210,15 +210,8 @@ int launch_resident(int b, int n, int m, const float *xyz, const int *len, int *
     const size_t idx_bytes = (size_t)m * sizeof(int);  // the selected indices are buffered in LDS
     const bool lds_xyz = xyz_bytes + slot_bytes + idx_bytes <= 150 * 1024;
     if (!lds_xyz && slot_bytes + idx_bytes > 150 * 1024) return MCP_ERR_UNSUPPORTED;
-    static McpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        for (const void *kern : {reinterpret_cast<const void *>(fps_lengths_resident_kernel<P, true>),
-                                 reinterpret_cast<const void *>(fps_lengths_resident_kernel<P, false>)}) {
-            const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return (int)e;
-        }
-        attr_once.done();
-    }
+    if (const int rc = mcp_allow_lds<fps_lengths_resident_kernel<P, true>>()) return rc;
+    if (const int rc = mcp_allow_lds<fps_lengths_resident_kernel<P, false>>()) return rc;
     if (lds_xyz) hipLaunchKernelGGL((fps_lengths_resident_kernel<P, true>), dim3(b), dim3(LT), slot_bytes + xyz_bytes + idx_bytes, s, n, m, xyz, len, idx, pts);
     else hipLaunchKernelGGL((fps_lengths_resident_kernel<P, false>), dim3(b), dim3(LT), slot_bytes + idx_bytes, s, n, m, xyz, len, idx, pts);
     return mcp_launch_status();

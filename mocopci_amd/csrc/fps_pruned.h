@@ -554,11 +554,7 @@ int launch_tiled(int b, int n, int m, const float *xyz, FPS_AUX_HOST_PARAM, int 
     if (lds > 160 * 1024) return MCP_ERR_UNSUPPORTED;
     float4 *sx = reinterpret_cast<float4 *>(ws);
     float *st = reinterpret_cast<float *>(ws + (size_t)b * np * sizeof(float4));
-    static McpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        { const hipError_t attr_e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(FPS_KERNEL(tiled)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); if (attr_e_ != hipSuccess) return (int)attr_e_; }
-        attr_once.done();
-    }
+    if (const int rc = mcp_allow_lds<FPS_KERNEL(tiled)>()) return rc;
     hipLaunchKernelGGL(FPS_KERNEL(tiled), dim3(b), dim3(TL_T), lds, s, n, m, tiles, lds_idx, xyz, FPS_AUX, idx, pts, sx, st);
     return mcp_launch_status();
 }
@@ -573,14 +569,8 @@ int launch_spatial(int b, int n, int m, int L, const float *xyz, FPS_AUX_HOST_PA
         lds_idx = (int)lds;
         lds += (size_t)m * 4;
     }
-    static McpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        { const hipError_t attr_e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(FPS_KERNEL(spatial)<T, P, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024); if (attr_e_ != hipSuccess) return (int)attr_e_; }
-        { const hipError_t attr_e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(FPS_KERNEL(spatial)<T, P, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024); if (attr_e_ != hipSuccess) return (int)attr_e_; }
-        attr_once.done();
-    }
+    if (const int rc = mcp_allow_lds<FPS_KERNEL(spatial)<T, P, true>>()) return rc;
+    if (const int rc = mcp_allow_lds<FPS_KERNEL(spatial)<T, P, false>>()) return rc;
     (void)L;  // n >= 1024: the reference block size is 1024 (asserted by the caller)
     if (lds_xyz) hipLaunchKernelGGL((FPS_KERNEL(spatial)<T, P, true>), dim3(b), dim3(T), lds, s, n, m, lds_idx, xyz, FPS_AUX, idx, pts);
     else hipLaunchKernelGGL((FPS_KERNEL(spatial)<T, P, false>), dim3(b), dim3(T), lds, s, n, m, lds_idx, xyz, FPS_AUX, idx, pts);

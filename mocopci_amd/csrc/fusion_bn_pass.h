@@ -479,13 +479,8 @@ template <int MODE, bool SAVE>
 int launch_fwd(long long total, int n, const float *p1, const float *p2, const int *idx, const int *idx2, const float *w1, const float *b1, const float *w2,
                const float *b2, const float *w3, const float *b3, const float *bn, float *out, unsigned grid, hipStream_t s, int *save_c, float *save_z,
                float *save_s, float *shift FBN_LENS_PARAM) {
-    auto kern = FBN_KERNEL(fwd)<MODE, SAVE>;
-    static McpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_once.done();
-    }
+    constexpr auto kern = FBN_KERNEL(fwd)<MODE, SAVE>;
+    if (const int rc = mcp_allow_lds<kern>()) return rc;
     const size_t lds = (size_t)L_F32 * 4 + (size_t)(W2_U4 + W3_U4) * 16;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WAVES), lds, s, total, n, p1, p2, idx, idx2, w1, b1, w2, b2, w3, b3, bn, out, save_c, save_z, save_s,
                        shift FBN_LENS);
@@ -1366,16 +1361,10 @@ int bn_backward(int b, int n, int nb, const float *p1, const float *p2, const in
     const float inv_rows = (float)(1.0 / ((double)total * NB));
     // grad_weights layout (mcp_fusion_grad): dW1 (64,4) | db1 | dW2 (64,64) | db2 | dW3 (128,64) | db3
     constexpr int G_W1 = 0, G_W2 = 320, G_B2 = G_W2 + 4096, G_W3 = G_B2 + 64, G_B3 = G_W3 + 8192, G_FLOATS = G_B3 + 128;
-    static McpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        const void *kerns[4] = {reinterpret_cast<const void *>(FBN_KERNEL(b1)), reinterpret_cast<const void *>(FBN_KERNEL(b2)), reinterpret_cast<const void *>(FBN_KERNEL(b3)),
-                                reinterpret_cast<const void *>(FBN_KERNEL(b4))};
-        for (const void *k : kerns) {
-            const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return (int)e;
-        }
-        attr_once.done();
-    }
+    if (const int rc = mcp_allow_lds<FBN_KERNEL(b1)>()) return rc;
+    if (const int rc = mcp_allow_lds<FBN_KERNEL(b2)>()) return rc;
+    if (const int rc = mcp_allow_lds<FBN_KERNEL(b3)>()) return rc;
+    if (const int rc = mcp_allow_lds<FBN_KERNEL(b4)>()) return rc;
     mcp_prof_begin(MCP_KERNEL_FUSION, s);
     (void)hipMemsetAsync(grad_weights, 0, G_FLOATS * sizeof(float), s);
     hipLaunchKernelGGL(transposed_image_kernel, dim3(16), dim3(256), 0, s, w3t, w3, C2, C3);

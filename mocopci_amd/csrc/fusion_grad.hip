@@ -464,12 +464,7 @@ MCP_EXPORT int mcp_fusion_grad(int b, int n, int nb, const float *p1, const floa
     const long long total = (long long)b * n;
     const unsigned grid = grad_grid(total);
     if (workspace_bytes < (size_t)grid * G_FLOATS * sizeof(float)) return MCP_ERR_BAD_ARG;
-    static McpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fusion_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_once.done();
-    }
+    if (const int rc = mcp_allow_lds<fusion_grad_kernel>()) return rc;
     mcp_prof_begin(MCP_KERNEL_FUSION, s);
     hipLaunchKernelGGL(fusion_grad_kernel, dim3(grid), dim3(64 * WAVES), LDS_BYTES, s, total, n, p1, p2, idx, idx2, w1, b1, w2, b2, w3, b3, grad_out,
                        grad_p1, grad_nb, static_cast<float *>(workspace));

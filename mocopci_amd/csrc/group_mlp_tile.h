@@ -192,12 +192,7 @@ inline int gm_pack_bwd(hipStream_t s, const float *w, int ld, int cfeat, int npo
 // attribute is set once per device and instantiation. ----
 template <auto KERN, class... Args>
 int gm_launch(long long units, int waves, int slots, size_t lds, hipStream_t s, const Args &...args) {
-    static McpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_once.done();
-    }
+    if (const int rc = mcp_allow_lds<KERN>()) return rc;
     const long long want = (units + waves - 1) / waves;
     const unsigned grid = (unsigned)max(1LL, min(want, (long long)slots));
     hipLaunchKernelGGL(KERN, dim3(grid), dim3(64 * waves), lds, s, args...);

@@ -118,12 +118,10 @@ template <int K, int MODE, int SPLIT, bool LEN>
 int launch_queue(const Args &a) {
     constexpr auto plain = knn_queue_kernel<K, MODE, SPLIT>;
     constexpr auto len = knn_len_queue_kernel<K, MODE, SPLIT>;
-    static McpPerDeviceOnce attr_once;  // one per instantiation, that is per kernel symbol
-    if (attr_once.need()) {
-        const void *kern = LEN ? reinterpret_cast<const void *>(len) : reinterpret_cast<const void *>(plain);
-        const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_once.done();
+    if constexpr (LEN) {
+        if (const int rc = mcp_allow_lds<len>()) return rc;
+    } else {
+        if (const int rc = mcp_allow_lds<plain>()) return rc;
     }
     return launch<LEN>(plain, len, SPLIT, (size_t)KnnLds<K>::WAVE_BYTES * SPLIT, a);
 }

@@ -390,11 +390,10 @@ int launch_cosine_split(const Args &a, const float *nq, const float *nr) {
     const size_t lds = (size_t)RS * QS * 64 * sizeof(uint2) + (C > 128 ? (size_t)(C / 2) * 64 * sizeof(float) : 0);
     constexpr auto plain = knn_cosine_split_kernel<C, RS>;
     constexpr auto len = knn_cosine_split_kernel<C, RS, Lengths>;
-    static McpPerDeviceOnce attr_once;   // one per instantiation, that is per kernel symbol
-    if (attr_once.need()) {
-        const void *kern = LEN ? reinterpret_cast<const void *>(len) : reinterpret_cast<const void *>(plain);
-        { const hipError_t attr_e_ = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); if (attr_e_ != hipSuccess) return (int)attr_e_; }
-        attr_once.done();
+    if constexpr (LEN) {
+        if (const int rc = mcp_allow_lds<len>()) return rc;
+    } else {
+        if (const int rc = mcp_allow_lds<plain>()) return rc;
     }
     const dim3 grid(mcp_divup(a.q, 32), a.b), block(64 * RS);
     if constexpr (LEN) hipLaunchKernelGGL(len, grid, block, lds, a.s, a.q, a.n, a.k, nq, nr, a.idx, a.dist, Lengths{a.qlen, a.rlen, a.q, a.n});
@@ -416,12 +415,8 @@ int launch_cosine_auto(const Args &a, const float *nq, const float *nr) {
 template <int C>
 int launch_cosine(int b, int q, int n, int k, const float *nq, const float *nr, int *idx, float *dist, hipStream_t s) {
     const size_t lds = (size_t)2 * RT * (C + 1) * sizeof(float) + (size_t)WAVES * QS * 64 * sizeof(uint2);
-    auto kern = knn_cosine_kernel<C>;
-    static McpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        { const hipError_t attr_e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); if (attr_e_ != hipSuccess) return (int)attr_e_; }
-        attr_once.done();
-    }
+    constexpr auto kern = knn_cosine_kernel<C>;
+    if (const int rc = mcp_allow_lds<kern>()) return rc;
     hipLaunchKernelGGL(kern, dim3(mcp_divup(q, 32 * WAVES), b), dim3(64 * WAVES), lds, s, q, n, k, nq, nr, idx, dist);
     return mcp_launch_status();
 }

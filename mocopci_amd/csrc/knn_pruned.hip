@@ -324,13 +324,9 @@ __global__ __launch_bounds__(BT) void build_cloud_kernel(int n, int tiles, const
 
 template <int IPT, bool LEN>
 int launch_build_cloud(int b, int n, int tiles, const float *xyz, const int *len, float *sorted_xyz, int *perm, float *boxes, hipStream_t s) {
-    auto kern = build_cloud_kernel<IPT, LEN>;
+    constexpr auto kern = build_cloud_kernel<IPT, LEN>;
     const size_t lds = 512 + sizeof(typename CloudSort<IPT>::Lds);
-    static McpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        { const hipError_t attr_e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); if (attr_e_ != hipSuccess) return (int)attr_e_; }
-        attr_once.done();
-    }
+    if (const int rc = mcp_allow_lds<kern>()) return rc;
     hipLaunchKernelGGL(kern, dim3(b), dim3(BT), lds, s, n, tiles, xyz, len, sorted_xyz, perm, boxes);
     return mcp_launch_status();
 }
@@ -1186,15 +1182,10 @@ struct SearchArgs {
 };
 
 // One wave per workgroup, LDS sized by the kernel's configuration.  The attribute lets the CU's whole 160 KB LDS count towards
-// residency (default budget: 64 KB); it is set once per kernel symbol and device.
+// residency (default budget: 64 KB): mcp_allow_lds, once per kernel symbol and device.
 template <auto KERN, typename... Args>
 int launch_search(dim3 grid, size_t lds, hipStream_t s, Args... args) {
-    static McpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_once.done();
-    }
+    if (const int rc = mcp_allow_lds<KERN>()) return rc;
     hipLaunchKernelGGL(KERN, grid, dim3(64), lds, s, args...);
     return mcp_launch_status();
 }

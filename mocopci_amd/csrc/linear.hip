@@ -392,14 +392,10 @@ int launch_linear_splitk(long long rows, int n, int nt_total, const Segs &sg, in
 template <int NT, int KC, int NW>
 int launch_linear_kc(long long rows, int n, const Segs &sg, int nseg, int total_chunks, float slope, const float *packed, const float *res, int rs_,
                      float *out, int os_, hipStream_t s, int col_blocks = 1) {
-    auto kern = linear_kernel<NT, KC, NW>;
+    constexpr auto kern = linear_kernel<NT, KC, NW>;
     const size_t lds = (2 * stage_floats(NT, KC, NW) + (size_t)NW * XT) * sizeof(float);
     static_assert((2 * stage_floats(NT, KC, NW) + (size_t)NW * XT) * sizeof(float) <= 160 * 1024, "LDS budget");
-    static McpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        { const hipError_t attr_e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); if (attr_e_ != hipSuccess) return (int)attr_e_; }
-        attr_once.done();
-    }
+    if (const int rc = mcp_allow_lds<kern>()) return rc;
     const long long groups = (rows + 32LL * NW - 1) / (32LL * NW);
     hipLaunchKernelGGL(kern, dim3((unsigned)groups, col_blocks), dim3(64 * NW), lds, s, rows, n, sg, nseg, total_chunks, slope, packed,
                        chunk_floats(NT * col_blocks), res, rs_, out, os_);

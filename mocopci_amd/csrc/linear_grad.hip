@@ -150,13 +150,8 @@ MCP_EXPORT int mcp_linear_wgrad(long long rows, int n, int k, const float *gz, i
     float *partial = reinterpret_cast<float *>(workspace);
 #define MCP_WGRAD_GO(T)                                                                                                                        \
     do {                                                                                                                                       \
-        auto kern = linear_wgrad_kernel<T>;                                                                                                    \
-        static McpPerDeviceOnce attr_once;                                                                                                     \
-        if (attr_once.need()) {                                                                                                                \
-            const hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-            if (e_ != hipSuccess) return (int)e_;                                                                                              \
-            attr_once.done();                                                                                                                  \
-        }                                                                                                                                      \
+        constexpr auto kern = linear_wgrad_kernel<T>;                                                                                          \
+        if (const int rc_ = mcp_allow_lds<kern>()) return rc_;                                                                                 \
         hipLaunchKernelGGL(kern, dim3(wgs), dim3(64 * WAVES), lds, s, rows, n, k, gz, gz_stride, x, x_stride, partial, stages, per);           \
     } while (0)
     if (tpw <= 1) MCP_WGRAD_GO(1);

@@ -161,13 +161,9 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp2_kernel(long long rows, int hi
 template <int CIN, int COT, int NW>
 int launch_mlp2(long long rows, int hidden, int cout, float slope, const float *x, int xs_, const float *res, int rs_, const float *packed,
                 float *out, int os_, hipStream_t s) {
-    auto kern = mlp2_kernel<CIN, COT, NW>;
+    constexpr auto kern = mlp2_kernel<CIN, COT, NW>;
     const size_t lds = 2 * (size_t)((chunk_floats(CIN, COT) / 4 + 64 * NW - 1) / (64 * NW)) * (64 * NW) * 4 * sizeof(float);
-    static McpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        { const hipError_t attr_e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); if (attr_e_ != hipSuccess) return (int)attr_e_; }
-        attr_once.done();
-    }
+    if (const int rc = mcp_allow_lds<kern>()) return rc;
     const long long groups = (rows + 32LL * NW - 1) / (32LL * NW);
     hipLaunchKernelGGL(kern, dim3((unsigned)groups), dim3(64 * NW), lds, s, rows, hidden, cout, slope, x, xs_, res, rs_, packed, out, os_);
     return mcp_launch_status();

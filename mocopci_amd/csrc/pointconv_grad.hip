@@ -12,7 +12,7 @@
 //     the end, waves in wave order, workgroups in workgroup order by a second kernel -- fixed orders, bit-reproducible.
 // grad_rows / grad_gxyz are scattered into dL/ds_points and dL/ds_xyz by the caller's deterministic segmented reduction.
 #define PCG_LEN 0
-#include "pointconv_grad_tile.h"   // pointconv_agg_grad_kernel; pointconv_lengths.hip holds the length form
+#include "pointconv_grad_tile.h"   // pointconv_agg_grad_kernel and its host side (pcg_run); pointconv_lengths.hip holds the length form
 
 MCP_EXPORT int mcp_pointconv_agg_grad_floats(void) { return G_FLOATS; }
 
@@ -25,26 +25,6 @@ MCP_EXPORT int mcp_pointconv_agg_grad(int b, int n, int s, int d, int k, const f
                                       const float *w0, const float *b0, const float *w1, const float *b1, const float *w2, const float *b2,
                                       const float *grad_out, float *grad_new_xyz, float *grad_gxyz, float *grad_rows, float *grad_weights,
                                       void *workspace, size_t workspace_bytes, mcp_stream_t stream) {
-    MCP_CHECK_ARGS(b > 0 && n > 0 && s > 0 && s_xyz && new_xyz && s_points && idx && w0 && b0 && w1 && b1 && w2 && b2 && grad_out && grad_new_xyz &&
-                   grad_gxyz && grad_rows && grad_weights && workspace);
-    if (k != K || d < 4 || (d & 3) || d > MAX_D) return MCP_ERR_UNSUPPORTED;
-    if ((((uintptr_t)s_points) | ((uintptr_t)grad_out) | ((uintptr_t)grad_rows)) & 15) return MCP_ERR_BAD_ARG;
-    const long long total = (long long)b * s;
-    const unsigned grid = grad_grid(total);
-    if (workspace_bytes < (size_t)grid * G_FLOATS * sizeof(float)) return MCP_ERR_BAD_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    size_t lds = (size_t)WAVES * 2 * (d + 3) * WN * sizeof(float);
-    if (lds < (size_t)WAVES * G_FLOATS * sizeof(float)) lds = (size_t)WAVES * G_FLOATS * sizeof(float);
-    static McpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(pointconv_agg_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_once.done();
-    }
-    mcp_prof_begin(MCP_KERNEL_POINTCONV, st);
-    hipLaunchKernelGGL(pointconv_agg_grad_kernel, dim3(grid), dim3(64 * WAVES), lds, st, total, n, s, d, s_xyz, new_xyz, s_points, idx, w0, b0, w1, b1, w2, b2,
-                       grad_out, grad_new_xyz, grad_gxyz, grad_rows, static_cast<float *>(workspace));
-    hipLaunchKernelGGL(pointconv_grad_reduce_kernel, dim3(1), dim3(256), 0, st, static_cast<const float *>(workspace), (int)grid, grad_weights);
-    mcp_prof_end(MCP_KERNEL_POINTCONV, st);
-    return mcp_launch_status();
+    return pcg_run(b, n, s, d, k, s_xyz, new_xyz, s_points, idx, w0, b0, w1, b1, w2, b2, grad_out, grad_new_xyz, grad_gxyz, grad_rows, grad_weights, workspace,
+                   workspace_bytes, (hipStream_t)stream);
 }

@@ -6,6 +6,7 @@
 // i < min(max(qlen[bb], 0), s); a padded centre has no input read (idx row, new_xyz, gathered rows, grad_out), its rows of
 // grad_new_xyz / grad_gxyz / grad_rows are exact zeros and it adds exact zeros to the 176 weight gradients -- from zeros in place of
 // its loads, never from padding times zero.  The deal of centre pairs to waves and the order of every sum are the dense kernel's.
+// The host side is stated once as well, under the same parameter: pcg_run at the end of this file, which both exported functions call.
 #pragma once
 #include "common.h"
 
@@ -15,10 +16,14 @@
 #if PCG_LEN
 #define PCG_KERNEL pointconv_agg_grad_lengths_kernel
 #define PCG_LENS_PARAM , const int *__restrict__ qlen
+#define PCG_LENS , qlen
+#define PCG_LENS_MISALIGNED || (((uintptr_t)qlen) & 3)   // host: scalar loads only
 #define PCG_LOAD(inside) (valid && (inside))   // a gathered row is read for a live centre only
 #else
 #define PCG_KERNEL pointconv_agg_grad_kernel
 #define PCG_LENS_PARAM
+#define PCG_LENS
+#define PCG_LENS_MISALIGNED
 #define PCG_LOAD(inside) (inside)
 #endif
 
@@ -257,6 +262,29 @@ unsigned grad_grid(long long total) {
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
     const long long want = (total + 2 * WAVES - 1) / (2 * WAVES), cap = cus;  // one resident workgroup per CU: 176 accumulators per lane, one wave per SIMD
     return (unsigned)(want < cap ? want : cap);
+}
+
+// ---- host side of mcp_pointconv_agg_grad (PCG_LEN 0) and mcp_pointconv_agg_grad_lengths (PCG_LEN 1), stated once: the argument
+// checks, the grid and LDS size from the PADDED shape, the two launches ----
+int pcg_run(int b, int n, int s, int d, int k, const float *s_xyz, const float *new_xyz, const float *s_points, const int *idx, const float *w0,
+            const float *b0, const float *w1, const float *b1, const float *w2, const float *b2, const float *grad_out, float *grad_new_xyz,
+            float *grad_gxyz, float *grad_rows, float *grad_weights, void *workspace, size_t workspace_bytes, hipStream_t st PCG_LENS_PARAM) {
+    MCP_CHECK_ARGS(b > 0 && n > 0 && s > 0 && s_xyz && new_xyz && s_points && idx && w0 && b0 && w1 && b1 && w2 && b2 && grad_out && grad_new_xyz &&
+                   grad_gxyz && grad_rows && grad_weights && workspace);
+    if (k != K || d < 4 || (d & 3) || d > MAX_D) return MCP_ERR_UNSUPPORTED;
+    if (((((uintptr_t)s_points) | ((uintptr_t)grad_out) | ((uintptr_t)grad_rows)) & 15) PCG_LENS_MISALIGNED) return MCP_ERR_BAD_ARG;
+    const long long total = (long long)b * s;
+    const unsigned grid = grad_grid(total);
+    if (workspace_bytes < (size_t)grid * G_FLOATS * sizeof(float)) return MCP_ERR_BAD_ARG;
+    size_t lds = (size_t)WAVES * 2 * (d + 3) * WN * sizeof(float);
+    if (lds < (size_t)WAVES * G_FLOATS * sizeof(float)) lds = (size_t)WAVES * G_FLOATS * sizeof(float);
+    if (const int rc = mcp_allow_lds<PCG_KERNEL>()) return rc;
+    mcp_prof_begin(MCP_KERNEL_POINTCONV, st);
+    hipLaunchKernelGGL(PCG_KERNEL, dim3(grid), dim3(64 * WAVES), lds, st, total, n, s, d, s_xyz, new_xyz, s_points, idx, w0, b0, w1, b1, w2, b2, grad_out,
+                       grad_new_xyz, grad_gxyz, grad_rows, static_cast<float *>(workspace) PCG_LENS);
+    hipLaunchKernelGGL(pointconv_grad_reduce_kernel, dim3(1), dim3(256), 0, st, static_cast<const float *>(workspace), (int)grid, grad_weights);
+    mcp_prof_end(MCP_KERNEL_POINTCONV, st);
+    return mcp_launch_status();
 }
 
 }  // namespace

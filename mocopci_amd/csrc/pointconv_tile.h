@@ -8,7 +8,11 @@
 // (zero, not leaky(bias)).  A workgroup whose centres are all padded writes its zeros and skips phases 1-3; the condition depends
 // on p0 alone, so every barrier of the persistent loop stays block-uniform.  Live centres run the dense arithmetic in the dense
 // order: the same bits.
+// The host side of both units is at the end of this file, stated once too (pc_agg_run, pc_linear_run): the exported functions of
+// pointconv.hip and pointconv_lengths.hip are thin calls into it, with an empty pack and with one PcLengths.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 #include "mfma_split.h"
 
@@ -583,6 +587,63 @@ __global__ __launch_bounds__(8 * D) __attribute__((amdgpu_waves_per_eu(D == 32 ?
             }
         }
     }
+}
+
+// ---- host side, stated once: the argument checks, the dispatch, the grids and the launches of mcp_pointconv_agg[_lengths] and
+// mcp_pointconv_linear[_lengths].  `len` is empty (pointconv.hip) or one PcLengths (pointconv_lengths.hip) and goes to the kernel of
+// the same pack; everything else is decided from the PADDED shape, so a call with every length s launches what the dense call
+// launches.  The lengths' own check (a 4-byte aligned array: scalar loads) sits beside the other alignment checks, so a call that
+// fails several checks gets the code it always got. ----
+template <typename... L>
+int pc_agg_run(int b, int n, int s, int d, int k, const float *s_xyz, const float *new_xyz, const float *s_points, const int *idx, const float *w0,
+               const float *b0, const float *w1, const float *b1, const float *w2, const float *b2, float *out, hipStream_t st, L... len) {
+    MCP_CHECK_ARGS(b > 0 && n > 0 && s > 0 && d > 0 && s_xyz && new_xyz && s_points && idx && w0 && b0 && w1 && b1 && w2 && b2 && out);
+    if (k != K) return MCP_ERR_UNSUPPORTED;
+    if ((((uintptr_t)out) & 15) || (... || (((uintptr_t)len.qlen) & 3))) return MCP_ERR_BAD_ARG;
+    const long long total = (long long)b * s;
+    const bool vec4 = !(d & 3) && !(((uintptr_t)s_points) & 15);  // float4 gathers of 4 adjacent channels need both
+    mcp_prof_begin(MCP_KERNEL_POINTCONV, st);
+    // one workgroup per `ppb` points (no persistent loop in practice): the dispatcher balances around whatever else holds CUs
+    auto launch = [&](auto kern, int ppb, int threads) {
+        const unsigned grid = (unsigned)min((total + ppb - 1) / ppb, 1LL << 20);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), 0, st, total, n, s, d, s_xyz, new_xyz, s_points, idx, w0, b0, w1, b1, w2, b2, out, len...);
+    };
+    if (total <= 16384 || !vec4) {
+        if (d >= 256 && total <= 8192) launch(pointconv_agg_lowlevel_kernel<1024, L...>, LPPB, 1024);
+        else launch(pointconv_agg_lowlevel_kernel<256, L...>, LPPB, 256);
+    }
+    // points per workgroup so that PPB * d / 4 phase-2 items fill the 256 threads: 32 at d = 32, 16 at d = 64, 8 from d = 128 up
+    else if (d <= 32) launch(pointconv_agg_kernel<256, 32, L...>, 32, 256);
+    else if (d <= 64) launch(pointconv_agg_kernel<256, 16, L...>, 16, 256);
+    else launch(pointconv_agg_kernel<256, 8, L...>, 8, 256);
+    mcp_prof_end(MCP_KERNEL_POINTCONV, st);
+    return mcp_launch_status();
+}
+
+template <typename... L>
+int pc_linear_run(int b, int n, int s, int d, int k, const float *s_xyz, const float *new_xyz, const float *s_points, const int *idx, const float *w0,
+                  const float *b0, const float *w1, const float *b1, const float *w2, const float *b2, const float *packed, int c_out, float slope,
+                  float *out, hipStream_t st, L... len) {
+    MCP_CHECK_ARGS(b > 0 && n > 0 && s > 0 && d > 0 && s_xyz && new_xyz && s_points && idx && w0 && b0 && w1 && b1 && w2 && b2 && packed && out);
+    if (k != K || !((d == 32 && c_out == 32) || (d == 64 && c_out == 64))) return MCP_ERR_UNSUPPORTED;
+    if (((((uintptr_t)out) | ((uintptr_t)s_points) | ((uintptr_t)packed)) & 15) || (... || (((uintptr_t)len.qlen) & 3))) return MCP_ERR_BAD_ARG;
+    const long long total = (long long)b * s;
+    const unsigned grid = (unsigned)min((total + FPPB - 1) / FPPB, 1LL << 20);
+    mcp_prof_begin(MCP_KERNEL_POINTCONV, st);
+    auto launch = [&](auto width, auto tiles) {   // as compile-time constants (decltype(width)::value)
+        constexpr int D = decltype(width)::value, NT = decltype(tiles)::value;
+        using C = FusedCfg<D, NT>;
+        constexpr auto kern = pointconv_linear_kernel<D, NT, L...>;
+        if (const int rc = mcp_allow_lds<kern>()) return rc;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(C::THREADS), C::LDS_BYTES, st, total, n, s, s_xyz, new_xyz, s_points, idx, w0, b0, w1, b1, w2, b2, packed,
+                           c_out, slope, out, len...);
+        return (int)MCP_OK;
+    };
+    using std::integral_constant;
+    const int rc = d == 32 ? launch(integral_constant<int, 32>{}, integral_constant<int, 1>{}) : launch(integral_constant<int, 64>{}, integral_constant<int, 2>{});
+    if (rc != MCP_OK) return rc;
+    mcp_prof_end(MCP_KERNEL_POINTCONV, st);
+    return mcp_launch_status();
 }
 
 }  // namespace

@@ -446,12 +446,7 @@ MCP_EXPORT int mcp_ptblock_grad(int b, int n, int c, int k, int qkv_stride, cons
     const unsigned grid = grad_grid(total);
     uint4 *wt = static_cast<uint4 *>(workspace);
     float *partial = reinterpret_cast<float *>(wt + 3 * W_U4);
-    static McpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ptblock_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_once.done();
-    }
+    if (const int rc = mcp_allow_lds<ptblock_grad_kernel>()) return rc;
     mcp_prof_begin(MCP_KERNEL_PTBLOCK, s);
     hipLaunchKernelGGL(ptblock_transposed_images_kernel, dim3(4, 3), dim3(256), 0, s, wt, wd2, wg1, wg2);
     hipLaunchKernelGGL(ptblock_grad_kernel, dim3(grid), dim3(64 * WAVES), LDS_BYTES, s, total, n, qkv_stride, xyz, q, kf, vf, idx, wd1, bd1, wd2, bd2, wg1, bg1,

@@ -238,13 +238,8 @@ MCP_EXPORT int mcp_scatter_segments(int b, int t, int n, const int *idx, int *or
     const int cap = long_rows_cap(b, t);
     const hipError_t e = hipMemsetAsync(long_list, 0, sizeof(int), s);
     if (e != hipSuccess) return (int)e;
-    static McpPerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        hipError_t a_ = hipFuncSetAttribute(reinterpret_cast<const void *>(csr_count_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (a_ == hipSuccess) a_ = hipFuncSetAttribute(reinterpret_cast<const void *>(csr_fill_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (a_ != hipSuccess) return (int)a_;
-        attr_once.done();
-    }
+    if (const int rc = mcp_allow_lds<csr_count_kernel>()) return rc;
+    if (const int rc = mcp_allow_lds<csr_fill_kernel>()) return rc;
     const int per = (t + CHUNKS - 1) / CHUNKS;
     const size_t lds = (size_t)n * sizeof(int);
     hipLaunchKernelGGL(csr_count_kernel, dim3(CHUNKS, b), dim3(CT), lds, s, t, n, per, idx, hist);

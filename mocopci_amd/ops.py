@@ -198,7 +198,8 @@ def _group_rows_grad(grad_out, idx, n, segments=None):
 class _PointConvAggFn(torch.autograd.Function):
     """mcp_pointconv_agg with its hand-written backward (mcp_pointconv_agg_grad): WeightNet recomputed per (centre, neighbour) pair in
     the backward kernel, per-neighbour gradients through the deterministic segmented scatter, weight gradients fixed-order sums.
-    qlen: (B,) int32 device tensor or None -- per-element centre lengths (the *_lengths entries), carried to the backward."""
+    qlen: (B,) int32 device tensor or None -- per-element centre lengths, carried to the backward.  Both directions call the *_lengths
+    entries: with a null qlen those are the dense entries themselves."""
 
     @staticmethod
     def forward(ctx, be, idx, s_xyz, new_xyz, s_points, w0, b0, w1, b1, w2, b2, qlen):
@@ -219,9 +220,8 @@ class _PointConvAggFn(torch.autograd.Function):
         d_w = torch.empty((lib.mcp_pointconv_agg_grad_floats(),), dtype=torch.float32, device=dev)
         need = lib.mcp_pointconv_agg_grad_workspace_bytes(B, S)
         ws = torch.empty((need,), dtype=torch.uint8, device=dev)
-        entry, lens = ("mcp_pointconv_agg_grad", ()) if qlen is None else ("mcp_pointconv_agg_grad_lengths", (_lib.iptr(qlen),))
-        _call(entry, s_points, B, N, S, D, 32, _lib.fptr(s_xyz), _lib.fptr(new_xyz), _lib.fptr(s_points), _lib.iptr(idx), *lens,
-              _lib.fptr(w0), _lib.fptr(b0), _lib.fptr(w1), _lib.fptr(b1), _lib.fptr(w2), _lib.fptr(b2), _lib.fptr(grad_out), _lib.fptr(d_new),
+        _call("mcp_pointconv_agg_grad_lengths", s_points, B, N, S, D, 32, _lib.fptr(s_xyz), _lib.fptr(new_xyz), _lib.fptr(s_points), _lib.iptr(idx),
+              _len_ptr(qlen), _lib.fptr(w0), _lib.fptr(b0), _lib.fptr(w1), _lib.fptr(b1), _lib.fptr(w2), _lib.fptr(b2), _lib.fptr(grad_out), _lib.fptr(d_new),
               _lib.fptr(d_gxyz), _lib.fptr(d_rows), _lib.fptr(d_w), ws.data_ptr(), need)
         d_sxyz = d_spoints = None
         if ctx.needs_input_grad[2] or ctx.needs_input_grad[4]:
@@ -295,9 +295,16 @@ def _len_ptr(lens):
     return None if lens is None else _lib.iptr(lens)
 
 
-class _AttentionSmallFn(torch.autograd.Function):
-    """mcp_attention_small (head dims 8 / 16) with its hand-written backward (mcp_attention_small_grad: row statistics, dQ, dK/dV).
-    qlen / klen: (BF,) int32 device tensors or None -- per-element lengths (the *_lengths entries), carried to the backward."""
+class _AttentionFn(torch.autograd.Function):
+    """The attention kernels with their hand-written backward, by head width: 8 / 16 mcp_attention_small_* (row statistics, dQ, dK/dV),
+    32 / 64 / 256 mcp_attention_wide_* (D = dO . O, dQ, dK/dV on fp32 MFMA).  The forward keeps the rows' log-sum-exp for the backward
+    (no statistics pass, no second forward there); dropout is the in-kernel hash mask.
+    qlen / klen: (BF,) int32 device tensors or None -- per-element lengths, carried to the backward.  Both directions call the *_lengths
+    entries: with both lengths null those are the dense entries themselves."""
+
+    @staticmethod
+    def _family(hd):
+        return "mcp_attention_small" if hd in (8, 16) else "mcp_attention_wide"
 
     @staticmethod
     def forward(ctx, be, q, kv, heads, scale, drop_p, seed, qlen=None, klen=None):
@@ -305,13 +312,9 @@ class _AttentionSmallFn(torch.autograd.Function):
         BF, Nq, C = q.shape
         Nk = kv.shape[1]
         out = torch.empty((BF, Nq, C), dtype=torch.float32, device=q.device)
-        lse = torch.empty((BF, heads, Nq), dtype=torch.float32, device=q.device)   # kept for the backward: no statistics pass there
-        if qlen is None and klen is None:
-            _call("mcp_attention_small_lse", q, BF, Nq, Nk, heads, C // heads, _lib.fptr(q), C, _lib.fptr(kv), 2 * C, kv.data_ptr() + 4 * C, 2 * C,
-                  float(scale), float(drop_p), int(seed), out.data_ptr(), lse.data_ptr())
-        else:
-            _call("mcp_attention_small_lse_lengths", q, BF, Nq, Nk, heads, C // heads, _lib.fptr(q), C, _lib.fptr(kv), 2 * C, kv.data_ptr() + 4 * C, 2 * C,
-                  float(scale), float(drop_p), int(seed), out.data_ptr(), lse.data_ptr(), _len_ptr(qlen), _len_ptr(klen))
+        lse = torch.empty((BF, heads, Nq), dtype=torch.float32, device=q.device)
+        _call(_AttentionFn._family(C // heads) + "_lse_lengths", q, BF, Nq, Nk, heads, C // heads, _lib.fptr(q), C, _lib.fptr(kv), 2 * C,
+              kv.data_ptr() + 4 * C, 2 * C, float(scale), float(drop_p), int(seed), out.data_ptr(), lse.data_ptr(), _len_ptr(qlen), _len_ptr(klen))
         ctx.heads, ctx.scale, ctx.drop_p, ctx.seed = heads, scale, drop_p, seed
         ctx.save_for_backward(q, kv, out, lse, qlen, klen)
         return out
@@ -320,64 +323,25 @@ class _AttentionSmallFn(torch.autograd.Function):
     def backward(ctx, grad_out):
         q, kv, out, lse, qlen, klen = ctx.saved_tensors
         BF, Nq, C = q.shape
-        Nk, heads = kv.shape[1], ctx.heads
-        lib = _lib.load()
+        Nk, heads, hd = kv.shape[1], ctx.heads, C // ctx.heads
+        lib, family = _lib.load(), _AttentionFn._family(hd)
         grad_out = grad_out.contiguous()
         dq, dkv = torch.empty_like(q), torch.empty_like(kv)
-        need = lib.mcp_attention_small_grad_workspace_bytes(BF, Nq, heads)
+        need = (lib.mcp_attention_small_grad_workspace_bytes(BF, Nq, heads) if hd in (8, 16)
+                else lib.mcp_attention_wide_grad_workspace_bytes(BF, Nq, Nk, heads, hd))
         ws = torch.empty((need,), dtype=torch.uint8, device=q.device)
-        if qlen is None and klen is None:
-            _call("mcp_attention_small_grad_lse", q, BF, Nq, Nk, heads, C // heads, q.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 4 * C, 2 * C,
-                  float(ctx.scale), float(ctx.drop_p), int(ctx.seed), _lib.fptr(out), _lib.fptr(grad_out), _lib.fptr(lse), _lib.fptr(dq), _lib.fptr(dkv),
-                  ws.data_ptr(), need)
-        else:
-            _call("mcp_attention_small_grad_lse_lengths", q, BF, Nq, Nk, heads, C // heads, q.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 4 * C,
-                  2 * C, float(ctx.scale), float(ctx.drop_p), int(ctx.seed), _lib.fptr(out), _lib.fptr(grad_out), _lib.fptr(lse), _lib.fptr(dq),
-                  _lib.fptr(dkv), ws.data_ptr(), need, _len_ptr(qlen), _len_ptr(klen))
+        _call(family + "_grad_lse_lengths", q, BF, Nq, Nk, heads, hd, q.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 4 * C, 2 * C,
+              float(ctx.scale), float(ctx.drop_p), int(ctx.seed), _lib.fptr(out), _lib.fptr(grad_out), _lib.fptr(lse), _lib.fptr(dq), _lib.fptr(dkv),
+              ws.data_ptr(), need, _len_ptr(qlen), _len_ptr(klen))
         return None, dq, dkv, None, None, None, None, None, None
 
 
-class _AttentionWideFn(torch.autograd.Function):
-    """mcp_attention_wide (head widths 32 / 64 / 256) with its hand-written backward (mcp_attention_wide_grad_lse: D = dO . O, dQ, dK/dV
-    on fp32 MFMA); the forward keeps the rows' log-sum-exp, dropout is the in-kernel hash mask of the narrow heads.
-    qlen / klen: (BF,) int32 device tensors or None -- per-element lengths (the *_lengths entries), carried to the backward."""
+class _AttentionSmallFn(_AttentionFn):
+    """_AttentionFn under the name its autograd node carries at head dims 8 / 16 (profiles and graph checks tell the families apart)."""
 
-    @staticmethod
-    def forward(ctx, be, q, kv, heads, scale, drop_p, seed, qlen=None, klen=None):
-        q, kv = q.detach().contiguous(), kv.detach().contiguous()
-        BF, Nq, C = q.shape
-        Nk = kv.shape[1]
-        out = torch.empty((BF, Nq, C), dtype=torch.float32, device=q.device)
-        lse = torch.empty((BF, heads, Nq), dtype=torch.float32, device=q.device)   # kept for the backward: no second forward there
-        if qlen is None and klen is None:
-            _call("mcp_attention_wide_lse", q, BF, Nq, Nk, heads, C // heads, _lib.fptr(q), C, _lib.fptr(kv), 2 * C, kv.data_ptr() + 4 * C, 2 * C,
-                  float(scale), float(drop_p), int(seed), out.data_ptr(), lse.data_ptr())
-        else:
-            _call("mcp_attention_wide_lse_lengths", q, BF, Nq, Nk, heads, C // heads, _lib.fptr(q), C, _lib.fptr(kv), 2 * C, kv.data_ptr() + 4 * C, 2 * C,
-                  float(scale), float(drop_p), int(seed), out.data_ptr(), lse.data_ptr(), _len_ptr(qlen), _len_ptr(klen))
-        ctx.heads, ctx.scale, ctx.drop_p, ctx.seed = heads, scale, drop_p, seed
-        ctx.save_for_backward(q, kv, out, lse, qlen, klen)
-        return out
 
-    @staticmethod
-    def backward(ctx, grad_out):
-        q, kv, out, lse, qlen, klen = ctx.saved_tensors
-        BF, Nq, C = q.shape
-        Nk, heads = kv.shape[1], ctx.heads
-        lib = _lib.load()
-        grad_out = grad_out.contiguous()
-        dq, dkv = torch.empty_like(q), torch.empty_like(kv)
-        need = lib.mcp_attention_wide_grad_workspace_bytes(BF, Nq, Nk, heads, C // heads)
-        ws = torch.empty((need,), dtype=torch.uint8, device=q.device)
-        if qlen is None and klen is None:
-            _call("mcp_attention_wide_grad_lse", q, BF, Nq, Nk, heads, C // heads, q.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 4 * C, 2 * C,
-                  float(ctx.scale), float(ctx.drop_p), int(ctx.seed), _lib.fptr(out), _lib.fptr(grad_out), _lib.fptr(lse), _lib.fptr(dq), _lib.fptr(dkv),
-                  ws.data_ptr(), need)
-        else:
-            _call("mcp_attention_wide_grad_lse_lengths", q, BF, Nq, Nk, heads, C // heads, q.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 4 * C,
-                  2 * C, float(ctx.scale), float(ctx.drop_p), int(ctx.seed), _lib.fptr(out), _lib.fptr(grad_out), _lib.fptr(lse), _lib.fptr(dq),
-                  _lib.fptr(dkv), ws.data_ptr(), need, _len_ptr(qlen), _len_ptr(klen))
-        return None, dq, dkv, None, None, None, None, None, None
+class _AttentionWideFn(_AttentionFn):
+    """_AttentionFn under the name its autograd node carries at head widths 32 / 64 / 256."""
 
 
 def _prelu_drop_fwd(z, slope, drop_p=0.0, seed=0):
@@ -2268,34 +2232,24 @@ class HipBackend:
         (its idx row, new_xyz, the gathered rows, the upstream gradient: they may hold NaN or out-of-range indices), its row is
         exact zeros, as are its gradient rows, and it adds nothing to the WeightNet's weight gradients.  No synchronisation."""
         D = s_points.shape[-1]
-        if centre_lengths is not None:
-            qlen = lengths_tensor(centre_lengths, new_xyz.shape[0], new_xyz.shape[1], s_points.device)
-            if not grad.wants_grad(s_xyz, new_xyz, s_points, w0, b0, w1, b1, w2, b2):
-                return self._pointconv_agg(s_xyz, new_xyz, s_points, idx, w0, b0, w1, b1, w2, b2, qlen=qlen)
-            if idx.shape[-1] != 32 or D % 4 or D > 256 or tuple(w2.shape) != (8, 8):   # no backward kernel: the masked torch formulation
-                return grad.run(lambda *a: self._pointconv_agg(*a, qlen=qlen),
-                                lambda *a: grad.pointconv_agg_lengths_twin(self.group_rows, *a, qlen), s_xyz, new_xyz, s_points, idx,
-                                w0, b0, w1, b1, w2, b2)
-            return _PointConvAggFn.apply(self, idx.contiguous(), s_xyz, new_xyz, s_points, w0, b0, w1, b1, w2, b2, qlen)
+        qlen = lengths_tensor(centre_lengths, new_xyz.shape[0], new_xyz.shape[1], s_points.device)   # None stays None
         if not grad.wants_grad(s_xyz, new_xyz, s_points, w0, b0, w1, b1, w2, b2):
-            return self._pointconv_agg(s_xyz, new_xyz, s_points, idx, w0, b0, w1, b1, w2, b2)
-        if idx.shape[-1] != 32 or D % 4 or D > 256 or tuple(w2.shape) != (8, 8):   # shapes the backward kernel is not built for
-            return grad.run(self._pointconv_agg, lambda *a: grad.pointconv_agg_twin(self.group_rows, *a), s_xyz, new_xyz, s_points, idx,
-                            w0, b0, w1, b1, w2, b2)
-        return _PointConvAggFn.apply(self, idx.contiguous(), s_xyz, new_xyz, s_points, w0, b0, w1, b1, w2, b2, None)
+            return self._pointconv_agg(s_xyz, new_xyz, s_points, idx, w0, b0, w1, b1, w2, b2, qlen=qlen)
+        if idx.shape[-1] != 32 or D % 4 or D > 256 or tuple(w2.shape) != (8, 8):   # no backward kernel: the (masked) torch formulation
+            twin = ((lambda *a: grad.pointconv_agg_twin(self.group_rows, *a)) if qlen is None
+                    else (lambda *a: grad.pointconv_agg_lengths_twin(self.group_rows, *a, qlen)))
+            return grad.run(lambda *a: self._pointconv_agg(*a, qlen=qlen), twin, s_xyz, new_xyz, s_points, idx, w0, b0, w1, b1, w2, b2)
+        return _PointConvAggFn.apply(self, idx.contiguous(), s_xyz, new_xyz, s_points, w0, b0, w1, b1, w2, b2, qlen)
 
     def _pointconv_agg(self, s_xyz, new_xyz, s_points, idx, w0, b0, w1, b1, w2, b2, qlen=None):
         s_xyz, new_xyz, s_points, w0, b0, w1, b1, w2, b2 = (t.contiguous() for t in (s_xyz, new_xyz, s_points, w0, b0, w1, b1, w2, b2))
         B, N, D = s_points.shape
         S = new_xyz.shape[1]
         out = torch.empty((B, S, (D + 3) * 8), dtype=torch.float32, device=s_points.device)
-        if qlen is not None:
-            _call("mcp_pointconv_agg_lengths", s_points, B, N, S, D, idx.shape[-1], _lib.fptr(s_xyz), _lib.fptr(new_xyz), _lib.fptr(s_points),
-                  _lib.iptr(idx), _lib.iptr(qlen), _lib.fptr(w0), _lib.fptr(b0), _lib.fptr(w1), _lib.fptr(b1), _lib.fptr(w2), _lib.fptr(b2),
-                  _lib.fptr(out))
-            return out
-        _call("mcp_pointconv_agg", s_points, B, N, S, D, idx.shape[-1], _lib.fptr(s_xyz), _lib.fptr(new_xyz), _lib.fptr(s_points),
-              _lib.iptr(idx), _lib.fptr(w0), _lib.fptr(b0), _lib.fptr(w1), _lib.fptr(b1), _lib.fptr(w2), _lib.fptr(b2), _lib.fptr(out))
+        # qlen None: a null pointer, and the entry is mcp_pointconv_agg itself
+        _call("mcp_pointconv_agg_lengths", s_points, B, N, S, D, idx.shape[-1], _lib.fptr(s_xyz), _lib.fptr(new_xyz), _lib.fptr(s_points),
+              _lib.iptr(idx), _len_ptr(qlen), _lib.fptr(w0), _lib.fptr(b0), _lib.fptr(w1), _lib.fptr(b1), _lib.fptr(w2), _lib.fptr(b2),
+              _lib.fptr(out))
         return out
 
     _PCL_MIN_ROWS = 16384   # from here mcp_linear runs linear_kernel, whose arithmetic the one-launch form reproduces bit for bit
@@ -2320,15 +2274,10 @@ class HipBackend:
         S, n = new_xyz.shape[1], w.shape[0]
         pk = packed if packed is not None else self.pointconv_linear_pack(w, b)
         out = torch.empty((B, S, n), dtype=torch.float32, device=s_points.device)
-        if centre_lengths is not None:
-            qlen = lengths_tensor(centre_lengths, B, S, s_points.device)
-            _call("mcp_pointconv_linear_lengths", s_points, B, N, S, D, idx.shape[-1], _lib.fptr(s_xyz), _lib.fptr(new_xyz),
-                  _lib.fptr(s_points), _lib.iptr(idx), _lib.iptr(qlen), _lib.fptr(w0), _lib.fptr(b0), _lib.fptr(w1), _lib.fptr(b1),
-                  _lib.fptr(w2), _lib.fptr(b2), _lib.fptr(pk), n, float(slope), _lib.fptr(out))
-            return out
-        _call("mcp_pointconv_linear", s_points, B, N, S, D, idx.shape[-1], _lib.fptr(s_xyz), _lib.fptr(new_xyz), _lib.fptr(s_points),
-              _lib.iptr(idx), _lib.fptr(w0), _lib.fptr(b0), _lib.fptr(w1), _lib.fptr(b1), _lib.fptr(w2), _lib.fptr(b2), _lib.fptr(pk), n,
-              float(slope), _lib.fptr(out))
+        qlen = lengths_tensor(centre_lengths, B, S, s_points.device)   # None stays None: the entry is then mcp_pointconv_linear itself
+        _call("mcp_pointconv_linear_lengths", s_points, B, N, S, D, idx.shape[-1], _lib.fptr(s_xyz), _lib.fptr(new_xyz),
+              _lib.fptr(s_points), _lib.iptr(idx), _len_ptr(qlen), _lib.fptr(w0), _lib.fptr(b0), _lib.fptr(w1), _lib.fptr(b1),
+              _lib.fptr(w2), _lib.fptr(b2), _lib.fptr(pk), n, float(slope), _lib.fptr(out))
         return out
 
     def attention(self, q, kv, heads, scale=None, dropout_p=0.0, query_lengths=None, key_lengths=None):
@@ -2344,61 +2293,37 @@ class HipBackend:
         hd = C // heads
         if scale is None:
             scale = hd ** -0.5
-        fn = _AttentionSmallFn if hd in (8, 16) else _AttentionWideFn
-        if query_lengths is not None or key_lengths is not None:
-            qlen = lengths_tensor(query_lengths, BF, Nq, q.device)
-            klen = lengths_tensor(key_lengths, BF, Nk, q.device)
-            if hd not in (8, 16, 32, 64, 256):
-                if dropout_p > 0.0:
-                    raise RuntimeError("attention dropout inside the kernel: head dims 8 / 16 / 32 / 64 / 256")
-                return grad.attention_lengths_twin(q, kv, heads, float(scale), qlen, klen)   # the dense masked formulation
-            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if dropout_p > 0.0 else 0  # CPU generator: no device synchronisation
-            if grad.wants_grad(q, kv):
-                return fn.apply(self, q, kv, heads, float(scale), float(dropout_p), seed, qlen, klen)
-            return self._attention_lengths(q, kv, heads, float(scale), float(dropout_p), seed, qlen, klen)
-        if dropout_p > 0.0:
-            if hd not in (8, 16, 32, 64, 256):
+        qlen = lengths_tensor(query_lengths, BF, Nq, q.device)   # None stays None
+        klen = lengths_tensor(key_lengths, BF, Nk, q.device)
+        if hd not in (8, 16, 32, 64, 256):  # head dims neither kernel is built for: the dense (masked) formulation, the twins' arithmetic
+            if dropout_p > 0.0:
                 raise RuntimeError("attention dropout inside the kernel: head dims 8 / 16 / 32 / 64 / 256")
-            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())  # CPU generator: no device synchronisation
-            if grad.wants_grad(q, kv):
-                return fn.apply(self, q, kv, heads, float(scale), float(dropout_p), seed)
-            return self._attention(q, kv, heads, float(scale), float(dropout_p), seed)
-        if hd not in (8, 16, 32, 64, 256):  # head dims neither kernel is built for: the dense formulation (same arithmetic as the twin)
-            return grad.attention_twin(q, kv, heads, float(scale))
+            if qlen is None and klen is None:
+                return grad.attention_twin(q, kv, heads, float(scale))
+            return grad.attention_lengths_twin(q, kv, heads, float(scale), qlen, klen)
+        seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if dropout_p > 0.0 else 0  # CPU generator: no device synchronisation
         if grad.wants_grad(q, kv):
-            return fn.apply(self, q, kv, heads, float(scale), 0.0, 0)
-        return self._attention(q, kv, heads, float(scale))
+            fn = _AttentionSmallFn if hd in (8, 16) else _AttentionWideFn
+            return fn.apply(self, q, kv, heads, float(scale), float(dropout_p), seed, qlen, klen)
+        return self._attention(q, kv, heads, float(scale), float(dropout_p), seed, qlen, klen)
 
-    def _attention(self, q, kv, heads, scale, drop_p=0.0, seed=0):
-        q, kv = q.contiguous(), kv.contiguous()
-        BF, Nq, C = q.shape
-        Nk, hd = kv.shape[1], C // heads
-        out = torch.empty((BF, Nq, C), dtype=torch.float32, device=q.device)
-        if drop_p > 0.0:
-            name = "mcp_attention_small_dropout" if hd in (8, 16) else "mcp_attention_wide_dropout"
-            _call(name, q, BF, Nq, Nk, heads, hd, q.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 4 * C, 2 * C,
-                  float(scale), float(drop_p), int(seed), out.data_ptr())
-            return out
-        # head dims 8/16: S on MFMA, P.V on packed FMAs; 32/64/256 (ei3, Cross_Frame_Att): both products on MFMA
-        name = "mcp_attention_small" if hd in (8, 16) else "mcp_attention_wide"
-        _call(name, q, BF, Nq, Nk, heads, hd, q.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 4 * C, 2 * C,
-              float(scale), out.data_ptr(), C)
-        return out
-
-    def _attention_lengths(self, q, kv, heads, scale, drop_p, seed, qlen, klen):
-        """_attention over a padded batch: qlen / klen (BF,) int32 device tensors or None."""
+    def _attention(self, q, kv, heads, scale, drop_p=0.0, seed=0, qlen=None, klen=None):
+        """The forward alone: qlen / klen (BF,) int32 device tensors or None.  With both None the *_lengths entries below are the dense
+        ones (mcp_attention; mcp_attention_{small,wide}_dropout, which is the *_lse forward without its log-sum-exp).
+        Head dims 8/16: S on MFMA, P.V on packed FMAs; 32/64/256 (ei3, Cross_Frame_Att): both products on MFMA."""
         q, kv = q.contiguous(), kv.contiguous()
         BF, Nq, C = q.shape
         Nk, hd = kv.shape[1], C // heads
         out = torch.empty((BF, Nq, C), dtype=torch.float32, device=q.device)
         if drop_p > 0.0:   # the training forward without its log-sum-exp
-            name = "mcp_attention_small_lse_lengths" if hd in (8, 16) else "mcp_attention_wide_lse_lengths"
-            _call(name, q, BF, Nq, Nk, heads, hd, q.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 4 * C, 2 * C,
+            _call(_AttentionFn._family(hd) + "_lse_lengths", q, BF, Nq, Nk, heads, hd, q.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 4 * C, 2 * C,
                   float(scale), float(drop_p), int(seed), out.data_ptr(), None, _len_ptr(qlen), _len_ptr(klen))
             return out
         _call("mcp_attention_lengths", q, BF, Nq, Nk, heads, hd, q.data_ptr(), C, kv.data_ptr(), 2 * C, kv.data_ptr() + 4 * C, 2 * C, 0,
               float(scale), _len_ptr(qlen), _len_ptr(klen), out.data_ptr(), C)
         return out
+
+    _attention_lengths = _attention   # the name the padded-batch callers use, same arguments
 
     def prelu_dropout(self, z, slope, drop_p):
         """dropout(prelu(z, slope), drop_p) of a training forward (Mlp_T's act + drop, mocopci.py:1561-1562) as one pass, with a
@@ -2420,13 +2345,9 @@ class HipBackend:
             if not (t.is_cuda and t.dtype == torch.float32 and t.stride(2) == 1 and t.stride(0) == n * t.stride(1)):
                 raise RuntimeError("attention_rot: (BF,N,C) float32 CUDA views with unit channel stride and dense batches")
         out = torch.empty((BF, Nq, C), dtype=torch.float32, device=q.device)
-        if query_lengths is not None or key_lengths is not None:
-            qlen, klen = lengths_tensor(query_lengths, BF, Nq, q.device), lengths_tensor(key_lengths, BF, Nk, q.device)
-            _call("mcp_attention_lengths", q, BF, Nq, Nk, heads, hd, q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), v.data_ptr(),
-                  v.stride(1), int(kv_shift), float(hd ** -0.5 if scale is None else scale), _len_ptr(qlen), _len_ptr(klen), out.data_ptr(), C)
-            return out
-        _call("mcp_attention", q, BF, Nq, Nk, heads, hd, q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), v.data_ptr(), v.stride(1),
-              int(kv_shift), float(hd ** -0.5 if scale is None else scale), out.data_ptr(), C)
+        qlen, klen = lengths_tensor(query_lengths, BF, Nq, q.device), lengths_tensor(key_lengths, BF, Nk, q.device)   # None stays None
+        _call("mcp_attention_lengths", q, BF, Nq, Nk, heads, hd, q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), v.data_ptr(),
+              v.stride(1), int(kv_shift), float(hd ** -0.5 if scale is None else scale), _len_ptr(qlen), _len_ptr(klen), out.data_ptr(), C)
         return out
 
     def add_layernorm(self, x, y=None, bias=None, eps=1e-6):

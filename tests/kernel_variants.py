@@ -60,20 +60,20 @@ def _mlp2(rows, cin, hidden, cout):
 
 
 def _attention(bf, nq, nk, heads, hd):
-    if hd in (8, 16):                                                # attention_any, attention.hip:532-538
+    if hd in (8, 16):                                                # attention_forward_run, csrc/attention_forward.h
         return f"attention_small_kernel<{hd}>"
-    if hd in (32, 64):                                               # attention.hip:541-542
+    if hd in (32, 64):                                               # attention_forward_run: widths 32 / 64 never split the keys
         return f"attention_wide_kernel<{hd}>"
-    if hd == 256:                                                    # attention.hip:545-547
+    if hd == 256:                                                    # attention_forward_run: wide_keys_split
         if _cdiv(nq, 128) * heads * bf * 4 < 1024 and nk >= 128:
             return "attention_wide_ksplit_kernel<256>"
         return "attention_wide_kernel<256>"
-    raise ValueError(f"attention: head width {hd} is not built")      # mcp_attention, attention.hip:574
+    raise ValueError(f"attention: head width {hd} is not built")      # mcp_attention, attention.hip
 
 
 # ---- the fused point layers.  launch_grid() mirrors the grid arithmetic beside each dispatch, so that test_kernel_variants_cpu.py can
 # check that the cases reach the loop edges their comments name ----
-POINTCONV_LOWLEVEL_MAX = 16384   # mcp_pointconv_agg, pointconv.hip:474
+POINTCONV_LOWLEVEL_MAX = 16384   # pc_agg_run, csrc/pointconv_tile.h
 FUSION_WAVES, FUSION_GRID_CAP = 4, 4096                      # fusion.hip:34, :298
 CROSS_WAVES = {64: 4, 128: 8, 256: 4}                        # CrossShape<D>::NW, cross.hip:150; X256_WAVES, cross.hip:330
 CROSS_GRID_CAP = {64: 768, 128: 256, 256: 256}               # CrossShape<D>::GRID, cross.hip:152; launch_cross256, cross.hip:439
@@ -95,25 +95,25 @@ def _cross(d, k=32):
 
 
 def _pointconv_agg(b, s, d, aligned=True, k=32):
-    if k != 32:                                                      # mcp_pointconv_agg, pointconv.hip:462
+    if k != 32:                                                      # pc_agg_run, csrc/pointconv_tile.h
         raise ValueError(f"pointconv_agg: {k} neighbours are not built")
     total = b * s
-    vec4 = d % 4 == 0 and aligned                                    # pointconv.hip:466 (aligned: s_points on a 16-byte boundary)
-    if total <= POINTCONV_LOWLEVEL_MAX or not vec4:                  # pointconv.hip:474
-        if d >= 256 and total <= 8192:                               # pointconv.hip:476-477
+    vec4 = d % 4 == 0 and aligned                                    # pc_agg_run: vec4 (aligned: s_points on a 16-byte boundary)
+    if total <= POINTCONV_LOWLEVEL_MAX or not vec4:                  # pc_agg_run: the low-level forms
+        if d >= 256 and total <= 8192:                               # pc_agg_run
             return "pointconv_agg_lowlevel_kernel<1024>"
-        return "pointconv_agg_lowlevel_kernel<256>"                  # pointconv.hip:479
-    if d <= 32:                                                      # pointconv.hip:480
+        return "pointconv_agg_lowlevel_kernel<256>"                  # pc_agg_run
+    if d <= 32:                                                      # pc_agg_run: points per workgroup by d
         return "pointconv_agg_kernel<256, 32>"
-    if d <= 64:                                                      # pointconv.hip:481
+    if d <= 64:                                                      # pc_agg_run
         return "pointconv_agg_kernel<256, 16>"
-    return "pointconv_agg_kernel<256, 8>"                            # pointconv.hip:482
+    return "pointconv_agg_kernel<256, 8>"                            # pc_agg_run
 
 
 def _pointconv_linear(d, c_out, k=32):
-    if k != 32 or (d, c_out) not in ((32, 32), (64, 64)):            # mcp_pointconv_linear, pointconv.hip:495
+    if k != 32 or (d, c_out) not in ((32, 32), (64, 64)):            # pc_linear_run, csrc/pointconv_tile.h
         raise ValueError(f"pointconv_linear: d={d}, c_out={c_out}, k={k} is not built")
-    return "pointconv_linear_kernel<32, 1>" if d == 32 else "pointconv_linear_kernel<64, 2>"   # pointconv.hip:501-520
+    return "pointconv_linear_kernel<32, 1>" if d == 32 else "pointconv_linear_kernel<64, 2>"   # pc_linear_run
 
 
 def _ptblock(c=64, k=16):
@@ -137,9 +137,9 @@ def launch_grid(op, **shape):
     if op == "pointconv_agg":
         total = shape["b"] * shape["s"]
         name = expected_kernel(op, **shape)
-        ppb = 8 if "lowlevel" in name else int(name[:-1].split(",")[1])  # LPPB, pointconv.hip:143; PPB :480-482
-        return min(_cdiv(total, ppb), 1 << 20), total, ppb              # pointconv.hip:471, :475
-    if op == "pointconv_linear":                                     # FPPB, pointconv.hip:260, :499
+        ppb = 8 if "lowlevel" in name else int(name[:-1].split(",")[1])  # LPPB, pointconv_tile.h; PPB: pc_agg_run
+        return min(_cdiv(total, ppb), 1 << 20), total, ppb              # pc_agg_run: the launch lambda's grid
+    if op == "pointconv_linear":                                     # FPPB, pointconv_tile.h; pc_linear_run's grid
         total = shape["b"] * shape["s"]
         return min(_cdiv(total, 32), 1 << 20), total, 32
     if op == "ptblock":                                              # ptblock.hip:103, :193-194
@@ -402,7 +402,7 @@ def grad_launch_grid(op, cus=256, **shape):
                     "w": dict(workgroups=slices, units=total, per=X256_W_PTS, by_xcd=False, dealt=w),   # times 4 column blocks, :188, :429
                     "dx": _role(total, 1, min(total, X256_DX_GRID), xcd_map=False)}                 # cross256_grad.hip:243, :381
         raise ValueError(f"cross grad: d={d} is not built")          # mcp_cross_grad, cross_grad.hip:514
-    if op == "pointconv_agg":                                        # grad_grid, pointconv_grad.hip:204-208; pairs :52
+    if op == "pointconv_agg":                                        # grad_grid, pointconv_grad_tile.h; pairs: the kernel's loop there
         total = shape["b"] * shape["s"]
         return {"pairs": _role((total + 1) // 2, GRAD_WAVES, min(_cdiv(total, 2 * GRAD_WAVES), cus))}
     if op == "ptblock":                                              # grad_grid, ptblock_grad.hip:417-421; pairs :147
@@ -423,7 +423,7 @@ def expected_grad_kernels(op, **shape):
             return {"cross256_grad_z_kernel", "cross256_grad_w_kernel", "cross256_grad_dx_kernel", "cross256_grad_reduce_kernel"}
         names = {f"cross_grad_kernel<{d}>", "cross_grad_reduce_kernel"}   # launch_cross_grad, cross_grad.hip:493-495
         return names | {"transposed_image_kernel"} if d == 128 else names   # !WT_LDS, cross_grad.hip:60, :491
-    if op == "pointconv_agg":                                        # mcp_pointconv_agg_grad, pointconv_grad.hip:241-243; ops.pointconv_agg: d % 4 == 0, d <= 256
+    if op == "pointconv_agg":                                        # pcg_run, pointconv_grad_tile.h; ops.pointconv_agg: d % 4 == 0, d <= 256
         if shape.get("k", 32) != 32 or shape["d"] % 4 or shape["d"] > 256:
             raise ValueError(f"pointconv_agg grad: d={shape['d']} is not built")
         return {"pointconv_agg_grad_kernel", "pointconv_grad_reduce_kernel"}

@@ -93,7 +93,7 @@ def test_expected_kernel_mirrors_the_dispatch_rules():
 
 
 def test_expected_kernel_mirrors_the_fused_dispatch_rules():
-    # pointconv.hip:466-482, :495-520; cross.hip:489-497; fusion.hip:291, :318; ptblock.hip:188, :197
+    # pointconv_tile.h: pc_agg_run, pc_linear_run; cross.hip:489-497; fusion.hip:291, :318; ptblock.hip:188, :197
     e = kv.expected_kernel
     agg = lambda total, d, **kw: e("pointconv_agg", b=1, s=total, d=d, **kw)
     assert agg(16384, 32) == "pointconv_agg_lowlevel_kernel<256>"
@@ -118,7 +118,7 @@ def test_expected_kernel_mirrors_the_fused_dispatch_rules():
                 dict(op="cross", d=64, k=16), dict(op="fusion", b=1, n=1, nb=32), dict(op="ptblock", c=128), dict(op="pointconv_agg", b=1, s=1, d=4, k=16)):
         with pytest.raises(ValueError):
             kv.expected_kernel(**bad)
-    # the grids beside the dispatch: fusion.hip:304, cross.hip:439, :459-462, pointconv.hip:471, :475, :499, ptblock.hip:193-194
+    # the grids beside the dispatch: fusion.hip:304, cross.hip:439, :459-462, pointconv_tile.h: pc_agg_run, pc_linear_run, ptblock.hip:193-194
     g = kv.launch_grid
     assert g("fusion", b=2, n=1500)[0] == 750 and g("fusion", b=3, n=5483)[0] == 4096 and g("fusion", b=1, n=1)[0] == 1
     assert g("cross", d=64, b=2, n1=2048)[0] == 128 and g("cross", d=64, b=40, n1=2048)[0] == 768
