@@ -16,7 +16,12 @@ unit, two grid caps in one call) and parametrise test_fusion_bn_variants_gpu.py.
 wgrad_launch() restates the host dispatch of the weight-gradient kernel (linear_grad.hip: tiles-per-wave variant, stages per
 workgroup, idle workgroups, how each operand is staged); WGRAD_CASES parametrises test_linear_grad_edges_gpu.py.
 attention_small_grad_launch() does the same for the three narrow-head attention backward kernels (attention_grad.hip) and
-ATTN_GRAD_COUNTS is the grid of query / key counts test_attention_grad_edges_gpu.py crosses.  A plain module, imported by the tests."""
+ATTN_GRAD_COUNTS is the grid of query / key counts test_attention_grad_edges_gpu.py crosses.
+
+attention_wide_train_kernels() names the kernels one training forward + backward of the wide-head attention launches
+(attention_wide_grad.hip, 43 instantiations) and attention_wide_grad_launch() mirrors their tiles and stages; WIDE_GRAD_COUNTS,
+WIDE_GUARD_CASES and WIDE_TRAIN_CASES parametrise test_attention_wide_grad_edges_gpu.py.  EMD_GRAD_CASES and INTERP3_GRAD_CASES are
+the shapes of test_emd_interp3_grad_edges_gpu.py, each with the kernels it launches.  A plain module, imported by the tests."""
 
 def _cdiv(a, b):
     return (a + b - 1) // b
@@ -673,3 +678,132 @@ def attention_small_grad_launch(nq, nk):
         return dict(workgroups=_cdiv(stationary, ATTN_GRAD_BLOCK), last_tile=(stationary - 1) % ATTN_GRAD_TILE + 1,
                     stages=_cdiv(streamed, ATTN_GRAD_KT), last_stage=(streamed - 1) % ATTN_GRAD_KT + 1)
     return {"attention_stats_kernel": role(nq, nk), "attention_dq_kernel": role(nq, nk), "attention_dkv_kernel": role(nk, nq)}
+
+
+# ---- the wide-head attention in a training graph (attention_wide_grad.hip; the forward bodies: attention_wide_fwd.h).  Head widths
+# 32 / 64: a workgroup is four independent waves of 32 stationary rows each; 256: the four waves share ONE block of 32 rows, each a
+# 64-channel slice (GradCfg, attention_wide_grad.hip:77-90).  The other side streams in stages of 32 rows, fetched one stage ahead ----
+WIDE_WAVES, WIDE_TILE = 4, 32                                # WAVES, attention_wide_fwd.h:17; the MFMA tile and KT (WideCfg, :33)
+WIDE_HEAD_WIDTHS = (32, 64, 256)                             # forward_with / backward_with, attention_wide_grad.hip:416, :439
+# one row; a wave's tile -1 / 0 / +1 (33: a second stage that holds one row, and at width 256 a second workgroup that holds one row);
+# two stages -1 / 0 / +1 (65: a third stage, which in the query-stationary forward reuses LDS buffer 0, attention_wide_fwd.h:128); 97:
+# four stages, each of the forward's two buffers used a second time; 127 / 128 / 129: the 128-row workgroup block of widths 32 / 64 -1 / 0 / +1, and the key-split forward's threshold (four stages,
+# one per wave; 129: five, wave 0 takes a second); 161: six stages, waves 0 and 1 take a second
+WIDE_GRAD_COUNTS = (1, 31, 32, 33, 63, 64, 65, 97, 127, 128, 129, 161)
+
+
+def wide_keys_split(bf, nq, nk, heads):
+    """wide_keys_split, attention_wide_fwd.h:393-395: read from the padded sizes, never from a length."""
+    return _cdiv(nq, WIDE_TILE * WIDE_WAVES) * heads * bf * WIDE_WAVES < 1024 and nk >= WIDE_TILE * WIDE_WAVES
+
+
+def attention_wide_train_kernels(bf, heads, hd, nq, nk, drop=False, lengths=False):
+    """The demangled kernels of one training forward (mcp_attention_wide_lse[_lengths]) plus one backward
+    (mcp_attention_wide_grad_lse[_lengths]): launch_forward, attention_wide_grad.hip:55-72; launch_backward :393-410.  drop: drop_p > 0
+    (:427, :452); lengths: at least one of the two length arrays is given (:490-491, :499-503)."""
+    if hd not in WIDE_HEAD_WIDTHS:
+        raise ValueError(f"attention_wide: head width {hd} is not built")
+    args = f"{hd}, {'true' if drop else 'false'}" + (", AttnLengths" if lengths else "")
+    fwd = "attention_wide_ksplit_lse_kernel" if hd == 256 and wide_keys_split(bf, nq, nk, heads) else "attention_wide_lse_kernel"
+    return {f"{fwd}<{args}>", f"attention_wide_dsum_kernel<{hd}>", f"attention_wide_dq_kernel<{args}>", f"attention_wide_dkv_kernel<{args}>"}
+
+
+def wide_ksplit_waves(keys):
+    """Key-split forward: wave w takes the 32-key stages w, w + 4, ... of the element's own key count (attention_wide_fwd.h:294-296)."""
+    stages = _cdiv(keys, WIDE_TILE)
+    per = [len(range(w, stages, WIDE_WAVES)) for w in range(WIDE_WAVES)]
+    return dict(stages_per_wave=per, idle_waves=per.count(0))
+
+
+def attention_wide_grad_launch(hd, nq, nk, bf=2, heads=2):
+    """{kernel: dict(block, workgroups, last_tile, stages, last_stage)} of one training forward + backward without lengths: `block` the
+    stationary rows of a workgroup (32 * RPW, GradCfg; the grids: attention_wide_grad.hip:405, :407; the forward's :62, :69),
+    `workgroups` along the stationary side, last_tile the live rows of the last 32-row tile, `stages` of the streamed side
+    (:215, :333; attention_wide_fwd.h:122, :294), last_stage the live rows of the last one.  The key-split forward adds
+    wide_ksplit_waves(nk); attention_wide_dsum_kernel is dict(workgroups, last_block_lanes): rows * hd / 4 lanes in blocks of 256 (:404)."""
+    if hd not in WIDE_HEAD_WIDTHS:
+        raise ValueError(f"attention_wide: head width {hd} is not built")
+
+    def role(stationary, streamed, block):
+        return dict(block=block, workgroups=_cdiv(stationary, block), last_tile=(stationary - 1) % WIDE_TILE + 1,
+                    stages=_cdiv(streamed, WIDE_TILE), last_stage=(streamed - 1) % WIDE_TILE + 1)
+    block = WIDE_TILE * (1 if hd > 64 else WIDE_WAVES)               # 32 * RPW, RPW = WAVES / SPLIT, SPLIT = HD > 64 ? WAVES : 1
+    lanes = bf * nq * heads * (hd // 4)
+    out = {"attention_wide_dq_kernel": role(nq, nk, block), "attention_wide_dkv_kernel": role(nk, nq, block),
+           "attention_wide_dsum_kernel": dict(workgroups=_cdiv(lanes, 256), last_block_lanes=(lanes - 1) % 256 + 1)}
+    if hd == 256 and wide_keys_split(bf, nq, nk, heads):
+        out["attention_wide_ksplit_lse_kernel"] = dict(role(nq, nk, WIDE_TILE), **wide_ksplit_waves(nk))
+    else:
+        out["attention_wide_lse_kernel"] = role(nq, nk, WIDE_TILE * WIDE_WAVES)
+    return out
+
+
+def _wt(kind, hd, nq, nk, bf=2, heads=2, drop=False, qlen=None, klen=None, **kw):
+    """kind: guard (canary rows around every output of the C entries), dropout, dropout-lengths, strides (q, k, v slices of one
+    (BF, n, 3C) tensor), logits (q scaled by `factor`).  qlen / klen: per-element lengths (None: that side is full)."""
+    return dict(kind=kind, bf=bf, heads=heads, hd=hd, nq=nq, nk=nk, drop=drop, qlen=qlen, klen=klen, **kw)
+
+
+def wide_case_kernels(c):
+    return attention_wide_train_kernels(c["bf"], c["heads"], c["hd"], c["nq"], c["nk"], c["drop"], c["qlen"] is not None or c["klen"] is not None)
+
+
+def wide_case_id(c):
+    fwd = "ksplit" if any("ksplit" in n for n in wide_case_kernels(c)) else "qs"
+    tail = "".join(f",{k}={'_'.join(map(str, c[k]))}" for k in ("qlen", "klen") if c[k] is not None) + (",drop" if c["drop"] else "")
+    return f"{c['kind']}[hd={c['hd']},{c['bf']}x{c['heads']},nq={c['nq']},nk={c['nk']},{fwd}{tail}]"
+
+
+# section (b): a partial tile on both sides per width, and the key-split forward; each once plain and once through the _lengths entries
+# with lengths shorter than the launch
+WIDE_GUARD_CASES = [c for hd, nq, nk, heads in ((32, 33, 65, 2), (64, 33, 65, 2), (256, 33, 65, 2), (256, 37, 130, 1))
+                    for c in (_wt("guard", hd, nq, nk, heads=heads), _wt("guard", hd, nq, nk, heads=heads, qlen=(nq - 2, 1), klen=(33, nk - 1)))]
+
+WIDE_DROP_SHAPES = ((33, 65), (129, 63), (1, 129), (128, 64))
+# (d): 0, 1, 31, 33 and the full count on either side, over three length sets of the two elements
+WIDE_LENGTH_SETS = (lambda nq, nk: ((nq, 1), (31, nk)), lambda nq, nk: ((33, 31), (1, 33)), lambda nq, nk: ((0, 33), (nk, 0)))
+
+WIDE_TRAIN_CASES = (
+    # (c) dropout at the edges: four shapes per width (at width 256, (1, 129) takes the key-split forward), and two key-split shapes
+    # with a partial last stage and unequal stages per wave (130: 5 stages, 2/1/1/1, the last holds 2 keys; 161: 6 stages, 2/2/1/1, 1 key)
+    [_wt("dropout", hd, nq, nk, drop=True) for hd in WIDE_HEAD_WIDTHS for nq, nk in WIDE_DROP_SHAPES]
+    + [_wt("dropout", 256, 37, nk, heads=1, drop=True) for nk in (130, 161)]
+    # (d) dropout with lengths: the query-stationary forward at every width, and the key-split one (a key length <= 32 leaves three
+    # waves without a stage, 33 two)
+    + [_wt("dropout-lengths", hd, nq, nk, heads=heads, drop=True, qlen=ls(nq, nk)[0], klen=ls(nq, nk)[1])
+       for hd, nq, nk, heads in ((32, 130, 100, 2), (64, 130, 100, 2), (256, 130, 100, 2), (256, 37, 130, 1)) for ls in WIDE_LENGTH_SETS]
+    # (e) q, k, v with row stride 3C: once per width, and once with dropout and lengths on the key-split forward
+    + [_wt("strides", hd, 65, 65) for hd in WIDE_HEAD_WIDTHS]
+    + [_wt("strides", 256, 130, 130, heads=1, drop=True, qlen=(33, 130), klen=(130, 31))]
+    # (f) large logits on partial tiles
+    + [_wt("logits", 256, 33, 65, factor=6.0)]
+)
+
+
+def wide_cases(kind):
+    return [c for c in WIDE_TRAIN_CASES if c["kind"] == kind]
+
+
+# ---- emd_grad.hip: emd_grad_kernel<SIDE, LEN> has 64 lane points per workgroup and streams the other cloud in tiles of 512 of which
+# wave w takes entries [64 w, 64 w + 64) (:24, :79-94); matchcost_grad1_kernel gives wave w the w-th eighth of m (:175: empty ranges
+# when m < 8), matchcost_grad2_kernel takes 8 rows per workgroup and strides 256 lanes over n (:199-217), matchcost_kernel 1024 (:138-146) ----
+EMD_LEAN_SHAPES = ((1, 1), (1, 513), (513, 1), (63, 65), (64, 64), (65, 63), (64, 512), (511, 64), (512, 513), (577, 129))
+EMD_MATCH_SHAPES = ((1, 1), (3, 5), (64, 7), (65, 8), (255, 9), (256, 16), (257, 17), (1023, 1), (1024, 3), (1025, 15))
+_EMD_PLAIN = ("emd_grad_kernel<1, false>", "emd_grad_kernel<2, false>")
+_EMD_LEN = ("emd_grad_kernel<1, true>", "emd_grad_kernel<2, true>")
+EMD_GRAD_CASES = (
+    [dict(kind="lean", n=n, m=m, len1=None, len2=None, kernels=_EMD_PLAIN) for n, m in EMD_LEAN_SHAPES]
+    # mcp_emd_grad_lengths (emd_grad.hip:264-270): full lengths must give the plain call's bits, short ones the sliced call's
+    + [dict(kind="lean-lengths", n=n, m=m, len1=(n, n), len2=(m, m), kernels=_EMD_LEN) for n, m in ((63, 65), (512, 513))]
+    + [dict(kind="lean-lengths", n=64, m=65, len1=(31, 64), len2=(65, 1), kernels=_EMD_LEN)]
+    + [dict(kind="match", n=n, m=m, len1=None, len2=None, kernels=("matchcost_kernel", "matchcost_grad1_kernel", "matchcost_grad2_kernel"))
+       for n, m in EMD_MATCH_SHAPES]
+)
+
+# ---- interp3_grad.hip: one thread per dense point, 256 per workgroup (:13, :19-20) ----
+INTERP3_GRAD_CASES = ([dict(n=n, s=s, coincident=0, kernels=("interp3_weights_grad_kernel",)) for n in (1, 255, 256, 257, 513) for s in (3, 40)]
+                      + [dict(n=257, s=40, coincident=5, kernels=("interp3_weights_grad_kernel",))])
+
+
+def emd_cases(kind):
+    return [c for c in EMD_GRAD_CASES if c["kind"] == kind]

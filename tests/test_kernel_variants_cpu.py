@@ -19,8 +19,13 @@ staging forms, stage counts and tile splits the cases must reach.  The narrow-he
 to pick from -- one kernel per head width -- so ATTN_GRAD_EDGES only states which query / key counts
 kernel_variants.ATTN_GRAD_COUNTS must hold, as predicates on kernel_variants.attention_small_grad_launch.
 
-Still outside: attention_wide_grad.hip, emd_grad.hip and interp3_grad.hip have no parity cases of this form; tests/test_grad_gpu.py and
-its neighbours compare them at workload-like shapes."""
+The wide-head attention in a training graph (attention_wide_grad: 43 instantiations over head width, dropout, per-element lengths and
+the forward's key split): every kernel must be in kernel_variants.attention_wide_train_kernels of the crossed grid WIDE_GRAD_COUNTS or of
+an entry of WIDE_GUARD_CASES / WIDE_TRAIN_CASES (the cases of test_attention_wide_grad_edges_gpu.py), WIDE_TRAIN_REQUIRED states which
+explicit cases must be there, and WIDE_GRAD_EDGES states, as predicates on kernel_variants.attention_wide_grad_launch, the tile, block
+and stage boundaries the grid must hold.  The EMD backward and the interpolation weights' backward (emd_grad: 7 kernels, interp3_grad: 1)
+are held by EMD_GRAD_CASES / INTERP3_GRAD_CASES (the cases of test_emd_interp3_grad_edges_gpu.py), each of which names the kernels it
+launches.  With these, every backward unit of the library has a mirror, a registry test and cases on its own loop edges."""
 import os
 import re
 import shutil
@@ -584,3 +589,184 @@ def test_the_attention_backward_grid_holds_every_boundary_class():
     assert not missing, missing
     # the counts the issue behind these tests lists, on both sides (the key-stationary kernel streams the queries)
     assert set(kv.ATTN_GRAD_COUNTS) >= {1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 193}
+
+
+# ---- the wide-head attention in a training graph: 43 instantiations, tiles of 32 rows, blocks of 128 or 32, stages of 32 ----------------
+WIDE_TRAIN_UNITS = ("attention_wide_grad",)
+WIDE_TRAIN_NOT_LAUNCHED = {}   # every instantiation is picked by some (head width, drop_p > 0, lengths given, key split) of the two entry pairs
+WIDE_BF, WIDE_HEADS = 2, 2     # BF, HEADS of test_attention_wide_grad_edges_gpu.py's grid
+
+
+def test_the_wide_attention_mirror_follows_the_c_conditions():
+    # wide_keys_split, attention_wide_fwd.h:393-395; launch_forward, attention_wide_grad.hip:55-72; GradCfg :77-90 (SPLIT :79, RPW :86);
+    # the backward's grids :404-407; the stage counts :215, :333, attention_wide_fwd.h:122, :294-296
+    split, names, L = kv.wide_keys_split, kv.attention_wide_train_kernels, kv.attention_wide_grad_launch
+    assert split(2, 37, 128, 1) and not split(2, 37, 127, 1) and split(16, 256, 256, 3) and not split(16, 512, 256, 4)
+    assert split(63, 128, 128, 4) and not split(64, 128, 128, 4) and split(64, 128, 128, 3)      # 63 * 4 * 4 = 1008 < 1024 <= 64 * 4 * 4
+    assert names(2, 2, 256, 33, 128) == {"attention_wide_ksplit_lse_kernel<256, false>", "attention_wide_dsum_kernel<256>",
+                                          "attention_wide_dq_kernel<256, false>", "attention_wide_dkv_kernel<256, false>"}
+    assert "attention_wide_lse_kernel<256, true, AttnLengths>" in names(2, 2, 256, 33, 127, drop=True, lengths=True)
+    assert "attention_wide_ksplit_lse_kernel<256, true, AttnLengths>" in names(2, 1, 256, 37, 130, drop=True, lengths=True)
+    assert "attention_wide_lse_kernel<64, true>" in names(2, 2, 64, 33, 200, drop=True)           # widths 32 / 64 never split the keys
+    assert "attention_wide_lse_kernel<256, false, AttnLengths>" in names(64, 4, 256, 128, 128, lengths=True)
+    with pytest.raises(ValueError):
+        names(2, 2, 128, 33, 65)
+    g = L(64, 129, 97)
+    assert g["attention_wide_dq_kernel"] == dict(block=128, workgroups=2, last_tile=1, stages=4, last_stage=1)
+    assert g["attention_wide_dkv_kernel"] == dict(block=128, workgroups=1, last_tile=1, stages=5, last_stage=1)
+    assert g["attention_wide_lse_kernel"] == dict(block=128, workgroups=2, last_tile=1, stages=4, last_stage=1)
+    assert g["attention_wide_dsum_kernel"] == dict(workgroups=33, last_block_lanes=64)             # 2 * 129 * 2 rows of 16 lanes = 8256 = 32 * 256 + 64
+    g = L(256, 33, 161)
+    assert g["attention_wide_dq_kernel"] == dict(block=32, workgroups=2, last_tile=1, stages=6, last_stage=1)
+    assert g["attention_wide_dkv_kernel"] == dict(block=32, workgroups=6, last_tile=1, stages=2, last_stage=1)
+    assert g["attention_wide_ksplit_lse_kernel"] == dict(block=32, workgroups=2, last_tile=1, stages=6, last_stage=1, stages_per_wave=[2, 2, 1, 1], idle_waves=0)
+    assert "attention_wide_lse_kernel" in L(256, 33, 127) and L(256, 33, 127)["attention_wide_lse_kernel"]["block"] == 128
+    assert L(256, 1, 1)["attention_wide_dsum_kernel"] == dict(workgroups=1, last_block_lanes=256)   # 4 rows of 64 lanes
+    assert L(32, 1, 1)["attention_wide_dsum_kernel"] == dict(workgroups=1, last_block_lanes=32)
+    assert kv.wide_ksplit_waves(31) == dict(stages_per_wave=[1, 0, 0, 0], idle_waves=3) and kv.wide_ksplit_waves(0)["idle_waves"] == 4
+    assert kv.wide_ksplit_waves(33)["stages_per_wave"] == [1, 1, 0, 0] and kv.wide_ksplit_waves(130)["stages_per_wave"] == [2, 1, 1, 1]
+
+
+def _wide_edges(role, side, block):
+    """Edges of one backward kernel: its stationary side in tiles of 32 and workgroup blocks of `block` rows, its streamed side in stages of 32."""
+    T = kv.WIDE_TILE
+    n = (lambda nq, nk: nq) if side == "query" else (lambda nq, nk: nk)
+    R = lambda g: g[role]
+    on = lambda g: R(g)["block"] == block
+    tag = f"{role}, block {block}"
+    return {
+        f"{tag}: one {side} row": lambda nq, nk, g: on(g) and n(nq, nk) == 1 and R(g)["workgroups"] == 1 and R(g)["last_tile"] == 1,
+        f"{tag}: a last wave tile with {T - 1} live rows": lambda nq, nk, g: on(g) and R(g)["last_tile"] == T - 1,
+        f"{tag}: a last wave tile with one live row behind full ones": lambda nq, nk, g: on(g) and R(g)["last_tile"] == 1 and n(nq, nk) > 1,
+        f"{tag}: one full tile": lambda nq, nk, g: on(g) and n(nq, nk) == T,
+        f"{tag}: a block one row short": lambda nq, nk, g: on(g) and n(nq, nk) == block - 1,
+        f"{tag}: one full block": lambda nq, nk, g: on(g) and n(nq, nk) == block and R(g)["workgroups"] == 1,
+        f"{tag}: a second workgroup that holds one row": lambda nq, nk, g: on(g) and n(nq, nk) == block + 1 and R(g)["workgroups"] == 2 and R(g)["last_tile"] == 1,
+        f"{tag}: one streamed row (no prefetch)": lambda nq, nk, g: on(g) and R(g)["stages"] == 1 and R(g)["last_stage"] == 1,
+        **{f"{tag}: one stage of {r} rows": (lambda r: lambda nq, nk, g: on(g) and R(g)["stages"] == 1 and R(g)["last_stage"] == r)(r) for r in (T - 1, T)},
+        **{f"{tag}: {s} stages, the last with one row": (lambda s: lambda nq, nk, g: on(g) and R(g)["stages"] == s and R(g)["last_stage"] == 1)(s) for s in (2, 3, 4)},
+    }
+
+
+def _ksplit(g):
+    return g.get("attention_wide_ksplit_lse_kernel", {}).get("stages_per_wave")
+
+
+WIDE_GRAD_EDGES = {
+    **{k: v for block in (128, 32) for role, side in (("attention_wide_dq_kernel", "query"), ("attention_wide_dkv_kernel", "key"))
+       for k, v in _wide_edges(role, side, block).items()},
+    "key-split forward: all four waves with one stage": lambda nq, nk, g: _ksplit(g) == [1, 1, 1, 1],
+    "key-split forward: wave 0 with a second stage": lambda nq, nk, g: _ksplit(g) == [2, 1, 1, 1],
+    "key-split forward: waves 0 and 1 with a second stage": lambda nq, nk, g: _ksplit(g) == [2, 2, 1, 1],
+    "width 256, query-stationary forward with three stages": lambda nq, nk, g: g["attention_wide_dq_kernel"]["block"] == 32 and g.get("attention_wide_lse_kernel", {}).get("stages") == 3,
+    "dsum: a last block of fewer than 256 lanes": lambda nq, nk, g: g["attention_wide_dsum_kernel"]["last_block_lanes"] < 256,
+    "dsum: more than one block, the last one full": lambda nq, nk, g: g["attention_wide_dsum_kernel"] == dict(workgroups=g["attention_wide_dsum_kernel"]["workgroups"], last_block_lanes=256)
+        and g["attention_wide_dsum_kernel"]["workgroups"] > 1,
+}
+
+
+def test_the_wide_attention_grid_holds_every_boundary_class():
+    """WIDE_GRAD_COUNTS, crossed with itself at the three head widths, puts a count on and on both sides of every boundary."""
+    grid = [(nq, nk, kv.attention_wide_grad_launch(hd, nq, nk, WIDE_BF, WIDE_HEADS)) for hd in kv.WIDE_HEAD_WIDTHS for nq in kv.WIDE_GRAD_COUNTS
+            for nk in kv.WIDE_GRAD_COUNTS]
+    missing = [edge for edge, pred in WIDE_GRAD_EDGES.items() if not any(pred(*p) for p in grid)]
+    assert not missing, missing
+    assert len(WIDE_GRAD_EDGES) == 4 * 13 + 6
+    assert set(kv.WIDE_GRAD_COUNTS) >= {1, 31, 32, 33, 63, 64, 65, 97, 127, 128, 129, 161}
+
+
+def _lens(c, side):
+    """The lengths of one side of a case with `full` for the padded count."""
+    return {"full" if v == c["nq" if side == "qlen" else "nk"] else v for v in (c[side] or ())}
+
+
+def _is(kind, hd=None, form=None, **shape):
+    def pred(c):
+        names = kv.wide_case_kernels(c)
+        return (c["kind"] == kind and (hd is None or c["hd"] == hd) and all(c[k] == v for k, v in shape.items())
+                and (form is None or any("ksplit" in n for n in names) == (form == "ksplit")))
+    return pred
+
+
+# what the explicit cases must hold, one entry per case the sections (b) to (f) of the issue behind them ask for: each is met by
+# exactly one case, so taking any case away fails here
+WIDE_TRAIN_REQUIRED = {
+    **{f"dropout at width {hd}, {nq} x {nk}": _is("dropout", hd, nq=nq, nk=nk, bf=2, heads=2, drop=True) for hd in kv.WIDE_HEAD_WIDTHS for nq, nk in ((33, 65), (129, 63), (1, 129), (128, 64))},
+    **{f"dropout, key-split forward (one head, 37 queries) with stages {per} and a partial last stage":
+       (lambda per: lambda c: _is("dropout", 256, "ksplit", drop=True, heads=1, nq=37)(c) and c["nk"] % 32 and kv.wide_ksplit_waves(c["nk"])["stages_per_wave"] == per)(per)
+       for per in ([2, 1, 1, 1], [2, 2, 1, 1])},
+    **{f"dropout with lengths at width {hd}, {form}, a length of {v} on the {side[0]} side":
+       (lambda hd, form, side, v: lambda c: _is("dropout-lengths", hd, form, drop=True)(c) and v in _lens(c, side))(hd, form, side, v)
+       for hd, form in ((32, "qs"), (64, "qs"), (256, "qs"), (256, "ksplit")) for side in ("qlen", "klen") for v in (0, 1, 31, 33, "full")},
+    "dropout with lengths, key-split forward: a key length that leaves three waves without a stage":
+        lambda c: _is("dropout-lengths", 256, "ksplit")(c) and any(kv.wide_ksplit_waves(v)["idle_waves"] == 3 for v in c["klen"]),
+    **{f"strides at width {hd}": _is("strides", hd, drop=False, qlen=None) for hd in kv.WIDE_HEAD_WIDTHS},
+    "strides with dropout and lengths": lambda c: c["kind"] == "strides" and c["drop"] and c["qlen"] is not None and c["klen"] is not None,
+    "large logits at width 256 on partial tiles": lambda c: _is("logits", 256, nq=33, nk=65)(c) and c["factor"] == 6.0,
+}
+WIDE_GUARD_REQUIRED = {
+    **{f"guard rows at width {hd}, {form}, {'lengths' if lengths else 'plain'}":
+       (lambda hd, form, lengths: lambda c: _is("guard", hd, form, drop=False)(c) and c["nq"] % 32 and c["nk"] % 32 and (c["qlen"] is not None) == lengths
+        and (not lengths or all(0 < a < c["nq"] for a in c["qlen"]) and all(0 < k < c["nk"] for k in c["klen"])))(hd, form, lengths)
+       for hd, form in ((32, "qs"), (64, "qs"), (256, "qs"), (256, "ksplit")) for lengths in (False, True)},
+}
+
+
+def test_the_wide_attention_cases_are_the_ones_the_sections_ask_for():
+    for required, cases in ((WIDE_TRAIN_REQUIRED, kv.WIDE_TRAIN_CASES), (WIDE_GUARD_REQUIRED, kv.WIDE_GUARD_CASES)):
+        missing = [what for what, pred in required.items() if not any(pred(c) for c in cases)]
+        assert not missing, missing
+        needed = [kv.wide_case_id(c) for c in cases if not any(pred(c) and sum(1 for o in cases if pred(o)) == 1 for pred in required.values())]
+        assert not needed, f"cases no requirement depends on alone: {needed}"
+    ids = [kv.wide_case_id(c) for c in kv.WIDE_GUARD_CASES + kv.WIDE_TRAIN_CASES]
+    assert len(set(ids)) == len(ids)
+    assert all(c["bf"] * c["nq"] * c["nk"] * c["heads"] <= 1 << 17 for c in kv.WIDE_GUARD_CASES + kv.WIDE_TRAIN_CASES)   # small: milliseconds on the device
+
+
+def test_every_wide_attention_training_kernel_has_a_case():
+    emitted = emitted_kernels(WIDE_TRAIN_UNITS)
+    assert len(emitted) == 43 and "attention_wide_dsum_kernel<256>" in emitted, sorted(emitted)   # the demangling worked
+    wanted = emitted - set(WIDE_TRAIN_NOT_LAUNCHED)
+    grid = set().union(*(kv.attention_wide_train_kernels(WIDE_BF, WIDE_HEADS, hd, nq, nk) for hd in kv.WIDE_HEAD_WIDTHS for nq in kv.WIDE_GRAD_COUNTS
+                         for nk in kv.WIDE_GRAD_COUNTS))
+    covered = grid.union(*(kv.wide_case_kernels(c) for c in kv.WIDE_GUARD_CASES + kv.WIDE_TRAIN_CASES))
+    missing = sorted(wanted - covered)
+    assert not missing, f"wide attention kernels without a case in tests/kernel_variants.py (grid, WIDE_GUARD_CASES, WIDE_TRAIN_CASES): {missing}"
+    stale = sorted(covered - wanted)
+    assert not stale, f"cases name kernels the library does not build: {stale}"
+    # dropout with lengths is reached by the dropout-lengths cases alone: 3 forward + 3 dq + 3 dkv + the key-split forward
+    both = {n for n in wanted if "true, AttnLengths" in n}
+    assert len(both) == 10 and both <= set().union(*(kv.wide_case_kernels(c) for c in kv.wide_cases("dropout-lengths")))
+
+
+# ---- the EMD backward and the interpolation weights' backward ----------------------------------------------------------------------------
+EMD_GRAD_UNITS, INTERP3_GRAD_UNITS = ("emd_grad",), ("interp3_grad",)
+
+
+def test_every_emd_and_interp3_backward_kernel_has_a_case():
+    for units, cases, count, probe in ((EMD_GRAD_UNITS, kv.EMD_GRAD_CASES, 7, "emd_grad_kernel<2, true>"),
+                                       (INTERP3_GRAD_UNITS, kv.INTERP3_GRAD_CASES, 1, "interp3_weights_grad_kernel")):
+        emitted = emitted_kernels(units)
+        assert len(emitted) == count and probe in emitted, sorted(emitted)   # the demangling worked
+        covered = {n for c in cases for n in c["kernels"]}
+        missing = sorted(emitted - covered)
+        assert not missing, f"{units[0]} kernels without a case in tests/kernel_variants.py: {missing}"
+        stale = sorted(covered - emitted)
+        assert not stale, f"cases name kernels the library does not build: {stale}"
+
+
+def test_the_emd_and_interp3_cases_sit_on_the_kernels_boundaries():
+    # emd_grad.hip:24 (64 lane points, tiles of 512 in wave slices of 64), :175 (eighths of m), :199 (8 rows, 256 lanes), :138 (1024 lanes);
+    # interp3_grad.hip:13 (256 points per workgroup)
+    lean = {(c["n"], c["m"]) for c in kv.emd_cases("lean")}
+    assert lean == {(1, 1), (1, 513), (513, 1), (63, 65), (64, 64), (65, 63), (64, 512), (511, 64), (512, 513), (577, 129)}
+    for lanes, streamed in (({n for n, _ in lean}, {m for _, m in lean}), ({m for _, m in lean}, {n for n, _ in lean})):   # grad1, grad2
+        assert lanes >= {1, 63, 64, 65} and streamed >= {1, 63, 64, 65, 512, 513}, (lanes, streamed)
+    lens = [(c["n"], c["m"], c["len1"], c["len2"]) for c in kv.emd_cases("lean-lengths")]
+    assert lens == [(63, 65, (63, 63), (65, 65)), (512, 513, (512, 512), (513, 513)), (64, 65, (31, 64), (65, 1))]
+    match = {(c["n"], c["m"]) for c in kv.emd_cases("match")}
+    assert match == {(1, 1), (3, 5), (64, 7), (65, 8), (255, 9), (256, 16), (257, 17), (1023, 1), (1024, 3), (1025, 15)}
+    assert {m for _, m in match} >= {1, 7, 8, 9} and {n for n, _ in match} >= {1, 255, 256, 257, 1023, 1024, 1025}
+    plain = {(c["n"], c["s"]) for c in kv.INTERP3_GRAD_CASES if not c["coincident"]}
+    assert plain == {(n, s) for n in (1, 255, 256, 257, 513) for s in (3, 40)}
+    assert [(c["n"], c["s"], c["coincident"]) for c in kv.INTERP3_GRAD_CASES if c["coincident"]] == [(257, 40, 5)]
