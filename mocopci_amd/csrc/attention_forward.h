@@ -7,7 +7,7 @@
 #pragma once
 #include <type_traits>
 
-#include "attention_small_fwd.h"  // attention_small_kernel; through it attention_wide_fwd.h: f32x16, WAVES, chan_of, the wide-head kernels' bodies
+#include "attention_small_fwd.h"  // attention_small_kernel; through it attention_wide_fwd.h: f32x16, WAVES, the wide-head kernels' bodies
 
 namespace {
 

@@ -18,7 +18,7 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int WAVES = 4, KT = 64;  // rows of the streamed side per LDS stage (two 32-row MFMA tiles)
 
-__device__ __forceinline__ int chan_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+// register r of lane half h of an accumulator tile -> its channel: mcp_chan_of (common.h)
 
 // An ordering point for the unrolled per-row loops: the accumulators pass through an empty volatile asm, so the row's fma chains
 // end before it and (volatile asms keep their order) the next row's LDS reads, whose address passes through one too, start after it.
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(64 * WAVES) void attention_small_drop_kernel(int nq
             if (kbase + 32 > kl) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    if (kbase + chan_of(r, h) >= kl) acc[r] = -INFINITY;
+                    if (kbase + mcp_chan_of(r, h) >= kl) acc[r] = -INFINITY;
             }
             float mt = acc[0];
 #pragma unroll
@@ -142,8 +142,8 @@ __global__ __launch_bounds__(64 * WAVES) void attention_small_drop_kernel(int nq
             for (int r = 0; r < 16; ++r) {
                 const float p = __builtin_amdgcn_exp2f(acc[r] - mn);
                 l += p;
-                float pm = DROP ? p * drop_scale(seed, row, (uint32_t)(kbase + chan_of(r, h)), threshold, inv_keep) : p;
-                int off = (sub * 32 + chan_of(r, h)) * HD;
+                float pm = DROP ? p * drop_scale(seed, row, (uint32_t)(kbase + mcp_chan_of(r, h)), threshold, inv_keep) : p;
+                int off = (sub * 32 + mcp_chan_of(r, h)) * HD;
                 asm volatile("" : "+v"(off), "+v"(pm));
                 const float *vr = &vt[cur][off];
 #pragma unroll
@@ -258,7 +258,7 @@ __global__ __launch_bounds__(64 * WAVES) void attention_stats_kernel(int nq, int
             if (kbase + 32 > nk) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    if (kbase + chan_of(r, h) >= nk) acc[r] = -INFINITY;
+                    if (kbase + mcp_chan_of(r, h) >= nk) acc[r] = -INFINITY;
             }
             float mt = acc[0];
 #pragma unroll
@@ -375,10 +375,10 @@ __global__ __launch_bounds__(64 * WAVES, 2) void attention_dq_kernel(int nq, int
             const int kbase = t * KT + sub * 32;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int key = sub * 32 + chan_of(r, h);
+                const int key = sub * 32 + mcp_chan_of(r, h);
                 float p = __builtin_amdgcn_exp2f(acc[r] - L);
-                if (kbase + chan_of(r, h) >= kl) p = 0.f;
-                const float mk = DROP ? drop_scale(seed, drow, (uint32_t)(kbase + chan_of(r, h)), threshold, inv_keep) : 1.0f;
+                if (kbase + mcp_chan_of(r, h) >= kl) p = 0.f;
+                const float mk = DROP ? drop_scale(seed, drow, (uint32_t)(kbase + mcp_chan_of(r, h)), threshold, inv_keep) : 1.0f;
                 float ds = p * (mk * accp[r] - D);
                 int off = key * HD;
                 asm volatile("" : "+v"(off), "+v"(ds));
@@ -511,7 +511,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void attention_dkv_kernel(int nq, in
             }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int qq = sub * 32 + chan_of(r, h);
+                const int qq = sub * 32 + mcp_chan_of(r, h);
                 const float p = __builtin_amdgcn_exp2f(acc[r] - lt[cur][qq]);
                 const float mk = DROP ? drop_scale(seed, rbase + (uint32_t)(t * KT + qq), (uint32_t)ki, threshold, inv_keep) : 1.0f;
                 const float pm = DROP ? p * mk : p;

@@ -2,7 +2,7 @@
 // mcp_attention_small (attention.hip) and mcp_attention_lengths (attention_lengths.hip: the same kernel with one AttnLengths behind its
 // parameters); both launch it through attention_forward_run (attention_forward.h).  The arrangement is described at the head of attention.hip.
 #pragma once
-#include "attention_wide_fwd.h"  // f32x16, WAVES, chan_of; attention_lengths.h
+#include "attention_wide_fwd.h"  // f32x16, WAVES; attention_lengths.h
 
 namespace {
 
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(64 * WAVES) void attention_small_kernel(int nq, int
             if (kbase + 32 > kl) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    if (kbase + chan_of(r, h) >= kl) acc[r] = -INFINITY;
+                    if (kbase + mcp_chan_of(r, h) >= kl) acc[r] = -INFINITY;
             }
             float mt = acc[0];
 #pragma unroll
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(64 * WAVES) void attention_small_kernel(int nq, int
             for (int r = 0; r < 16; ++r) {
                 const float p = __builtin_amdgcn_exp2f(acc[r] - mn);
                 l += p;
-                const float *vr = &vt[cur][(sub * 32 + chan_of(r, h)) * HD];
+                const float *vr = &vt[cur][(sub * 32 + mcp_chan_of(r, h)) * HD];
                 const f2 p2 = {p, p};
 #pragma unroll
                 for (int d = 0; d < HD; d += 4) {

@@ -16,14 +16,14 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int WAVES = 4;
 
-__device__ __forceinline__ int chan_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+// register r of lane half h of an accumulator tile -> its channel: mcp_chan_of (common.h)
 
 // ---- wide heads (32: EI cross-former of level 3, mocopci.py:72-86 with dim 256 / 8 heads; 256: Cross_Frame_Att, whose 4 "heads"
 // are C = 256 wide, mocopci.py:499-522) --------------------------------------------------------------------------------
 // Both products on fp32 MFMA.  A wave owns 32 queries (MFMA column); per 32-key tile
 //   S^T = K . Q^T      : HD/2 v_mfma_f32_32x32x2_f32, A = K tile from LDS (padded rows), B = Q resident in VGPRs (pre-scaled);
 //   O^T += V^T . P     : per 32-channel tile of the head, 16 MFMAs whose B operand is the P tile exactly as the softmax left
-//                        it in the accumulator layout (k-step r <-> keys chan_of(r, half)), A = V rows read from LDS in that
+//                        it in the accumulator layout (k-step r <-> keys mcp_chan_of(r, half)), A = V rows read from LDS in that
 //                        same key order; O^T stays in HD/32 accumulator tiles, every register of a lane belongs to that
 //                        lane's query, so the online-softmax rescale is lane-local.
 // The running maximum is shared by the two lane halves of a query (one cross-half exchange per tile) because both halves feed
@@ -153,7 +153,7 @@ __device__ __forceinline__ void attention_wide_body(float *lds_w, int nq, int nk
         if (kbase + KT > kl) {
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                if (kbase + chan_of(r, h) >= kl) acc[r] = -INFINITY;
+                if (kbase + mcp_chan_of(r, h) >= kl) acc[r] = -INFINITY;
         }
         float mt = acc[0];
 #pragma unroll
@@ -172,13 +172,13 @@ __device__ __forceinline__ void attention_wide_body(float *lds_w, int nq, int nk
         for (int r = 0; r < 16; ++r) {
             p[r] = __builtin_amdgcn_exp2f(acc[r] - mn);
             l += p[r];
-            if (DROP) p[r] *= drop_scale(seed, row, (uint32_t)(kbase + chan_of(r, h)), threshold, inv_keep);
+            if (DROP) p[r] *= drop_scale(seed, row, (uint32_t)(kbase + mcp_chan_of(r, h)), threshold, inv_keep);
         }
 #pragma unroll
         for (int d = 0; d < TD; ++d) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float a = vt[(cur * KT + chan_of(r, h)) * HD + 32 * d + col];
+                const float a = vt[(cur * KT + mcp_chan_of(r, h)) * HD + 32 * d + col];
                 o[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, p[r], o[d], 0, 0, 0);
             }
             if (HD > 64) __builtin_amdgcn_sched_barrier(0);
@@ -312,7 +312,7 @@ __device__ __forceinline__ void attention_wide_ksplit_body(float *lds_ws, int nq
         if (kbase + KT > kl) {
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                if (kbase + chan_of(r, h) >= kl) acc[r] = -INFINITY;
+                if (kbase + mcp_chan_of(r, h) >= kl) acc[r] = -INFINITY;
         }
         float mt = acc[0];
 #pragma unroll
@@ -331,13 +331,13 @@ __device__ __forceinline__ void attention_wide_ksplit_body(float *lds_ws, int nq
         for (int r = 0; r < 16; ++r) {
             p[r] = __builtin_amdgcn_exp2f(acc[r] - mn);
             l += p[r];
-            if (DROP) p[r] *= drop_scale(seed, row, (uint32_t)(kbase + chan_of(r, h)), threshold, inv_keep);
+            if (DROP) p[r] *= drop_scale(seed, row, (uint32_t)(kbase + mcp_chan_of(r, h)), threshold, inv_keep);
         }
 #pragma unroll
         for (int d = 0; d < TD; ++d) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float a = buf[chan_of(r, h) * HD + 32 * d + col];
+                const float a = buf[mcp_chan_of(r, h) * HD + 32 * d + col];
                 o[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, p[r], o[d], 0, 0, 0);
             }
             __builtin_amdgcn_sched_barrier(0);

@@ -8,7 +8,7 @@
 //   dsum      D = dO . O per (batch, head, query), one elementwise pass.
 //   dq        query-stationary: a wave owns 32 queries on the MFMA column, keys stream through LDS in 32-key tiles:
 //             S^T = K Q^T, dP^T = V dO^T, p = exp2(s - L), ds = p (m dP - D), dQ^T += K^T ds  (ds stays in the accumulator layout
-//             and is the B operand of the last product through chan_of, as P is in the forward).
+//             and is the B operand of the last product through mcp_chan_of, as P is in the forward).
 //   dkv       key-stationary, the same with the roles exchanged: S = Q K^T, dP = dO V^T, dV^T += dO^T (m p), dK^T += Q^T ds.
 //             In all three the score's factor scale * log2 e sits on Q, so at head widths 32 / 64 (no channel split) the backward's s
 //             is the forward's bit for bit and p = exp2(s - L) is exactly the P the forward normalised.
@@ -21,7 +21,7 @@
 // is the unsplit one (3 HD/2 for dq, 4 HD/2 for dkv), registers per wave are those of head width 64, and the 16 x 3 x 256 x 256 call of
 // the training step is 384 workgroups instead of 96.  Head widths 32 / 64: no split, a workgroup is four independent waves.
 #include "common.h"
-#include "attention_wide_fwd.h"  // f32x16, WAVES, chan_of, drop_scale; the forward bodies
+#include "attention_wide_fwd.h"  // f32x16, WAVES, drop_scale; the forward bodies
 
 namespace {
 
@@ -233,7 +233,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void attention_wide_dq_kernel(int nq
         float ds[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int key = kbase + chan_of(r, h);
+            const int key = kbase + mcp_chan_of(r, h);
             float p = __builtin_amdgcn_exp2f(acc[r] - L);
             if (key >= kl) p = 0.f;
             const float mk = DROP ? drop_scale(seed, drow, (uint32_t)key, threshold, inv_keep) : 1.0f;
@@ -242,8 +242,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void attention_wide_dq_kernel(int nq
 #pragma unroll
         for (int d = 0; d < TD; ++d)
 #pragma unroll
-            for (int r = 0; r < 16; ++r)   // dQ^T[channel][query] += K[key][channel] ds[key][query]; k-step r <-> keys chan_of(r, half)
-                acc_q[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(kt[chan_of(r, h) * RS + 32 * d + col], ds[r], acc_q[d], 0, 0, 0);
+            for (int r = 0; r < 16; ++r)   // dQ^T[channel][query] += K[key][channel] ds[key][query]; k-step r <-> keys mcp_chan_of(r, half)
+                acc_q[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(kt[mcp_chan_of(r, h) * RS + 32 * d + col], ds[r], acc_q[d], 0, 0, 0);
         __builtin_amdgcn_wave_barrier();   // this tile's LDS reads are issued before the next tile is written (a wave's LDS accesses are served in order)
     }
     if constexpr (LEN) {
@@ -355,7 +355,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void attention_wide_dkv_kernel(int n
         float pm[16], ds[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int qq = chan_of(r, h);
+            const int qq = mcp_chan_of(r, h);
             const float p = __builtin_amdgcn_exp2f(acc[r] - st[qq]);
             const float mk = DROP ? drop_scale(seed, rbase + (uint32_t)(t * 32 + qq), (uint32_t)ki, threshold, inv_keep) : 1.0f;
             pm[r] = DROP ? p * mk : p;
@@ -364,9 +364,9 @@ __global__ __launch_bounds__(64 * WAVES, 1) void attention_wide_dkv_kernel(int n
 #pragma unroll
         for (int d = 0; d < TD; ++d)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {   // k-step r <-> queries chan_of(r, half)
-                acc_v[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(gt[chan_of(r, h) * RS + 32 * d + col], pm[r], acc_v[d], 0, 0, 0);   // dV^T += dO^T (m p)
-                acc_k[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(qt[chan_of(r, h) * RS + 32 * d + col], ds[r], acc_k[d], 0, 0, 0);   // dK^T += Q^T ds
+            for (int r = 0; r < 16; ++r) {   // k-step r <-> queries mcp_chan_of(r, half)
+                acc_v[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(gt[mcp_chan_of(r, h) * RS + 32 * d + col], pm[r], acc_v[d], 0, 0, 0);   // dV^T += dO^T (m p)
+                acc_k[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(qt[mcp_chan_of(r, h) * RS + 32 * d + col], ds[r], acc_k[d], 0, 0, 0);   // dK^T += Q^T ds
             }
         __builtin_amdgcn_wave_barrier();
     }

@@ -66,6 +66,9 @@ __device__ __forceinline__ uint32_t mcp_wave_max_u32(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 
+// Row (channel) of a 32x32 MFMA accumulator tile that register r of lane half h holds
+__device__ __forceinline__ int mcp_chan_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
 // ---- host-side helpers ----
 struct McpProf;
 void mcp_prof_begin(int kernel_id, hipStream_t s);

@@ -24,7 +24,7 @@
 // k-values instead of eight f32-input ones) at every D; the weight pieces are prepared once by mcp_cross_pack, x0 is split in
 // registers as layer 1 leaves it.
 #include "common.h"
-#include "mfma_split.h"
+#include "cross_tile.h"  // f32x16, KNB, leaky, CrossLds, cross_nbr, the X256_* constants
 
 #ifdef MCP_CROSS_DIAG
 // diagnostic build only (never in the product library): shader-cycle totals per phase of the per-point loop, wave 0 of workgroup 0
@@ -44,14 +44,7 @@ __device__ unsigned long long g_cross_diag[8];
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr int KNB = 32;
-constexpr float SLOPE = 0.1f;  // pointconv_util.py:10
 constexpr int MAX_MAPPED_BATCH = 1024;  // batch elements a batch map may have (it is kept in LDS)
-
-__device__ __forceinline__ int chan_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-// LeakyReLU with 0 < slope < 1 is max(v, slope*v): two instructions, same value for every finite v (and for +-0)
-__device__ __forceinline__ float leaky(float v) { return mcp_max_raw(v, v * SLOPE); }
 
 template <int CTRL>
 __device__ __forceinline__ float dppf(float v) {
@@ -101,18 +94,6 @@ __device__ __forceinline__ float scatter_max(const f32x16 &acc, int lane) {
 }
 __device__ __forceinline__ int scatter_reg(int lane) { return ((lane >> 4) & 1) * 8 + ((lane >> 3) & 1) * 4 + ((lane >> 2) & 1) * 2 + ((lane >> 1) & 1); }
 
-template <int D>
-struct CrossLds {
-    static constexpr int T = D / 32;
-    static constexpr bool BF = true;      // D -> D layer on the split-bf16 path (D = 256 too: cross256_stream_kernel below)
-    // f32 image [t_out][kquad][lane][4] = D*D floats; split image [t_out][kstep = 2T][piece = 3][lane] x uint4 = 1.5 D*D floats
-    static constexpr int W_FLOATS = BF ? T * (2 * T) * 3 * 64 * 4 : T * (T * 16 / 4) * 64 * 4;
-    static constexpr int POS_FLOATS = T * 2 * 64;               // [t][kstep][lane]
-    static constexpr int B_FLOATS = T * 2 * 16;                 // [t][half][r]
-    static constexpr int OFF_W = 0, OFF_POS = W_FLOATS, OFF_B = OFF_POS + POS_FLOATS;
-    static constexpr int FLOATS = OFF_B + B_FLOATS;
-};
-
 // Packs (wpos, bpos, wmlp, bmlp) into the LDS image the kernel uses: done once per layer by the caller
 // (mcp_cross_pack), so a workgroup stages its weights with plain float4 copies.
 template <int D>
@@ -120,25 +101,20 @@ __global__ __launch_bounds__(256) void cross_pack_kernel(const float *__restrict
                                                          const float *__restrict__ wmlp, const float *__restrict__ bmlp,
                                                          float *__restrict__ packed) {
     using L = CrossLds<D>;
-    constexpr int T = L::T, KQ = T * 4;
     for (int e = blockIdx.x * 256 + threadIdx.x; e < L::FLOATS; e += gridDim.x * 256) {
         float v;
-        if (e < L::OFF_POS) {  // [t][q][lane][4]: k-step s = 4q + j -> input tile s >> 4, register s & 15
-            if (L::BF) continue;  // written below as split pieces
-            const int j = e & 3, lane = (e >> 2) & 63, q = (e >> 8) % KQ, t = (e >> 8) / KQ;
-            const int s = 4 * q + j, tin = s >> 4, r = s & 15;
-            v = wmlp[(32 * t + (lane & 31)) * D + 32 * tin + chan_of(r, lane >> 5)];
-        } else if (e < L::OFF_B) {  // [t][s][lane]: columns (dx,dy | dz,1)
+        if (e < L::OFF_POS) continue;  // the weight image: written below as split pieces
+        else if (e < L::OFF_B) {  // [t][s][lane]: columns (dx,dy | dz,1)
             const int f = e - L::OFF_POS, lane = f & 63, s = (f >> 6) & 1, t = f >> 7;
             const int row = 32 * t + (lane & 31), c = 2 * s + (lane >> 5);
             v = c < 3 ? wpos[row * 3 + c] : bpos[row];
         } else {  // [t][h][r]
             const int f = e - L::OFF_B, r = f & 15, h = (f >> 4) & 1, t = f >> 5;
-            v = bmlp[32 * t + chan_of(r, h)];
+            v = bmlp[32 * t + mcp_chan_of(r, h)];
         }
         packed[e] = v;
     }
-    if (L::BF) mcp_split_weights(reinterpret_cast<uint4 *>(packed + L::OFF_W), wmlp, D, T, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
+    mcp_split_weights(reinterpret_cast<uint4 *>(packed + L::OFF_W), wmlp, D, L::T, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
 }
 
 // The kernel is latency-bound (one point in flight per wave through idx -> gathers -> MFMA -> reduce), so residency
@@ -159,7 +135,7 @@ __global__ __launch_bounds__(64 * CrossShape<D>::NW, CrossShape<D>::WG_PER_CU) v
                                                            const int *__restrict__ idx2, const int *__restrict__ bmap, int shared,
                                                            const float *__restrict__ packed, float *__restrict__ out) {
     using L = CrossLds<D>;
-    constexpr int T = L::T, KQ = T * 4;  // k-quads per output tile (f32 image)
+    constexpr int T = L::T;
     constexpr int WAVES = CrossShape<D>::NW;
     constexpr int TO = T / SPLIT;        // output tiles of this workgroup: TO * split .. TO * split + TO - 1
     constexpr int WH = L::W_FLOATS / SPLIT, SMALL = L::POS_FLOATS + L::B_FLOATS;  // LDS image: [this half of W | pos | bias]
@@ -177,7 +153,6 @@ __global__ __launch_bounds__(64 * CrossShape<D>::NW, CrossShape<D>::WG_PER_CU) v
     __syncthreads();
 
     const int lane = tid & 63, wave = tid >> 6, h = lane >> 5, col = lane & 31;
-    const float4 *wq = reinterpret_cast<const float4 *>(lds);
     const float *lpos = lds + WH, *lbias = lds + WH + L::POS_FLOATS;
     float *row1_lds = lds + WH + SMALL + wave * D;               // this wave's copy of the current point's points1 row
     const int *bmap_lds = reinterpret_cast<const int *>(lds + WH + SMALL + WAVES * D);
@@ -231,12 +206,7 @@ __global__ __launch_bounds__(64 * CrossShape<D>::NW, CrossShape<D>::WG_PER_CU) v
 #pragma unroll
             for (int g = 0; g < 4; ++g) rg[t][g] = row2[(32 * t + 8 * g + 4 * h) >> 2];  // channels 32t + 8g + 4h .. +3 -> registers 4g .. 4g+3
     };
-    // idx2 != NULL: the 16 feature-space and the 16 coordinate-space neighbours come as two (B,N1,16) lists
-    auto nbr = [&](long long pp, Pos q) {
-        if (!idx2) return idx[pp * KNB + col];
-        const long long ps = mapped(q.bb, 4) * n1 + q.off;
-        return col >= 16 ? idx2[pp * 16 + col - 16] : idx[ps * 16 + col];
-    };
+    auto nbr = [&](long long pp, Pos q) { return cross_nbr(idx, idx2, pp, [&] { return mapped(q.bb, 4) * n1 + q.off; }, col); };
     long long pn = p + stride;
     Pos qp{(int)(p / n1), (int)(p % n1)};
     Pos qn = advance(qp), qnn = advance(qn);
@@ -251,8 +221,7 @@ __global__ __launch_bounds__(64 * CrossShape<D>::NW, CrossShape<D>::WG_PER_CU) v
 #endif
     for (; p < limit; p = pn, pn += stride) {
         CROSS_STAMP(0);  // loop overhead / previous store
-        f32x16 x0[L::BF ? 1 : T];
-        McpSplit3 xs[L::BF ? 2 * T : 1];
+        McpSplit3 xs[2 * T];
         const float in0 = h ? q2y - p1y : q2x - p1x, in1 = h ? 1.0f : q2z - p1z;  // k-step 0: (dx,dy); k-step 1: (dz,1)
         if (lane < D / 4) reinterpret_cast<float4 *>(row1_lds)[lane] = r1;
         __builtin_amdgcn_wave_barrier();
@@ -273,12 +242,8 @@ __global__ __launch_bounds__(64 * CrossShape<D>::NW, CrossShape<D>::WG_PER_CU) v
                 acc[4 * g + 2] = leaky(acc[4 * g + 2] + rg[t][g].z);
                 acc[4 * g + 3] = leaky(acc[4 * g + 3] + rg[t][g].w);
             }
-            if (L::BF) {
-                xs[L::BF ? 2 * t : 0] = mcp_split_kstep(acc, 0);
-                xs[L::BF ? 2 * t + 1 : 0] = mcp_split_kstep(acc, 1);
-            } else {
-                x0[L::BF ? 0 : t] = acc;
-            }
+            xs[2 * t + 0] = mcp_split_kstep(acc, 0);
+            xs[2 * t + 1] = mcp_split_kstep(acc, 1);
         }
         __builtin_amdgcn_wave_barrier();  // the row has been read: the next point's may be written over it
         CROSS_STAMP(1);  // x0 build: waits for the prefetched loads, pos MFMA, epilogue, split
@@ -295,23 +260,10 @@ __global__ __launch_bounds__(64 * CrossShape<D>::NW, CrossShape<D>::WG_PER_CU) v
             f32x16 acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = lbias[(t * 2 + h) * 16 + r];
-            if (L::BF) {
-                const uint4 *ws = reinterpret_cast<const uint4 *>(lds) + (size_t)tl * (2 * T) * 3 * 64 + lane;
-                acc = mcp_tile_split<(L::BF ? 2 * T : 1)>(ws, xs, acc);
-            } else {
-#pragma unroll
-                for (int q4 = 0; q4 < KQ; ++q4) {
-                    const float4 w = wq[(tl * KQ + q4) * 64 + lane];
-                    const int tin = L::BF ? 0 : q4 >> 2, r0 = (q4 & 3) * 4;
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w.x, x0[tin][r0 + 0], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w.y, x0[tin][r0 + 1], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w.z, x0[tin][r0 + 2], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w.w, x0[tin][r0 + 3], acc, 0, 0, 0);
-                }
-            }
+            acc = mcp_tile_split<2 * T>(reinterpret_cast<const uint4 *>(lds) + (size_t)tl * (2 * T) * 3 * 64 + lane, xs, acc);
             CROSS_STAMP(3);  // D x D tile: bias + MFMA chain
             const float m = leaky(scatter_max(acc, lane));  // leaky is monotone: it commutes with the max
-            if ((lane & 1) == 0) out[p * D + 32 * t + chan_of(scatter_reg(lane), h)] = m;
+            if ((lane & 1) == 0) out[p * D + 32 * t + mcp_chan_of(scatter_reg(lane), h)] = m;
             CROSS_STAMP(4);  // neighbour max + store
         }
     }
@@ -327,7 +279,6 @@ __global__ __launch_bounds__(64 * CrossShape<D>::NW, CrossShape<D>::WG_PER_CU) v
 // pipe and written to the other half of a double-buffered LDS tile behind it -- one barrier per tile, 393 KB of L2 reads per four
 // points.  Same arithmetic as the D = 64 / 128 kernel (six bf16 MFMAs per 16 k-values, small terms first, bias as the initial
 // accumulator), 768 MFMAs x 32 cycles per point against 1 024 x 64 on the f32-input MFMA.
-constexpr int X256_T = 8, X256_KS = 16, X256_TILE_U4 = X256_KS * 3 * 64, X256_WAVES = 4;
 __global__ __launch_bounds__(64 * X256_WAVES, 1) void cross256_stream_kernel(long long total, int n1, int n2, const float *__restrict__ xyz1,
                                                                           const float *__restrict__ xyz2, const float *__restrict__ points1,
                                                                           const float *__restrict__ points2, const int *__restrict__ idx,
@@ -415,7 +366,7 @@ __global__ __launch_bounds__(64 * X256_WAVES, 1) void cross256_stream_kernel(lon
             for (int r = 0; r < 16; ++r) acc[r] = lbias[(t * 2 + h) * 16 + r];
             acc = mcp_tile_split<2 * T>(wbuf + (size_t)cur * X256_TILE_U4 + lane, xs, acc);
             const float m = leaky(scatter_max(acc, lane));  // leaky is monotone: it commutes with the max
-            if (live && (lane & 1) == 0) out[p * D + 32 * t + chan_of(scatter_reg(lane), h)] = m;
+            if (live && (lane & 1) == 0) out[p * D + 32 * t + mcp_chan_of(scatter_reg(lane), h)] = m;
             uint4 *ndst = wbuf + (size_t)(cur ^ 1) * X256_TILE_U4 + tid;
 #pragma unroll
             for (int i = 0; i < X256_TILE_U4 / (64 * WAVES); ++i) ndst[i * 64 * WAVES] = nx[i];
@@ -427,8 +378,7 @@ __global__ __launch_bounds__(64 * X256_WAVES, 1) void cross256_stream_kernel(lon
 
 int launch_cross256(long long total, int n1, int n2, const float *xyz1, const float *xyz2, const float *points1, const float *points2, const int *idx,
                     const int *idx2, const int *bmap, int shared, const float *packed, float *out, hipStream_t s) {
-    using L = CrossLds<256>;
-    const size_t lds = (size_t)2 * X256_TILE_U4 * 16 + (size_t)(L::POS_FLOATS + L::B_FLOATS + X256_WAVES * 256 + (bmap ? MAX_MAPPED_BATCH : 0)) * sizeof(float);
+    const size_t lds = (size_t)(X256_LDS_FLOATS + (bmap ? MAX_MAPPED_BATCH : 0)) * sizeof(float);
     if (const int rc = mcp_allow_lds<cross256_stream_kernel>()) return rc;
     const long long want = (total + X256_WAVES - 1) / X256_WAVES;
     const unsigned grid = (unsigned)max(1LL, min(want, 256LL));  // one resident workgroup per CU

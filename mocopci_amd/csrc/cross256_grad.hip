@@ -20,40 +20,18 @@
 //      thread = row c with 64 accumulators; a point's 32 x 64 block of x goes through LDS, thread c reads row j*(c) of it.
 // A last kernel adds the workgroups' partial vectors in workgroup order: every sum has a fixed order, the gradients repeat bit for bit.
 #include "common.h"
-#include "mfma_split.h"
+#include "cross_tile.h"  // KNB, SLOPE, CrossLds<256> and the X256_* constants, cross_nbr, cross_layer1, cross_winner, the entry checks
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr int D = 256, KNB = 32, T = D / 32, KS = 2 * T, WAVES = 4;
-constexpr float SLOPE = 0.1f;  // pointconv_util.py:10
-// the image mcp_cross_pack(256) writes (cross.hip, CrossLds<256>): split Wmlp [t_out][k-step][piece][lane] x uint4 | pos [t][s][lane] | bias [t][h][r]
-constexpr int TILE_U4 = KS * 3 * 64, IMG_W = T * TILE_U4 * 4, IMG_POS = T * 2 * 64, IMG_B = T * 32, IMG_FLOATS = IMG_W + IMG_POS + IMG_B;
-constexpr int SMALL = IMG_POS + IMG_B;
-constexpr size_t Z_LDS_BYTES = (size_t)2 * TILE_U4 * 16 + (size_t)(SMALL + WAVES * D) * sizeof(float);
-static_assert(Z_LDS_BYTES <= 160 * 1024, "LDS budget");
+constexpr int D = 256, T = X256_T, WAVES = X256_WAVES, TILE_U4 = X256_TILE_U4, SMALL = X256_SMALL;
+using L = CrossLds<D>;  // the image mcp_cross_pack writes
+constexpr size_t Z_LDS_BYTES = (size_t)X256_LDS_FLOATS * sizeof(float);
 // weight-gradient vector (floats): dWpos (D,3) | dbpos (D) | dWmlp (D,D) | dbmlp (D)
 constexpr int G_WM = 4 * D, G_BM = 4 * D + D * D, G_FLOATS = G_BM + D;
 // a DX workgroup's partial vector: dWpos | dbpos (the first 4 D floats of the gradient vector as they are) | dbmlp
 constexpr int P_WP = 0, P_BP = 3 * D, P_BM = 4 * D, P_FLOATS = 5 * D;
 constexpr int DX_GRID = 512, W_SLICES = 64, W_COLS = 64, W_PTS = 4, W_STRIDE = W_COLS + 4, DU_STRIDE = D + 8;
-
-__device__ __forceinline__ float leaky(float v) { return mcp_max_raw(v, v * SLOPE); }  // as the forward (cross.hip)
-
-template <int CTRL>
-__device__ __forceinline__ uint32_t max_dpp(uint32_t v) {
-    const uint32_t o = mcp_dpp<CTRL>(v);
-    return v > o ? v : o;
-}
-// maximum over the 32 lanes that share lane >> 5, in every lane (as cross_grad.hip)
-__device__ __forceinline__ uint32_t half_max_u32(uint32_t v) {
-    v = max_dpp<0xB1>(v);   // quad_perm [1,0,3,2]
-    v = max_dpp<0x4E>(v);   // quad_perm [2,3,0,1]
-    v = max_dpp<0x141>(v);  // row_half_mirror
-    v = max_dpp<0x140>(v);  // row_mirror
-    const auto sw = __builtin_amdgcn_permlane16_swap(v, v, false, false);  // odd rows of one copy <-> even rows of the other
-    return sw[0] > sw[1] ? sw[0] : sw[1];
-}
 
 // ---- pass Z: x, z as the forward computes them; j*(c), gz[c] per (point, channel); x parked in x_rows (B,N1,32,256) ----
 __global__ __launch_bounds__(64 * WAVES, 1) void cross256_grad_z_kernel(long long total, int n1, int n2, const float *__restrict__ xyz1,
@@ -68,10 +46,10 @@ __global__ __launch_bounds__(64 * WAVES, 1) void cross256_grad_z_kernel(long lon
     float *row1_all = small + SMALL;               // [WAVES][D]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, col = lane & 31;
     const uint4 *wimg = reinterpret_cast<const uint4 *>(packed);
-    for (int e = tid; e < SMALL / 4; e += 64 * WAVES) reinterpret_cast<float4 *>(small)[e] = reinterpret_cast<const float4 *>(packed + IMG_W)[e];
+    for (int e = tid; e < SMALL / 4; e += 64 * WAVES) reinterpret_cast<float4 *>(small)[e] = reinterpret_cast<const float4 *>(packed + L::OFF_POS)[e];
     for (int e = tid; e < TILE_U4; e += 64 * WAVES) wbuf[e] = wimg[e];  // tile 0
     __syncthreads();
-    const float *lpos = small, *lbias = small + IMG_POS;
+    const float *lpos = small, *lbias = small + L::POS_FLOATS;
     float *row1_lds = row1_all + wave * D;
     const uint32_t lower_lanes = (1u << col) - 1u;
 
@@ -84,7 +62,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void cross256_grad_z_kernel(long lon
         const bool live = pw < total;
         const long long p = live ? pw : total - 1;  // a wave without a point works on the last one and does not store
         const int bb = (int)(p / n1);
-        const int id = idx2 ? (col >= 16 ? idx2[p * 16 + col - 16] : idx[p * 16 + col]) : idx[p * KNB + col];
+        const int id = cross_nbr(idx, idx2, p, col);
         const float *q2 = xyz2 + ((long long)bb * n2 + id) * 3;
         const float dx = q2[0] - xyz1[p * 3 + 0], dy = q2[1] - xyz1[p * 3 + 1], dz = q2[2] - xyz1[p * 3 + 2];
         const float in0 = h ? dy : dx, in1 = h ? 1.0f : dz;  // k-step 0: (dx,dy); k-step 1: (dz,1)
@@ -96,24 +74,12 @@ __global__ __launch_bounds__(64 * WAVES, 1) void cross256_grad_z_kernel(long lon
         McpSplit3 xs[2 * T];
 #pragma unroll
         for (int t = 0; t < T; ++t) {
-            f32x16 acc;
-            float4 rg[4];
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const float4 a = reinterpret_cast<const float4 *>(row1_lds)[(32 * t + 8 * gq + 4 * h) >> 2];
-                rg[gq] = row2[(32 * t + 8 * gq + 4 * h) >> 2];
-                acc[4 * gq + 0] = a.x; acc[4 * gq + 1] = a.y; acc[4 * gq + 2] = a.z; acc[4 * gq + 3] = a.w;
-            }
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(lpos[(t * 2 + 0) * 64 + lane], in0, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(lpos[(t * 2 + 1) * 64 + lane], in1, acc, 0, 0, 0);
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                acc[4 * gq + 0] = leaky(acc[4 * gq + 0] + rg[gq].x);
-                acc[4 * gq + 1] = leaky(acc[4 * gq + 1] + rg[gq].y);
-                acc[4 * gq + 2] = leaky(acc[4 * gq + 2] + rg[gq].z);
-                acc[4 * gq + 3] = leaky(acc[4 * gq + 3] + rg[gq].w);
-                if (live) xrow[(32 * t + 8 * gq + 4 * h) >> 2] = make_float4(acc[4 * gq + 0], acc[4 * gq + 1], acc[4 * gq + 2], acc[4 * gq + 3]);
-            }
+            const f32x16 acc = cross_layer1(
+                lpos, t, lane, in0, in1, [&](int gq) { return reinterpret_cast<const float4 *>(row1_lds)[cross_at(t, gq, h)]; },
+                [&](int gq) { return row2[cross_at(t, gq, h)]; },
+                [&](int gq, const f32x16 &x) {
+                    if (live) xrow[cross_at(t, gq, h)] = make_float4(x[4 * gq + 0], x[4 * gq + 1], x[4 * gq + 2], x[4 * gq + 3]);
+                });
             xs[2 * t + 0] = mcp_split_kstep(acc, 0);
             xs[2 * t + 1] = mcp_split_kstep(acc, 1);
         }
@@ -134,16 +100,13 @@ __global__ __launch_bounds__(64 * WAVES, 1) void cross256_grad_z_kernel(long lon
             // gz[c] = g[c] LeakyReLU'(z_j[c]) at the arg-max neighbour (lowest list position among equals); exactly one lane of a half wins
 #pragma unroll
             for (int gq = 0; gq < 4; ++gq) {
-                const float4 gv = grow[(32 * t + 8 * gq + 4 * h) >> 2];
+                const float4 gv = grow[cross_at(t, gq, h)];
                 const float gi[4] = {gv.x, gv.y, gv.z, gv.w};
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const float zv = acc[4 * gq + i];
-                    const uint32_t key = mcp_ord(zv);
-                    const bool top = key == half_max_u32(key);
-                    const unsigned long long mask = __builtin_amdgcn_ballot_w64(top);
-                    const uint32_t mine = h ? (uint32_t)(mask >> 32) : (uint32_t)mask;
-                    if (live && top && (mine & lower_lanes) == 0u) {
+                    const bool wins = cross_winner(zv, h, lower_lanes);
+                    if (live && wins) {
                         const long long at = p * D + 32 * t + mcp_chan_of(4 * gq + i, h);
                         jstar[at] = col;
                         gz[at] = zv > 0.f ? gi[i] : SLOPE * gi[i];
@@ -250,7 +213,7 @@ __global__ __launch_bounds__(256) void cross256_grad_dx_kernel(long long total, 
         dbm += gk;
         if (k < KNB) {
             const int bb = (int)(p / n1);
-            const int id = idx2 ? (k >= 16 ? idx2[p * 16 + k - 16] : idx[p * 16 + k]) : idx[p * KNB + k];
+            const int id = cross_nbr(idx, idx2, p, k);
             const float *q2 = xyz2 + ((long long)bb * n2 + id) * 3;
             dir_s[k * 4 + 0] = q2[0] - xyz1[p * 3 + 0];
             dir_s[k * 4 + 1] = q2[1] - xyz1[p * 3 + 1];
@@ -382,7 +345,7 @@ Plan plan(long long total) {
     const long long sl = (total + 2 * W_PTS - 1) / (2 * W_PTS);
     pl.slices = (unsigned)(sl < W_SLICES ? sl : W_SLICES);
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    pl.off_j = up((size_t)IMG_FLOATS * 4);
+    pl.off_j = up((size_t)L::FLOATS * 4);  // the packed image comes first
     pl.off_gz = pl.off_j + up((size_t)total * D * 4);
     pl.off_pdx = pl.off_gz + up((size_t)total * D * 4);
     pl.off_pw = pl.off_pdx + up((size_t)pl.grid_dx * P_FLOATS * 4);
@@ -395,7 +358,7 @@ Plan plan(long long total) {
 MCP_EXPORT int mcp_cross256_grad_floats(void) { return G_FLOATS; }
 
 MCP_EXPORT size_t mcp_cross256_grad_workspace_bytes(int b, int n1) {
-    if (b <= 0 || n1 <= 0 || mcp_cross_packed_floats(D) != IMG_FLOATS) return 0;
+    if (b <= 0 || n1 <= 0) return 0;
     return plan((long long)b * n1).bytes;
 }
 
@@ -403,10 +366,9 @@ MCP_EXPORT int mcp_cross256_grad(int b, int n1, int n2, int k, const float *xyz1
                                  const int *idx, const int *idx2, const float *wpos, const float *bpos, const float *wmlp, const float *bmlp,
                                  const float *grad_out, float *grad_xyz1, float *grad_dir, float *grad_points1, float *grad_rows, float *grad_weights,
                                  void *workspace, size_t workspace_bytes, mcp_stream_t stream) {
-    MCP_CHECK_ARGS(b > 0 && n1 > 0 && n2 > 0 && xyz1 && xyz2 && points1 && points2 && idx && wpos && bpos && wmlp && bmlp && grad_out && grad_xyz1 &&
-                   grad_dir && grad_points1 && grad_rows && grad_weights && workspace);
-    if (k != KNB || mcp_cross_packed_floats(D) != IMG_FLOATS) return MCP_ERR_UNSUPPORTED;
-    if ((((uintptr_t)points1) | ((uintptr_t)points2) | ((uintptr_t)grad_out) | ((uintptr_t)grad_rows) | ((uintptr_t)workspace)) & 15) return MCP_ERR_BAD_ARG;
+    if (const int rc = cross_grad_check(b, n1, n2, true, k, xyz1, xyz2, points1, points2, idx, wpos, bpos, wmlp, bmlp, grad_out, grad_xyz1, grad_dir,
+                                        grad_points1, grad_rows, grad_weights, workspace))
+        return rc;
     const long long total = (long long)b * n1;
     const Plan pl = plan(total);
     if (workspace_bytes < pl.bytes) return MCP_ERR_BAD_ARG;

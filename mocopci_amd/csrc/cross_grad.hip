@@ -15,37 +15,17 @@
 //   Weight gradients accumulate in registers over a wave's points; waves are added in wave order through LDS, workgroups in
 //   workgroup order by a second kernel: every sum has a fixed order, the gradients repeat bit for bit.
 #include "common.h"
+#include "cross_tile.h"  // KNB, SLOPE, leaky, CrossLds, cross_nbr, cross_layer1, cross_winner, the entry checks
 #include "mfma_grad.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr int KNB = 32;
-constexpr float SLOPE = 0.1f;  // pointconv_util.py:10
 constexpr int TS = MCP_TS;
-
-__device__ __forceinline__ int chan_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-__device__ __forceinline__ float leaky(float v) { return mcp_max_raw(v, v * SLOPE); }  // as the forward (cross.hip)
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
-}
-
-template <int CTRL>
-__device__ __forceinline__ uint32_t max_dpp(uint32_t v) {
-    const uint32_t o = mcp_dpp<CTRL>(v);
-    return v > o ? v : o;
-}
-// maximum over the 32 lanes that share lane >> 5, in every lane
-__device__ __forceinline__ uint32_t half_max_u32(uint32_t v) {
-    v = max_dpp<0xB1>(v);   // quad_perm [1,0,3,2]
-    v = max_dpp<0x4E>(v);   // quad_perm [2,3,0,1]
-    v = max_dpp<0x141>(v);  // row_half_mirror
-    v = max_dpp<0x140>(v);  // row_mirror
-    const auto sw = __builtin_amdgcn_permlane16_swap(v, v, false, false);  // odd rows of one copy <-> even rows of the other
-    return sw[0] > sw[1] ? sw[0] : sw[1];
 }
 
 template <int D>
@@ -60,8 +40,8 @@ struct GradShape {
     static constexpr bool WT_LDS = D == 64;  // the Wmlp^T image: in LDS beside Wmlp (D = 64), or read from the workspace through L2 (98 KB at D = 128)
     // weight-gradient vector (floats): dWpos (D,3) | dbpos (D) | dWmlp (D,D) | dbmlp (D)
     static constexpr int G_WP = 0, G_BP = 3 * D, G_WM = 4 * D, G_BM = 4 * D + D * D, G_FLOATS = G_BM + D;
-    // LDS, floats: pos image [t][s][lane] | bmlp [t][h][r] | Wpos rows [t][h][r][4]
-    static constexpr int L_POS = 0, L_B = T * 2 * 64, L_WPR = L_B + T * 32, L_F32 = L_WPR + T * 32 * 4;
+    // LDS, floats: the forward's pos and bias images (CrossLds<D>) | Wpos rows [t][h][r][4]
+    static constexpr int L_POS = 0, L_B = CrossLds<D>::POS_FLOATS, L_WPR = L_B + CrossLds<D>::B_FLOATS, L_F32 = L_WPR + T * 32 * 4;
     static constexpr int W_U4 = T * (2 * T) * 3 * 64;  // uint4 per split image (Wmlp, Wmlp^T)
     static constexpr int W_LDS_U4 = WT_LDS ? 2 * W_U4 : W_U4;
     // per wave (floats): tile [64][TS] (two 32-channel tiles at a time) | directions [32][4]
@@ -104,17 +84,17 @@ __device__ __forceinline__ void cross_grad_body(float *lds, long long total, int
         const int row = 32 * t + (l & 31), c = 2 * s + (l >> 5);
         lds[S::L_POS + e] = c < 3 ? wpos[row * 3 + c] : bpos[row];
         const int k = e & 3, r = (e >> 2) & 15, hh = (e >> 6) & 1;  // Wpos rows in accumulator order, for d_dir = Wpos^T du
-        lds[S::L_WPR + e] = k < 3 ? wpos[(32 * t + chan_of(r, hh)) * 3 + k] : 0.f;
+        lds[S::L_WPR + e] = k < 3 ? wpos[(32 * t + mcp_chan_of(r, hh)) * 3 + k] : 0.f;
     }
     for (int e = tid; e < T * 32; e += 64 * WAVES) {
         const int r = e & 15, hh = (e >> 4) & 1, t = e >> 5;
-        lds[S::L_B + e] = bmlp[32 * t + chan_of(r, hh)];
+        lds[S::L_B + e] = bmlp[32 * t + mcp_chan_of(r, hh)];
     }
     mcp_split_weights(wms, wmlp, D, T, tid, 64 * WAVES);
     if (S::WT_LDS) mcp_split_weights_transposed(wmts_lds, wmlp, D, D, tid, 64 * WAVES);
     __syncthreads();
 
-    f32x16 dWa[2][HAS_OWN ? T : 1];  // dWmlp tiles: row = 32 (OWN + a) + chan_of(r, h), column = 32 nt + col
+    f32x16 dWa[2][HAS_OWN ? T : 1];  // dWmlp tiles: row = 32 (OWN + a) + mcp_chan_of(r, h), column = 32 nt + col
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -135,7 +115,7 @@ __device__ __forceinline__ void cross_grad_body(float *lds, long long total, int
         float q[3], c[3];
         float4 r1[4 * T], r2[4 * T], gr[4 * T];
     };
-    auto load_id = [&](long long pp) -> int { return idx2 ? (col >= 16 ? idx2[pp * 16 + col - 16] : idx[pp * 16 + col]) : idx[pp * KNB + col]; };
+    auto load_id = [&](long long pp) -> int { return cross_nbr(idx, idx2, pp, col); };
     auto fetch = [&](long long pp, int idn, Pre &o) {
         const long long bn = mcp_div(pp, n1, mcp_fits32(total));
         const float *q2n = xyz2 + ((long long)bn * n2 + idn) * 3;
@@ -148,7 +128,7 @@ __device__ __forceinline__ void cross_grad_body(float *lds, long long total, int
         for (int t = 0; t < T; ++t)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const int at = (32 * t + 8 * g + 4 * h) >> 2;
+                const int at = cross_at(t, g, h);
                 o.r1[4 * t + g] = r1n[at];
                 o.r2[4 * t + g] = r2n[at];
                 o.gr[4 * t + g] = grn[at];
@@ -189,23 +169,9 @@ __device__ __forceinline__ void cross_grad_body(float *lds, long long total, int
             McpSplit3 xs[2 * T];
 #pragma unroll
             for (int t = 0; t < T; ++t) {
-                f32x16 acc;
-                float4 rg[4];
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const float4 a = PIPE ? cur.r1[4 * t + g] : row1[(32 * t + 8 * g + 4 * h) >> 2];
-                    rg[g] = PIPE ? cur.r2[4 * t + g] : row2[(32 * t + 8 * g + 4 * h) >> 2];
-                    acc[4 * g + 0] = a.x; acc[4 * g + 1] = a.y; acc[4 * g + 2] = a.z; acc[4 * g + 3] = a.w;
-                }
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(lds[S::L_POS + (t * 2 + 0) * 64 + lane], in0, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(lds[S::L_POS + (t * 2 + 1) * 64 + lane], in1, acc, 0, 0, 0);
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    acc[4 * g + 0] = leaky(acc[4 * g + 0] + rg[g].x);
-                    acc[4 * g + 1] = leaky(acc[4 * g + 1] + rg[g].y);
-                    acc[4 * g + 2] = leaky(acc[4 * g + 2] + rg[g].z);
-                    acc[4 * g + 3] = leaky(acc[4 * g + 3] + rg[g].w);
-                }
+                const f32x16 acc = cross_layer1(
+                    lds + S::L_POS, t, lane, in0, in1, [&](int g) { return PIPE ? cur.r1[4 * t + g] : row1[cross_at(t, g, h)]; },
+                    [&](int g) { return PIPE ? cur.r2[4 * t + g] : row2[cross_at(t, g, h)]; }, CrossNoXSink());
                 x[t] = acc;
                 xs[2 * t + 0] = mcp_split_kstep(acc, 0);
                 xs[2 * t + 1] = mcp_split_kstep(acc, 1);
@@ -231,19 +197,14 @@ __device__ __forceinline__ void cross_grad_body(float *lds, long long total, int
                 f32x16 dzt;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    const float4 gv = PIPE ? cur.gr[4 * t + g] : grow[(32 * t + 8 * g + 4 * h) >> 2];
+                    const float4 gv = PIPE ? cur.gr[4 * t + g] : grow[cross_at(t, g, h)];
                     const float gq[4] = {gv.x, gv.y, gv.z, gv.w};
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const int r = 4 * g + i;
                         const float zv = acc[r];
-                        const uint32_t key = mcp_ord(zv);
-                        const bool top = key == half_max_u32(key);
-                        const unsigned long long mask = __builtin_amdgcn_ballot_w64(top);
-                        const uint32_t mine = h ? (uint32_t)(mask >> 32) : (uint32_t)mask;
-                        const bool winner = top && (mine & lower_lanes) == 0u;
-                        dzt[r] = winner ? (zv > 0.f ? gq[i] : SLOPE * gq[i]) : 0.f;
-                        if (own) tb[(32 * (t - OWN0) + chan_of(r, h)) * TS + col] = dzt[r];
+                        dzt[r] = cross_winner(zv, h, lower_lanes) ? (zv > 0.f ? gq[i] : SLOPE * gq[i]) : 0.f;
+                        if (own) tb[(32 * (t - OWN0) + mcp_chan_of(r, h)) * TS + col] = dzt[r];
                     }
                 }
                 if (DATA) {
@@ -301,7 +262,7 @@ __device__ __forceinline__ void cross_grad_body(float *lds, long long total, int
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const f32x16 &dt = du[DATA ? t : 0];
-                    orow[(32 * t + 8 * g + 4 * h) >> 2] = make_float4(dt[4 * g + 0], dt[4 * g + 1], dt[4 * g + 2], dt[4 * g + 3]);
+                    orow[cross_at(t, g, h)] = make_float4(dt[4 * g + 0], dt[4 * g + 1], dt[4 * g + 2], dt[4 * g + 3]);
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const float4 w = reinterpret_cast<const float4 *>(lds + S::L_WPR)[(t * 2 + h) * 16 + 4 * g + i];
@@ -376,7 +337,7 @@ __device__ __forceinline__ void cross_grad_body(float *lds, long long total, int
 #pragma unroll
                 for (int nt = 0; nt < T; ++nt)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) red[S::G_WM + (32 * (OWN0 + a) + chan_of(r, h)) * D + 32 * nt + col] += dWa[a][HAS_OWN ? nt : 0][r];
+                    for (int r = 0; r < 16; ++r) red[S::G_WM + (32 * (OWN0 + a) + mcp_chan_of(r, h)) * D + 32 * nt + col] += dWa[a][HAS_OWN ? nt : 0][r];
                 const float vb = dbm[a] + __shfl_xor(dbm[a], 32);
                 if (h == 0) red[S::G_BM + 32 * (OWN0 + a) + col] += vb;
             }
@@ -504,10 +465,9 @@ MCP_EXPORT int mcp_cross_grad(int b, int n1, int n2, int d, int k, const float *
                               const int *idx, const int *idx2, const float *wpos, const float *bpos, const float *wmlp, const float *bmlp,
                               const float *grad_out, float *grad_xyz1, float *grad_dir, float *grad_points1, float *grad_rows, float *grad_weights,
                               void *workspace, size_t workspace_bytes, mcp_stream_t stream) {
-    MCP_CHECK_ARGS(b > 0 && n1 > 0 && n2 > 0 && xyz1 && xyz2 && points1 && points2 && idx && wpos && bpos && wmlp && bmlp && grad_out && grad_xyz1 &&
-                   grad_dir && grad_points1 && grad_rows && grad_weights && workspace);
-    if (k != KNB || (d != 64 && d != 128)) return MCP_ERR_UNSUPPORTED;
-    if ((((uintptr_t)points1) | ((uintptr_t)points2) | ((uintptr_t)grad_out) | ((uintptr_t)grad_rows) | ((uintptr_t)workspace)) & 15) return MCP_ERR_BAD_ARG;
+    if (const int rc = cross_grad_check(b, n1, n2, d == 64 || d == 128, k, xyz1, xyz2, points1, points2, idx, wpos, bpos, wmlp, bmlp, grad_out, grad_xyz1,
+                                        grad_dir, grad_points1, grad_rows, grad_weights, workspace))
+        return rc;
     if (workspace_bytes < mcp_cross_grad_workspace_bytes(b, n1, d)) return MCP_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
     const long long total = (long long)b * n1;

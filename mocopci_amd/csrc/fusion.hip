@@ -34,7 +34,7 @@ constexpr int C1 = 64, C2 = 64, NB = 64;  // layer widths 4 -> 64 -> 64 -> 128  
 constexpr int WAVES = 4;
 
 
-__device__ __forceinline__ int chan_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+// register r of lane half h of an accumulator tile -> its channel: mcp_chan_of (common.h)
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -71,21 +71,21 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fusion_kernel(long long total, 
     for (int e = tid; e < 4096; e += 64 * WAVES) {  // w2: [t][q][lane][j]: k-step s=4q+j -> tin=s>>4, r=s&15
         const int j = e & 3, lane = (e >> 2) & 63, q = (e >> 8) & 7, t = e >> 11;
         const int s = 4 * q + j, tin = s >> 4, r = s & 15;
-        lds[OFF_W2 + e] = w2[(32 * t + (lane & 31)) * C1 + 32 * tin + chan_of(r, lane >> 5)];
+        lds[OFF_W2 + e] = w2[(32 * t + (lane & 31)) * C1 + 32 * tin + mcp_chan_of(r, lane >> 5)];
     }
     for (int e = tid; e < 8192; e += 64 * WAVES) {
         const int j = e & 3, lane = (e >> 2) & 63, q = (e >> 8) & 7, t = e >> 11;
         const int s = 4 * q + j, tin = s >> 4, r = s & 15;
-        lds[OFF_W3 + e] = w3[(32 * t + (lane & 31)) * C2 + 32 * tin + chan_of(r, lane >> 5)];
+        lds[OFF_W3 + e] = w3[(32 * t + (lane & 31)) * C2 + 32 * tin + mcp_chan_of(r, lane >> 5)];
     }
     for (int e = tid; e < 64; e += 64 * WAVES) {  // biases: [t][h][r]
         const int r = e & 15, h = (e >> 4) & 1, t = e >> 5;
-        lds[OFF_B1 + e] = b1[32 * t + chan_of(r, h)];
-        lds[OFF_B2 + e] = b2[32 * t + chan_of(r, h)];
+        lds[OFF_B1 + e] = b1[32 * t + mcp_chan_of(r, h)];
+        lds[OFF_B2 + e] = b2[32 * t + mcp_chan_of(r, h)];
     }
     for (int e = tid; e < 128; e += 64 * WAVES) {
         const int r = e & 15, h = (e >> 4) & 1, t = e >> 5;
-        lds[OFF_B3 + e] = b3[32 * t + chan_of(r, h)];
+        lds[OFF_B3 + e] = b3[32 * t + mcp_chan_of(r, h)];
     }
     __syncthreads();
 
@@ -241,12 +241,12 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fusion_split_kernel(long long t
     mcp_split_weights(w3s, w3, C2, 4, tid, 64 * WAVES);
     for (int e = tid; e < 64; e += 64 * WAVES) {  // biases: [t][h][r]
         const int r = e & 15, h = (e >> 4) & 1, t = e >> 5;
-        lds[SP_B1 + e] = b1[32 * t + chan_of(r, h)];
-        lds[SP_B2 + e] = b2[32 * t + chan_of(r, h)];
+        lds[SP_B1 + e] = b1[32 * t + mcp_chan_of(r, h)];
+        lds[SP_B2 + e] = b2[32 * t + mcp_chan_of(r, h)];
     }
     for (int e = tid; e < 128; e += 64 * WAVES) {
         const int r = e & 15, h = (e >> 4) & 1, t = e >> 5;
-        lds[SP_B3 + e] = b3[32 * t + chan_of(r, h)];
+        lds[SP_B3 + e] = b3[32 * t + mcp_chan_of(r, h)];
     }
     __syncthreads();
 

@@ -109,8 +109,8 @@ constexpr int L_W1 = 0, L_B1 = 256, L_B2 = L_B1 + 64, L_B3 = L_B2 + 64, L_BN1 = 
               L_F32 = L_BN3 + 4 * C3;  // 1536
 constexpr int W2_U4 = 2 * 4 * 3 * 64, W3_U4 = 4 * 4 * 3 * 64;
 
-__device__ __forceinline__ int chan_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-__device__ __forceinline__ int acc_to_channel(int e) { return 32 * (e >> 5) + chan_of(e & 15, (e >> 4) & 1); }  // [t][h][r] -> channel
+// register r of lane half h of an accumulator tile -> its channel: mcp_chan_of (common.h)
+__device__ __forceinline__ int acc_to_channel(int e) { return 32 * (e >> 5) + mcp_chan_of(e & 15, (e >> 4) & 1); }  // [t][h][r] -> channel
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -370,7 +370,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void FBN_KERNEL(fwd)(FBN_FWD_PARAMS 
                 }
             }
             if (SAVE) {
-                const int mc = 32 * (mr >> 4) + chan_of(mr & 15, h);
+                const int mc = 32 * (mr >> 4) + mcp_chan_of(mr & 15, h);
                 const float om = __shfl_xor(m, 32), oz = __shfl_xor(zb, 32);
                 const int oc = __shfl_xor(mc, 32);
                 const bool other = om > m || (om == m && oc < mc);
@@ -636,7 +636,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void FBN_KERNEL(b1)(FBN_B1_PARAMS FB
                     mr = up ? 16 * t + r : mr;
                 }
             }
-            const int mc = 32 * (mr >> 4) + chan_of(mr & 15, h);
+            const int mc = 32 * (mr >> 4) + mcp_chan_of(mr & 15, h);
             const float om = __shfl_xor(m, 32), oz = __shfl_xor(zb, 32);
             const int oc = __shfl_xor(mc, 32);
             const bool other = om > m || (om == m && oc < mc);
@@ -913,7 +913,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void FBN_KERNEL(b2)(FBN_B2_PARAMS FB
                 f32x16 zh, v, dy, dz;
                 bn_tile<C3>(lds + L_BN3 + (t * 2 + h) * 16, z3, zh, v);
 #pragma unroll
-                for (int r = 0; r < 16; ++r) dy[r] = (32 * t + chan_of(r, h)) == cst ? dys : 0.f;
+                for (int r = 0; r < 16; ++r) dy[r] = (32 * t + mcp_chan_of(r, h)) == cst ? dys : 0.f;
                 dz_tile<C3>(lds + B2_L_DZ + (t * 2 + h) * 16, dy, zh, dz);
                 __builtin_amdgcn_wave_barrier();
                 mcp_write_tile(tz, dz, col, h);
@@ -974,7 +974,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void FBN_KERNEL(b2)(FBN_B2_PARAMS FB
 #pragma unroll
                 for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) red[(32 * mt + chan_of(r, h)) * C2 + 32 * nt + col] += dW3a[mt][nt][r];
+                    for (int r = 0; r < 16; ++r) red[(32 * mt + mcp_chan_of(r, h)) * C2 + 32 * nt + col] += dW3a[mt][nt][r];
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt) {
                 const float a = s2[mt] + __shfl_xor(s2[mt], 32), b = g2[mt] + __shfl_xor(g2[mt], 32);
@@ -1123,7 +1123,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void FBN_KERNEL(b3)(FBN_B3_PARAMS FB
 #pragma unroll
                 for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) red[(32 * mt + chan_of(r, h)) * C1 + 32 * nt + col] += dW2a[mt][nt][r];
+                    for (int r = 0; r < 16; ++r) red[(32 * mt + mcp_chan_of(r, h)) * C1 + 32 * nt + col] += dW2a[mt][nt][r];
                 const float a = s1[mt] + __shfl_xor(s1[mt], 32), b = g1[mt] + __shfl_xor(g1[mt], 32);
                 if (h == 0) {
                     red[C2 * C1 + 32 * mt + col] += a;
@@ -1155,7 +1155,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void FBN_KERNEL(b4)(FBN_B4_PARAMS FB
     stage_dz_consts(lds + B4_L_DZ, bn + BN_L1, sums1, C1, fbn_inv_rows(inv_rows, C1, total, n FBN_LENS), tid, 64 * WAVES);
     for (int e = tid; e < 256; e += 64 * WAVES) {  // W1 rows in accumulator order, for dx0 = W1^T dz1
         const int k = e & 3, r = (e >> 2) & 15, hh = (e >> 6) & 1, tt = e >> 7;
-        lds[B4_L_W1R + e] = w1[(32 * tt + chan_of(r, hh)) * 4 + k];
+        lds[B4_L_W1R + e] = w1[(32 * tt + mcp_chan_of(r, hh)) * 4 + k];
     }
     __syncthreads();
     const int lane = tid & 63, wave = tid >> 6, h = lane >> 5, col = lane & 31;

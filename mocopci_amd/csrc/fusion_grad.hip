@@ -44,7 +44,7 @@ constexpr size_t LDS_BYTES = (size_t)L_F32 * 4 + (size_t)(2 * L_W2_U4 + L_W3_U4)
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 static_assert((size_t)G_FLOATS * 4 <= (size_t)L_F32 * 4 + (size_t)(2 * L_W2_U4 + L_W3_U4) * 16, "the reduction buffer overlays the weight image");
 
-__device__ __forceinline__ int chan_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+// register r of lane half h of an accumulator tile -> its channel: mcp_chan_of (common.h)
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -80,23 +80,23 @@ __global__ __launch_bounds__(64 * WAVES, 1) void fusion_grad_kernel(long long to
         const int l = e & 63, s = (e >> 6) & 1, t = e >> 7;
         lds[L_W1 + e] = w1[(32 * t + (l & 31)) * 4 + 2 * s + (l >> 5)];
         const int k = e & 3, r = (e >> 2) & 15, hh = (e >> 6) & 1, tt = e >> 7;  // W1 rows in accumulator order, for dx0 = W1^T dz1
-        lds[L_W1R + e] = w1[(32 * tt + chan_of(r, hh)) * 4 + k];
+        lds[L_W1R + e] = w1[(32 * tt + mcp_chan_of(r, hh)) * 4 + k];
     }
     mcp_split_weights(w2s, w2, C1, 2, tid, 64 * WAVES);
     mcp_split_weights(w3s, w3, C2, 4, tid, 64 * WAVES);
     mcp_split_weights_transposed(w2ts, w2, C1, C2, tid, 64 * WAVES);
     for (int e = tid; e < 64; e += 64 * WAVES) {  // biases: [t][h][r]
         const int r = e & 15, hh = (e >> 4) & 1, t = e >> 5;
-        lds[L_B1 + e] = b1[32 * t + chan_of(r, hh)];
-        lds[L_B2 + e] = b2[32 * t + chan_of(r, hh)];
+        lds[L_B1 + e] = b1[32 * t + mcp_chan_of(r, hh)];
+        lds[L_B2 + e] = b2[32 * t + mcp_chan_of(r, hh)];
     }
     for (int e = tid; e < 128; e += 64 * WAVES) {
         const int r = e & 15, hh = (e >> 4) & 1, t = e >> 5;
-        lds[L_B3 + e] = b3[32 * t + chan_of(r, hh)];
+        lds[L_B3 + e] = b3[32 * t + mcp_chan_of(r, hh)];
     }
     __syncthreads();
 
-    // weight-gradient accumulators of this wave.  MFMA tiles: row = 32 mt + chan_of(r, h), column = 32 nt + col.
+    // weight-gradient accumulators of this wave.  MFMA tiles: row = 32 mt + mcp_chan_of(r, h), column = 32 nt + col.
     f32x16 dW2a[2][2], dW3a[4][2];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void fusion_grad_kernel(long long to
                     mr = up ? 16 * t + r : mr;
                 }
             }
-            int mc = 32 * (mr >> 4) + chan_of(mr & 15, h);
+            int mc = 32 * (mr >> 4) + mcp_chan_of(mr & 15, h);
             const float om = __shfl_xor(m, 32);
             const int oc = __shfl_xor(mc, 32);
             const bool other = om > m || (om == m && oc < mc);
@@ -224,7 +224,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void fusion_grad_kernel(long long to
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) tb[(32 * t + chan_of(r, h)) * TS + col] = dz3 * h2[t][r];
+                for (int r = 0; r < 16; ++r) tb[(32 * t + mcp_chan_of(r, h)) * TS + col] = dz3 * h2[t][r];
             if (h == 0) {
                 csb[col] = cst;
                 dzb[col] = dz3;
@@ -272,7 +272,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void fusion_grad_kernel(long long to
                 for (int t = 0; t < 2; ++t)
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        const float4 w = w3row[8 * t + 2 * q + h];  // channels 32 t + 8 q + 4 h + (0..3) = chan_of(4 q + i, h)
+                        const float4 w = w3row[8 * t + 2 * q + h];  // channels 32 t + 8 q + 4 h + (0..3) = mcp_chan_of(4 q + i, h)
                         dz2[t][4 * q + 0] = h2[t][4 * q + 0] > 0.f ? dz3 * w.x : 0.f;
                         dz2[t][4 * q + 1] = h2[t][4 * q + 1] > 0.f ? dz3 * w.y : 0.f;
                         dz2[t][4 * q + 2] = h2[t][4 * q + 2] > 0.f ? dz3 * w.z : 0.f;
@@ -392,7 +392,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void fusion_grad_kernel(long long to
                 for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        float *o = red + G_W2 + (32 * mt + chan_of(r, h)) * C1 + 32 * nt + col;
+                        float *o = red + G_W2 + (32 * mt + mcp_chan_of(r, h)) * C1 + 32 * nt + col;
                         *o = first ? dW2a[mt][nt][r] : *o + dW2a[mt][nt][r];
                     }
 #pragma unroll
@@ -401,7 +401,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void fusion_grad_kernel(long long to
                 for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        float *o = red + G_W3 + (32 * mt + chan_of(r, h)) * C2 + 32 * nt + col;
+                        float *o = red + G_W3 + (32 * mt + mcp_chan_of(r, h)) * C2 + 32 * nt + col;
                         *o = first ? dW3a[mt][nt][r] : *o + dW3a[mt][nt][r];
                     }
 #pragma unroll

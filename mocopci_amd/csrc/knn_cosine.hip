@@ -24,7 +24,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define KEY_INF MCP_KEY_INF
 constexpr int K = 16, QS = 16, CHK = 4, RT = 32, WAVES = 4;
 
-__device__ __forceinline__ int chan_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+// register r of lane half h of an accumulator tile -> its channel: mcp_chan_of (common.h)
 
 // Per-cloud lengths of a padded batch (mcp_knn_cosine_lengths), the compile-time switch of the two shipped kernels: each is stated once
 // with a trailing parameter pack L that is either empty -- the plain kernel, with the parameter list and the code it always had -- or
@@ -203,7 +203,7 @@ __global__ __launch_bounds__(64 * WAVES) void knn_cosine_kernel(int q, int n, in
         for (int r0 = 0; r0 < 16; r0 += CHK) {
 #pragma unroll
             for (int r = r0; r < r0 + CHK; ++r) {
-                const int ri = base + chan_of(r, h);
+                const int ri = base + mcp_chan_of(r, h);
                 const float d = 1.0f - acc[r];
                 if (ri < n && d < tau) {
                     queue[cnt][lane] = make_uint2(__float_as_uint(d), (uint32_t)ri);
@@ -341,7 +341,7 @@ __global__ __launch_bounds__(64 * RS) void knn_cosine_split_kernel(int q, int n_
         for (int r0 = 0; r0 < 16; r0 += CHK) {
 #pragma unroll
             for (int r = r0; r < r0 + CHK; ++r) {
-                const int ri = base + chan_of(r, h);
+                const int ri = base + mcp_chan_of(r, h);
                 const float d = 1.0f - acc[r];
                 if (ri < n && d < tau) {
                     queue[cnt][lane] = make_uint2(__float_as_uint(d), (uint32_t)ri);

@@ -20,7 +20,7 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int WG_ROWS = 32, WAVES = 4, MAX_WGS = 256;
 
-__device__ __forceinline__ int chan_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+// register r of lane half h of an accumulator tile -> its channel: mcp_chan_of (common.h)
 
 // TPW: output tiles per wave (tiles wave, wave + 4, ...); the host picks the smallest of 1, 2, 4, 8, 16 that covers (n/32)(k/32)/4
 template <int TPW>
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(64 * WAVES) void linear_wgrad_kernel(long long rows
             const int a = t / kt, b = t - a * kt;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int ch = 32 * a + chan_of(r, h), col = 32 * b + c;
+                const int ch = 32 * a + mcp_chan_of(r, h), col = 32 * b + c;
                 if (ch < n && col < k) out[(size_t)ch * k + col] = acc[i][r];
             }
         }

@@ -19,7 +19,6 @@
 typedef float mcp_f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 mcp_bf16x8 __attribute__((ext_vector_type(8)));
 
-__device__ __forceinline__ int mcp_chan_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 __device__ __forceinline__ uint32_t mcp_top16(float x) { return __float_as_uint(x) & 0xFFFF0000u; }
 // (hi16(odd) << 16) | hi16(even): two bf16 pieces in one dword, element 2j in the low half
 __device__ __forceinline__ uint32_t mcp_pack_hi(float even, float odd) {

@@ -23,7 +23,7 @@ constexpr int WSPLIT = 2 * 4 * 3 * 64 * 4;  // floats per 64x64 layer
 constexpr int OFF_D1 = 0, OFF_D2 = 256, OFF_G1 = OFF_D2 + WSPLIT, OFF_G2 = OFF_G1 + WSPLIT, OFF_BD2 = OFF_G2 + WSPLIT,
               OFF_BG1 = OFF_BD2 + 64, OFF_BG2 = OFF_BG1 + 64, PACK_FLOATS = OFF_BG2 + 64;
 
-__device__ __forceinline__ int chan_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+// register r of lane half h of an accumulator tile -> its channel: mcp_chan_of (common.h)
 
 template <int CTRL>
 __device__ __forceinline__ float dppf(float v) {
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void ptblock_pack_kernel(const float *__restri
             const int f = (e - OFF_BD2) & 63, which = (e - OFF_BD2) >> 6;
             const float *bb = which == 0 ? bd2 : which == 1 ? bg1 : bg2;
             const int r = f & 15, h = (f >> 4) & 1, t = f >> 5;
-            v = bb[32 * t + chan_of(r, h)];
+            v = bb[32 * t + mcp_chan_of(r, h)];
         }
         packed[e] = v;
     }

@@ -32,7 +32,7 @@ constexpr size_t LDS_BYTES = (size_t)L_F32 * 4 + (size_t)3 * W_U4 * 16 + (size_t
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 static_assert((size_t)G_FLOATS * 4 <= (size_t)L_F32 * 4 + (size_t)3 * W_U4 * 16, "the reduction buffer overlays the weight images");
 
-__device__ __forceinline__ int chan_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+// register r of lane half h of an accumulator tile -> its channel: mcp_chan_of (common.h)
 template <int CTRL>
 __device__ __forceinline__ float dppf(float v) {
     return __uint_as_float(mcp_dpp<CTRL>(__float_as_uint(v)));
@@ -121,10 +121,10 @@ __global__ __launch_bounds__(64 * WAVES, 1) void ptblock_grad_kernel(long long t
         const int row = 32 * t + (l & 31), c = 2 * s + (l >> 5);
         lds[L_D1 + e] = c < 3 ? wd1[row * 3 + c] : bd1[row];
         const int k = e & 3, r = (e >> 2) & 15, hh = (e >> 6) & 1;  // Wd1 rows in accumulator order, for dd = Wd1^T dzd
-        lds[L_WD1R + e] = k < 3 ? wd1[(32 * t + chan_of(r, hh)) * 3 + k] : 0.f;
+        lds[L_WD1R + e] = k < 3 ? wd1[(32 * t + mcp_chan_of(r, hh)) * 3 + k] : 0.f;
     }
     for (int e = tid; e < 64; e += 64 * WAVES) {
-        const int r = e & 15, hh = (e >> 4) & 1, t = e >> 5, c = 32 * t + chan_of(r, hh);
+        const int r = e & 15, hh = (e >> 4) & 1, t = e >> 5, c = 32 * t + mcp_chan_of(r, hh);
         lds[L_BD2 + e] = bd2[c];
         lds[L_BG1 + e] = bg1[c];
         lds[L_BG2 + e] = bg2[c];
@@ -383,7 +383,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void ptblock_grad_kernel(long long t
                 for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int o = (32 * mt + chan_of(r, h)) * C + 32 * nt + col;
+                        const int o = (32 * mt + mcp_chan_of(r, h)) * C + 32 * nt + col;
                         red[G_WD2 + o] += dWd2a[mt][nt][r];
                         red[G_WG1 + o] += dWg1a[mt][nt][r];
                         red[G_WG2 + o] += dWg2a[mt][nt][r];

@@ -80,8 +80,8 @@ def _attention(bf, nq, nk, heads, hd):
 # check that the cases reach the loop edges their comments name ----
 POINTCONV_LOWLEVEL_MAX = 16384   # pc_agg_run, csrc/pointconv_tile.h
 FUSION_WAVES, FUSION_GRID_CAP = 4, 4096                      # fusion.hip:34, :298
-CROSS_WAVES = {64: 4, 128: 8, 256: 4}                        # CrossShape<D>::NW, cross.hip:150; X256_WAVES, cross.hip:330
-CROSS_GRID_CAP = {64: 768, 128: 256, 256: 256}               # CrossShape<D>::GRID, cross.hip:152; launch_cross256, cross.hip:439
+CROSS_WAVES = {64: 4, 128: 8, 256: 4}                        # CrossShape<D>::NW, cross.hip; X256_WAVES, cross_tile.h
+CROSS_GRID_CAP = {64: 768, 128: 256, 256: 256}               # CrossShape<D>::GRID and launch_cross256, cross.hip
 PTBLOCK_WAVES, PTBLOCK_GRID_CAP = 4, 768                     # ptblock.hip:19, :194
 
 
@@ -92,11 +92,11 @@ def _fusion(b, n, nb=64):
 
 
 def _cross(d, k=32):
-    if k != 32 or d not in (64, 128, 256):                           # mcp_cross_volume, cross.hip:489
+    if k != 32 or d not in (64, 128, 256):                           # mcp_cross_volume, cross.hip
         raise ValueError(f"cross: d={d}, k={k} is not built")
-    if d == 256:                                                     # cross.hip:495-497 -> launch_cross256 :440
+    if d == 256:                                                     # mcp_cross_volume -> launch_cross256
         return "cross256_stream_kernel"
-    return f"cross_kernel<{d}, 1>"                                   # launch_cross<D, 1>, cross.hip:452
+    return f"cross_kernel<{d}, 1>"                                   # launch_cross<D, 1>, cross.hip
 
 
 def _pointconv_agg(b, s, d, aligned=True, k=32):
@@ -129,16 +129,16 @@ def _ptblock(c=64, k=16):
 
 def launch_grid(op, **shape):
     """(workgroups, units, units per workgroup step) of the launch: `units` are what the kernel's persistent loop deals out (points,
-    or point pairs in ptblock_kernel).  mcp_units_by_xcd (common.h:101-111) and cross_kernel (cross.hip:197-204) deal units by XCD
-    when the grid is a multiple of 8; cross256_stream_kernel always deals round-robin (cross.hip:356-358)."""
+    or point pairs in ptblock_kernel).  mcp_units_by_xcd (common.h) and cross_kernel (its own deal, cross.hip) deal units by XCD
+    when the grid is a multiple of 8; cross256_stream_kernel always deals round-robin (its `rounds`, cross.hip)."""
     if op == "fusion":                                               # fusion.hip:304
         total = shape["b"] * shape["n"]
         return min(_cdiv(total, FUSION_WAVES), FUSION_GRID_CAP), total, FUSION_WAVES
     if op == "cross":
         d, total = shape["d"], shape["b"] * shape["n1"]
         nw = CROSS_WAVES[d]
-        want = _cdiv(total, nw) if d == 256 else _cdiv(total, nw * 8)   # cross.hip:438, :459
-        return max(1, min(want, CROSS_GRID_CAP[d])), total, nw          # cross.hip:439, :462
+        want = _cdiv(total, nw) if d == 256 else _cdiv(total, nw * 8)   # launch_cross256, launch_cross
+        return max(1, min(want, CROSS_GRID_CAP[d])), total, nw          # launch_cross256, launch_cross
     if op == "pointconv_agg":
         total = shape["b"] * shape["s"]
         name = expected_kernel(op, **shape)
@@ -353,17 +353,17 @@ def cases(op):
 
 # ---- the backward units of the fused point layers.  Every backward kernel is persistent: one workgroup per CU at the most, units
 # (points, or point pairs) dealt statically, weight-gradient partial vectors added by a second kernel over ALL workgroups ----
-GRAD_WAVES = 4                    # WAVES, fusion_grad.hip:30, cross_grad.hip:54, cross256_grad.hip:28, pointconv_grad.hip:18, ptblock_grad.hip
-X256_DX_GRID, X256_W_SLICES, X256_W_PTS = 512, 64, 4     # DX_GRID, W_SLICES, W_PTS, cross256_grad.hip:39
-X256_Z_GRID_CAP = 256             # plan(), cross256_grad.hip:380 (a constant there, not the CU count)
+GRAD_WAVES = 4                    # WAVES, fusion_grad.hip:30, GradShape<D>::WAVES in cross_grad.hip, X256_WAVES in cross_tile.h, pointconv_grad.hip:18, ptblock_grad.hip
+X256_DX_GRID, X256_W_SLICES, X256_W_PTS = 512, 64, 4     # DX_GRID, W_SLICES, W_PTS, cross256_grad.hip
+X256_Z_GRID_CAP = 256             # plan(), cross256_grad.hip (a constant there, not the CU count)
 
 
 def _deal(units, per, g, base=0, xcd_map=True):
     """(dealt by XCD, [workgroup][round] -> list of units) for g workgroups of one role that starts at workgroup `base` of the launch.
-    mcp_units_by_xcd, common.h:101-111 (base = 0) and deal(), cross_grad.hip:419-430: by XCD when g >= 8, g % 8 == 0 and base % 8 == 0
+    mcp_units_by_xcd (common.h; base = 0) and cross_grad_kernel's deal() (cross_grad.hip): by XCD when g >= 8, g % 8 == 0 and base % 8 == 0
     -- eighths of ceil(steps / 8) whole steps, workgroup k starts at step k >> 3 of eighth k & 7 and strides g >> 3 steps --, else
     workgroup k starts at step k and strides g steps.  Wave w of a workgroup takes unit first + w + round * stride while below the limit
-    (fusion_grad.hip:113, cross_grad.hip:167, pointconv_grad.hip:54, ptblock_grad.hip:149)."""
+    (fusion_grad.hip:113, cross_grad_body's point loop in cross_grad.hip, pointconv_grad.hip:54, ptblock_grad.hip:149)."""
     by_xcd = xcd_map and g >= 8 and g % 8 == 0 and base % 8 == 0
     dealt = []
     for k in range(g):
@@ -393,20 +393,20 @@ def grad_launch_grid(op, cus=256, **shape):
     if op == "cross":
         d, total = shape["d"], shape["b"] * shape["n1"]
         want = _cdiv(total, GRAD_WAVES)
-        if d == 64:                                                  # grad_grid<64>, cross_grad.hip:462-465 (one role), deal :432
+        if d == 64:                                                  # grad_grid<64>, cross_grad.hip (one role), cross_grad_kernel's deal
             return {"all": _role(total, GRAD_WAVES, min(want, cus))}
-        if d == 128:                                                 # grad_grid<128>, cross_grad.hip:462-465; roles :434-442
+        if d == 128:                                                 # grad_grid<128>, cross_grad.hip; the roles of cross_grad_kernel
             g0, g1 = min(want, max(cus // 2, 1)), min(want, max(cus // 4, 1))
             return {"data": _role(total, GRAD_WAVES, g0, 0), "own0": _role(total, GRAD_WAVES, g1, g0), "own2": _role(total, GRAD_WAVES, g1, g0 + g1)}
-        if d == 256:                                                 # plan(), cross256_grad.hip:377-390
+        if d == 256:                                                 # plan(), cross256_grad.hip
             slices = min(_cdiv(total, 2 * X256_W_PTS), X256_W_SLICES)
-            per = _cdiv(total, slices)                               # cross256_grad_w_kernel, cross256_grad.hip:189: slice s takes points s per .. (s + 1) per
+            per = _cdiv(total, slices)                               # cross256_grad_w_kernel: slice s takes points s per .. (s + 1) per
             w = [[list(range(p, min(p + X256_W_PTS, total, (s + 1) * per))) for p in range(s * per, min((s + 1) * per, total), X256_W_PTS)]
                  for s in range(slices)]                             # in stages of W_PTS points, :195
-            return {"z": _role(total, GRAD_WAVES, min(want, X256_Z_GRID_CAP), xcd_map=False),     # round-robin rounds, cross256_grad.hip:78-83
+            return {"z": _role(total, GRAD_WAVES, min(want, X256_Z_GRID_CAP), xcd_map=False),     # round-robin rounds, cross256_grad_z_kernel
                     "w": dict(workgroups=slices, units=total, per=X256_W_PTS, by_xcd=False, dealt=w),   # times 4 column blocks, :188, :429
-                    "dx": _role(total, 1, min(total, X256_DX_GRID), xcd_map=False)}                 # cross256_grad.hip:243, :381
-        raise ValueError(f"cross grad: d={d} is not built")          # mcp_cross_grad, cross_grad.hip:514
+                    "dx": _role(total, 1, min(total, X256_DX_GRID), xcd_map=False)}                 # cross256_grad_dx_kernel's point loop; plan()
+        raise ValueError(f"cross grad: d={d} is not built")          # mcp_cross_grad, cross_grad.hip
     if op == "pointconv_agg":                                        # grad_grid, pointconv_grad_tile.h; pairs: the kernel's loop there
         total = shape["b"] * shape["s"]
         return {"pairs": _role((total + 1) // 2, GRAD_WAVES, min(_cdiv(total, 2 * GRAD_WAVES), cus))}
@@ -424,10 +424,10 @@ def expected_grad_kernels(op, **shape):
     if op == "cross":
         d = shape["d"]
         _cross(d, shape.get("k", 32))
-        if d == 256:                                                 # mcp_cross256_grad, cross256_grad.hip:427-433
+        if d == 256:                                                 # mcp_cross256_grad's launches, cross256_grad.hip
             return {"cross256_grad_z_kernel", "cross256_grad_w_kernel", "cross256_grad_dx_kernel", "cross256_grad_reduce_kernel"}
-        names = {f"cross_grad_kernel<{d}>", "cross_grad_reduce_kernel"}   # launch_cross_grad, cross_grad.hip:493-495
-        return names | {"transposed_image_kernel"} if d == 128 else names   # !WT_LDS, cross_grad.hip:60, :491
+        names = {f"cross_grad_kernel<{d}>", "cross_grad_reduce_kernel"}   # launch_cross_grad, cross_grad.hip
+        return names | {"transposed_image_kernel"} if d == 128 else names   # !GradShape<D>::WT_LDS, launch_cross_grad
     if op == "pointconv_agg":                                        # pcg_run, pointconv_grad_tile.h; ops.pointconv_agg: d % 4 == 0, d <= 256
         if shape.get("k", 32) != 32 or shape["d"] % 4 or shape["d"] > 256:
             raise ValueError(f"pointconv_agg grad: d={shape['d']} is not built")

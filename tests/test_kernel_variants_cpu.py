@@ -98,7 +98,7 @@ def test_expected_kernel_mirrors_the_dispatch_rules():
 
 
 def test_expected_kernel_mirrors_the_fused_dispatch_rules():
-    # pointconv_tile.h: pc_agg_run, pc_linear_run; cross.hip:489-497; fusion.hip:291, :318; ptblock.hip:188, :197
+    # pointconv_tile.h: pc_agg_run, pc_linear_run; mcp_cross_volume (cross.hip); fusion.hip:291, :318; ptblock.hip:188, :197
     e = kv.expected_kernel
     agg = lambda total, d, **kw: e("pointconv_agg", b=1, s=total, d=d, **kw)
     assert agg(16384, 32) == "pointconv_agg_lowlevel_kernel<256>"
@@ -123,7 +123,7 @@ def test_expected_kernel_mirrors_the_fused_dispatch_rules():
                 dict(op="cross", d=64, k=16), dict(op="fusion", b=1, n=1, nb=32), dict(op="ptblock", c=128), dict(op="pointconv_agg", b=1, s=1, d=4, k=16)):
         with pytest.raises(ValueError):
             kv.expected_kernel(**bad)
-    # the grids beside the dispatch: fusion.hip:304, cross.hip:439, :459-462, pointconv_tile.h: pc_agg_run, pc_linear_run, ptblock.hip:193-194
+    # the grids beside the dispatch: fusion.hip:304, launch_cross256 and launch_cross (cross.hip), pointconv_tile.h: pc_agg_run, pc_linear_run, ptblock.hip:193-194
     g = kv.launch_grid
     assert g("fusion", b=2, n=1500)[0] == 750 and g("fusion", b=3, n=5483)[0] == 4096 and g("fusion", b=1, n=1)[0] == 1
     assert g("cross", d=64, b=2, n1=2048)[0] == 128 and g("cross", d=64, b=40, n1=2048)[0] == 768
@@ -136,7 +136,7 @@ def test_expected_kernel_mirrors_the_fused_dispatch_rules():
 
 
 def _by_xcd(case):
-    """(dealt by XCD, units per eighth, units per workgroup step) of a case's launch: common.h:101-111, cross.hip:197-204."""
+    """(dealt by XCD, units per eighth, units per workgroup step) of a case's launch: mcp_units_by_xcd (common.h), cross_kernel's own deal (cross.hip)."""
     grid, units, per = kv.launch_grid(**case)
     xcd = grid % 8 == 0 and not (case["op"] == "cross" and case["d"] == 256)
     if not xcd:
@@ -215,8 +215,9 @@ CUS = 256   # compute units of the MI355X: the grid cap of every backward kernel
 
 
 def test_the_backward_mirror_follows_the_c_conditions():
-    # grad_grid / plan: fusion_grad.hip:440-445, cross_grad.hip:458-466, cross256_grad.hip:377-390, pointconv_grad.hip:204-208,
-    # ptblock_grad.hip:417-421; the deals: common.h:101-111, cross_grad.hip:419-430, cross256_grad.hip:78-83, :189, :243
+    # grad_grid / plan: fusion_grad.hip:440-445, grad_grid (cross_grad.hip), plan (cross256_grad.hip), pointconv_grad.hip:204-208,
+    # ptblock_grad.hip:417-421; the deals: mcp_units_by_xcd (common.h), cross_grad_kernel's deal() (cross_grad.hip); the rounds of
+    # cross256_grad_z_kernel, the slices of cross256_grad_w_kernel, the point loop of cross256_grad_dx_kernel
     g, e = kv.grad_launch_grid, kv.expected_grad_kernels
     fus = lambda total, **kw: g("fusion", b=1, n=total, **kw)["points"]
     assert fus(1024)["workgroups"] == 256 and fus(1024)["by_xcd"] and fus(1020)["workgroups"] == 255 and not fus(1020)["by_xcd"]
@@ -400,7 +401,7 @@ def test_every_backward_kernel_of_the_fused_layers_has_a_parity_case():
 
 # ---- the fusion layer on batch statistics: two grid caps in one call --------------------------------------------------------------------
 def test_the_batch_statistics_mirror_follows_the_c_conditions():
-    # fwd_grid, fusion_bn.hip:377-382; bwd_grid :1179-1184 with per_cu 2 (B1, B4: :1326, :1351) and 1 (B2, B3: :1337, :1344); the deal: common.h:101-120
+    # fwd_grid, fusion_bn.hip:377-382; bwd_grid :1179-1184 with per_cu 2 (B1, B4: :1326, :1351) and 1 (B2, B3: :1337, :1344); the deal: mcp_units_by_xcd (common.h)
     g, e = kv.bn_launch_grid, kv.expected_bn_kernels
     sizes = lambda total, **kw: tuple((r["workgroups"], r["by_xcd"]) for r in g(b=1, n=total, **kw).values())
     assert sizes(1) == ((1, False), (1, False)) and sizes(5) == ((2, False), (2, False)) and sizes(61) == ((16, True), (16, True))
