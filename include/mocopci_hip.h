@@ -384,6 +384,27 @@ int mcp_fusion_grad(int b, int n, int nb, const float *p1, const float *p2, cons
                     const float *w2, const float *b2, const float *w3, const float *b3, const float *grad_out, float *grad_p1, float *grad_nb,
                     float *grad_weights, void *workspace, size_t workspace_bytes, mcp_stream_t stream);
 
+/* mcp_fusion / mcp_fusion_grad on a padded batch of clouds of different sizes (csrc/fusion_lengths.hip: kernels of their own, stated
+ * once with the dense ones in csrc/fusion_tile.h / fusion_grad_tile.h).
+ *   len     (B) device int32, clamped to [0, n] inside the kernels: point p of element bb is live iff p < len[bb].  NULL: the call is
+ *           the dense entry point itself.
+ * One wave owns one point, so liveness is wave-uniform: the length is a scalar load and a padded point costs one branch and the
+ * store of its zeros.  A padded point, forward: none of its row of p1, idx, idx2 is read and nothing is gathered through those lists
+ * (they may hold NaN and out-of-range indices); its row of out is written as exact zeros.  Backward: its row of grad_out is not read
+ * either, its row of grad_p1 and its 64 rows of grad_nb are exact zeros and it adds nothing to any accumulator of grad_weights (the
+ * caller's mcp_scatter_segments still walks its row of idx and leaves out-of-range values out).  The indices of live points are
+ * trusted; the caller makes them point at live rows of p2.  A live point gets the bits of the dense call.
+ * No length is read on the host, nothing is allocated, no atomics.  The grids are those of b * n points and the points are dealt to
+ * workgroups and waves in padded order, exactly as the dense kernels deal them, so grad_weights is the dense call's sum with the
+ * padded points' terms left out -- bit-identical to mcp_fusion_grad on the batch with zeroed padding and zero upstream rows -- and
+ * with every len[bb] == n every output is bit-identical to the dense entry point.  Argument checks and error codes are the dense
+ * entries'; workspace: mcp_fusion_grad_workspace_bytes(b, n), as dense. */
+int mcp_fusion_lengths(int b, int n, int nb, const float *p1, const float *p2, const int *idx, const int *idx2, const int *len, const float *w1,
+                       const float *b1, const float *w2, const float *b2, const float *w3, const float *b3, float *out, mcp_stream_t stream);
+int mcp_fusion_grad_lengths(int b, int n, int nb, const float *p1, const float *p2, const int *idx, const int *idx2, const int *len, const float *w1,
+                            const float *b1, const float *w2, const float *b2, const float *w3, const float *b3, const float *grad_out, float *grad_p1,
+                            float *grad_nb, float *grad_weights, void *workspace, size_t workspace_bytes, mcp_stream_t stream);
+
 /* The fusion layer in net.train() mode (train.py:130): its three Conv2d + BatchNorm2d + ReLU layers (mocopci.py:749-755, :810-816)
  * normalise with the statistics of the batch they are given -- one call here = one reference call = one set of statistics over
  * all b * n * 64 (point, neighbour) rows.  Arguments as mcp_fusion with the RAW conv weights (w, b), then
@@ -442,8 +463,12 @@ int mcp_fusion_bn_backward_saved(int b, int n, int nb, const float *p1, const fl
  * No length is read on the host, nothing is allocated, no atomics: every sum runs in a fixed order and two calls give identical
  * bits.  The grids are those of b * n points and live points are dealt in padded order, so with every len[bb] == n every output is
  * bit-identical to the dense entry point.  Workspaces: mcp_fusion_bn_workspace_bytes / mcp_fusion_bn_grad_workspace_bytes (b, n), as
- * dense.  The pair that keeps the forward's scores (mcp_fusion_bn_forward_save / mcp_fusion_bn_backward_saved) has no length form:
- * the backward here re-evaluates the layer. */
+ * dense.
+ * mcp_fusion_bn_forward_save_lengths / mcp_fusion_bn_backward_saved_lengths: the pair that keeps the forward's scores (save_c, save_z,
+ * save_s as for mcp_fusion_bn_forward_save), with lengths.  A padded point's rows of save_c / save_z / save_s are UNSPECIFIED: the
+ * forward does not write them and the backward does not read them.  Otherwise the pair is mcp_fusion_bn_forward_lengths /
+ * mcp_fusion_bn_backward_lengths bit for bit (out / bn / var / count; grad_p1 / grad_nb / grad_weights / grad_affine), as the dense pair
+ * is mcp_fusion_bn_forward / mcp_fusion_bn_backward; len == NULL: the dense pair itself (count then receives b * n). */
 int mcp_fusion_bn_forward_lengths(int b, int n, int nb, const float *p1, const float *p2, const int *idx, const int *idx2, const int *len,
                                   const float *w1, const float *b1, const float *w2, const float *b2, const float *w3, const float *b3, float eps,
                                   float *bn, float *var, float *out, int *count, void *workspace, size_t workspace_bytes, mcp_stream_t stream);
@@ -452,6 +477,15 @@ int mcp_fusion_bn_backward_lengths(int b, int n, int nb, const float *p1, const 
                                    const float *grad_out, int *row_c, float *row_dy, float *row_a, float *dy2, float *dy1, float *grad_p1,
                                    float *grad_nb, float *grad_weights, float *grad_affine, void *workspace, size_t workspace_bytes,
                                    mcp_stream_t stream);
+int mcp_fusion_bn_forward_save_lengths(int b, int n, int nb, const float *p1, const float *p2, const int *idx, const int *idx2, const int *len,
+                                       const float *w1, const float *b1, const float *w2, const float *b2, const float *w3, const float *b3, float eps,
+                                       float *bn, float *var, float *out, int *count, int *save_c, float *save_z, float *save_s, void *workspace,
+                                       size_t workspace_bytes, mcp_stream_t stream);
+int mcp_fusion_bn_backward_saved_lengths(int b, int n, int nb, const float *p1, const float *p2, const int *idx, const int *idx2, const int *len,
+                                         const float *w1, const float *b1, const float *w2, const float *b2, const float *w3, const float *b3,
+                                         const float *bn, const float *grad_out, const int *save_c, const float *save_z, const float *save_s, int *row_c,
+                                         float *row_dy, float *row_a, float *dy2, float *dy1, float *grad_p1, float *grad_nb, float *grad_weights,
+                                         float *grad_affine, void *workspace, size_t workspace_bytes, mcp_stream_t stream);
 
 /* BatchNorm on BATCH statistics of a channels-last tensor, forward and backward, with per-group lengths (csrc/bn_batch.hip): what
  * nn.BatchNorm1d / 2d in training mode computes when the reference's blocks call it once per sample (mocopci.py:503-506, :554-561).

@@ -77,6 +77,10 @@ SIGNATURES = {
     "mcp_fusion_bn_backward_saved": [_i, _i, _i] + [_p] * 25 + [ctypes.c_size_t, _p],
     "mcp_fusion_bn_forward_lengths": [_i, _i, _i] + [_p] * 11 + [_f] + [_p] * 5 + [ctypes.c_size_t, _p],
     "mcp_fusion_bn_backward_lengths": [_i, _i, _i] + [_p] * 23 + [ctypes.c_size_t, _p],
+    "mcp_fusion_bn_forward_save_lengths": [_i, _i, _i] + [_p] * 11 + [_f] + [_p] * 8 + [ctypes.c_size_t, _p],
+    "mcp_fusion_bn_backward_saved_lengths": [_i, _i, _i] + [_p] * 26 + [ctypes.c_size_t, _p],
+    "mcp_fusion_lengths": [_i, _i, _i] + [_p] * 13,
+    "mcp_fusion_grad_lengths": [_i, _i, _i] + [_p] * 16 + [ctypes.c_size_t, _p],
     "mcp_bn_batch_parts": [_i, _i, _i, _i],
     "mcp_bn_batch_workspace_bytes": [_i, _i, _i, _i],
     "mcp_bn_batch_forward": [_i] * 4 + [_p] * 4 + [_f] + [_p] * 5 + [ctypes.c_size_t, _p],

@@ -1,6 +1,6 @@
 // fusion_bn_pass.h -- the passes of the train-mode fusion layer, stated once for fusion_bn.hip (every point of the call) and
 // fusion_bn_lengths.hip (per-cloud lengths: one FbnLengths behind every pass's parameters).  What lives here: the kernels of the
-// passes under the unit's names (FBN_KERNEL, below: fusion_bn.hip emits the 13 kernels it always did), the two kernels that no
+// passes under the unit's names (FBN_KERNEL, below: fusion_bn.hip emits the 13 kernels it always did, fusion_bn_lengths.hip a length form of every pass), the two kernels that no
 // length touches (transposed_image_kernel, sum_partials_kernel) and the host's walk over the passes (bn_forward, bn_backward); a
 // unit adds its entry points.  With lengths, point p of element bb is live iff p < len[bb] (clamped to
 // [0, n] here); a pass walks the points in padded order on the grid of b * n points and steps over a padded point before it reads
@@ -709,13 +709,13 @@ __global__ __launch_bounds__(64 * WAVES, 2) void FBN_KERNEL(b1)(FBN_B1_PARAMS FB
 
 // ---- B1 with the forward's per-neighbour (score, c*, zhat3 at c*) saved (mcp_fusion_bn_forward_save): no layer to re-evaluate -- the
 // softmax over the 64 scores, ds, the per-row outputs and the two per-channel sums, exactly as above from its `score / zstar / cstar` on ----
-// No length form: fusion_bn.hip alone wraps it (lds: WAVES * 256 floats -- the per-wave scratch first, the reduction buffer afterwards).
+// With lengths: the liveness rule of FBN_KERNEL(b1) -- a padded point's rows of save_c / save_z / save_s are not read (the forward did
+// not write them).  (lds: WAVES * 256 floats -- the per-wave scratch first, the reduction buffer afterwards.)
 #define FBN_B1_SAVED_PARAMS                                                                                                              \
     long long total, int n, const float *__restrict__ p2, const int *__restrict__ idx, const int *__restrict__ idx2,                     \
         const float *__restrict__ gout, const int *__restrict__ save_c, const float *__restrict__ save_z, const float *__restrict__ save_s, \
         int *__restrict__ row_c, float *__restrict__ row_dy, float *__restrict__ row_a, float *__restrict__ partial
-#if !FBN_LEN
-__global__ __launch_bounds__(64 * WAVES, 2) void fusion_bn_b1_saved_kernel(FBN_B1_SAVED_PARAMS) {
+__global__ __launch_bounds__(64 * WAVES, 2) void FBN_KERNEL(b1_saved)(FBN_B1_SAVED_PARAMS FBN_LENS_PARAM) {
     __shared__ float lds[WAVES * 256];   // the per-wave scratch first, the reduction buffer afterwards
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6, h = lane >> 5, col = lane & 31;
@@ -727,6 +727,9 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fusion_bn_b1_saved_kernel(FBN_B
     const McpUnits units = mcp_units_by_xcd(total, WAVES);   // the same points per workgroup as fusion_bn_b1_kernel: the same summation order
     for (long long p = units.first + wave; p < units.limit; p += units.stride) {
         const long long bb = mcp_div(p, n, mcp_fits32(total));
+        if constexpr (LEN) {
+            if (!fbn_live(p, bb, n FBN_LENS)) continue;
+        }
         const float gx = gout[p * 3 + 0], gy = gout[p * 3 + 1], gz = gout[p * 3 + 2];
         float score[2], zstar[2], nbx[2], nby[2], nbz[2];
         int cstar[2];
@@ -802,7 +805,6 @@ __global__ __launch_bounds__(64 * WAVES, 2) void fusion_bn_b1_saved_kernel(FBN_B
         partial[(size_t)blockIdx.x * 256 + tid] = v;
     }
 }
-#endif
 
 // ---- B2: dz3 (dense), dW3 += dz3 . y2^T, dh2 = W3^T dz3 -> dy2' (stored), sums of dy2' and dy2' zhat2 ----
 constexpr int B2_L_DZ = L_F32, B2_F32 = L_F32 + 3 * C3;                  // + a | c1 | c2 of layer 3 (accumulator order)
@@ -1330,13 +1332,11 @@ int bn_forward(int b, int n, int nb, const float *p1, const float *p2, const int
     rc = launch_fwd<3, false>(total, n, p1, p2, idx, idx2, w1, b1, w2, b2, w3, b3, bn, partial, grid, s, nullptr, nullptr, nullptr, shift FBN_LENS);
     if (rc) return rc;
     launch_stats(s, partial, (int)grid, C3, rows, shift, eps, bn + BN_L3, var + C1 + C2, total, n, no_count FBN_LENS);
-#if !FBN_LEN
     if (save_c) {
-        rc = launch_fwd<0, true>(total, n, p1, p2, idx, idx2, w1, b1, w2, b2, w3, b3, bn, out, grid, s, save_c, save_z, save_s, nullptr);
+        rc = launch_fwd<0, true>(total, n, p1, p2, idx, idx2, w1, b1, w2, b2, w3, b3, bn, out, grid, s, save_c, save_z, save_s, nullptr FBN_LENS);
         mcp_prof_end(MCP_KERNEL_FUSION, s);
         return rc;
     }
-#endif
     rc = launch_fwd<0, false>(total, n, p1, p2, idx, idx2, w1, b1, w2, b2, w3, b3, bn, out, grid, s, nullptr, nullptr, nullptr, nullptr FBN_LENS);
     mcp_prof_end(MCP_KERNEL_FUSION, s);
     return rc;
@@ -1371,15 +1371,10 @@ int bn_backward(int b, int n, int nb, const float *p1, const float *p2, const in
     {   // B1
         const unsigned grid = bwd_grid(total, 2);
         const size_t lds = (size_t)L_F32 * 4 + (size_t)(W2_U4 + W3_U4) * 16 + (size_t)WAVES * B1_SCR * 4;
-        bool kept = false;
-#if !FBN_LEN
-        if (save_c) {
-            hipLaunchKernelGGL(fusion_bn_b1_saved_kernel, dim3(grid), dim3(64 * WAVES), 0, s, total, n, p2, idx, idx2, grad_out, save_c, save_z, save_s, row_c, row_dy,
-                               row_a, partial);
-            kept = true;
-        }
-#endif
-        if (!kept)
+        if (save_c)
+            hipLaunchKernelGGL(FBN_KERNEL(b1_saved), dim3(grid), dim3(64 * WAVES), 0, s, total, n, p2, idx, idx2, grad_out, save_c, save_z, save_s, row_c, row_dy,
+                               row_a, partial FBN_LENS);
+        else
             hipLaunchKernelGGL(FBN_KERNEL(b1), dim3(grid), dim3(64 * WAVES), lds, s, total, n, p1, p2, idx, idx2, w1, b1, w2, b2, w3, b3, bn, grad_out, row_c, row_dy,
                                row_a, partial FBN_LENS);
         hipLaunchKernelGGL(sum_partials_kernel, dim3(16), dim3(256), 0, s, partial, (int)grid, 256, 256, sums3);

@@ -1198,38 +1198,48 @@ class _PtblockFn(torch.autograd.Function):
         return (None, None, d_xyz, d_q, d_k, d_v, *pieces)
 
 
+def _scatter_lists(ia, ib, lens, n):
+    """The fusion layer's neighbour list(s) as the segmented scatter of grad_nb (B,N,64,3) sorts them.  With lengths a padded point's
+    rows of grad_nb are zeros and its list rows may hold anything -- the searches leave 0 there, so every padded entry of an element
+    would land on row 0 and ONE thread of the reduction would walk them all (24 x 8192 points at half lengths: 186 ms against 0.43 ms,
+    profiles/fusion_lengths_times.json; the effect _PointConvAggFn documents): padded point i names row i mod n instead
+    (grad.spread_padded_rows).  Zeros land elsewhere: no sum changes."""
+    idx = ia if ib is None else torch.cat((ia, ib), dim=-1)
+    if lens is None:
+        return idx
+    return grad.spread_padded_rows(idx, grad.live_points(lens, idx.shape[0], idx.shape[1], idx.device), n)
+
+
 class _FusionBNFn(torch.autograd.Function):
     """The fusion layer of one reference call on BATCH statistics (net.train()), forward and backward on the multi-pass kernels of
     csrc/fusion_bn.hip.  Returns (out, bn, var): bn = per layer mean | rstd | gamma | beta, var = the biased batch variances (both
-    non-differentiable by-products for the caller's running-estimate update)."""
+    non-differentiable by-products for the caller's running-estimate update); with per-cloud lengths (csrc/fusion_bn_lengths.hip)
+    (out, bn, var, count)."""
 
     @staticmethod
     def forward(ctx, be, eps, ia, ib, lens, p1, p2, w1, b1, w2, b2, w3, b3, g1, e1, g2, e2, g3, e3):
         conv = [t.detach().contiguous() for t in (w1, b1, w2, b2, w3, b3)]
         p1, p2 = p1.detach().contiguous(), p2.detach().contiguous()
         ctx.has_lengths = lens is not None
-        if lens is not None:
-            # per-cloud lengths (csrc/fusion_bn_lengths.hip): the forward keeps no scores, the backward re-evaluates the layer
-            out, bn, var, count = be.fusion_bn_forward(p1, p2, ia if ib is None else (ia, ib), conv, (g1, e1, g2, e2, g3, e3), eps, lengths=lens)
-            ctx.save_for_backward(ia, ib, p1, p2, *conv, bn, lens)
-            ctx.mark_non_differentiable(bn, var, count)
-            return out, bn, var, count
-        rows = p1.shape[0] * p1.shape[1] * 64
-        # kept for the backward: every neighbour's score, its layer-3 channel and zhat3 there (12 bytes per row) -- the backward's first
-        # pass then has no layer to re-evaluate
-        saved = (torch.empty((rows,), dtype=torch.int32, device=p1.device), torch.empty((rows,), dtype=torch.float32, device=p1.device),
-                 torch.empty((rows,), dtype=torch.float32, device=p1.device))
-        out, bn, var = be.fusion_bn_forward(p1, p2, ia if ib is None else (ia, ib), conv, (g1, e1, g2, e2, g3, e3), eps, saved=saved)
-        ctx.save_for_backward(ia, ib, p1, p2, *conv, bn, *saved)
-        ctx.mark_non_differentiable(bn, var)
-        return out, bn, var
+        ctx.kept = lens is None or be.FUSION_BN_KEEP_SCORES_WITH_LENGTHS
+        saved = ()
+        if ctx.kept:
+            rows = p1.shape[0] * p1.shape[1] * 64
+            # kept for the backward: every neighbour's score, its layer-3 channel and zhat3 there (12 bytes per row) -- the backward's
+            # first pass then has no layer to re-evaluate
+            saved = (torch.empty((rows,), dtype=torch.int32, device=p1.device), torch.empty((rows,), dtype=torch.float32, device=p1.device),
+                     torch.empty((rows,), dtype=torch.float32, device=p1.device))
+        res = be.fusion_bn_forward(p1, p2, ia if ib is None else (ia, ib), conv, (g1, e1, g2, e2, g3, e3), eps, saved=saved or None, lengths=lens)
+        ctx.save_for_backward(ia, ib, p1, p2, *conv, res[1], *(() if lens is None else (lens,)), *saved)
+        ctx.mark_non_differentiable(*res[1:])
+        return res   # (out, bn, var), with lengths (out, bn, var, count)
 
     @staticmethod
     def backward(ctx, grad_out, _gbn, _gvar, _gcount=None):
-        if ctx.has_lengths:
-            ia, ib, p1, p2, w1, b1, w2, b2, w3, b3, bn, lens = ctx.saved_tensors
-        else:
-            ia, ib, p1, p2, w1, b1, w2, b2, w3, b3, bn, save_c, save_z, save_s = ctx.saved_tensors
+        ia, ib, p1, p2, w1, b1, w2, b2, w3, b3, bn = ctx.saved_tensors[:11]
+        rest = ctx.saved_tensors[11:]
+        lens = rest[0] if ctx.has_lengths else None
+        save_c, save_z, save_s = rest[-3:] if ctx.kept else (None, None, None)
         B, N, _ = p1.shape
         rows = B * N * 64
         lib, dev = _lib.load(), p1.device
@@ -1245,7 +1255,11 @@ class _FusionBNFn(torch.autograd.Function):
         ws = torch.empty((need,), dtype=torch.uint8, device=dev)
         scratch = (_lib.iptr(row_c), _lib.fptr(row_dy), _lib.fptr(row_a), _lib.fptr(dy2), _lib.fptr(dy1), _lib.fptr(d_p1), _lib.fptr(d_nb), _lib.fptr(d_w),
                    _lib.fptr(d_aff), ws.data_ptr(), need)
-        if ctx.has_lengths:
+        if ctx.has_lengths and ctx.kept:
+            _call("mcp_fusion_bn_backward_saved_lengths", p1, B, N, 64, _lib.fptr(p1), _lib.fptr(p2), _lib.iptr(ia), None if ib is None else _lib.iptr(ib),
+                  _lib.iptr(lens), *[_lib.fptr(t) for t in (w1, b1, w2, b2, w3, b3, bn, grad_out)], _lib.iptr(save_c), _lib.fptr(save_z),
+                  _lib.fptr(save_s), *scratch)
+        elif ctx.has_lengths:
             _call("mcp_fusion_bn_backward_lengths", p1, B, N, 64, _lib.fptr(p1), _lib.fptr(p2), _lib.iptr(ia), None if ib is None else _lib.iptr(ib),
                   _lib.iptr(lens), *[_lib.fptr(t) for t in (w1, b1, w2, b2, w3, b3, bn, grad_out)], *scratch)
         else:
@@ -1253,8 +1267,7 @@ class _FusionBNFn(torch.autograd.Function):
                   *[_lib.fptr(t) for t in (w1, b1, w2, b2, w3, b3, bn, grad_out)], _lib.iptr(save_c), _lib.fptr(save_z), _lib.fptr(save_s), *scratch)
         d_p2 = None
         if ctx.needs_input_grad[6]:
-            # (a padded point's rows of d_nb are zeros and its list may hold anything: the segmented scatter leaves out-of-range entries out)
-            d_p2 = _group_rows_grad(d_nb, ia if ib is None else torch.cat((ia, ib), dim=-1), p2.shape[1])
+            d_p2 = _group_rows_grad(d_nb, _scatter_lists(ia, ib, lens, p2.shape[1]), p2.shape[1])
         pieces, at = [], 0
         for t in (w1, b1, w2, b2, w3, b3):
             pieces.append(d_w[at:at + t.numel()].view(t.shape))
@@ -1305,17 +1318,19 @@ class _BNBatchFn(torch.autograd.Function):
 
 class _FusionFn(torch.autograd.Function):
     """mcp_fusion with its hand-written backward (mcp_fusion_grad): the layer is re-evaluated inside the backward kernel, the
-    neighbour gradients go through the deterministic segmented scatter, weight gradients are fixed-order sums."""
+    neighbour gradients go through the deterministic segmented scatter, weight gradients are fixed-order sums.
+    lens: (B,) int32 device tensor or None -- per-cloud lengths, carried to the backward.  Both directions call the *_lengths entries
+    (csrc/fusion_lengths.hip): with null lengths those are the dense entries themselves."""
 
     @staticmethod
-    def forward(ctx, be, ia, ib, p1, p2, w1, b1, w2, b2, w3, b3):
+    def forward(ctx, be, ia, ib, lens, p1, p2, w1, b1, w2, b2, w3, b3):
         args = [t.detach().contiguous() for t in (p1, p2, w1, b1, w2, b2, w3, b3)]
-        ctx.save_for_backward(ia, ib, *args)
-        return be._fusion_mlp(args[0], args[1], ia if ib is None else (ia, ib), *args[2:])
+        ctx.save_for_backward(ia, ib, *args, lens)
+        return be._fusion_mlp(args[0], args[1], ia if ib is None else (ia, ib), *args[2:], lens=lens)
 
     @staticmethod
     def backward(ctx, grad_out):
-        ia, ib, p1, p2, w1, b1, w2, b2, w3, b3 = ctx.saved_tensors
+        ia, ib, p1, p2, w1, b1, w2, b2, w3, b3, lens = ctx.saved_tensors
         B, N, _ = p1.shape
         lib = _lib.load()
         grad_out = grad_out.contiguous()
@@ -1324,17 +1339,17 @@ class _FusionFn(torch.autograd.Function):
         d_w = torch.empty((lib.mcp_fusion_grad_floats(),), dtype=torch.float32, device=p1.device)
         need = lib.mcp_fusion_grad_workspace_bytes(B, N)
         ws = torch.empty((need,), dtype=torch.uint8, device=p1.device)
-        _call("mcp_fusion_grad", p1, B, N, 64, _lib.fptr(p1), _lib.fptr(p2), _lib.iptr(ia), None if ib is None else _lib.iptr(ib), _lib.fptr(w1),
-              _lib.fptr(b1), _lib.fptr(w2), _lib.fptr(b2), _lib.fptr(w3), _lib.fptr(b3), _lib.fptr(grad_out), _lib.fptr(d_p1), _lib.fptr(d_nb),
-              _lib.fptr(d_w), ws.data_ptr(), need)
+        _call("mcp_fusion_grad_lengths", p1, B, N, 64, _lib.fptr(p1), _lib.fptr(p2), _lib.iptr(ia), None if ib is None else _lib.iptr(ib), _len_ptr(lens),
+              _lib.fptr(w1), _lib.fptr(b1), _lib.fptr(w2), _lib.fptr(b2), _lib.fptr(w3), _lib.fptr(b3), _lib.fptr(grad_out), _lib.fptr(d_p1),
+              _lib.fptr(d_nb), _lib.fptr(d_w), ws.data_ptr(), need)
         d_p2 = None
-        if ctx.needs_input_grad[4]:
-            d_p2 = _group_rows_grad(d_nb, ia if ib is None else torch.cat((ia, ib), dim=-1), p2.shape[1])
+        if ctx.needs_input_grad[5]:
+            d_p2 = _group_rows_grad(d_nb, _scatter_lists(ia, ib, lens, p2.shape[1]), p2.shape[1])
         pieces, at = [], 0
         for t in (w1, b1, w2, b2, w3, b3):
             pieces.append(d_w[at:at + t.numel()].view(t.shape))
             at += t.numel()
-        return (None, None, None, d_p1, d_p2, *pieces)
+        return (None, None, None, None, d_p1, d_p2, *pieces)
 
 
 class HipBackend:
@@ -1682,10 +1697,21 @@ class HipBackend:
 
     def fusion_mlp(self, p1, p2, idx, w1, b1, w2, b2, w3, b3, lengths=None):
         """fusion after the neighbour searches (mocopci.py:803-819), BN folded into (w,b): -> (B,N,3).  Differentiable.
-        lengths (forms: lengths_tensor): rows of p1 / p2 at or beyond lengths[b] are padding.  This is the DENSE kernel plus
-        masking, no kernel of its own (every sum of this layer is per point, so lengths only save work): padded rows of p1 and p2
-        are replaced by zeros and padded rows of idx by 0 before the call, out is zero on padded rows, live rows have the dense
-        call's bits, and gradients reach live rows only."""
+        lengths (forms: lengths_tensor): rows of p1 / p2 at or beyond lengths[b] are padding.  With 64 neighbours per point (2 x 32
+        or one list of 64) the kernels take the lengths themselves (mcp_fusion_lengths / mcp_fusion_grad_lengths,
+        csrc/fusion_lengths.hip): a padded point costs one branch, nothing of its rows of p1 and idx is read -- they may hold
+        anything -- and nothing is masked around the call.  Every sum of this layer is per point, so lengths only save work: out is
+        zero on padded rows, live rows have the bits of the dense call on the cloud alone, and gradients reach live rows only (the
+        weight gradients are the dense sums with the padded points' terms left out).  The indices of live points must point at
+        live rows of p2.  Other list widths: the dense kernel plus masking (padded rows of p1 and p2 replaced by zeros and padded
+        rows of idx by 0 before the call, out masked after it), same results."""
+        ia, ib = idx if isinstance(idx, (tuple, list)) else (idx, None)
+        kernel_lists = ia.shape[-1] + (0 if ib is None else ib.shape[-1]) == 64
+        if lengths is not None and kernel_lists:
+            lens = lengths_tensor(lengths, p1.shape[0], p1.shape[1], p1.device)
+            if not grad.wants_grad(p1, p2, w1, b1, w2, b2, w3, b3):
+                return self._fusion_mlp(p1, p2, idx, w1, b1, w2, b2, w3, b3, lens=lens)
+            return _FusionFn.apply(self, ia.contiguous(), None if ib is None else ib.contiguous(), lens, p1, p2, w1, b1, w2, b2, w3, b3)
         if lengths is not None:
             B, N, _ = p1.shape
             live = grad.live_points(lengths_tensor(lengths, B, N, p1.device), B, N, p1.device).unsqueeze(-1)
@@ -1696,15 +1722,20 @@ class HipBackend:
             return torch.where(live, out, zero)
         if not grad.wants_grad(p1, p2, w1, b1, w2, b2, w3, b3):
             return self._fusion_mlp(p1, p2, idx, w1, b1, w2, b2, w3, b3)
-        ia, ib = idx if isinstance(idx, (tuple, list)) else (idx, None)
-        if ia.shape[-1] + (0 if ib is None else ib.shape[-1]) != 64:   # the kernels take the 2 x 32 lists only: autograd over the unfused twin
+        if not kernel_lists:   # the kernels take the 2 x 32 lists only: autograd over the unfused twin
             return grad.fusion_twin(self.group_rows, p1, p2, idx, w1, b1, w2, b2, w3, b3)
-        return _FusionFn.apply(self, ia.contiguous(), None if ib is None else ib.contiguous(), p1, p2, w1, b1, w2, b2, w3, b3)
+        return _FusionFn.apply(self, ia.contiguous(), None if ib is None else ib.contiguous(), None, p1, p2, w1, b1, w2, b2, w3, b3)
+
+    # Under lengths, True: the forward keeps every live neighbour's score (mcp_fusion_bn_forward_save_lengths) and the backward's first
+    # pass reads them (mcp_fusion_bn_backward_saved_lengths), as the dense route does.  False (the A/B): the forward keeps nothing and
+    # the backward's first pass re-evaluates the layer (mcp_fusion_bn_forward_lengths / mcp_fusion_bn_backward_lengths).  Same bits.
+    FUSION_BN_KEEP_SCORES_WITH_LENGTHS = True
 
     def fusion_bn(self, p1, p2, idx, conv, affine, eps, lengths=None):
         """The fusion layer of ONE reference call on batch statistics, differentiable w.r.t. p1, p2, the conv weights and the
         BatchNorm weight / bias: -> (out (B,N,3), bn, var) -- see _FusionBNFn.
-        lengths (forms: lengths_tensor): the rows of p1 and p2 at or beyond lengths[b] are padding (mcp_fusion_bn_forward_lengths /
+        lengths (forms: lengths_tensor): the rows of p1 and p2 at or beyond lengths[b] are padding (mcp_fusion_bn_forward_save_lengths /
+        mcp_fusion_bn_backward_saved_lengths; FUSION_BN_KEEP_SCORES_WITH_LENGTHS = False: mcp_fusion_bn_forward_lengths /
         mcp_fusion_bn_backward_lengths): every statistic and every gradient runs over the live points' rows only, out and the
         gradients of p1 are zero on padded rows, whose values and index rows are never read.  -> (out, bn, var, count) with count the
         live points (one int32 on the device; the statistics' rows are 64 * count).  The indices of live points must point at live
@@ -1721,10 +1752,9 @@ class HipBackend:
         -> out (B,N,3), bn (1024: per layer mean | rstd | gamma | beta), var (256: biased batch variances 64 | 64 | 128).  No autograd.
         saved: (int32, float32, float32) tensors of B*N*64 elements that receive every neighbour's arg-max channel, zhat3 there and score
         (mcp_fusion_bn_forward_save; what mcp_fusion_bn_backward_saved reads).
-        lengths: per-cloud lengths (see fusion_bn; not together with saved) -> (out, bn, var, count)."""
+        lengths: per-cloud lengths (see fusion_bn) -> (out, bn, var, count); together with saved the rows of live points are kept
+        (mcp_fusion_bn_forward_save_lengths), a padded point's rows of the three tensors stay as they were."""
         lib = _lib.load()
-        if lengths is not None and saved is not None:
-            raise ValueError("fusion_bn_forward: the forward that keeps its scores has no length form")
         p1, p2 = p1.contiguous(), p2.contiguous()
         conv = [t.detach().contiguous() for t in conv]
         B, N, _ = p1.shape
@@ -1742,9 +1772,10 @@ class HipBackend:
         if lengths is not None:
             lens = lengths_tensor(lengths, B, N, p1.device)
             count = torch.empty((1,), dtype=torch.int32, device=p1.device)
-            _call("mcp_fusion_bn_forward_lengths", p1, B, N, 64, _lib.fptr(p1), _lib.fptr(p2), _lib.iptr(ia), None if ib is None else _lib.iptr(ib),
-                  _lib.iptr(lens), *[_lib.fptr(t) for t in conv], float(eps), _lib.fptr(bn), _lib.fptr(var), _lib.fptr(out), _lib.iptr(count), ws.data_ptr(),
-                  need)
+            keep = () if saved is None else (_lib.iptr(saved[0]), _lib.fptr(saved[1]), _lib.fptr(saved[2]))
+            _call("mcp_fusion_bn_forward_lengths" if saved is None else "mcp_fusion_bn_forward_save_lengths", p1, B, N, 64, _lib.fptr(p1), _lib.fptr(p2),
+                  _lib.iptr(ia), None if ib is None else _lib.iptr(ib), _lib.iptr(lens), *[_lib.fptr(t) for t in conv], float(eps), _lib.fptr(bn),
+                  _lib.fptr(var), _lib.fptr(out), _lib.iptr(count), *keep, ws.data_ptr(), need)
             return out, bn, var, count.view(())
         if saved is None:
             _call("mcp_fusion_bn_forward", p1, B, N, 64, _lib.fptr(p1), _lib.fptr(p2), _lib.iptr(ia), None if ib is None else _lib.iptr(ib),
@@ -1774,14 +1805,18 @@ class HipBackend:
         y, mean, var, count = _BNBatchFn.apply(float(eps), lens, x.reshape(G, -1, N, C), weight, bias)
         return y.reshape(x.shape), mean, var, count
 
-    def _fusion_mlp(self, p1, p2, idx, w1, b1, w2, b2, w3, b3):
+    def _fusion_mlp(self, p1, p2, idx, w1, b1, w2, b2, w3, b3, lens=None):
         p1, p2, w1, b1, w2, b2, w3, b3 = (t.contiguous() for t in (p1, p2, w1, b1, w2, b2, w3, b3))
         B, N, _ = p1.shape
         out = torch.empty((B, N, 3), dtype=torch.float32, device=p1.device)
         ia, ib = idx if isinstance(idx, (tuple, list)) else (idx, None)   # the two searches' lists as they are, or one (B,N,64) list
         nb = ia.shape[-1] if ib is None else ia.shape[-1] + ib.shape[-1]
-        _call("mcp_fusion", p1, B, N, nb, _lib.fptr(p1), _lib.fptr(p2), _lib.iptr(ia), None if ib is None else _lib.iptr(ib), _lib.fptr(w1), _lib.fptr(b1),
-              _lib.fptr(w2), _lib.fptr(b2), _lib.fptr(w3), _lib.fptr(b3), _lib.fptr(out))
+        if lens is None:
+            _call("mcp_fusion", p1, B, N, nb, _lib.fptr(p1), _lib.fptr(p2), _lib.iptr(ia), None if ib is None else _lib.iptr(ib), _lib.fptr(w1),
+                  _lib.fptr(b1), _lib.fptr(w2), _lib.fptr(b2), _lib.fptr(w3), _lib.fptr(b3), _lib.fptr(out))
+        else:   # per-cloud lengths: the kernel of csrc/fusion_lengths.hip
+            _call("mcp_fusion_lengths", p1, B, N, nb, _lib.fptr(p1), _lib.fptr(p2), _lib.iptr(ia), None if ib is None else _lib.iptr(ib), _lib.iptr(lens),
+                  _lib.fptr(w1), _lib.fptr(b1), _lib.fptr(w2), _lib.fptr(b2), _lib.fptr(w3), _lib.fptr(b3), _lib.fptr(out))
         return out
 
     def cross_pack(self, wpos, bpos, wmlp, bmlp):
