@@ -41,6 +41,36 @@ def _call(name, ref_tensor, *args):
         _lib.check(rc)
 
 
+def _opt(t, ptr=_lib.fptr):
+    """Device pointer of an optional tensor: NULL for None."""
+    return None if t is None else ptr(t)
+
+
+def _ptr_array(tensors, ptr=_lib.fptr):
+    """A host array of device pointers, NULL for None."""
+    return (ctypes.c_void_p * len(tensors))(*[_opt(t, ptr) for t in tensors])
+
+
+def _int_array(values):
+    return (ctypes.c_int * len(values))(*values)
+
+
+def _split_flat(buf, like):
+    """A flat buffer cut into consecutive views with the shapes of the tensors of `like`, in their order (the weight gradients a
+    backward kernel writes side by side)."""
+    pieces, at = [], 0
+    for t in like:
+        pieces.append(buf[at:at + t.numel()].view(t.shape))
+        at += t.numel()
+    return pieces
+
+
+def _two_lists(idx):
+    """(ia, ib or None, neighbours per point) of a neighbour list given as the two searches' halves or as one tensor."""
+    ia, ib = idx if isinstance(idx, (tuple, list)) else (idx, None)
+    return ia, ib, ia.shape[-1] + (0 if ib is None else ib.shape[-1])
+
+
 def _group_rows_fwd(points, idx):
     B, N, C = points.shape
     idx = idx.contiguous()
@@ -236,11 +266,7 @@ class _PointConvAggFn(torch.autograd.Function):
                 d_sxyz = _group_rows_grad(d_gxyz, idx, N, segments)
             if ctx.needs_input_grad[4]:
                 d_spoints = _group_rows_grad(d_rows, idx, N, segments)
-        pieces, at = [], 0
-        for t in (w0, b0, w1, b1, w2, b2):
-            pieces.append(d_w[at:at + t.numel()].view(t.shape))
-            at += t.numel()
-        return (None, None, d_sxyz, d_new, d_spoints, *pieces, None)   # (no gradient for the lengths)
+        return (None, None, d_sxyz, d_new, d_spoints, *_split_flat(d_w, (w0, b0, w1, b1, w2, b2)), None)   # (no gradient for the lengths)
 
 
 class _CrossFn(torch.autograd.Function):
@@ -283,11 +309,7 @@ class _CrossFn(torch.autograd.Function):
                 d_xyz2 = _group_rows_grad(d_dir, whole, N2, segments)
             if ctx.needs_input_grad[6]:
                 d_points2 = _group_rows_grad(d_rows, whole, N2, segments)
-        pieces, at = [], 0
-        for t in (wpos, bpos, wmlp, bmlp):
-            pieces.append(d_w[at:at + t.numel()].view(t.shape))
-            at += t.numel()
-        return (None, None, None, d_xyz1, d_xyz2, d_points1, d_points2, *pieces)
+        return (None, None, None, d_xyz1, d_xyz2, d_points1, d_points2, *_split_flat(d_w, (wpos, bpos, wmlp, bmlp)))
 
 
 def _len_ptr(lens):
@@ -633,55 +655,107 @@ def group_mlp_class(c, widths, nsample):
     return (8 if nsample <= 8 else 16 if nsample <= 16 else 32 if nsample <= 32 else 64, int(c), tuple(int(w) for w in widths))
 
 
+def _routes(table, cls, count):
+    """One route predicate for every fused layer: the class has a row in the table and the call is at least that large."""
+    least = table.get(cls)
+    return least is not None and count >= least
+
+
 def group_mlp_routes_fused(c, widths, nsample, centres):
     """The modules' route predicate: a pure function of the padded shapes."""
-    least = GROUP_MLP_FUSED_CLASSES.get(group_mlp_class(c, widths, nsample))
-    return least is not None and centres >= least
+    return _routes(GROUP_MLP_FUSED_CLASSES, group_mlp_class(c, widths, nsample), centres)
+
+
+def _fold_params(conv, bn):
+    return conv.weight, conv.bias, getattr(bn, "weight", None), getattr(bn, "bias", None)
+
+
+def _fold(bn, weight, bias, gamma, beta):
+    """The float64 fold of fold_conv_bn / fold_conv_bn_grad on the tensors the caller chose (detached or in the graph); the running
+    statistics are constants either way."""
+    w = weight.double().flatten(1)
+    b = bias.double() if bias is not None else w.new_zeros(w.shape[0])
+    if bn is not None:
+        g = gamma.double() if gamma is not None else w.new_ones(w.shape[0])
+        beta = beta.double() if beta is not None else w.new_zeros(w.shape[0])
+        scale = g / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+        w, b = w * scale[:, None], (b - bn.running_mean.detach().double()) * scale + beta
+    return w.float().contiguous(), b.float().contiguous()
+
+
+def _det(t, contiguous=True):
+    """An optional tensor out of the graph -- and, as the kernels of an autograd function read it, contiguous."""
+    if t is None:
+        return None
+    return t.detach().contiguous() if contiguous else t.detach()
+
+
+def _pairs(flat):
+    """[(W, b), ...] of the flat parameter list an autograd function takes."""
+    return list(zip(flat[0::2], flat[1::2]))
+
+
+def _quads(flat):
+    """[(W, b, gamma, beta), ...] of the flat parameter list an autograd function takes."""
+    return list(zip(flat[0::4], flat[1::4], flat[2::4], flat[3::4]))
+
+
+def _flat(groups):
+    return [t for group in groups for t in group]
+
+
+def _unused_zeros(t, wanted):
+    """The gradient of coordinates that never enter a set-abstraction layer (use_xyz = False)."""
+    return torch.zeros_like(t) if wanted else None
 
 
 def fold_conv_bn(conv, bn=None):
     """(W (out, in), b (out,)) fp32 of a 1x1 convolution (or Linear) followed by an eval-mode BatchNorm with the layer's own eps:
     W' = W * g / sqrt(var + eps), b' = (b - mean) * g / sqrt(var + eps) + beta, folded in float64 and rounded once."""
-    w = conv.weight.detach().double().flatten(1)
-    b = conv.bias.detach().double() if conv.bias is not None else w.new_zeros(w.shape[0])
-    if bn is not None:
-        g = bn.weight.detach().double() if bn.weight is not None else w.new_ones(w.shape[0])
-        beta = bn.bias.detach().double() if bn.bias is not None else w.new_zeros(w.shape[0])
-        scale = g / torch.sqrt(bn.running_var.detach().double() + bn.eps)
-        w, b = w * scale[:, None], (b - bn.running_mean.detach().double()) * scale + beta
-    return w.float().contiguous(), b.float().contiguous()
+    return _fold(bn, *[_det(t, False) for t in _fold_params(conv, bn)])
 
 
 def fold_conv_bn_grad(conv, bn=None):
     """fold_conv_bn as an autograd function of conv.weight, conv.bias, bn.weight and bn.bias (the running statistics are constants):
     the same float64 expressions and the same single rounding, so the values have fold_conv_bn's bits; the gradient of (W', b')
     reaches the four parameters through autograd's chain rule.  For the differentiable fused layers (HipBackend.fp_mlp_layer)."""
-    w = conv.weight.double().flatten(1)
-    b = conv.bias.double() if conv.bias is not None else w.new_zeros(w.shape[0])
-    if bn is not None:
-        g = bn.weight.double() if bn.weight is not None else w.new_ones(w.shape[0])
-        beta = bn.bias.double() if bn.bias is not None else w.new_zeros(w.shape[0])
-        scale = g / torch.sqrt(bn.running_var.detach().double() + bn.eps)
-        w, b = w * scale[:, None], (b - bn.running_mean.detach().double()) * scale + beta
-    return w.float().contiguous(), b.float().contiguous()
+    return _fold(bn, *_fold_params(conv, bn))
+
+
+def _check_layers(name, layers, cin, widths):
+    """Every layer's W (out, in) and its per-channel vectors -- b, or b, gamma, beta where None stands for an absent one -- against
+    the first layer's input columns and the widths."""
+    for (w, *vecs), k, o in zip(layers, [cin, *widths[:-1]], widths):
+        if tuple(w.shape) != (o, k) or any(t is not None and tuple(t.shape) != (o,) for t in vecs):
+            got = [tuple(w.shape), *(None if t is None else tuple(t.shape) for t in vecs)]
+            raise RuntimeError(f"{name}: expected W {(o, k)} and {'b' if len(vecs) == 1 else 'b, gamma, beta'} {(o,)}, got {got}")
+
+
+def _pack_image(name, lead, shape, ok, weights, cin=None, grad_alloc=False, floats_lead=None):
+    """mcp_<name>_pack's image of [(W (out, in), b (out,)), ...] fp32 device tensors -> (packed, widths).  lead: the integers both
+    mcp_<name>_packed_floats (floats_lead where it takes others) and mcp_<name>_pack take in front of (layers, widths); shape, ok:
+    how the message names the shape, and what it must satisfy before the library is asked for a size; cin: the first layer's
+    input columns where the (W, b) shapes are checked; grad_alloc: the image is one of the backward's buffers (_grad_empty)."""
+    widths = [int(w.shape[0]) for w, _ in weights]
+    wid = _int_array(widths)
+    floats = getattr(_lib.load(), f"mcp_{name}_packed_floats")
+    n = floats(*(lead if floats_lead is None else floats_lead), len(widths), wid) if len(widths) <= 3 and ok else 0
+    if n == 0:
+        raise _lib.Unsupported(f"{name}: unsupported shape {shape} widths={widths}")
+    if cin is not None:
+        _check_layers(name, weights, cin, widths)
+    ws = [w.contiguous() for w, _ in weights]
+    bs = [b.contiguous() for _, b in weights]
+    dev = ws[0].device
+    packed = _grad_empty((n,), torch.float32, dev) if grad_alloc else torch.empty((n,), dtype=torch.float32, device=dev)
+    _call(f"mcp_{name}_pack", packed, *lead, len(widths), wid, _ptr_array(ws), _ptr_array(bs), _lib.fptr(packed))
+    return packed, widths
 
 
 def group_mlp_pack_weights(weights, use_xyz=True):
     """The MFMA-operand image of mcp_group_mlp from [(W (out, in), b (out,)), ...] fp32 device tensors -> (packed, widths)."""
-    widths = [int(w.shape[0]) for w, _ in weights]
-    c = int(weights[0][0].shape[1]) - (3 if use_xyz else 0)
-    lib = _lib.load()
-    wid = (ctypes.c_int * len(widths))(*widths)
-    n = lib.mcp_group_mlp_packed_floats(c, len(widths), wid) if len(widths) <= 3 else 0
-    if n == 0 or (c == 0 and not use_xyz):
-        raise _lib.Unsupported(f"group_mlp: unsupported shape c={c} widths={widths}")
-    ws = [w.contiguous() for w, _ in weights]
-    bs = [b.contiguous() for _, b in weights]
-    packed = torch.empty((n,), dtype=torch.float32, device=ws[0].device)
-    wp = (ctypes.c_void_p * len(ws))(*[_lib.fptr(w) for w in ws])
-    bp = (ctypes.c_void_p * len(bs))(*[_lib.fptr(b) for b in bs])
-    _call("mcp_group_mlp_pack", packed, c, int(bool(use_xyz)), len(widths), wid, wp, bp, _lib.fptr(packed))
-    return packed, widths
+    c, xyz = int(weights[0][0].shape[1]) - (3 if use_xyz else 0), int(bool(use_xyz))
+    return _pack_image("group_mlp", (c, xyz), f"c={c}", c != 0 or xyz, weights, floats_lead=(c,))
 
 
 def group_mlp_pack(convs, bns=None, use_xyz=True):
@@ -733,30 +807,14 @@ GROUP_MLP_GRAD_FUSED_CLASSES = {}
 
 def group_mlp_grad_routes_fused(c, widths, nsample, centres):
     """PointnetSAModuleMSG's route predicate when a gradient is wanted: a pure function of the padded shapes."""
-    least = GROUP_MLP_GRAD_FUSED_CLASSES.get(group_mlp_class(c, widths, nsample))
-    return least is not None and centres >= least
+    return _routes(GROUP_MLP_GRAD_FUSED_CLASSES, group_mlp_class(c, widths, nsample), centres)
 
 
 def group_mlp_grad_pack_weights(weights, use_xyz=True):
     """mcp_group_mlp_grad_pack's image from [(W (out, in), b (out,)), ...] fp32 device tensors -> (packed, widths)."""
-    widths = [int(w.shape[0]) for w, _ in weights]
-    c = int(weights[0][0].shape[1]) - (3 if use_xyz else 0)
-    lib = _lib.load()
-    wid = (ctypes.c_int * len(widths))(*widths)
-    n = lib.mcp_group_mlp_grad_packed_floats(c, int(bool(use_xyz)), len(widths), wid) if len(widths) <= 3 and c >= 0 else 0
-    if n == 0:
-        raise _lib.Unsupported(f"group_mlp_grad: unsupported shape c={c} widths={widths}")
-    cin = [c + (3 if use_xyz else 0), *widths[:-1]]
-    for (w, b), k, o in zip(weights, cin, widths):
-        if tuple(w.shape) != (o, k) or tuple(b.shape) != (o,):
-            raise RuntimeError(f"group_mlp_grad: expected W {(o, k)} and b {(o,)}, got {tuple(w.shape)} and {tuple(b.shape)}")
-    ws = [w.contiguous() for w, _ in weights]
-    bs = [b.contiguous() for _, b in weights]
-    packed = _grad_empty((n,), torch.float32, ws[0].device)
-    wp = (ctypes.c_void_p * len(ws))(*[_lib.fptr(w) for w in ws])
-    bp = (ctypes.c_void_p * len(bs))(*[_lib.fptr(b) for b in bs])
-    _call("mcp_group_mlp_grad_pack", packed, c, int(bool(use_xyz)), len(widths), wid, wp, bp, _lib.fptr(packed))
-    return packed, widths
+    cin, xyz = int(weights[0][0].shape[1]), int(bool(use_xyz))
+    c = cin - (3 if use_xyz else 0)
+    return _pack_image("group_mlp_grad", (c, xyz), f"c={c}", c >= 0, weights, cin=cin, grad_alloc=True)
 
 
 class _GroupMlpLayerFn(torch.autograd.Function):
@@ -767,11 +825,8 @@ class _GroupMlpLayerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, be, pool, use_xyz, idx, ql, xyz, new_xyz, features, row_bias, *wb):
-        xyz, new_xyz = xyz.detach().contiguous(), new_xyz.detach().contiguous()
-        features = None if features is None else features.detach().contiguous()
-        row_bias = None if row_bias is None else row_bias.detach().contiguous()
-        wb = [t.detach().contiguous() for t in wb]
-        packed, widths = group_mlp_pack_weights(list(zip(wb[0::2], wb[1::2])), use_xyz)
+        xyz, new_xyz, features, row_bias, *wb = [_det(t) for t in (xyz, new_xyz, features, row_bias, *wb)]
+        packed, widths = group_mlp_pack_weights(_pairs(wb), use_xyz)
         out = be._group_mlp(xyz, new_xyz, features, idx, packed, widths, pool, use_xyz, ql, row_bias)
         ctx.be, ctx.pool, ctx.use_xyz = be, pool, use_xyz
         ctx.save_for_backward(idx, ql, xyz, new_xyz, features, row_bias, *wb)
@@ -783,14 +838,12 @@ class _GroupMlpLayerFn(torch.autograd.Function):
         idx, ql, xyz, new_xyz, features, row_bias, *wb = ctx.saved_tensors
         need = ctx.needs_input_grad
         d_feat, d_xyz, d_new, d_rb, d_w, d_b, _ = ctx.be.group_mlp_grad(
-            xyz, new_xyz, features, idx, list(zip(wb[0::2], wb[1::2])), grad_out, pool=ctx.pool, use_xyz=ctx.use_xyz, new_xyz_lengths=ql,
+            xyz, new_xyz, features, idx, _pairs(wb), grad_out, pool=ctx.pool, use_xyz=ctx.use_xyz, new_xyz_lengths=ql,
             row_bias=row_bias, want_features=need[7] and features is not None, want_xyz=need[5] and ctx.use_xyz,
             want_new_xyz=need[6] and ctx.use_xyz, want_row_bias=need[8] and row_bias is not None)
-        zeros = lambda t, wanted: torch.zeros_like(t) if wanted and t is not None else None   # coordinates that never enter the layer
         if not ctx.use_xyz:
-            d_xyz, d_new = zeros(xyz, need[5]), zeros(new_xyz, need[6])
-        pieces = [t for pair in zip(d_w, d_b) for t in pair]
-        return (None, None, None, None, None, d_xyz, d_new, d_feat, d_rb, *pieces)
+            d_xyz, d_new = _unused_zeros(xyz, need[5]), _unused_zeros(new_xyz, need[6])
+        return (None, None, None, None, None, d_xyz, d_new, d_feat, d_rb, *_flat(zip(d_w, d_b)))
 
 
 # ---- feature-propagation layer (csrc/fp_mlp.hip) ----
@@ -839,32 +892,19 @@ def fp_mlp_class(c2, c1, widths):
 
 def fp_mlp_routes_fused(c2, c1, widths, rows):
     """PointnetFPModule's route predicate: a pure function of the padded shapes."""
-    least = FP_MLP_FUSED_CLASSES.get(fp_mlp_class(c2, c1, widths))
-    return least is not None and rows >= least
+    return _routes(FP_MLP_FUSED_CLASSES, fp_mlp_class(c2, c1, widths), rows)
+
+
+def _fp_pack(name, weights, c2, grad_alloc):
+    """The fp family's images: the first c2 columns of the first W meet the interpolated features, the rest the skip row."""
+    c2, cin = int(c2), int(weights[0][0].shape[1])
+    return _pack_image(name, (c2, cin - c2), f"c2={c2} c1={cin - c2}", cin >= c2, weights, cin=cin, grad_alloc=grad_alloc)
 
 
 def fp_mlp_pack_weights(weights, c2):
     """The MFMA-operand image of mcp_fp_mlp from [(W (out, in), b (out,)), ...] fp32 device tensors; the first c2 columns of the
     first W meet the interpolated features, the rest the skip row -> (packed, widths)."""
-    widths = [int(w.shape[0]) for w, _ in weights]
-    c2 = int(c2)
-    c1 = int(weights[0][0].shape[1]) - c2
-    lib = _lib.load()
-    wid = (ctypes.c_int * len(widths))(*widths)
-    n = lib.mcp_fp_mlp_packed_floats(c2, c1, len(widths), wid) if len(widths) <= 3 and c1 >= 0 else 0
-    if n == 0:
-        raise _lib.Unsupported(f"fp_mlp: unsupported shape c2={c2} c1={c1} widths={widths}")
-    cin = [c2 + c1, *widths[:-1]]
-    for (w, b), k, o in zip(weights, cin, widths):
-        if tuple(w.shape) != (o, k) or tuple(b.shape) != (o,):
-            raise RuntimeError(f"fp_mlp: expected W {(o, k)} and b {(o,)}, got {tuple(w.shape)} and {tuple(b.shape)}")
-    ws = [w.contiguous() for w, _ in weights]
-    bs = [b.contiguous() for _, b in weights]
-    packed = torch.empty((n,), dtype=torch.float32, device=ws[0].device)
-    wp = (ctypes.c_void_p * len(ws))(*[_lib.fptr(w) for w in ws])
-    bp = (ctypes.c_void_p * len(bs))(*[_lib.fptr(b) for b in bs])
-    _call("mcp_fp_mlp_pack", packed, c2, c1, len(widths), wid, wp, bp, _lib.fptr(packed))
-    return packed, widths
+    return _fp_pack("fp_mlp", weights, c2, False)
 
 
 def fp_mlp_pack(convs, bns=None, c2=None):
@@ -910,8 +950,7 @@ FP_MLP_GRAD_FUSED_CLASSES = {(256, 3, (256, 256)): 8 * 16384}
 
 def fp_mlp_grad_routes_fused(c2, c1, widths, rows):
     """PointnetFPModule's route predicate when a gradient is wanted: a pure function of the padded shapes."""
-    least = FP_MLP_GRAD_FUSED_CLASSES.get(fp_mlp_class(c2, c1, widths))
-    return least is not None and rows >= least
+    return _routes(FP_MLP_GRAD_FUSED_CLASSES, fp_mlp_class(c2, c1, widths), rows)
 
 
 def _grad_empty(shape, dtype, device):
@@ -921,25 +960,7 @@ def _grad_empty(shape, dtype, device):
 
 def fp_mlp_grad_pack_weights(weights, c2):
     """mcp_fp_mlp_grad_pack's image from [(W (out, in), b (out,)), ...] fp32 device tensors -> (packed, widths)."""
-    widths = [int(w.shape[0]) for w, _ in weights]
-    c2 = int(c2)
-    c1 = int(weights[0][0].shape[1]) - c2
-    lib = _lib.load()
-    wid = (ctypes.c_int * len(widths))(*widths)
-    n = lib.mcp_fp_mlp_grad_packed_floats(c2, c1, len(widths), wid) if len(widths) <= 3 and c1 >= 0 else 0
-    if n == 0:
-        raise _lib.Unsupported(f"fp_mlp_grad: unsupported shape c2={c2} c1={c1} widths={widths}")
-    cin = [c2 + c1, *widths[:-1]]
-    for (w, b), k, o in zip(weights, cin, widths):
-        if tuple(w.shape) != (o, k) or tuple(b.shape) != (o,):
-            raise RuntimeError(f"fp_mlp_grad: expected W {(o, k)} and b {(o,)}, got {tuple(w.shape)} and {tuple(b.shape)}")
-    ws = [w.contiguous() for w, _ in weights]
-    bs = [b.contiguous() for _, b in weights]
-    packed = _grad_empty((n,), torch.float32, ws[0].device)
-    wp = (ctypes.c_void_p * len(ws))(*[_lib.fptr(w) for w in ws])
-    bp = (ctypes.c_void_p * len(bs))(*[_lib.fptr(b) for b in bs])
-    _call("mcp_fp_mlp_grad_pack", packed, c2, c1, len(widths), wid, wp, bp, _lib.fptr(packed))
-    return packed, widths
+    return _fp_pack("fp_mlp_grad", weights, c2, True)
 
 
 class _FpMlpLayerFn(torch.autograd.Function):
@@ -949,11 +970,8 @@ class _FpMlpLayerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, be, rule, idx, dist, w3, ulen, known_feats, skip, *wb):
-        known_feats = known_feats.detach().contiguous()
-        skip = None if skip is None else skip.detach().contiguous()
-        wb = [t.detach().contiguous() for t in wb]
-        weights = list(zip(wb[0::2], wb[1::2]))
-        packed, widths = fp_mlp_pack_weights(weights, known_feats.shape[-1])
+        known_feats, skip, *wb = [_det(t) for t in (known_feats, skip, *wb)]
+        packed, widths = fp_mlp_pack_weights(_pairs(wb), known_feats.shape[-1])
         out = be.fp_mlp(known_feats, skip, idx, dist, packed, widths, rule=rule, w3=w3, unknown_lengths=ulen)
         ctx.be, ctx.rule, ctx.has_skip = be, rule, skip is not None
         ctx.save_for_backward(idx, dist, w3, ulen, known_feats, skip, *wb)
@@ -963,11 +981,9 @@ class _FpMlpLayerFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         idx, dist, w3, ulen, known_feats, skip, *wb = ctx.saved_tensors
-        weights = list(zip(wb[0::2], wb[1::2]))
-        d_known, d_skip, d_w, d_b, _ = ctx.be.fp_mlp_grad(known_feats, skip, idx, dist, weights, grad_out, rule=ctx.rule, w3=w3, unknown_lengths=ulen,
+        d_known, d_skip, d_w, d_b, _ = ctx.be.fp_mlp_grad(known_feats, skip, idx, dist, _pairs(wb), grad_out, rule=ctx.rule, w3=w3, unknown_lengths=ulen,
                                                           want_known=ctx.needs_input_grad[6])
-        pieces = [t for pair in zip(d_w, d_b) for t in pair]
-        return (None, None, None, None, None, None, d_known, d_skip if ctx.needs_input_grad[7] else None, *pieces)
+        return (None, None, None, None, None, None, d_known, d_skip if ctx.needs_input_grad[7] else None, *_flat(zip(d_w, d_b)))
 
 
 # ---- feature-propagation layer with training-mode BatchNorm (csrc/fp_mlp_bn.hip) ----
@@ -987,14 +1003,21 @@ FP_MLP_BN_FUSED_CLASSES = {(256, 3, (256, 256)): 8 * 16384}
 
 def fp_mlp_bn_routes_fused(c2, c1, widths, rows):
     """PointnetFPModule's route predicate under a training-mode BatchNorm: a pure function of the padded shapes."""
-    least = FP_MLP_BN_FUSED_CLASSES.get(fp_mlp_class(c2, c1, widths))
-    return least is not None and rows >= least
+    return _routes(FP_MLP_BN_FUSED_CLASSES, fp_mlp_class(c2, c1, widths), rows)
 
 
-def _ptr_array(tensors, ptr=None):
-    """A host array of device pointers, NULL for None."""
-    ptr = _lib.fptr if ptr is None else ptr
-    return (ctypes.c_void_p * len(tensors))(*[None if t is None else ptr(t) for t in tensors])
+def _bn_layer_outputs(ctx, out, mean, var, count):
+    """What the forward of a *BnLayerFn returns: out, per layer (mean, biased variance), the live count; all but out are marked
+    non-differentiable."""
+    stats = _flat(zip(mean, var))
+    ctx.mark_non_differentiable(*stats, count)
+    return (out, *stats, count)
+
+
+def _bn_layer_saved(ctx, own):
+    """The saved tensors of a *BnLayerFn cut back: its `own` leading inputs, then [(W, b, gamma, beta), ...], [mean_l], [rstd_l]."""
+    saved, L = ctx.saved_tensors, ctx.layers
+    return (*saved[:own], _quads(saved[own:own + 4 * L]), saved[own + 4 * L:own + 5 * L], saved[own + 5 * L:])
 
 
 class _FpMlpBnLayerFn(torch.autograd.Function):
@@ -1005,28 +1028,20 @@ class _FpMlpBnLayerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, be, rule, idx, dist, w3, ulen, eps, known_feats, skip, *params):
-        known_feats = known_feats.detach().contiguous()
-        skip = None if skip is None else skip.detach().contiguous()
-        params = [None if t is None else t.detach().contiguous() for t in params]
-        layers = list(zip(params[0::4], params[1::4], params[2::4], params[3::4]))
+        known_feats, skip, *params = [_det(t) for t in (known_feats, skip, *params)]
+        layers = _quads(params)
         out, mean, var, rstd, count = be.fp_mlp_bn_forward(known_feats, skip, idx, dist, layers, eps, rule=rule, w3=w3, unknown_lengths=ulen)
         ctx.be, ctx.rule, ctx.layers = be, rule, len(layers)
         ctx.save_for_backward(idx, dist, w3, ulen, known_feats, skip, *params, *mean, *rstd)
-        stats = [t for pair in zip(mean, var) for t in pair]
-        ctx.mark_non_differentiable(*stats, count)
-        return (out, *stats, count)
+        return _bn_layer_outputs(ctx, out, mean, var, count)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out, *_):
-        idx, dist, w3, ulen, known_feats, skip, *rest = ctx.saved_tensors
-        L = ctx.layers
-        params, mean, rstd = rest[:4 * L], rest[4 * L:5 * L], rest[5 * L:]
-        layers = list(zip(params[0::4], params[1::4], params[2::4], params[3::4]))
+        idx, dist, w3, ulen, known_feats, skip, layers, mean, rstd = _bn_layer_saved(ctx, 6)
         d_known, d_skip, d_layers = ctx.be.fp_mlp_bn_backward(known_feats, skip, idx, dist, layers, mean, rstd, grad_out, rule=ctx.rule, w3=w3,
                                                               unknown_lengths=ulen, want_known=ctx.needs_input_grad[7])
-        pieces = [t for quad in d_layers for t in quad]
-        return (None, None, None, None, None, None, None, d_known, d_skip if ctx.needs_input_grad[8] else None, *pieces)
+        return (None, None, None, None, None, None, None, d_known, d_skip if ctx.needs_input_grad[8] else None, *_flat(d_layers))
 
 
 # ---- set-abstraction layer with training-mode BatchNorm (csrc/group_mlp_bn.hip) ----
@@ -1063,24 +1078,13 @@ GROUP_MLP_BN_FUSED_CLASSES = {}
 
 def group_mlp_bn_routes_fused(c, widths, nsample, centres):
     """PointnetSAModuleMSG's route predicate under a training-mode BatchNorm: a pure function of the padded shapes."""
-    least = GROUP_MLP_BN_FUSED_CLASSES.get(group_mlp_class(c, widths, nsample))
-    return least is not None and centres >= least
+    return _routes(GROUP_MLP_BN_FUSED_CLASSES, group_mlp_class(c, widths, nsample), centres)
 
 
 def group_mlp_bn_pack_weights(weights, use_xyz=True):
     """mcp_group_mlp_bn_pack's image from the unfolded [(W (out, in), b (out,)), ...] fp32 device tensors -> (packed, widths)."""
-    widths = [int(w.shape[0]) for w, _ in weights]
-    c = int(weights[0][0].shape[1]) - (3 if use_xyz else 0)
-    lib = _lib.load()
-    wid = (ctypes.c_int * len(widths))(*widths)
-    n = lib.mcp_group_mlp_bn_packed_floats(c, int(bool(use_xyz)), len(widths), wid) if len(widths) <= 3 and c >= 0 else 0
-    if n == 0:
-        raise _lib.Unsupported(f"group_mlp_bn: unsupported shape c={c} widths={widths}")
-    ws = [w.contiguous() for w, _ in weights]
-    bs = [b.contiguous() for _, b in weights]
-    packed = _grad_empty((n,), torch.float32, ws[0].device)
-    _call("mcp_group_mlp_bn_pack", packed, c, int(bool(use_xyz)), len(widths), wid, _ptr_array(ws), _ptr_array(bs), _lib.fptr(packed))
-    return packed, widths
+    c, xyz = int(weights[0][0].shape[1]) - (3 if use_xyz else 0), int(bool(use_xyz))
+    return _pack_image("group_mlp_bn", (c, xyz), f"c={c}", c >= 0, weights, grad_alloc=True)
 
 
 class _GroupMlpBnLayerFn(torch.autograd.Function):
@@ -1091,33 +1095,24 @@ class _GroupMlpBnLayerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, be, pool, use_xyz, idx, ql, eps, xyz, new_xyz, features, *params):
-        xyz, new_xyz = xyz.detach().contiguous(), new_xyz.detach().contiguous()
-        features = None if features is None else features.detach().contiguous()
-        params = [None if t is None else t.detach().contiguous() for t in params]
-        layers = list(zip(params[0::4], params[1::4], params[2::4], params[3::4]))
+        xyz, new_xyz, features, *params = [_det(t) for t in (xyz, new_xyz, features, *params)]
+        layers = _quads(params)
         out, mean, var, rstd, count = be.group_mlp_bn_forward(xyz, new_xyz, features, idx, layers, eps, pool=pool, use_xyz=use_xyz, new_xyz_lengths=ql)
         ctx.be, ctx.pool, ctx.use_xyz, ctx.layers = be, pool, use_xyz, len(layers)
         ctx.save_for_backward(idx, ql, xyz, new_xyz, features, *params, *mean, *rstd)
-        stats = [t for pair in zip(mean, var) for t in pair]
-        ctx.mark_non_differentiable(*stats, count)
-        return (out, *stats, count)
+        return _bn_layer_outputs(ctx, out, mean, var, count)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out, *_):
-        idx, ql, xyz, new_xyz, features, *rest = ctx.saved_tensors
-        L = ctx.layers
-        params, mean, rstd = rest[:4 * L], rest[4 * L:5 * L], rest[5 * L:]
-        layers = list(zip(params[0::4], params[1::4], params[2::4], params[3::4]))
+        idx, ql, xyz, new_xyz, features, layers, mean, rstd = _bn_layer_saved(ctx, 5)
         need = ctx.needs_input_grad
         d_feat, d_xyz, d_new, d_layers = ctx.be.group_mlp_bn_backward(
             xyz, new_xyz, features, idx, layers, mean, rstd, grad_out, pool=ctx.pool, use_xyz=ctx.use_xyz, new_xyz_lengths=ql,
             want_features=need[8] and features is not None, want_xyz=need[6] and ctx.use_xyz, want_new_xyz=need[7] and ctx.use_xyz)
-        zeros = lambda t, wanted: torch.zeros_like(t) if wanted else None   # coordinates that never enter the layer
         if not ctx.use_xyz:
-            d_xyz, d_new = zeros(xyz, need[6]), zeros(new_xyz, need[7])
-        pieces = [t for quad in d_layers for t in quad]
-        return (None, None, None, None, None, None, d_xyz, d_new, d_feat, *pieces)
+            d_xyz, d_new = _unused_zeros(xyz, need[6]), _unused_zeros(new_xyz, need[7])
+        return (None, None, None, None, None, None, d_xyz, d_new, d_feat, *_flat(d_layers))
 
 
 class _ChamferLengthsFn(torch.autograd.Function):
@@ -1191,11 +1186,7 @@ class _PtblockFn(torch.autograd.Function):
         d_xyz = d_xyz_c + _group_rows_grad(d_xyz_rows, idx, N, segments) if ctx.needs_input_grad[2] else None
         d_k = _group_rows_grad(d_k_rows, idx, N, segments) if ctx.needs_input_grad[4] else None
         d_v = _group_rows_grad(d_v_rows, idx, N, segments) if ctx.needs_input_grad[5] else None
-        pieces, at = [], 0
-        for t in ws:
-            pieces.append(d_w[at:at + t.numel()].view(t.shape))
-            at += t.numel()
-        return (None, None, d_xyz, d_q, d_k, d_v, *pieces)
+        return (None, None, d_xyz, d_q, d_k, d_v, *_split_flat(d_w, ws))
 
 
 def _scatter_lists(ia, ib, lens, n):
@@ -1208,6 +1199,16 @@ def _scatter_lists(ia, ib, lens, n):
     if lens is None:
         return idx
     return grad.spread_padded_rows(idx, grad.live_points(lens, idx.shape[0], idx.shape[1], idx.device), n)
+
+
+def _fusion_lead(p1, p2, idx, lens, conv, null_lens=False):
+    """The arguments every fusion entry starts with: B, N, the neighbours per point, p1, p2, the list(s), [the lengths,] and the
+    tensors of conv (w1 .. b3, and what the entry takes right after them).  The length pointer stands there when there are lengths:
+    the dense entries have no such argument -- or, null_lens, always (mcp_fusion_grad_lengths, which takes NULL)."""
+    ia, ib, nb = _two_lists(idx)
+    B, N, _ = p1.shape
+    return (B, N, nb, _lib.fptr(p1), _lib.fptr(p2), _lib.iptr(ia), _opt(ib, _lib.iptr), *((_len_ptr(lens),) if null_lens or lens is not None else ()),
+            *[_lib.fptr(t) for t in conv])
 
 
 class _FusionBNFn(torch.autograd.Function):
@@ -1236,7 +1237,7 @@ class _FusionBNFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out, _gbn, _gvar, _gcount=None):
-        ia, ib, p1, p2, w1, b1, w2, b2, w3, b3, bn = ctx.saved_tensors[:11]
+        ia, ib, p1, p2, *conv, bn = ctx.saved_tensors[:11]   # conv = (w1, b1, w2, b2, w3, b3)
         rest = ctx.saved_tensors[11:]
         lens = rest[0] if ctx.has_lengths else None
         save_c, save_z, save_s = rest[-3:] if ctx.kept else (None, None, None)
@@ -1255,25 +1256,17 @@ class _FusionBNFn(torch.autograd.Function):
         ws = torch.empty((need,), dtype=torch.uint8, device=dev)
         scratch = (_lib.iptr(row_c), _lib.fptr(row_dy), _lib.fptr(row_a), _lib.fptr(dy2), _lib.fptr(dy1), _lib.fptr(d_p1), _lib.fptr(d_nb), _lib.fptr(d_w),
                    _lib.fptr(d_aff), ws.data_ptr(), need)
-        if ctx.has_lengths and ctx.kept:
-            _call("mcp_fusion_bn_backward_saved_lengths", p1, B, N, 64, _lib.fptr(p1), _lib.fptr(p2), _lib.iptr(ia), None if ib is None else _lib.iptr(ib),
-                  _lib.iptr(lens), *[_lib.fptr(t) for t in (w1, b1, w2, b2, w3, b3, bn, grad_out)], _lib.iptr(save_c), _lib.fptr(save_z),
-                  _lib.fptr(save_s), *scratch)
-        elif ctx.has_lengths:
-            _call("mcp_fusion_bn_backward_lengths", p1, B, N, 64, _lib.fptr(p1), _lib.fptr(p2), _lib.iptr(ia), None if ib is None else _lib.iptr(ib),
-                  _lib.iptr(lens), *[_lib.fptr(t) for t in (w1, b1, w2, b2, w3, b3, bn, grad_out)], *scratch)
+        if lens is not None:   # (the condition under which _fusion_lead passes the length pointer)
+            entry = "mcp_fusion_bn_backward_saved_lengths" if ctx.kept else "mcp_fusion_bn_backward_lengths"
         else:
-            _call("mcp_fusion_bn_backward_saved", p1, B, N, 64, _lib.fptr(p1), _lib.fptr(p2), _lib.iptr(ia), None if ib is None else _lib.iptr(ib),
-                  *[_lib.fptr(t) for t in (w1, b1, w2, b2, w3, b3, bn, grad_out)], _lib.iptr(save_c), _lib.fptr(save_z), _lib.fptr(save_s), *scratch)
+            entry = "mcp_fusion_bn_backward_saved"
+        keep = (_lib.iptr(save_c), _lib.fptr(save_z), _lib.fptr(save_s)) if ctx.kept else ()
+        _call(entry, p1, *_fusion_lead(p1, p2, (ia, ib), lens, (*conv, bn, grad_out)), *keep, *scratch)
         d_p2 = None
         if ctx.needs_input_grad[6]:
             d_p2 = _group_rows_grad(d_nb, _scatter_lists(ia, ib, lens, p2.shape[1]), p2.shape[1])
-        pieces, at = [], 0
-        for t in (w1, b1, w2, b2, w3, b3):
-            pieces.append(d_w[at:at + t.numel()].view(t.shape))
-            at += t.numel()
         aff = [d_aff[0:64], d_aff[64:128], d_aff[128:192], d_aff[192:256], d_aff[256:384], d_aff[384:512]]
-        return (None, None, None, None, None, d_p1, d_p2, *pieces, *aff)
+        return (None, None, None, None, None, d_p1, d_p2, *_split_flat(d_w, conv), *aff)
 
 
 class _BNBatchFn(torch.autograd.Function):
@@ -1330,7 +1323,7 @@ class _FusionFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        ia, ib, p1, p2, w1, b1, w2, b2, w3, b3, lens = ctx.saved_tensors
+        ia, ib, p1, p2, *conv, lens = ctx.saved_tensors   # conv = (w1, b1, w2, b2, w3, b3)
         B, N, _ = p1.shape
         lib = _lib.load()
         grad_out = grad_out.contiguous()
@@ -1339,17 +1332,106 @@ class _FusionFn(torch.autograd.Function):
         d_w = torch.empty((lib.mcp_fusion_grad_floats(),), dtype=torch.float32, device=p1.device)
         need = lib.mcp_fusion_grad_workspace_bytes(B, N)
         ws = torch.empty((need,), dtype=torch.uint8, device=p1.device)
-        _call("mcp_fusion_grad_lengths", p1, B, N, 64, _lib.fptr(p1), _lib.fptr(p2), _lib.iptr(ia), None if ib is None else _lib.iptr(ib), _len_ptr(lens),
-              _lib.fptr(w1), _lib.fptr(b1), _lib.fptr(w2), _lib.fptr(b2), _lib.fptr(w3), _lib.fptr(b3), _lib.fptr(grad_out), _lib.fptr(d_p1),
+        _call("mcp_fusion_grad_lengths", p1, *_fusion_lead(p1, p2, (ia, ib), lens, (*conv, grad_out), null_lens=True), _lib.fptr(d_p1),
               _lib.fptr(d_nb), _lib.fptr(d_w), ws.data_ptr(), need)
         d_p2 = None
         if ctx.needs_input_grad[5]:
             d_p2 = _group_rows_grad(d_nb, _scatter_lists(ia, ib, lens, p2.shape[1]), p2.shape[1])
-        pieces, at = [], 0
-        for t in (w1, b1, w2, b2, w3, b3):
-            pieces.append(d_w[at:at + t.numel()].view(t.shape))
-            at += t.numel()
-        return (None, None, None, None, d_p1, d_p2, *pieces)
+        return (None, None, None, None, d_p1, d_p2, *_split_flat(d_w, conv))
+
+
+# ---- the fused point layers' entries: each family's argument checks and leading arguments, stated once ----
+def _check_grad_out(name, grad_out, shape):
+    if tuple(grad_out.shape) != shape:
+        raise RuntimeError(f"{name}: grad_out {tuple(grad_out.shape)}, expected {shape}")
+
+
+def _group_check(name, xyz, new_xyz, features, idx, layers, use_xyz, grad_out=None):
+    """The checks of the set-abstraction entries that take the layers themselves, [(W, b), ...] or [(W, b or None, gamma or None, beta
+    or None), ...] -> ((B, N, M, C, nsample), widths).  grad_out: the _grad entry's, checked where it always was; the layer shapes
+    of that entry are checked once, when its image is built (group_mlp_grad_pack_weights)."""
+    B, N, _ = xyz.shape
+    M, nsample = new_xyz.shape[1], idx.shape[2]
+    C = 0 if features is None else features.shape[2]
+    if tuple(idx.shape[:2]) != (B, M) or (features is not None and tuple(features.shape[:2]) != (B, N)):
+        raise RuntimeError(f"{name}: idx {tuple(idx.shape)} / features do not match B={B}, N={N}, M={M}")
+    widths = [int(l[0].shape[0]) for l in layers]
+    cin = C + (3 if use_xyz else 0)
+    if not group_mlp_supported(C, widths, nsample, use_xyz) or int(layers[0][0].shape[1]) != cin:   # (the _grad and _bn kernels take every shape of it)
+        raise _lib.Unsupported(f"{name}: unsupported shape c={C} widths={widths} nsample={nsample}")
+    if grad_out is not None:
+        _check_grad_out(name, grad_out, (B, M, widths[-1]))
+    else:
+        _check_layers(name, layers, cin, widths)
+    if B == 0 or N == 0 or M == 0:
+        raise RuntimeError(f"{name}: empty batch, cloud or centre list")
+    return (B, N, M, C, nsample), widths
+
+
+def _group_lead(dims, pool, use_xyz, wid, xyz, new_xyz, features, idx, ql):
+    """What mcp_group_mlp, mcp_group_mlp_grad, mcp_group_mlp_bn_forward and mcp_group_mlp_bn_backward take first: dims = (B, N, M, C,
+    nsample), the flags, the widths, the clouds, the features, the list and the centre lengths."""
+    return (*dims, int(bool(use_xyz)), GROUP_MLP_POOLS[pool], len(wid), wid, _lib.fptr(xyz), _lib.fptr(new_xyz), _opt(features), _lib.iptr(idx),
+            _len_ptr(ql))
+
+
+def _fp_check(name, known_feats, skip, idx, dist, rule, w3, layers, widths=None, grad_out=None):
+    """The checks of the feature-propagation entries -> ((B, n, m, C2, C1, rule code), widths).  layers: [(W, b), ...] or [(W, b or None,
+    gamma or None, beta or None), ...]; None for the eval call, which has an image and `widths` instead and takes an empty batch.
+    grad_out: the _grad entry's, checked where it always was; the layer shapes of that entry are checked once, when its image is
+    built (fp_mlp_grad_pack_weights)."""
+    B, m, C2 = known_feats.shape
+    n = idx.shape[1]
+    C1 = 0 if skip is None else skip.shape[2]
+    code = FP_MLP_RULES[rule]
+    if tuple(idx.shape) != (B, n, 3) or (skip is not None and tuple(skip.shape[:2]) != (B, n)):
+        raise RuntimeError(f"{name}: idx {tuple(idx.shape)} / skip do not match B={B}, n={n}")
+    what, t = ("w3", w3) if code == 0 else ("dist", dist)
+    if t is None or tuple(t.shape) != (B, n, 3):
+        raise RuntimeError(f"{name}: rule {rule!r} needs {what} of shape {(B, n, 3)}")
+    if layers is not None:
+        widths = [int(l[0].shape[0]) for l in layers]
+    if not fp_mlp_supported(C2, C1, widths) or (layers is not None and int(layers[0][0].shape[1]) != C2 + C1):   # (_grad, _bn: every shape of it)
+        raise _lib.Unsupported(f"{name}: unsupported shape c2={C2} c1={C1} widths={widths}")
+    if layers is not None:
+        if grad_out is not None:
+            _check_grad_out(name, grad_out, (B, n, widths[-1]))
+        else:
+            _check_layers(name, layers, C2 + C1, widths)
+        if B == 0 or n == 0 or m == 0:
+            raise RuntimeError(f"{name}: empty batch, unknown or known cloud")
+    return (B, n, m, C2, C1, code), widths
+
+
+def _fp_lead(dims, wid, known_feats, skip, idx, dist, w3, ul, packed):
+    """What mcp_fp_mlp, mcp_fp_mlp_grad, mcp_fp_mlp_bn_forward and mcp_fp_mlp_bn_backward take first: dims = (B, n, m, C2, C1, rule code),
+    the widths, the features, the skip rows (NULL without channels), the list, dist or -- rule "given" -- w3, the lengths, the image."""
+    C1, code = dims[4], dims[5]
+    return (*dims, len(wid), wid, _lib.fptr(known_feats), None if C1 == 0 else _lib.fptr(skip), _lib.iptr(idx), None if code == 0 else _lib.fptr(dist),
+            _lib.fptr(w3) if code == 0 else None, _len_ptr(ul), _lib.fptr(packed))
+
+
+def _bn_pairs(layers):
+    """[(W, b), ...] of [(W, b or None, gamma, beta), ...] for the operand image: zeros stand for an absent bias."""
+    return [(w, torch.zeros_like(w[:, 0]) if b is None else b) for w, b, _, _ in layers]
+
+
+def _bn_affine(layers):
+    """The host arrays of the layers' gamma and beta pointers (NULL where a layer has none)."""
+    return _ptr_array([g for _, _, g, _ in layers]), _ptr_array([bt for _, _, _, bt in layers])
+
+
+def _bn_eps(name, eps, layers):
+    if len(eps) != len(layers) or not all(float(e) > 0 for e in eps):
+        raise RuntimeError(f"{name}: one eps > 0 per layer")
+    return (ctypes.c_float * len(eps))(*[float(e) for e in eps])
+
+
+def _bn_grads(layers, dev):
+    """One gradient buffer per parameter that is there -> ([(dW, db or None, dgamma or None, dbeta or None), ...], the four host arrays of
+    their pointers)."""
+    d_layers = [tuple(None if t is None else _grad_empty(tuple(t.shape), torch.float32, dev) for t in layer) for layer in layers]
+    return d_layers, [_ptr_array([d[i] for d in d_layers]) for i in range(4)]
 
 
 class HipBackend:
@@ -1705,8 +1787,8 @@ class HipBackend:
         weight gradients are the dense sums with the padded points' terms left out).  The indices of live points must point at
         live rows of p2.  Other list widths: the dense kernel plus masking (padded rows of p1 and p2 replaced by zeros and padded
         rows of idx by 0 before the call, out masked after it), same results."""
-        ia, ib = idx if isinstance(idx, (tuple, list)) else (idx, None)
-        kernel_lists = ia.shape[-1] + (0 if ib is None else ib.shape[-1]) == 64
+        ia, ib, nb = _two_lists(idx)
+        kernel_lists = nb == 64
         if lengths is not None and kernel_lists:
             lens = lengths_tensor(lengths, p1.shape[0], p1.shape[1], p1.device)
             if not grad.wants_grad(p1, p2, w1, b1, w2, b2, w3, b3):
@@ -1740,8 +1822,8 @@ class HipBackend:
         gradients of p1 are zero on padded rows, whose values and index rows are never read.  -> (out, bn, var, count) with count the
         live points (one int32 on the device; the statistics' rows are 64 * count).  The indices of live points must point at live
         rows of p2."""
-        ia, ib = idx if isinstance(idx, (tuple, list)) else (idx, None)
-        if ia.shape[-1] + (0 if ib is None else ib.shape[-1]) != 64:
+        ia, ib, nb = _two_lists(idx)
+        if nb != 64:
             raise ValueError("fusion_bn: the batch-statistics kernels take 64 neighbours per point (2 x 32 or one list of 64)")
         lens = lengths_tensor(lengths, p1.shape[0], p1.shape[1], p1.device)
         return _FusionBNFn.apply(self, float(eps), ia.contiguous(), None if ib is None else ib.contiguous(), lens, p1, p2, *conv, *affine)
@@ -1758,7 +1840,6 @@ class HipBackend:
         p1, p2 = p1.contiguous(), p2.contiguous()
         conv = [t.detach().contiguous() for t in conv]
         B, N, _ = p1.shape
-        ia, ib = idx if isinstance(idx, (tuple, list)) else (idx, None)
         bn = torch.empty((lib.mcp_fusion_bn_floats(),), dtype=torch.float32, device=p1.device)
         at = 0
         for c, (g, b) in zip((64, 64, 128), zip(affine[0::2], affine[1::2])):
@@ -1769,21 +1850,15 @@ class HipBackend:
         out = torch.empty((B, N, 3), dtype=torch.float32, device=p1.device)
         need = lib.mcp_fusion_bn_workspace_bytes(B, N)
         ws = torch.empty((need,), dtype=torch.uint8, device=p1.device)
+        keep = () if saved is None else (_lib.iptr(saved[0]), _lib.fptr(saved[1]), _lib.fptr(saved[2]))
         if lengths is not None:
             lens = lengths_tensor(lengths, B, N, p1.device)
             count = torch.empty((1,), dtype=torch.int32, device=p1.device)
-            keep = () if saved is None else (_lib.iptr(saved[0]), _lib.fptr(saved[1]), _lib.fptr(saved[2]))
-            _call("mcp_fusion_bn_forward_lengths" if saved is None else "mcp_fusion_bn_forward_save_lengths", p1, B, N, 64, _lib.fptr(p1), _lib.fptr(p2),
-                  _lib.iptr(ia), None if ib is None else _lib.iptr(ib), _lib.iptr(lens), *[_lib.fptr(t) for t in conv], float(eps), _lib.fptr(bn),
-                  _lib.fptr(var), _lib.fptr(out), _lib.iptr(count), *keep, ws.data_ptr(), need)
+            _call("mcp_fusion_bn_forward_lengths" if saved is None else "mcp_fusion_bn_forward_save_lengths", p1, *_fusion_lead(p1, p2, idx, lens, conv),
+                  float(eps), _lib.fptr(bn), _lib.fptr(var), _lib.fptr(out), _lib.iptr(count), *keep, ws.data_ptr(), need)
             return out, bn, var, count.view(())
-        if saved is None:
-            _call("mcp_fusion_bn_forward", p1, B, N, 64, _lib.fptr(p1), _lib.fptr(p2), _lib.iptr(ia), None if ib is None else _lib.iptr(ib),
-                  *[_lib.fptr(t) for t in conv], float(eps), _lib.fptr(bn), _lib.fptr(var), _lib.fptr(out), ws.data_ptr(), need)
-        else:
-            _call("mcp_fusion_bn_forward_save", p1, B, N, 64, _lib.fptr(p1), _lib.fptr(p2), _lib.iptr(ia), None if ib is None else _lib.iptr(ib),
-                  *[_lib.fptr(t) for t in conv], float(eps), _lib.fptr(bn), _lib.fptr(var), _lib.fptr(out), _lib.iptr(saved[0]), _lib.fptr(saved[1]),
-                  _lib.fptr(saved[2]), ws.data_ptr(), need)
+        _call("mcp_fusion_bn_forward" if saved is None else "mcp_fusion_bn_forward_save", p1, *_fusion_lead(p1, p2, idx, None, conv),
+              float(eps), _lib.fptr(bn), _lib.fptr(var), _lib.fptr(out), *keep, ws.data_ptr(), need)
         return out, bn, var
 
     BN_BATCH_CHANNELS = (32, 64, 128, 256)
@@ -1806,17 +1881,11 @@ class HipBackend:
         return y.reshape(x.shape), mean, var, count
 
     def _fusion_mlp(self, p1, p2, idx, w1, b1, w2, b2, w3, b3, lens=None):
-        p1, p2, w1, b1, w2, b2, w3, b3 = (t.contiguous() for t in (p1, p2, w1, b1, w2, b2, w3, b3))
+        p1, p2, *conv = (t.contiguous() for t in (p1, p2, w1, b1, w2, b2, w3, b3))
         B, N, _ = p1.shape
         out = torch.empty((B, N, 3), dtype=torch.float32, device=p1.device)
-        ia, ib = idx if isinstance(idx, (tuple, list)) else (idx, None)   # the two searches' lists as they are, or one (B,N,64) list
-        nb = ia.shape[-1] if ib is None else ia.shape[-1] + ib.shape[-1]
-        if lens is None:
-            _call("mcp_fusion", p1, B, N, nb, _lib.fptr(p1), _lib.fptr(p2), _lib.iptr(ia), None if ib is None else _lib.iptr(ib), _lib.fptr(w1),
-                  _lib.fptr(b1), _lib.fptr(w2), _lib.fptr(b2), _lib.fptr(w3), _lib.fptr(b3), _lib.fptr(out))
-        else:   # per-cloud lengths: the kernel of csrc/fusion_lengths.hip
-            _call("mcp_fusion_lengths", p1, B, N, nb, _lib.fptr(p1), _lib.fptr(p2), _lib.iptr(ia), None if ib is None else _lib.iptr(ib), _lib.iptr(lens),
-                  _lib.fptr(w1), _lib.fptr(b1), _lib.fptr(w2), _lib.fptr(b2), _lib.fptr(w3), _lib.fptr(b3), _lib.fptr(out))
+        # idx: the two searches' lists as they are, or one (B,N,64) list; per-cloud lengths: the kernel of csrc/fusion_lengths.hip
+        _call("mcp_fusion" if lens is None else "mcp_fusion_lengths", p1, *_fusion_lead(p1, p2, idx, lens, conv), _lib.fptr(out))
         return out
 
     def cross_pack(self, wpos, bpos, wmlp, bmlp):
@@ -1839,8 +1908,7 @@ class HipBackend:
         D = points1.shape[2]
         N2 = xyz2.shape[1]
         out = torch.empty((B, N1, D), dtype=torch.float32, device=points1.device)
-        ia, ib = idx if isinstance(idx, (tuple, list)) else (idx, None)   # the 16 + 16 halves as the searches produce them, or one list
-        k = ia.shape[-1] if ib is None else ia.shape[-1] + ib.shape[-1]
+        ia, ib, k = _two_lists(idx)   # the 16 + 16 halves as the searches produce them, or one list
         if bmap is not None and (shared & 4) and ib is None:
             raise RuntimeError("a shared index list needs the two-list form")
         _call("mcp_cross_volume", points1, B, N1, N2, D, k, _lib.fptr(xyz1), _lib.fptr(xyz2), _lib.fptr(points1),
@@ -1857,8 +1925,7 @@ class HipBackend:
             return self.cross_volume(x1.contiguous(), x2.contiguous(), f1.contiguous(), f2.contiguous(), i, pk, bmap=bmap, shared=shared)
         if bmap is not None:
             return fused(xyz1, xyz2, points1, points2, idx, wpos, bpos, wmlp, bmlp)
-        ia, ib = idx if isinstance(idx, (tuple, list)) else (idx, None)
-        k_total = ia.shape[-1] + (0 if ib is None else ib.shape[-1])   # the backward kernel is built for the 32-neighbour lists
+        ia, ib, k_total = _two_lists(idx)   # the backward kernel is built for the 32-neighbour lists
         if grad.wants_grad(xyz1, xyz2, points1, points2, wpos, bpos, wmlp, bmlp) and k_total == 32 and wmlp.shape[0] in (64, 128, 256):
             return _CrossFn.apply(self, ia.contiguous(), None if ib is None else ib.contiguous(), xyz1, xyz2, points1, points2, wpos, bpos, wmlp, bmlp)
         return grad.run(fused, lambda *a: grad.cross_twin(self.group_rows, *a), xyz1, xyz2, points1, points2, idx, wpos, bpos, wmlp, bmlp)
@@ -1883,12 +1950,10 @@ class HipBackend:
         out = torch.empty((B, M, widths[-1]), dtype=torch.float32, device=xyz.device)
         if B == 0 or M == 0:
             return out
-        wid = (ctypes.c_int * len(widths))(*widths)
         if row_bias is not None and tuple(row_bias.shape) != (B, M, widths[0]):
             raise RuntimeError(f"row_bias: expected {(B, M, widths[0])}, got {tuple(row_bias.shape)}")
-        _call("mcp_group_mlp", xyz, B, N, M, C, nsample, int(bool(use_xyz)), GROUP_MLP_POOLS[pool], len(widths), wid, _lib.fptr(xyz),
-              _lib.fptr(new_xyz), None if features is None else _lib.fptr(features), _lib.iptr(idx), None if ql is None else _lib.iptr(ql),
-              None if row_bias is None else _lib.fptr(row_bias), _lib.fptr(packed), _lib.fptr(out))
+        _call("mcp_group_mlp", xyz, *_group_lead((B, N, M, C, nsample), pool, use_xyz, _int_array(widths), xyz, new_xyz, features, idx, ql),
+              _opt(row_bias), _lib.fptr(packed), _lib.fptr(out))
         return out
 
     def group_mlp_grad(self, xyz, new_xyz, features, idx, weights, grad_out, pool="max", use_xyz=True, new_xyz_lengths=None, row_bias=None,
@@ -1897,27 +1962,16 @@ class HipBackend:
         deterministic scatters and one weight-gradient product per layer (mcp_group_mlp_grad) -> (grad_features (B,N,C), grad_xyz
         (B,N,3), grad_new_xyz (B,M,3), grad_row_bias (B,M,widths[0]) -- each None when not wanted or not part of the layer --, [dW_l],
         [db_l], the recomputed out or None).  Bit-reproducible; unsupported shapes raise _lib.Unsupported."""
-        B, N, _ = xyz.shape
-        M, nsample = new_xyz.shape[1], idx.shape[2]
-        C = 0 if features is None else features.shape[2]
+        dims, widths = _group_check("group_mlp_grad", xyz, new_xyz, features, idx, weights, use_xyz, grad_out=grad_out)
+        B, N, M, C, nsample = dims
         dev = xyz.device
-        widths = [int(w.shape[0]) for w, _ in weights]
-        if tuple(idx.shape[:2]) != (B, M):
-            raise RuntimeError(f"group_mlp_grad: idx {tuple(idx.shape)} does not match B={B}, M={M}")
-        if not group_mlp_grad_supported(C, widths, nsample, use_xyz) or int(weights[0][0].shape[1]) != C + (3 if use_xyz else 0):
-            raise _lib.Unsupported(f"group_mlp_grad: unsupported shape c={C} widths={widths} nsample={nsample}")
-        if tuple(grad_out.shape) != (B, M, widths[-1]):
-            raise RuntimeError(f"group_mlp_grad: grad_out {tuple(grad_out.shape)}, expected {(B, M, widths[-1])}")
         if row_bias is not None and tuple(row_bias.shape) != (B, M, widths[0]):
             raise RuntimeError(f"row_bias: expected {(B, M, widths[0])}, got {tuple(row_bias.shape)}")
-        if B == 0 or M == 0 or N == 0:
-            raise RuntimeError("group_mlp_grad: empty batch, cloud or centre list")
-        lib = _lib.load()
         ql = lengths_tensor(new_xyz_lengths, B, M, dev)
         grad_out = grad_out.contiguous()
         packed, _ = group_mlp_grad_pack_weights(weights, use_xyz)
-        wid = (ctypes.c_int * len(widths))(*widths)
-        need = lib.mcp_group_mlp_grad_workspace_bytes(B, M, C, nsample, int(bool(use_xyz)), len(widths), wid)
+        wid = _int_array(widths)
+        need = _lib.load().mcp_group_mlp_grad_workspace_bytes(B, M, C, nsample, int(bool(use_xyz)), len(widths), wid)
         if need == 0:
             raise _lib.Unsupported(f"group_mlp_grad: unsupported shape c={C} widths={widths} pairs={B * M * nsample}")
         want_features, want_xyz, want_new_xyz = bool(want_features) and C > 0, bool(want_xyz) and use_xyz, bool(want_new_xyz) and use_xyz
@@ -1931,12 +1985,9 @@ class HipBackend:
         d_b = [_grad_empty(tuple(b.shape), torch.float32, dev) for _, b in weights]
         out = _grad_empty((B, M, widths[-1]), torch.float32, dev) if recompute_out else None
         order, seg = _scatter_segments(idx.reshape(B, M * nsample), N) if (want_features or want_xyz) else (None, None)
-        gw = (ctypes.c_void_p * len(d_w))(*[_lib.fptr(t) for t in d_w])
-        gb = (ctypes.c_void_p * len(d_b))(*[_lib.fptr(t) for t in d_b])
-        opt = lambda t, ptr=_lib.fptr: None if t is None else ptr(t)
-        _call("mcp_group_mlp_grad", xyz, B, N, M, C, nsample, int(bool(use_xyz)), GROUP_MLP_POOLS[pool], len(widths), wid, _lib.fptr(xyz),
-              _lib.fptr(new_xyz), opt(features), _lib.iptr(idx), opt(ql, _lib.iptr), opt(row_bias), _lib.fptr(packed), _lib.fptr(grad_out),
-              opt(order, _lib.iptr), opt(seg, _lib.iptr), opt(d_feat), opt(d_xyz), opt(d_new), opt(d_rb), gw, gb, opt(out), ws.data_ptr(), need)
+        _call("mcp_group_mlp_grad", xyz, *_group_lead(dims, pool, use_xyz, wid, xyz, new_xyz, features, idx, ql), _opt(row_bias), _lib.fptr(packed),
+              _lib.fptr(grad_out), _opt(order, _lib.iptr), _opt(seg, _lib.iptr), _opt(d_feat), _opt(d_xyz), _opt(d_new), _opt(d_rb), _ptr_array(d_w),
+              _ptr_array(d_b), _opt(out), ws.data_ptr(), need)
         return d_feat, d_xyz, d_new, d_rb, d_w, d_b, out
 
     def group_mlp_layer(self, xyz, new_xyz, features, idx, weights, pool="max", use_xyz=True, new_xyz_lengths=None, row_bias=None):
@@ -1944,11 +1995,11 @@ class HipBackend:
         the parameters in the graph); arguments as group_mlp.  Without a wanted gradient it is group_mlp on a pack of `weights`; with
         one it is an autograd function -- mcp_group_mlp forward, mcp_group_mlp_grad backward -- that returns gradients for xyz,
         new_xyz, features, row_bias and every W and b, each only when needed, and keeps only its inputs."""
-        flat = [t for pair in weights for t in pair]
+        flat = _flat(weights)
         if not grad.wants_grad(xyz, new_xyz, features, row_bias, *flat):
             packed, widths = group_mlp_pack_weights([(w.detach(), b.detach()) for w, b in weights], use_xyz)
-            det = lambda t: None if t is None else t.detach()
-            return self._group_mlp(xyz.detach(), new_xyz.detach(), det(features), idx, packed, widths, pool, use_xyz, new_xyz_lengths, det(row_bias))
+            xyz, new_xyz, features, row_bias = [_det(t, False) for t in (xyz, new_xyz, features, row_bias)]
+            return self._group_mlp(xyz, new_xyz, features, idx, packed, widths, pool, use_xyz, new_xyz_lengths, row_bias)
         B, M = new_xyz.shape[0], new_xyz.shape[1]
         C = 0 if features is None else features.shape[2]
         if not group_mlp_grad_supported(C, [int(w.shape[0]) for w, _ in weights], idx.shape[2], use_xyz):
@@ -1964,19 +2015,10 @@ class HipBackend:
         1e-10), normalised) or "given" (w3 (B,n,3) as it is; dist may be None).  A slot with dist = +inf weighs exactly 0 under the
         two computed rules.  unknown_lengths (forms: lengths_tensor): rows at or beyond the length give zeros and are never read.
         Inference only (no gradient); unsupported shapes raise _lib.Unsupported."""
-        B, m, C2 = known_feats.shape
-        n = idx.shape[1]
-        C1 = 0 if skip is None else skip.shape[2]
-        widths = [int(w) for w in widths]
-        code = FP_MLP_RULES[rule]
-        if tuple(idx.shape) != (B, n, 3) or (skip is not None and tuple(skip.shape[:2]) != (B, n)):
-            raise RuntimeError(f"fp_mlp: idx {tuple(idx.shape)} / skip do not match B={B}, n={n}")
-        for name, t in (("w3", w3),) if code == 0 else (("dist", dist),):
-            if t is None or tuple(t.shape) != (B, n, 3):
-                raise RuntimeError(f"fp_mlp: rule {rule!r} needs {name} of shape {(B, n, 3)}")
-        if not fp_mlp_supported(C2, C1, widths):
-            raise _lib.Unsupported(f"fp_mlp: unsupported shape c2={C2} c1={C1} widths={widths}")
-        if packed.numel() != _lib.load().mcp_fp_mlp_packed_floats(C2, C1, len(widths), (ctypes.c_int * len(widths))(*widths)):
+        dims, widths = _fp_check("fp_mlp", known_feats, skip, idx, dist, rule, w3, None, widths=[int(w) for w in widths])
+        B, n, m, C2, C1, _ = dims
+        wid = _int_array(widths)
+        if packed.numel() != _lib.load().mcp_fp_mlp_packed_floats(C2, C1, len(widths), wid):
             raise RuntimeError("fp_mlp: the packed image was built for another shape")
         ul = lengths_tensor(unknown_lengths, B, n, known_feats.device)
         out = torch.empty((B, n, widths[-1]), dtype=torch.float32, device=known_feats.device)
@@ -1984,10 +2026,7 @@ class HipBackend:
             return out
         if m == 0:
             raise RuntimeError("fp_mlp: the known cloud is empty")
-        wid = (ctypes.c_int * len(widths))(*widths)
-        _call("mcp_fp_mlp", known_feats, B, n, m, C2, C1, code, len(widths), wid, _lib.fptr(known_feats),
-              None if skip is None or C1 == 0 else _lib.fptr(skip), _lib.iptr(idx), None if code == 0 else _lib.fptr(dist),
-              _lib.fptr(w3) if code == 0 else None, None if ul is None else _lib.iptr(ul), _lib.fptr(packed), _lib.fptr(out))
+        _call("mcp_fp_mlp", known_feats, *_fp_lead(dims, wid, known_feats, skip, idx, dist, w3, ul, packed), _lib.fptr(out))
         return out
 
     def fp_mlp_grad(self, known_feats, skip, idx, dist, weights, grad_out, rule="pointnet2", w3=None, unknown_lengths=None, want_known=True,
@@ -1995,29 +2034,14 @@ class HipBackend:
         """Backward of fp_mlp for weights = [(W, b), ...] (folded, fp32) and grad_out (B,n,widths[-1]) in one kernel launch plus the
         deterministic scatter and one weight-gradient product per layer (mcp_fp_mlp_grad) -> (grad_known_feats (B,m,C2) or None,
         grad_skip (B,n,C1) or None, [dW_l], [db_l], the recomputed out or None).  Bit-reproducible; unsupported shapes raise."""
-        B, m, C2 = known_feats.shape
-        n = idx.shape[1]
-        C1 = 0 if skip is None else skip.shape[2]
-        code = FP_MLP_RULES[rule]
+        dims, widths = _fp_check("fp_mlp_grad", known_feats, skip, idx, dist, rule, w3, weights, grad_out=grad_out)
+        B, n, m, C2, C1, _ = dims
         dev = known_feats.device
-        if tuple(idx.shape) != (B, n, 3) or (skip is not None and tuple(skip.shape[:2]) != (B, n)):
-            raise RuntimeError(f"fp_mlp_grad: idx {tuple(idx.shape)} / skip do not match B={B}, n={n}")
-        for name, t in (("w3", w3),) if code == 0 else (("dist", dist),):
-            if t is None or tuple(t.shape) != (B, n, 3):
-                raise RuntimeError(f"fp_mlp_grad: rule {rule!r} needs {name} of shape {(B, n, 3)}")
-        widths = [int(w.shape[0]) for w, _ in weights]
-        if not fp_mlp_grad_supported(C2, C1, widths) or int(weights[0][0].shape[1]) != C2 + C1:
-            raise _lib.Unsupported(f"fp_mlp_grad: unsupported shape c2={C2} c1={C1} widths={widths}")
-        if tuple(grad_out.shape) != (B, n, widths[-1]):
-            raise RuntimeError(f"fp_mlp_grad: grad_out {tuple(grad_out.shape)}, expected {(B, n, widths[-1])}")
-        if B == 0 or n == 0 or m == 0:
-            raise RuntimeError("fp_mlp_grad: empty batch, unknown or known cloud")
-        lib = _lib.load()
         ul = lengths_tensor(unknown_lengths, B, n, dev)
         grad_out = grad_out.contiguous()
         packed, _ = fp_mlp_grad_pack_weights(weights, C2)
-        wid = (ctypes.c_int * len(widths))(*widths)
-        need = lib.mcp_fp_mlp_grad_workspace_bytes(B, n, C2, C1, len(widths), wid)
+        wid = _int_array(widths)
+        need = _lib.load().mcp_fp_mlp_grad_workspace_bytes(B, n, C2, C1, len(widths), wid)
         if need == 0:
             raise _lib.Unsupported(f"fp_mlp_grad: unsupported shape c2={C2} c1={C1} widths={widths} rows={B * n}")
         ws = _grad_empty((need,), torch.uint8, dev)
@@ -2027,13 +2051,8 @@ class HipBackend:
         d_b = [_grad_empty(tuple(b.shape), torch.float32, dev) for _, b in weights]
         out = _grad_empty((B, n, widths[-1]), torch.float32, dev) if recompute_out else None
         order, seg = _scatter_segments(idx, m) if want_known else (None, None)
-        gw = (ctypes.c_void_p * len(d_w))(*[_lib.fptr(t) for t in d_w])
-        gb = (ctypes.c_void_p * len(d_b))(*[_lib.fptr(t) for t in d_b])
-        _call("mcp_fp_mlp_grad", known_feats, B, n, m, C2, C1, code, len(widths), wid, _lib.fptr(known_feats),
-              None if C1 == 0 else _lib.fptr(skip), _lib.iptr(idx), None if code == 0 else _lib.fptr(dist), _lib.fptr(w3) if code == 0 else None,
-              None if ul is None else _lib.iptr(ul), _lib.fptr(packed), _lib.fptr(grad_out), None if order is None else _lib.iptr(order),
-              None if seg is None else _lib.iptr(seg), None if d_known is None else _lib.fptr(d_known), None if d_skip is None else _lib.fptr(d_skip),
-              gw, gb, None if out is None else _lib.fptr(out), ws.data_ptr(), need)
+        _call("mcp_fp_mlp_grad", known_feats, *_fp_lead(dims, wid, known_feats, skip, idx, dist, w3, ul, packed), _lib.fptr(grad_out),
+              _opt(order, _lib.iptr), _opt(seg, _lib.iptr), _opt(d_known), _opt(d_skip), _ptr_array(d_w), _ptr_array(d_b), _opt(out), ws.data_ptr(), need)
         return d_known, d_skip, d_w, d_b, out
 
     def fp_mlp_layer(self, known_feats, skip, idx, dist, weights, rule="pointnet2", w3=None, unknown_lengths=None):
@@ -2041,7 +2060,7 @@ class HipBackend:
         keeps the parameters in the graph); arguments as fp_mlp.  Without a wanted gradient it is fp_mlp on a pack of `weights`;
         with one it is an autograd function -- mcp_fp_mlp forward, mcp_fp_mlp_grad backward -- that returns gradients for
         known_feats, skip and every W and b, and keeps only its inputs."""
-        flat = [t for pair in weights for t in pair]
+        flat = _flat(weights)
         if not grad.wants_grad(known_feats, skip, *flat):
             packed, widths = fp_mlp_pack_weights([(w.detach(), b.detach()) for w, b in weights], known_feats.shape[-1])
             return self.fp_mlp(known_feats.detach(), None if skip is None else skip.detach(), idx, dist, packed, widths, rule=rule, w3=w3,
@@ -2050,50 +2069,26 @@ class HipBackend:
         ul = lengths_tensor(unknown_lengths, B, n, known_feats.device)
         return _FpMlpLayerFn.apply(self, rule, idx.contiguous(), dist, w3, ul, known_feats, skip, *flat)
 
-    def _fp_mlp_bn_check(self, name, known_feats, skip, idx, dist, layers, rule, w3):
-        B, m, C2 = known_feats.shape
-        n = idx.shape[1]
-        C1 = 0 if skip is None else skip.shape[2]
-        code = FP_MLP_RULES[rule]
-        if tuple(idx.shape) != (B, n, 3) or (skip is not None and tuple(skip.shape[:2]) != (B, n)):
-            raise RuntimeError(f"{name}: idx {tuple(idx.shape)} / skip do not match B={B}, n={n}")
-        for what, t in (("w3", w3),) if code == 0 else (("dist", dist),):
-            if t is None or tuple(t.shape) != (B, n, 3):
-                raise RuntimeError(f"{name}: rule {rule!r} needs {what} of shape {(B, n, 3)}")
-        widths = [int(l[0].shape[0]) for l in layers]
-        if not fp_mlp_bn_supported(C2, C1, widths) or int(layers[0][0].shape[1]) != C2 + C1:
-            raise _lib.Unsupported(f"{name}: unsupported shape c2={C2} c1={C1} widths={widths}")
-        for (w, b, gamma, beta), k, o in zip(layers, [C2 + C1, *widths[:-1]], widths):
-            if tuple(w.shape) != (o, k) or any(t is not None and tuple(t.shape) != (o,) for t in (b, gamma, beta)):
-                raise RuntimeError(f"{name}: expected W {(o, k)} and b, gamma, beta {(o,)}")
-        if B == 0 or n == 0 or m == 0:
-            raise RuntimeError(f"{name}: empty batch, unknown or known cloud")
-        return B, n, m, C2, C1, code, widths
-
     def fp_mlp_bn_forward(self, known_feats, skip, idx, dist, layers, eps, rule="pointnet2", w3=None, unknown_lengths=None):
         """The feature-propagation layer with batch statistics (mcp_fp_mlp_bn_forward): arguments as fp_mlp, layers = [(W (out, in),
         b or None, gamma or None, beta or None), ...] fp32, eps one float per layer -> (out (B,n,widths[-1]), [mean_l], [biased
         var_l], [rstd_l], count (1,) int32: the live rows, on the device).  Padded rows give zeros and enter no statistic."""
-        B, n, m, C2, C1, code, widths = self._fp_mlp_bn_check("fp_mlp_bn_forward", known_feats, skip, idx, dist, layers, rule, w3)
-        if len(eps) != len(layers) or not all(float(e) > 0 for e in eps):
-            raise RuntimeError("fp_mlp_bn_forward: one eps > 0 per layer")
+        dims, widths = _fp_check("fp_mlp_bn_forward", known_feats, skip, idx, dist, rule, w3, layers)
+        B, n, m, C2, C1, _ = dims
+        eps = _bn_eps("fp_mlp_bn_forward", eps, layers)
         dev = known_feats.device
-        lib = _lib.load()
         ul = lengths_tensor(unknown_lengths, B, n, dev)
-        packed, _ = fp_mlp_pack_weights([(w, torch.zeros_like(w[:, 0]) if b is None else b) for w, b, _, _ in layers], C2)
-        wid = (ctypes.c_int * len(widths))(*widths)
-        need = lib.mcp_fp_mlp_bn_workspace_bytes(B, n, C2, C1, len(widths), wid, 0)
+        packed, _ = fp_mlp_pack_weights(_bn_pairs(layers), C2)
+        wid = _int_array(widths)
+        need = _lib.load().mcp_fp_mlp_bn_workspace_bytes(B, n, C2, C1, len(widths), wid, 0)
         if need == 0:
             raise _lib.Unsupported(f"fp_mlp_bn_forward: unsupported shape c2={C2} c1={C1} widths={widths} rows={B * n}")
         ws = _grad_empty((need,), torch.uint8, dev)
         out = _grad_empty((B, n, widths[-1]), torch.float32, dev)
         mean, var, rstd = ([_grad_empty((o,), torch.float32, dev) for o in widths] for _ in range(3))
         count = _grad_empty((1,), torch.int32, dev)
-        _call("mcp_fp_mlp_bn_forward", known_feats, B, n, m, C2, C1, code, len(widths), wid, _lib.fptr(known_feats),
-              None if C1 == 0 else _lib.fptr(skip), _lib.iptr(idx), None if code == 0 else _lib.fptr(dist), _lib.fptr(w3) if code == 0 else None,
-              None if ul is None else _lib.iptr(ul), _lib.fptr(packed), _ptr_array([g for _, _, g, _ in layers]), _ptr_array([bt for _, _, _, bt in layers]),
-              (ctypes.c_float * len(eps))(*[float(e) for e in eps]), _lib.fptr(out), _ptr_array(mean), _ptr_array(var), _ptr_array(rstd),
-              _lib.iptr(count), ws.data_ptr(), need)
+        _call("mcp_fp_mlp_bn_forward", known_feats, *_fp_lead(dims, wid, known_feats, skip, idx, dist, w3, ul, packed), *_bn_affine(layers), eps,
+              _lib.fptr(out), _ptr_array(mean), _ptr_array(var), _ptr_array(rstd), _lib.iptr(count), ws.data_ptr(), need)
         return out, mean, var, rstd, count
 
     def fp_mlp_bn_backward(self, known_feats, skip, idx, dist, layers, mean, rstd, grad_out, rule="pointnet2", w3=None, unknown_lengths=None,
@@ -2101,30 +2096,25 @@ class HipBackend:
         """Backward of fp_mlp_bn_forward (mcp_fp_mlp_bn_backward) from the forward's inputs, its per-layer (mean, rstd) and grad_out
         (B,n,widths[-1]) -> (grad_known_feats (B,m,C2) or None, grad_skip (B,n,C1) or None, [(dW, db or None, dgamma or None, dbeta
         or None), ...]; a parameter that is None gets None).  Bit-reproducible; unsupported shapes raise."""
-        B, n, m, C2, C1, code, widths = self._fp_mlp_bn_check("fp_mlp_bn_backward", known_feats, skip, idx, dist, layers, rule, w3)
-        if tuple(grad_out.shape) != (B, n, widths[-1]):
-            raise RuntimeError(f"fp_mlp_bn_backward: grad_out {tuple(grad_out.shape)}, expected {(B, n, widths[-1])}")
+        dims, widths = _fp_check("fp_mlp_bn_backward", known_feats, skip, idx, dist, rule, w3, layers)
+        B, n, m, C2, C1, _ = dims
+        _check_grad_out("fp_mlp_bn_backward", grad_out, (B, n, widths[-1]))
         dev = known_feats.device
-        lib = _lib.load()
         ul = lengths_tensor(unknown_lengths, B, n, dev)
         grad_out = grad_out.contiguous()
-        packed, _ = fp_mlp_grad_pack_weights([(w, torch.zeros_like(w[:, 0]) if b is None else b) for w, b, _, _ in layers], C2)
-        wid = (ctypes.c_int * len(widths))(*widths)
-        need = lib.mcp_fp_mlp_bn_workspace_bytes(B, n, C2, C1, len(widths), wid, 1)
+        packed, _ = fp_mlp_grad_pack_weights(_bn_pairs(layers), C2)
+        wid = _int_array(widths)
+        need = _lib.load().mcp_fp_mlp_bn_workspace_bytes(B, n, C2, C1, len(widths), wid, 1)
         if need == 0:
             raise _lib.Unsupported(f"fp_mlp_bn_backward: unsupported shape c2={C2} c1={C1} widths={widths} rows={B * n}")
         ws = _grad_empty((need,), torch.uint8, dev)
         d_known = _grad_empty((B, m, C2), torch.float32, dev) if want_known else None
         d_skip = _grad_empty((B, n, C1), torch.float32, dev) if C1 else None
-        like = lambda t: None if t is None else _grad_empty(tuple(t.shape), torch.float32, dev)
-        d_layers = [tuple(like(t) for t in layer) for layer in layers]
+        d_layers, d_arrays = _bn_grads(layers, dev)
         order, seg = _scatter_segments(idx, m) if want_known else (None, None)
-        _call("mcp_fp_mlp_bn_backward", known_feats, B, n, m, C2, C1, code, len(widths), wid, _lib.fptr(known_feats),
-              None if C1 == 0 else _lib.fptr(skip), _lib.iptr(idx), None if code == 0 else _lib.fptr(dist), _lib.fptr(w3) if code == 0 else None,
-              None if ul is None else _lib.iptr(ul), _lib.fptr(packed), _ptr_array([g for _, _, g, _ in layers]), _ptr_array([bt for _, _, _, bt in layers]),
-              _ptr_array(list(mean)), _ptr_array(list(rstd)), _lib.fptr(grad_out), None if order is None else _lib.iptr(order),
-              None if seg is None else _lib.iptr(seg), None if d_known is None else _lib.fptr(d_known), None if d_skip is None else _lib.fptr(d_skip),
-              *[_ptr_array([d[i] for d in d_layers]) for i in range(4)], ws.data_ptr(), need)
+        _call("mcp_fp_mlp_bn_backward", known_feats, *_fp_lead(dims, wid, known_feats, skip, idx, dist, w3, ul, packed), *_bn_affine(layers),
+              _ptr_array(mean), _ptr_array(rstd), _lib.fptr(grad_out), _opt(order, _lib.iptr), _opt(seg, _lib.iptr), _opt(d_known), _opt(d_skip),
+              *d_arrays, ws.data_ptr(), need)
         return d_known, d_skip, d_layers
 
     def fp_mlp_bn_layer(self, known_feats, skip, idx, dist, layers, rule="pointnet2", w3=None, unknown_lengths=None):
@@ -2135,52 +2125,31 @@ class HipBackend:
         a wanted gradient (the caller's running statistics need the batch statistics either way)."""
         B, n = idx.shape[0], idx.shape[1]
         ul = lengths_tensor(unknown_lengths, B, n, known_feats.device)
-        flat = [t for layer in layers for t in layer[:4]]
+        flat = _flat(layer[:4] for layer in layers)
         out, *rest = _FpMlpBnLayerFn.apply(self, rule, idx.contiguous(), dist, w3, ul, tuple(float(layer[4]) for layer in layers), known_feats, skip, *flat)
-        return out, list(zip(rest[0:-1:2], rest[1:-1:2])), rest[-1]
-
-    def _group_mlp_bn_check(self, name, xyz, new_xyz, features, idx, layers, use_xyz):
-        B, N, _ = xyz.shape
-        M, nsample = new_xyz.shape[1], idx.shape[2]
-        C = 0 if features is None else features.shape[2]
-        if tuple(idx.shape[:2]) != (B, M) or (features is not None and tuple(features.shape[:2]) != (B, N)):
-            raise RuntimeError(f"{name}: idx {tuple(idx.shape)} / features do not match B={B}, N={N}, M={M}")
-        widths = [int(l[0].shape[0]) for l in layers]
-        cin = C + (3 if use_xyz else 0)
-        if not group_mlp_bn_supported(C, widths, nsample, use_xyz) or int(layers[0][0].shape[1]) != cin:
-            raise _lib.Unsupported(f"{name}: unsupported shape c={C} widths={widths} nsample={nsample}")
-        for (w, b, gamma, beta), k, o in zip(layers, [cin, *widths[:-1]], widths):
-            if tuple(w.shape) != (o, k) or any(t is not None and tuple(t.shape) != (o,) for t in (b, gamma, beta)):
-                raise RuntimeError(f"{name}: expected W {(o, k)} and b, gamma, beta {(o,)}")
-        if B == 0 or N == 0 or M == 0:
-            raise RuntimeError(f"{name}: empty batch, cloud or centre list")
-        return B, N, M, C, nsample, widths
+        return out, _pairs(rest[:-1]), rest[-1]
 
     def group_mlp_bn_forward(self, xyz, new_xyz, features, idx, layers, eps, pool="max", use_xyz=True, new_xyz_lengths=None):
         """The set-abstraction layer with batch statistics (mcp_group_mlp_bn_forward): arguments as group_mlp, layers = [(W (out, in),
         b or None, gamma or None, beta or None), ...] fp32 with W_1's position columns first, eps one float per layer -> (out
         (B,M,widths[-1]), [mean_l], [biased var_l], [rstd_l], count (1,) int32: the live (centre, slot) pairs, on the device).
         Padded centres give zeros and enter no statistic."""
-        B, N, M, C, nsample, widths = self._group_mlp_bn_check("group_mlp_bn_forward", xyz, new_xyz, features, idx, layers, use_xyz)
-        if len(eps) != len(layers) or not all(float(e) > 0 for e in eps):
-            raise RuntimeError("group_mlp_bn_forward: one eps > 0 per layer")
+        dims, widths = _group_check("group_mlp_bn_forward", xyz, new_xyz, features, idx, layers, use_xyz)
+        B, N, M, C, nsample = dims
+        eps = _bn_eps("group_mlp_bn_forward", eps, layers)
         dev = xyz.device
-        lib = _lib.load()
         ql = lengths_tensor(new_xyz_lengths, B, M, dev)
-        packed, _ = group_mlp_bn_pack_weights([(w, torch.zeros_like(w[:, 0]) if b is None else b) for w, b, _, _ in layers], use_xyz)
-        wid = (ctypes.c_int * len(widths))(*widths)
-        need = lib.mcp_group_mlp_bn_workspace_bytes(B, M, C, nsample, int(bool(use_xyz)), len(widths), wid, 0)
+        packed, _ = group_mlp_bn_pack_weights(_bn_pairs(layers), use_xyz)
+        wid = _int_array(widths)
+        need = _lib.load().mcp_group_mlp_bn_workspace_bytes(B, M, C, nsample, int(bool(use_xyz)), len(widths), wid, 0)
         if need == 0:
             raise _lib.Unsupported(f"group_mlp_bn_forward: unsupported shape c={C} widths={widths} pairs={B * M * nsample}")
         ws = _grad_empty((need,), torch.uint8, dev)
         out = _grad_empty((B, M, widths[-1]), torch.float32, dev)
         mean, var, rstd = ([_grad_empty((o,), torch.float32, dev) for o in widths] for _ in range(3))
         count = _grad_empty((1,), torch.int32, dev)
-        _call("mcp_group_mlp_bn_forward", xyz, B, N, M, C, nsample, int(bool(use_xyz)), GROUP_MLP_POOLS[pool], len(widths), wid, _lib.fptr(xyz),
-              _lib.fptr(new_xyz), None if features is None else _lib.fptr(features), _lib.iptr(idx), None if ql is None else _lib.iptr(ql),
-              _lib.fptr(packed), _ptr_array([g for _, _, g, _ in layers]), _ptr_array([bt for _, _, _, bt in layers]),
-              (ctypes.c_float * len(eps))(*[float(e) for e in eps]), _lib.fptr(out), _ptr_array(mean), _ptr_array(var), _ptr_array(rstd),
-              _lib.iptr(count), ws.data_ptr(), need)
+        _call("mcp_group_mlp_bn_forward", xyz, *_group_lead(dims, pool, use_xyz, wid, xyz, new_xyz, features, idx, ql), _lib.fptr(packed),
+              *_bn_affine(layers), eps, _lib.fptr(out), _ptr_array(mean), _ptr_array(var), _ptr_array(rstd), _lib.iptr(count), ws.data_ptr(), need)
         return out, mean, var, rstd, count
 
     def group_mlp_bn_backward(self, xyz, new_xyz, features, idx, layers, mean, rstd, grad_out, pool="max", use_xyz=True, new_xyz_lengths=None,
@@ -2189,16 +2158,15 @@ class HipBackend:
         grad_out (B,M,widths[-1]) -> (grad_features (B,N,C), grad_xyz (B,N,3), grad_new_xyz (B,M,3) -- each None when not wanted or not
         part of the layer --, [(dW, db or None, dgamma or None, dbeta or None), ...]; a parameter that is None gets None).
         Bit-reproducible; unsupported shapes raise."""
-        B, N, M, C, nsample, widths = self._group_mlp_bn_check("group_mlp_bn_backward", xyz, new_xyz, features, idx, layers, use_xyz)
-        if tuple(grad_out.shape) != (B, M, widths[-1]):
-            raise RuntimeError(f"group_mlp_bn_backward: grad_out {tuple(grad_out.shape)}, expected {(B, M, widths[-1])}")
+        dims, widths = _group_check("group_mlp_bn_backward", xyz, new_xyz, features, idx, layers, use_xyz)
+        B, N, M, C, nsample = dims
+        _check_grad_out("group_mlp_bn_backward", grad_out, (B, M, widths[-1]))
         dev = xyz.device
-        lib = _lib.load()
         ql = lengths_tensor(new_xyz_lengths, B, M, dev)
         grad_out = grad_out.contiguous()
-        packed, _ = group_mlp_bn_pack_weights([(w, torch.zeros_like(w[:, 0]) if b is None else b) for w, b, _, _ in layers], use_xyz)
-        wid = (ctypes.c_int * len(widths))(*widths)
-        need = lib.mcp_group_mlp_bn_workspace_bytes(B, M, C, nsample, int(bool(use_xyz)), len(widths), wid, 1)
+        packed, _ = group_mlp_bn_pack_weights(_bn_pairs(layers), use_xyz)
+        wid = _int_array(widths)
+        need = _lib.load().mcp_group_mlp_bn_workspace_bytes(B, M, C, nsample, int(bool(use_xyz)), len(widths), wid, 1)
         if need == 0:
             raise _lib.Unsupported(f"group_mlp_bn_backward: unsupported shape c={C} widths={widths} pairs={B * M * nsample}")
         want_features, want_xyz, want_new_xyz = bool(want_features) and C > 0, bool(want_xyz) and use_xyz, bool(want_new_xyz) and use_xyz
@@ -2206,15 +2174,11 @@ class HipBackend:
         d_feat = _grad_empty((B, N, C), torch.float32, dev) if want_features else None
         d_xyz = _grad_empty((B, N, 3), torch.float32, dev) if want_xyz else None
         d_new = _grad_empty((B, M, 3), torch.float32, dev) if want_new_xyz else None
-        like = lambda t: None if t is None else _grad_empty(tuple(t.shape), torch.float32, dev)
-        d_layers = [tuple(like(t) for t in layer) for layer in layers]
+        d_layers, d_arrays = _bn_grads(layers, dev)
         order, seg = _scatter_segments(idx.reshape(B, M * nsample), N) if (want_features or want_xyz) else (None, None)
-        opt = lambda t, ptr=_lib.fptr: None if t is None else ptr(t)
-        _call("mcp_group_mlp_bn_backward", xyz, B, N, M, C, nsample, int(bool(use_xyz)), GROUP_MLP_POOLS[pool], len(widths), wid, _lib.fptr(xyz),
-              _lib.fptr(new_xyz), opt(features), _lib.iptr(idx), opt(ql, _lib.iptr), _lib.fptr(packed), _ptr_array([g for _, _, g, _ in layers]),
-              _ptr_array([bt for _, _, _, bt in layers]), _ptr_array(list(mean)), _ptr_array(list(rstd)), _lib.fptr(grad_out),
-              opt(order, _lib.iptr), opt(seg, _lib.iptr), opt(d_feat), opt(d_xyz), opt(d_new),
-              *[_ptr_array([d[i] for d in d_layers]) for i in range(4)], ws.data_ptr(), need)
+        _call("mcp_group_mlp_bn_backward", xyz, *_group_lead(dims, pool, use_xyz, wid, xyz, new_xyz, features, idx, ql), _lib.fptr(packed),
+              *_bn_affine(layers), _ptr_array(mean), _ptr_array(rstd), _lib.fptr(grad_out), _opt(order, _lib.iptr), _opt(seg, _lib.iptr),
+              _opt(d_feat), _opt(d_xyz), _opt(d_new), *d_arrays, ws.data_ptr(), need)
         return d_feat, d_xyz, d_new, d_layers
 
     def group_mlp_bn_layer(self, xyz, new_xyz, features, idx, layers, pool="max", use_xyz=True, new_xyz_lengths=None):
@@ -2226,10 +2190,10 @@ class HipBackend:
         statistics either way)."""
         B, M = new_xyz.shape[0], new_xyz.shape[1]
         ql = lengths_tensor(new_xyz_lengths, B, M, xyz.device)
-        flat = [t for layer in layers for t in layer[:4]]
+        flat = _flat(layer[:4] for layer in layers)
         out, *rest = _GroupMlpBnLayerFn.apply(self, pool, bool(use_xyz), idx.contiguous(), ql, tuple(float(layer[4]) for layer in layers), xyz, new_xyz,
                                               features, *flat)
-        return out, list(zip(rest[0:-1:2], rest[1:-1:2])), rest[-1]
+        return out, _pairs(rest[:-1]), rest[-1]
 
     def ptblock_layer(self, xyz, q, k, v, idx, weights, packed=None):
         """TransformerBlock vector attention from the block's own weights (wd1,bd1,wd2,bd2,wg1,bg1,wg2,bg2); differentiable."""
