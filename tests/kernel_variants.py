@@ -21,7 +21,12 @@ ATTN_GRAD_COUNTS is the grid of query / key counts test_attention_grad_edges_gpu
 attention_wide_train_kernels() names the kernels one training forward + backward of the wide-head attention launches
 (attention_wide_grad.hip, 43 instantiations) and attention_wide_grad_launch() mirrors their tiles and stages; WIDE_GRAD_COUNTS,
 WIDE_GUARD_CASES and WIDE_TRAIN_CASES parametrise test_attention_wide_grad_edges_gpu.py.  EMD_GRAD_CASES and INTERP3_GRAD_CASES are
-the shapes of test_emd_interp3_grad_edges_gpu.py, each with the kernels it launches.  A plain module, imported by the tests."""
+the shapes of test_emd_interp3_grad_edges_gpu.py, each with the kernels it launches.
+
+primitive_launch() restates the host side of every C entry of the oldest units (pointnet2_ops.hip, interp3.hip, norm.hip: gathers,
+scatters, the 3-NN blend, the row normalisation) -- instantiation, grid, grid-stride rounds, the live items of the last round and of
+the last workgroup, with the alignment of the operands as an input; PRIMITIVE_CASES parametrises test_primitive_edges_gpu.py and
+test_primitive_variants_cpu.py holds it to the units' device assembly.  A plain module, imported by the tests."""
 
 def _cdiv(a, b):
     return (a + b - 1) // b
@@ -807,3 +812,259 @@ INTERP3_GRAD_CASES = ([dict(n=n, s=s, coincident=0, kernels=("interp3_weights_gr
 
 def emd_cases(kind):
     return [c for c in EMD_GRAD_CASES if c["kind"] == kind]
+
+
+# ---- index, blend and normalisation primitives (pointnet2_ops.hip, interp3.hip, norm.hip): the neighbour-row gathers, the scatters
+# that carry every coordinate and feature gradient, the 3-NN blend and the Crossformer's normalisation.  Two launch forms: a 1-D
+# grid-stride loop whose grid is capped (group_rows and everything channel-last), and one thread per point with the batch element
+# (and a chunk of PRIM_CCH channels) on the other grid axes (the channel-major entries of the reference API) ----
+MCP_OK, MCP_ERR_BAD_ARG, MCP_ERR_UNSUPPORTED = 0, 10001, 10002   # include/mocopci_hip.h:35-37
+PRIM_BLK = 256                                                # BLK, pointnet2_ops.hip:12, interp3.hip:10
+PRIM_CCH = 8                                                  # CCH, pointnet2_ops.hip:40
+PRIM_SUB = 8                                                  # NARROW_SUB, pointnet2_ops.hip:186; I3_SUB, interp3.hip:88
+PRIM_NN_TILE = 1024                                           # NN_TILE, pointnet2_ops.hip:335
+PRIM_CAP_8K, PRIM_CAP_16K, PRIM_CAP_MFA = 8192, 16384, 1 << 16
+PRIM_LN_ROWS, PRIM_LN_MAX_C = 4, 1024                         # one wave per row, four per workgroup: norm.hip:24, :68; :66
+PRIM_LN_PER = (1, 2, 4, 16)                                   # norm.hip:69-72
+
+
+def _prim_loop(kernel, items, per_wg, cap):
+    """A capped grid-stride launch: workgroup w takes items [w per_wg, (w + 1) per_wg) + r grid per_wg of round r."""
+    grid = min(_cdiv(min(items, 0x7fffffff), per_wg), cap)
+    per_round = grid * per_wg
+    rounds = _cdiv(items, per_round)
+    last_round = items - (rounds - 1) * per_round
+    return dict(kernel=kernel, grid=(grid,), items=items, per_wg=per_wg, cap=cap, rounds=rounds, last_round=last_round,
+                last_wg=(last_round - 1) % per_wg + 1)
+
+
+def _prim_blocks(kernel, points, b, c=None):
+    """One thread per point, PRIM_BLK per workgroup, no loop; c: the kernel walks chunks of PRIM_CCH channels on blockIdx.y."""
+    grid = (_cdiv(points, PRIM_BLK), b) if c is None else (_cdiv(points, PRIM_BLK), _cdiv(c, PRIM_CCH), b)
+    out = dict(kernel=kernel, grid=grid, items=points, per_wg=PRIM_BLK, cap=None, rounds=1, last_round=points,
+               last_wg=(points - 1) % PRIM_BLK + 1)
+    if c is not None:
+        out["last_chunk"] = (c - 1) % PRIM_CCH + 1
+    return out
+
+
+# which operands each entry tests for a 16-byte base (the route it takes when one is off: "scalar" twin or MCP_ERR_BAD_ARG)
+PRIM_ALIGNED_OPERANDS = {
+    "mcp_group_rows": ("points", "out"),                                   # pointnet2_ops.hip:475
+    "mcp_group_rows_add_leaky": ("points", "centre", "out"),               # :494
+    "mcp_group_rows_grad_sorted": ("grad_out", "grad_points"),             # :523
+    "mcp_interp3_apply": ("feat", "out"),                                  # interp3.hip:193
+    "mcp_interp3_apply_grad_sorted": ("grad_out", "feat", "grad_feat"),    # interp3.hip:161 (grad_w3), :168 (grad_feat)
+    "mcp_mfa_prepare": ("fea", "te_self", "te_partner", "scale", "shift", "x", "xn", "xr"),   # norm.hip:108
+}
+
+
+def primitive_launch(entry, aligned=True, off=None, **s):
+    """dict(status, launches) of one call of a C entry of the three units: the status the host returns (no launch unless MCP_OK) and, per
+    kernel in launch order, dict(kernel, grid, items, per_wg, cap, rounds = ceil(items / (grid x per_wg)), last_round = live items of
+    the last round, last_wg = live items of its last live workgroup), plus last_chunk (channels of the last blockIdx.y), tiles /
+    last_tile (three_nn) and registers / last_register (add_layernorm) where the kernel has them.  aligned=False: every operand the
+    host tests (PRIM_ALIGNED_OPERANDS) is off a 16-byte boundary; off=(names): only those.  Shape keywords are the C arguments."""
+    tested = PRIM_ALIGNED_OPERANDS.get(entry, ())
+    bad = set(tested if off is None and not aligned else off or ())
+    if bad - set(tested):
+        raise ValueError(f"{entry} does not test the alignment of {sorted(bad - set(tested))}")
+
+    def al(*names):
+        return not bad & set(names)
+
+    def ok(*launches):
+        return dict(status=MCP_OK, launches=list(launches))
+
+    def err(status):
+        return dict(status=status, launches=[])
+    if any(v <= 0 for k, v in s.items() if k not in ("want", "x_stride", "y_stride", "out_stride", "with_y")):
+        return err(MCP_ERR_BAD_ARG)                                         # MCP_CHECK_ARGS of every entry
+    g = s.get
+    if entry == "mcp_gather_points":                                        # pointnet2_ops.hip:424
+        return ok(_prim_blocks("gather_points_kernel", g("npoints"), g("b")))
+    if entry == "mcp_gather_points_grad":                                   # :432
+        return ok(_prim_blocks("gather_points_grad_kernel", g("npoints"), g("b")))
+    if entry == "mcp_group_points":                                         # :440-441
+        return ok(_prim_blocks("group_points_kernel", g("npoints") * g("nsample"), g("b"), g("c")))
+    if entry == "mcp_group_points_grad":                                    # :449-450
+        return ok(_prim_blocks("group_points_grad_kernel", g("npoints") * g("nsample"), g("b"), g("c")))
+    if entry == "mcp_group_points_grad_sorted":                             # :458: one thread per DESTINATION n
+        return ok(_prim_blocks("scatter_cm_sorted_kernel<false>", g("n"), g("b"), g("c")))
+    if entry == "mcp_three_interpolate_grad_sorted":                        # :466: destinations m
+        return ok(_prim_blocks("scatter_cm_sorted_kernel<true>", g("m"), g("b"), g("c")))
+    if entry == "mcp_three_interpolate":                                    # :585
+        return ok(_prim_blocks("three_interpolate_kernel", g("n"), g("b"), g("c")))
+    if entry == "mcp_three_interpolate_grad":                               # :593
+        return ok(_prim_blocks("three_interpolate_grad_kernel", g("n"), g("b"), g("c")))
+    if entry == "mcp_three_nn":                                             # :577; the tile walk :350-351
+        out = _prim_blocks("three_nn_kernel", g("n"), g("b"))
+        out.update(tiles=_cdiv(g("m"), PRIM_NN_TILE), last_tile=(g("m") - 1) % PRIM_NN_TILE + 1)
+        return ok(out)
+    if entry == "mcp_group_rows":                                           # :475-486
+        b, c, t = g("b"), g("c"), g("t")
+        if c % 4 == 0 and al("points", "out"):
+            return ok(_prim_loop("group_rows_kernel<HIP_vector_type<float, 4u>, 4>", b * t * (c // 4), PRIM_BLK, PRIM_CAP_8K))
+        return ok(_prim_loop("group_rows_kernel<float, 1>", b * t * c, PRIM_BLK, PRIM_CAP_8K))
+    if entry == "mcp_group_rows_add_leaky":                                 # :494-498
+        if g("c") % 4 or not al("points", "centre", "out"):
+            return err(MCP_ERR_BAD_ARG)
+        return ok(_prim_loop("group_rows_add_leaky_kernel", g("b") * g("s") * g("k") * (g("c") // 4), PRIM_BLK, PRIM_CAP_16K))
+    if entry == "mcp_group_rows_grad":                                      # :507-509
+        return ok(_prim_loop("group_rows_grad_kernel", g("b") * g("t") * g("c"), PRIM_BLK, PRIM_CAP_8K))
+    if entry == "mcp_group_rows_grad_sorted":                               # :516-531
+        b, n, c = g("b"), g("n"), g("c")
+        if c <= 4:                                                          # :516-518: NARROW_SUB lanes per row, whatever the alignment
+            return ok(_prim_loop("group_rows_grad_sorted_narrow_kernel", b * n, PRIM_BLK // PRIM_SUB, PRIM_CAP_16K))
+        vec4 = c % 4 == 0 and al("grad_out", "grad_points")                 # :523
+        return ok(_prim_loop(f"group_rows_grad_sorted_kernel<{'true' if vec4 else 'false'}>", b * n * (c // 4 if vec4 else c),
+                             PRIM_BLK, PRIM_CAP_16K))
+    if entry == "mcp_interp3_apply":                                        # interp3.hip:193-204
+        b, n, c = g("b"), g("n"), g("c")
+        if c % 4 == 0 and al("feat", "out"):
+            return ok(_prim_loop("interp3_apply_kernel<HIP_vector_type<float, 4u>, 4>", b * n * (c // 4), PRIM_BLK, PRIM_CAP_8K))
+        return ok(_prim_loop("interp3_apply_kernel<float, 1>", b * n * c, PRIM_BLK, PRIM_CAP_8K))
+    if entry == "mcp_interp3_apply_grad":                                   # interp3.hip:182-183
+        return ok(_prim_loop("interp3_apply_grad_kernel", g("b") * g("n") * g("c"), PRIM_BLK, PRIM_CAP_8K))
+    if entry == "mcp_interp3_apply_grad_sorted":                            # interp3.hip:155-176
+        b, n, sp, c, want = g("b"), g("n"), g("s"), g("c"), g("want", ("feat", "w"))
+        if not want:
+            return err(MCP_ERR_BAD_ARG)                                     # :155
+        launches = []
+        if "w" in want:                                                     # :160-163: I3_SUB lanes per (point, neighbour)
+            w = _prim_loop("interp3_grad_w_kernel", b * n * 3, PRIM_BLK // PRIM_SUB, PRIM_CAP_16K)
+            w["vec"] = int(c % 4 == 0 and al("grad_out", "feat"))
+            w["passes"] = _cdiv(c // 4 if w["vec"] else c, PRIM_SUB)        # :101, :106: strides of I3_SUB lanes over the row
+            launches.append(w)
+        if "feat" in want:                                                  # :168-174
+            vec4 = c % 4 == 0 and al("grad_out", "grad_feat")
+            launches.append(_prim_loop(f"interp3_grad_feat_sorted_kernel<{'true' if vec4 else 'false'}>", b * sp * (c // 4 if vec4 else c),
+                                       PRIM_BLK, PRIM_CAP_16K))
+        return ok(*launches)
+    if entry == "mcp_interp3_weights":                                      # interp3.hip:211
+        return ok(_prim_blocks("interp3_weights_kernel", g("n"), g("b")))
+    if entry == "mcp_interp3":                                              # interp3.hip:221-223: the search (knn.hip) is not mirrored here
+        return ok(_prim_blocks("interp3_weights_kernel", g("n"), g("b")), *primitive_launch("mcp_interp3_apply", aligned, off, **s)["launches"])
+    if entry == "mcp_add_layernorm":                                        # norm.hip:65-72
+        rows, c = g("rows"), g("c")
+        if g("x_stride", c) < c or g("out_stride", c) < c or (g("with_y", True) and g("y_stride", c) < c):
+            return err(MCP_ERR_BAD_ARG)                                     # :65
+        if c > PRIM_LN_MAX_C:
+            return err(MCP_ERR_UNSUPPORTED)                                 # :66
+        per = next(p for p in PRIM_LN_PER if c <= 64 * p)                   # :69-72
+        return ok(dict(kernel=f"add_layernorm_kernel<{per}>", grid=(_cdiv(rows, PRIM_LN_ROWS),), items=rows, per_wg=PRIM_LN_ROWS, cap=None,
+                       rounds=1, last_round=rows, last_wg=(rows - 1) % PRIM_LN_ROWS + 1,      # live waves of the last workgroup, :24-25
+                       per=per, registers=_cdiv(c, 64), last_register=(c - 1) % 64 + 1))       # live lanes of the last live register, :30-32
+    if entry == "mcp_mfa_prepare":                                          # norm.hip:107-113
+        if g("c") & 3:
+            return err(MCP_ERR_UNSUPPORTED)                                 # :107
+        if bad:
+            return err(MCP_ERR_BAD_ARG)                                     # :108-110
+        return ok(_prim_loop("mfa_prepare_kernel", g("rows") * g("n") * (g("c") // 4), 256, PRIM_CAP_MFA))
+    raise ValueError(f"{entry}: not an entry of the index, blend and normalisation units")
+
+
+def _pc(entry, edge, off=(), **kw):
+    """One case.  shape: the C arguments; off: operands placed 4 bytes past a 16-byte boundary; every other keyword is read by the test
+    of that entry (src: rows / points gathered from, data="real": random reals against the C oracle, segments="ops": (order, seg) from
+    ops._scatter_segments, grid: coordinates on a half-unit grid, coincident: dense points on sparse points)."""
+    extras = {k: kw.pop(k) for k in ("data", "segments", "grid", "coincident", "twice") if k in kw}
+    launch = primitive_launch(entry, aligned=not off, off=off, **kw)
+    return dict(entry=entry, shape=kw, off=tuple(off), status=launch["status"], kernels=tuple(l["kernel"] for l in launch["launches"]),
+                edge=edge, **extras)
+
+
+PRIM_PAST_8K_VEC = dict(b=3, t=10923, c=256)      # 2 097 216 float4 items: 64 past 8192 x 256
+PRIM_PAST_8K_SCALAR = dict(b=3, t=19973, c=35)    # 2 097 165 items: 13 past
+# thread-axis count x channels of the channel-major entries: every count and every c once, and (257, 9) together
+PRIM_CM_PAIRS = ((1, 1), (255, 7), (256, 8), (257, 9), (255, 17))
+_CM_SPLIT = {1: (1, 1), 255: (85, 3), 256: (32, 8), 257: (257, 1)}     # group_points: npoints x nsample
+
+PRIMITIVE_CASES = (
+    # -- channel-major entries: BLK -1 / 0 / +1 on the thread axis, CCH -1 / 0 / +1 and the third chunk's first channel on blockIdx.y --
+    [_pc(e, f"points={p},c={c}", b=3, c=c, n=37, npoints=p, **({"data": "real"} if (p, c) == (257, 9) and not e.endswith("grad") else {}))
+     for e in ("mcp_gather_points", "mcp_gather_points_grad") for p, c in PRIM_CM_PAIRS]
+    + [_pc(e, f"points={p},c={c}", b=3, c=c, n=37, npoints=_CM_SPLIT[p][0], nsample=_CM_SPLIT[p][1],
+           **({"data": "real"} if (p, c) == (257, 9) and not e.endswith("grad") else {}))
+       for e in ("mcp_group_points", "mcp_group_points_grad") for p, c in PRIM_CM_PAIRS]
+    + [_pc(e, f"points={p},c={c}", b=3, c=c, m=37, n=p, **({"data": "real"} if (p, c) == (257, 9) and not e.endswith("grad") else {}))
+       for e in ("mcp_three_interpolate", "mcp_three_interpolate_grad") for p, c in PRIM_CM_PAIRS]
+    + [_pc("mcp_group_points_grad_sorted", f"destinations={p},c={c}", b=3, c=c, n=p, t=700) for p, c in PRIM_CM_PAIRS]
+    + [_pc("mcp_group_points_grad_sorted", "the oracle's loop on real data", b=3, c=9, n=257, t=700, data="real"),
+       _pc("mcp_group_points_grad_sorted", "segments from ops._scatter_segments", b=3, c=9, n=257, t=700, segments="ops")]
+    + [_pc("mcp_three_interpolate_grad_sorted", f"destinations={p},c={c}", b=3, c=c, n=233, m=p) for p, c in PRIM_CM_PAIRS]
+    + [_pc("mcp_three_interpolate_grad_sorted", "the oracle's loop on real data", b=3, c=9, n=233, m=257, data="real"),
+       _pc("mcp_three_interpolate_grad_sorted", "segments from ops._scatter_segments", b=3, c=9, n=233, m=257, segments="ops")]
+    # -- group_rows / interp3_apply: both routes, both reasons for the scalar one, one item, a second round of a few items --
+    + [_pc("mcp_group_rows", "one item", b=1, n=1, c=1, t=1)]
+    + [_pc("mcp_group_rows", f"c={c}", b=3, n=50, c=c, t=70) for c in (1, 3, 4, 5, 256)]
+    + [_pc("mcp_group_rows", f"c=64, {o} off 16 bytes", off=(o,), b=3, n=50, c=64, t=70) for o in ("points", "out")]
+    + [_pc("mcp_group_rows", "second round, float4", n=50, twice=True, **PRIM_PAST_8K_VEC),
+       _pc("mcp_group_rows", "second round, scalar", n=50, twice=True, **PRIM_PAST_8K_SCALAR)]
+    + [_pc("mcp_interp3_apply", "one item", b=1, n=1, s=3, c=1)]
+    + [_pc("mcp_interp3_apply", f"c={c}", b=3, n=70, s=50, c=c) for c in (1, 3, 4, 5, 256)]
+    + [_pc("mcp_interp3_apply", f"c=64, {o} off 16 bytes", off=(o,), b=3, n=70, s=50, c=64) for o in ("feat", "out")]
+    + [_pc("mcp_interp3_apply", "second round, float4", b=3, n=10923, s=50, c=256, twice=True),
+       _pc("mcp_interp3_apply", "second round, scalar", b=3, n=19973, s=50, c=35, twice=True)]
+    # -- group_rows_add_leaky: float4 only; the refusals --
+    + [_pc("mcp_group_rows_add_leaky", f"c={c}", b=3, n=40, c=c, s=7, k=5) for c in (4, 24, 256)]
+    + [_pc("mcp_group_rows_add_leaky", "second round", b=1, n=50, c=256, s=8193, k=8, twice=True),
+       _pc("mcp_group_rows_add_leaky", "c % 4 != 0 is refused", b=3, n=40, c=6, s=7, k=5)]
+    + [_pc("mcp_group_rows_add_leaky", f"{o} off 16 bytes is refused", off=(o,), b=3, n=40, c=64, s=7, k=5) for o in ("points", "centre", "out")]
+    # -- group_rows_grad_sorted: the narrow kernel, both wide ones, both reasons for <false>, a second round of each --
+    + [_pc("mcp_group_rows_grad_sorted", f"narrow c={c}", b=3, n=61, c=c, t=2300) for c in (1, 2, 3, 4)]
+    + [_pc("mcp_group_rows_grad_sorted", f"c={c}", b=3, n=61, c=c, t=2300) for c in (5, 8, 35, 256)]
+    + [_pc("mcp_group_rows_grad_sorted", f"c=64, {o} off 16 bytes", off=(o,), b=3, n=61, c=64, t=2300) for o in ("grad_out", "grad_points")]
+    + [_pc("mcp_group_rows_grad_sorted", "narrow, off 16 bytes: still the narrow kernel", off=("grad_out", "grad_points"), b=3, n=61, c=4, t=2300),
+       _pc("mcp_group_rows_grad_sorted", "segments from ops._scatter_segments", b=3, n=61, c=8, t=2300, segments="ops"),
+       _pc("mcp_group_rows_grad_sorted", "narrow, segments from ops._scatter_segments", b=3, n=61, c=3, t=2300, segments="ops"),
+       _pc("mcp_group_rows_grad_sorted", "second round, <true>", b=3, n=21846, c=256, t=2300, twice=True),
+       _pc("mcp_group_rows_grad_sorted", "second round, <false>", b=3, n=39946, c=35, t=2300, twice=True),
+       _pc("mcp_group_rows_grad_sorted", "second round, narrow", b=1, n=524289 + 5, c=3, t=2300, twice=True)]
+    # -- interp3_apply_grad_sorted: both kernels, each alone, vec by c % 4 and by alignment, lane strides below / at / above one pass --
+    + [_pc("mcp_interp3_apply_grad_sorted", f"c={c}", b=3, n=70, s=50, c=c) for c in (1, 4, 28, 32, 36)]
+    + [_pc("mcp_interp3_apply_grad_sorted", f"c=32, {'grad_' + w if w == 'feat' else 'grad_w3'} alone", b=3, n=70, s=50, c=32, want=(w,)) for w in ("feat", "w")]
+    + [_pc("mcp_interp3_apply_grad_sorted", f"c=64, {o} off 16 bytes", off=(o,), b=3, n=70, s=50, c=64) for o in ("grad_out", "feat", "grad_feat")]
+    + [_pc("mcp_interp3_apply_grad_sorted", "segments from ops._scatter_segments", b=3, n=70, s=50, c=32, segments="ops"),
+       _pc("mcp_interp3_apply_grad_sorted", "second round of grad_feat, <true>", b=3, n=700, s=21846, c=256, twice=True),
+       _pc("mcp_interp3_apply_grad_sorted", "second round of grad_feat, <false>", b=3, n=700, s=39946, c=35, twice=True),
+       _pc("mcp_interp3_apply_grad_sorted", "second round of grad_w3", b=1, n=174764 + 3, s=50, c=8, twice=True)]
+    # -- the atomic scatters of the public ABI --
+    + [_pc("mcp_group_rows_grad", f"c={c}", b=3, n=50, c=c, t=70) for c in (1, 3, 4, 5, 256)]
+    + [_pc("mcp_group_rows_grad", "second round", n=50, **PRIM_PAST_8K_SCALAR)]
+    + [_pc("mcp_interp3_apply_grad", f"c={c}", b=3, n=70, s=50, c=c) for c in (1, 3, 4, 5, 256)]
+    + [_pc("mcp_interp3_apply_grad", "second round", b=3, n=19973, s=50, c=35)]
+    # -- three_nn: fewer known points than neighbours, NN_TILE -1 / 0 / +1, a third tile of one point; BLK -1 / 0 / +1 unknown points --
+    + [_pc("mcp_three_nn", f"n={n},m={m}", b=3, n=n, m=m) for n, m in ((1, 1), (255, 2), (256, 3), (257, 4), (1, 1023), (255, 1024), (256, 1025), (257, 2049))]
+    + [_pc("mcp_three_nn", "ties across the tile boundaries", b=3, n=257, m=2049, grid=True)]
+    # -- interp3 / interp3_weights --
+    + [_pc("mcp_interp3", f"n={n},s={sp}", b=3, n=n, s=sp, c=c) for n, c in ((1, 5), (255, 8), (256, 5), (257, 8)) for sp in (3, 40)]
+    + [_pc("mcp_interp3", "dense points on sparse points: the 1e-10 clamp", b=3, n=257, s=40, c=8, coincident=5)]
+    + [_pc("mcp_interp3_weights", f"n={n},s={sp}", b=3, n=n, s=sp) for n in (1, 255, 256, 257) for sp in (3, 40)]
+    + [_pc("mcp_interp3_weights", "dense points on sparse points: the 1e-10 clamp", b=3, n=257, s=40, coincident=5)]
+    # -- add_layernorm: every register boundary of every PER at five rows (one live wave in the second workgroup), every row count at c = 65 --
+    + [_pc("mcp_add_layernorm", f"rows=5,c={c}", rows=5, c=c) for c in (1, 63, 64, 65, 127, 128, 129, 255, 256, 257, 1023, 1024)]
+    + [_pc("mcp_add_layernorm", f"rows={r},c=65", rows=r, c=65) for r in (1, 2, 3, 4, 1027)]
+    + [_pc("mcp_add_layernorm", f"rows=1027,c={c}", rows=1027, c=c) for c in (64, 256, 1024)]
+    + [_pc("mcp_add_layernorm", "c = 1025 is unsupported", rows=5, c=1025),
+       _pc("mcp_add_layernorm", "a stride below c is refused", rows=5, c=65, x_stride=64)]
+    # -- mfa_prepare --
+    + [_pc("mcp_mfa_prepare", f"rows={r},n={n},c={c}", rows=r, n=n, c=c) for r, n, c in ((1, 1, 4), (5, 33, 64), (1, 33, 64), (5, 1, 4))]
+    + [_pc("mcp_mfa_prepare", "c = 6 is unsupported", rows=5, n=33, c=6)]
+    + [_pc("mcp_mfa_prepare", f"{o} off 16 bytes is refused", off=(o,), rows=5, n=33, c=64) for o in PRIM_ALIGNED_OPERANDS["mcp_mfa_prepare"]]
+)
+
+
+def primitive_cases(entry, ok=None):
+    """The cases of one entry; ok=True / False: only those the host accepts / refuses."""
+    return [c for c in PRIMITIVE_CASES if c["entry"] == entry and (ok is None or (c["status"] == MCP_OK) == ok)]
+
+
+def primitive_case_launch(c):
+    return primitive_launch(c["entry"], aligned=not c["off"], off=c["off"], **c["shape"])
+
+
+def primitive_case_id(c):
+    shape = ",".join(f"{k}={'+'.join(v) if isinstance(v, tuple) else v}" for k, v in c["shape"].items())
+    tail = "".join(f",{k}" for k in ("data", "segments", "grid", "coincident") if c.get(k)) + ("".join(f",{o}+4B" for o in c["off"]))
+    return f"{c['entry'][4:]}[{shape}{tail}]"
